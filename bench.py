@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- scored triples/s of the holE.py hot path on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
   (N>1 under a launcher: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...;
    N>1 WITHOUT one: this file starts its own N ranks, graphembeddings_amd/launch.py, before anything touches the GPU)
 
@@ -66,6 +66,9 @@ def parse():
                          "all-to-all (two cross-rank barriers per step); rehearsed on one device only, needs peer access on hardware")
     ap.add_argument("--entities", type=int, default=1_200_000)
     ap.add_argument("--triples", type=int, default=30_000_000)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="1 GPU: after the timed steps, write what their last step computed (the step's hinge losses and "
+                         "the updated table; a fixed sample of its rows if it would pass 32 MB) as DIR/<name>.npy, float32")
     return ap.parse_args()
 
 
@@ -361,6 +364,25 @@ def cpu_baseline_fb15k(fb, type_arrays, d, B, seconds):
             "reference_host_resample_s_per_step": round(resample_s, 3)}
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """Write each device array as out_dir/<name>.npy in float32.  An array larger than its share of DUMP_BYTES is
+    written as a fixed, seeded sample of its rows (sorted row ids), the same rows in every run of the same shape."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BYTES // len(arrays)
+    for name, t in arrays.items():
+        a = t.detach().float()
+        if a.numel() * 4 > share:
+            row_bytes = max(1, a[0].numel()) * 4
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], share // row_bytes, replace=False))
+            a = a[torch.as_tensor(rows, dtype=torch.int64, device=a.device)]
+            name += "_sample"
+        np.save(os.path.join(out_dir, f"{name}.npy"), a.cpu().numpy().astype(np.float32))
+
+
 def run_single(args):
     import torch
     from graphembeddings_amd import data as D
@@ -411,39 +433,33 @@ def run_single(args):
     if args.model == "hole":
         kernel_names[1] = "complex_hinge_grad_plan_kernel<SPEC>"   # same kernel template, Hermitian weights
 
-    # timed region.  One "call" = one ge_train_steps call of exactly K steps, as the driver asks; the
-    # call is repeated back to back until the region is >= MIN_TIMED_MS long, because K=20 steps are
-    # 0.4 ms -- too short for a stable wall-clock figure.  `value` is the steady state over those calls
-    # (each call continues the sequence, so its prepared records were built ahead on the side stream);
-    # `cold_call` is ONE K-step call right after a pipeline reset, with its first prepare launch exposed.
-    # HIP events ride on the dominant kernel's dispatch in every 4th step of the first call only --
-    # every step would add two barrier packets per step and perturb `value`.
-    MIN_TIMED_MS, EVERY = 5.0, 4
+    # timed region: ONE ge_train_steps call of exactly K steps, as the driver asks (`value` and `ms_per_step`).  It
+    # continues the sequence, so its prepared records were built ahead on the side stream.  Before it, untimed:
+    # `cold_call`, one K-step call right after a pipeline reset with its first prepare launch exposed, then one K-step
+    # call with HIP events on the dominant kernel's dispatch in every 4th step (`kernel_ms`) -- events in every step
+    # would add two barrier packets per step, and none ride in the timed call.
+    EVERY = 4
     tr.invalidate()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     tr.run(K)
     torch.cuda.synchronize()
     cold_el = time.perf_counter() - t0
-    t0 = time.perf_counter()
-    tr.run(K)
-    torch.cuda.synchronize()
-    est = max(time.perf_counter() - t0, 1e-6)
-    reps = max(1, int(np.ceil(1.3 * MIN_TIMED_MS * 1e-3 / est)))   # the lone pilot call is slower than the steady state
     ev = H.Events(2 * ((K + EVERY - 1) // EVERY))
     handles = []
     for i in range(K):
         handles += ([ev.handles[2 * (i // EVERY)], ev.handles[2 * (i // EVERY) + 1]] if i % EVERY == 0 else [None, None])
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
     tr.run(K, events=handles, ev_kernel=dom)
-    for _ in range(reps - 1):
-        tr.run(K)
     torch.cuda.synchronize()
-    el = (time.perf_counter() - t0) / reps
     n_ev = len(ev.handles) // 2
     kern_ms = sum(ev.elapsed_ms(2 * i, 2 * i + 1) for i in range(n_ev)) / n_ev
     ev.close()
+    t0 = time.perf_counter()
+    loss = tr.run(K)
+    torch.cuda.synchronize()
+    el = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"loss": loss, "embeddings": tr.real_embeddings()})
     loss_mean = float(tr.last_loss.mean())
     assert np.isfinite(loss_mean), "training diverged / invalid ids"
 
@@ -456,7 +472,7 @@ def run_single(args):
         "metric": "scored triples/sec/GPU (d=200)", "value": value, "unit": "scored triples/s",
         "n_gpus": 1, "ranks_seen": 1, "backend": "none (one rank: no collective runs)",
         "steps": K, "warmup": W, "ms_per_step": el / K * 1e3, "higher_is_better": True,
-        "timed_calls": reps, "timed_ms": el * reps * 1e3,
+        "timed_calls": 1, "timed_ms": el * 1e3,
         "cold_call": {"value": 2.0 * B * K / cold_el, "ms_per_step": cold_el / K * 1e3,
                       "note": "one K-step call right after a pipeline reset (first prepare launch exposed)"},
         "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
@@ -531,6 +547,9 @@ def run_single(args):
 def main():
     os.environ.setdefault("OMP_WAIT_POLICY", "passive")   # idle OpenMP workers of the CPU baseline must not spin
     args = parse()
+    if args.dump_outputs and (args.gpus > 1 or args.sharded):
+        print("bench.py: --dump-outputs is implemented for the 1-GPU path only", file=sys.stderr)
+        sys.exit(2)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no launcher around us: this process becomes the parent of N ranks.  It has not touched the GPU (nothing imported
         # so far initialises HIP; counting devices does not) and it never execs -- the ranks are ordinary children that

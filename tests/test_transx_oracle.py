@@ -1,6 +1,9 @@
 """Pins oracle/transx_oracle.py against the reference's OWN native code: oracle/_ref/init.so is
 init.cpp compiled from where it lies in /root/reference (oracle/Makefile, make.sh:1 flags).  The
-binary is run in a child process on generated ./data files; every batch must be bit-identical."""
+binary is run in a child process on generated ./data files; every batch must be bit-identical.
+What the binary yields on those files is stored in tests/golden/transx_init_batches_v1.npz
+(tests/golden/make_transx_golden.py), so the restatement is pinned wherever the binary was not built;
+where it was, the binary is run as well and must still yield the stored batches."""
 import os
 import subprocess
 import sys
@@ -12,6 +15,8 @@ from oracle import transx_oracle as TO
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF_SO = os.path.join(ROOT, "oracle", "_ref", "init.so")
+GOLDEN = os.path.join(ROOT, "tests", "golden", "transx_init_batches_v1.npz")
+B, K = 64, 5
 
 RUNNER = r"""
 import ctypes, os, sys, numpy as np
@@ -45,11 +50,9 @@ def _make_kg(seed, E=60, R=5, T=400):
     return tri.astype(np.int64), E, R
 
 
-@pytest.mark.skipif(not os.path.exists(REF_SO), reason="oracle/_ref/init.so not built (reference absent)")
-@pytest.mark.parametrize("seed", [0, 1])
-def test_restatement_equals_reference_binary(tmp_path, seed):
-    tri, E, R = _make_kg(seed)
-    data = tmp_path / "data"
+def run_reference_binary(work, tri, E, R):
+    """init.so's first K batches of B on `tri`, [K, 6, B], and its (entity, relation, triple) totals."""
+    data = work / "data"
     data.mkdir()
     (data / "relation2id.txt").write_text(f"{R}\n")
     (data / "entity2id.txt").write_text(f"{E}\n")
@@ -57,12 +60,23 @@ def test_restatement_equals_reference_binary(tmp_path, seed):
         f.write(f"{len(tri)}\n")
         for h, t, r in tri:
             f.write(f"{h} {t} {r}\n")              # init.cpp:70-73 reads h, t, r
-    B, K = 64, 5
-    res = subprocess.run([sys.executable, "-c", RUNNER, REF_SO, str(tmp_path), str(B), str(K)],
+    res = subprocess.run([sys.executable, "-c", RUNNER, REF_SO, str(work), str(B), str(K)],
                          capture_output=True, text=True, timeout=120)
     assert res.returncode == 0, res.stderr
-    assert res.stdout.split() == [str(E), str(R), str(len(tri))]
-    ref = np.load(tmp_path / "batches.npy")        # [K, 6, B]
+    return np.load(work / "batches.npy"), [int(x) for x in res.stdout.split()]
+
+
+@pytest.mark.parametrize("seed", [0, 1])
+def test_restatement_equals_reference_binary(tmp_path, seed):
+    tri, E, R = _make_kg(seed)
+    g = np.load(GOLDEN)
+    assert np.array_equal(g[f"seed{seed}/triples"], tri), "the generated graph is the one the batches were recorded on"
+    ref = g[f"seed{seed}/batches"]                 # [K, 6, B]
+    assert g[f"seed{seed}/totals"].tolist() == [E, R, len(tri)]
+    if os.path.exists(REF_SO):
+        got, totals = run_reference_binary(tmp_path, tri, E, R)
+        assert totals == [E, R, len(tri)]
+        assert np.array_equal(got, ref), "the reference binary no longer yields the stored batches"
     mine = TO.InitCppRestatement(tri, E, R, reproduce_defects=True)
     for k in range(K):
         got = np.stack(mine.getBatch(B))
