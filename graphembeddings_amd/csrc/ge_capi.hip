@@ -48,6 +48,12 @@ int shard_owner_apply_launch(float*, int32_t, const int32_t*, int64_t, const flo
 int pipeline_create(void**);
 int pipeline_reset(void*);
 int pipeline_destroy(void*);
+int transx_max_dim();
+size_t transx_ws_bytes(int64_t, int64_t, int32_t, int64_t);
+int transx_score_launch(int, int, const float*, int64_t, const float*, int64_t, const float*, const float*, const float*, int32_t, const int32_t*, int64_t, float*, hipStream_t);
+int transx_hinge_step_run(int, int, float*, int64_t, float*, int64_t, float*, float*, float*, int32_t, const int32_t*, const int32_t*, int64_t, float, float, float*, void*, size_t, hipStream_t);
+int transx_draw_launch(const int32_t*, int64_t, int64_t, const int64_t*, const int32_t*, const int64_t*, const int32_t*, int64_t, const uint32_t*, int32_t, int32_t, uint64_t, uint64_t, int32_t*, int32_t*, hipStream_t);
+int transx_train_steps_run(int, int, float*, int64_t, float*, int64_t, float*, float*, float*, int32_t, const int32_t*, int64_t, const int64_t*, const int32_t*, const int64_t*, const int32_t*, int64_t, const uint32_t*, uint64_t, uint64_t, int64_t, int64_t, float, float, float*, void*, size_t, hipStream_t);
 }  // namespace ge
 
 using namespace ge;
@@ -274,6 +280,77 @@ int ge_bernoulli_corrupt_batch(const int32_t* pos, int64_t B, const int64_t* bh_
   if (B > 0 && (!pos || !neg)) return GE_EINVAL;
   return bernoulli_corrupt_launch(pos, B, bh_key, bh_ent, bt_key, bt_ent, n_known, tail_threshold, n_rel,
                                   ent_lo, n_ent, seed, step, neg, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------- TransE / TransH / TransD
+static inline bool aligned4(const void* p) { return ((uintptr_t)p & 3) == 0; }
+// shapes and the model's tables: every table it has present and 4-byte aligned, ids fit the sort's 32-bit keys
+static inline int transx_tables_ok(int model, const void* ent, int64_t E, const void* rel, int64_t R,
+                                   const void* normal, const void* ent_transfer, const void* rel_transfer, int32_t d) {
+  if (model < GE_TRANSX_TRANSE || model > GE_TRANSX_TRANSD) return GE_EINVAL;
+  if (!ent || !rel || E <= 0 || R <= 0 || E + R >= ((int64_t)1 << 31)) return GE_EINVAL;
+  if (d <= 0) return GE_EINVAL;
+  if (d > transx_max_dim()) return GE_ENOTSUP;
+  if (model == GE_TRANSX_TRANSH && !normal) return GE_EINVAL;
+  if (model == GE_TRANSX_TRANSD && (!ent_transfer || !rel_transfer)) return GE_EINVAL;
+  for (const void* p : {ent, rel, normal, ent_transfer, rel_transfer})
+    if (p && !aligned4(p)) return GE_EINVAL;
+  return 0;
+}
+static inline bool transx_batch_ok(int64_t B) { return B > 0 && B <= ((int64_t)1 << 31) / 5 - 1; }
+
+int ge_transx_max_dim(void) { return transx_max_dim(); }
+
+int ge_transx_score(int model, int l1, const float* ent, int64_t n_ent, const float* rel, int64_t n_rel,
+                    const float* normal, const float* ent_transfer, const float* rel_transfer, int32_t d,
+                    const int32_t* triples, int64_t B, float* out, void* stream) {
+  if (int rc = transx_tables_ok(model, ent, n_ent, rel, n_rel, normal, ent_transfer, rel_transfer, d)) return rc;
+  if (B < 0) return GE_EINVAL;
+  if (B > 0 && (!triples || !out || !aligned4(triples) || !aligned4(out))) return GE_EINVAL;
+  return transx_score_launch(model, l1, ent, n_ent, rel, n_rel, normal, ent_transfer, rel_transfer, d, triples, B, out,
+                             (hipStream_t)stream);
+}
+
+size_t ge_transx_step_workspace_bytes(int64_t n_ent, int64_t n_rel, int32_t d, int64_t B) {
+  if (n_ent <= 0 || n_rel <= 0 || d <= 0 || d > transx_max_dim() || !transx_batch_ok(B)) return 0;
+  return transx_ws_bytes(n_ent, n_rel, d, B);
+}
+
+int ge_transx_hinge_step(int model, int l1, float* ent, int64_t n_ent, float* rel, int64_t n_rel, float* normal,
+                         float* ent_transfer, float* rel_transfer, int32_t d, const int32_t* pos, const int32_t* neg,
+                         int64_t B, float margin, float lr, float* loss, void* workspace, size_t workspace_bytes,
+                         void* stream) {
+  if (int rc = transx_tables_ok(model, ent, n_ent, rel, n_rel, normal, ent_transfer, rel_transfer, d)) return rc;
+  if (!transx_batch_ok(B) || !pos || !neg || !loss || !workspace) return GE_EINVAL;
+  if (!aligned4(pos) || !aligned4(neg) || !aligned4(loss) || ((uintptr_t)workspace & 255)) return GE_EINVAL;
+  return transx_hinge_step_run(model, l1, ent, n_ent, rel, n_rel, normal, ent_transfer, rel_transfer, d, pos, neg, B,
+                               margin, lr, loss, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int ge_transx_draw_batch(const int32_t* triples, int64_t T, int64_t B, const int64_t* bh_key, const int32_t* bh_ent,
+                         const int64_t* bt_key, const int32_t* bt_ent, int64_t n_known, const uint32_t* tail_threshold,
+                         int32_t n_rel, int32_t n_ent, uint64_t seed, uint64_t step, int32_t* pos, int32_t* neg,
+                         void* stream) {
+  if (!triples || T <= 0 || T > ((int64_t)1 << 32) || B < 0 || !tail_threshold || n_rel <= 0 || n_ent <= 0) return GE_EINVAL;
+  if (n_known < 0 || (n_known > 0 && (!bh_key || !bh_ent || !bt_key || !bt_ent))) return GE_EINVAL;
+  if (B > 0 && (!pos || !neg)) return GE_EINVAL;
+  return transx_draw_launch(triples, T, B, bh_key, bh_ent, bt_key, bt_ent, n_known, tail_threshold, n_rel, n_ent, seed,
+                            step, pos, neg, (hipStream_t)stream);
+}
+
+int ge_transx_train_steps(int model, int l1, float* ent, int64_t n_ent, float* rel, int64_t n_rel, float* normal,
+                          float* ent_transfer, float* rel_transfer, int32_t d, const int32_t* triples, int64_t T,
+                          const int64_t* bh_key, const int32_t* bh_ent, const int64_t* bt_key, const int32_t* bt_ent,
+                          int64_t n_known, const uint32_t* tail_threshold, uint64_t seed, uint64_t first_step,
+                          int64_t n_steps, int64_t B, float margin, float lr, float* losses, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+  if (int rc = transx_tables_ok(model, ent, n_ent, rel, n_rel, normal, ent_transfer, rel_transfer, d)) return rc;
+  if (!transx_batch_ok(B) || n_steps < 0 || !losses || !workspace || ((uintptr_t)workspace & 255)) return GE_EINVAL;
+  if (!triples || T <= 0 || T > ((int64_t)1 << 32) || !tail_threshold) return GE_EINVAL;
+  if (n_known < 0 || (n_known > 0 && (!bh_key || !bh_ent || !bt_key || !bt_ent))) return GE_EINVAL;
+  return transx_train_steps_run(model, l1, ent, n_ent, rel, n_rel, normal, ent_transfer, rel_transfer, d, triples, T,
+                                bh_key, bh_ent, bt_key, bt_ent, n_known, tail_threshold, seed, first_step, n_steps, B,
+                                margin, lr, losses, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int ge_complex_score_1vK(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B,

@@ -835,10 +835,14 @@ class BernoulliSampler:
     rows [relation_count, entity_count)).  Known triples -> two sorted device indexes + per-relation
     tail-corruption thresholds from tails-per-head / heads-per-tail (init.cpp:107-127, defects fixed)."""
 
-    def __init__(self, known_triples: np.ndarray, relation_count: int, entity_count: int, device="cuda"):
+    def __init__(self, known_triples: np.ndarray, relation_count: int, entity_count: int, device="cuda", *,
+                 ent_lo: Optional[int] = None):
+        """entity_count counts table rows; entities are rows [ent_lo, entity_count).  ent_lo defaults to
+        relation_count (the shared holE.py table); ent_lo=0 serves a separate entity table (the TransX models)."""
         tri = np.unique(np.asarray(known_triples, dtype=np.int64), axis=0)
         R = int(relation_count)
-        self.n_rel, self.ent_lo, self.n_ent = R, R, int(entity_count) - R
+        lo = R if ent_lo is None else int(ent_lo)
+        self.n_rel, self.ent_lo, self.n_ent = R, lo, int(entity_count) - lo
         bh = tri[np.lexsort((tri[:, 1], tri[:, 2], tri[:, 0]))]
         bt = tri[np.lexsort((tri[:, 0], tri[:, 2], tri[:, 1]))]
         freq = np.bincount(tri[:, 2], minlength=R).astype(np.float64)

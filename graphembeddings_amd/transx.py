@@ -1,0 +1,199 @@
+"""TransE / TransH / TransD (transE.py, transH.py, transD.py) on the MI355X: tables, batch scoring, the
+margin-hinge SGD step and the native multi-step loop of include/ge_hip.h's ge_transx_* entry points.
+
+Reference semantics: separate `ent [E,d]` / `rel [R,d]` tables (TransH adds `normal_vector [R,d]`, TransD adds
+`ent_transfer [E,d]` and `rel_transfer [R,d]`), every table xavier_initializer(uniform=False) for its own shape,
+D = sum |h_p + r - t_p| (L1) or sum (h_p + r - t_p)^2, loss = sum_batch max(D+ - D- + margin, 0), plain SGD
+(tf.train.GradientDescentOptimizer) on every table.  There is no CPU path: every call runs a HIP kernel.
+"""
+from __future__ import annotations
+
+import os
+from typing import Dict, Optional
+
+import numpy as np
+import torch
+
+from . import _lib
+from .hole import BernoulliSampler, _need_cuda, _stream, init_embeddings
+
+MODELS = {"transe": 0, "transh": 1, "transd": 2}
+# the extra tables of each model, in the order they are stored
+EXTRA_TABLES = {"transe": (), "transh": ("normal_vector",), "transd": ("ent_transfer", "rel_transfer")}
+
+
+def _count(path: str) -> int:
+    """The leading count of a *2id.txt file, read the way init.cpp:53-62 reads it (one `%d`, the rest unread)."""
+    with open(path) as f:
+        tok = f.read().split(maxsplit=1)
+    if not tok:
+        raise ValueError(f"{path}: empty file, expected a leading count")
+    try:
+        n = int(tok[0])
+    except ValueError:
+        raise ValueError(f"{path}: leading count {tok[0]!r} is not an integer") from None
+    if n <= 0:
+        raise ValueError(f"{path}: count {n} must be positive")
+    return n
+
+
+def read_kg(data_dir: str):
+    """(entity_total, relation_total, triples int32 [T,3] as (h, t, r)) from relation2id.txt, entity2id.txt and
+    triple2id.txt (init.cpp:47-86).  Each file begins with its count; the triples follow as `h t r` rows and are
+    read until the input ends, as init.cpp's `while (fscanf(...) == 1)` does.  Where init.cpp would read garbage or
+    write past its buffers (a partial last triple, more triples than declared, an id out of range) this raises."""
+    R = _count(os.path.join(data_dir, "relation2id.txt"))
+    E = _count(os.path.join(data_dir, "entity2id.txt"))
+    path = os.path.join(data_dir, "triple2id.txt")
+    with open(path) as f:
+        tok = f.read().split()
+    if not tok:
+        raise ValueError(f"{path}: empty file, expected a leading count")
+    try:
+        vals = np.array([int(x) for x in tok], dtype=np.int64)
+    except ValueError as e:
+        raise ValueError(f"{path}: non-integer token ({e})") from None
+    declared, body = int(vals[0]), vals[1:]
+    if body.size % 3:
+        raise ValueError(f"{path}: {body.size} ids after the count is not a whole number of (h, t, r) triples")
+    tri = body.reshape(-1, 3)
+    if len(tri) == 0:
+        raise ValueError(f"{path}: no triples")
+    if len(tri) > declared:
+        raise ValueError(f"{path}: {len(tri)} triples but the file declares {declared}")
+    if tri[:, :2].min() < 0 or tri[:, :2].max() >= E:
+        raise ValueError(f"{path}: entity id outside [0, {E})")
+    if tri[:, 2].min() < 0 or tri[:, 2].max() >= R:
+        raise ValueError(f"{path}: relation id outside [0, {R})")
+    return E, R, tri.astype(np.int32)
+
+
+def _pairs(t: torch.Tensor, name: str) -> torch.Tensor:
+    _need_cuda(t, name)
+    if t.dim() != 2 or t.shape[1] != 3:
+        raise ValueError(f"{name} must have shape [B, 3] (head, tail, relation)")
+    return t.to(torch.int32).contiguous()
+
+
+class TransX:
+    """The tables of one translation model.  `model` in {"transe", "transh", "transd"}; `l1` selects the L1
+    distance (the reference's L1_flag), else the squared L2 one."""
+
+    def __init__(self, model: str, n_ent: int, n_rel: int, d: int, l1: bool = True, seed: Optional[int] = 0,
+                 device="cuda"):
+        model = model.lower()
+        if model not in MODELS:
+            raise ValueError(f"model must be one of {sorted(MODELS)}, got {model!r}")
+        if n_ent <= 0 or n_rel <= 0:
+            raise ValueError("n_ent and n_rel must be positive")
+        if not 1 <= d <= 1024:
+            raise ValueError(f"d must lie in [1, 1024], got {d}")
+        self.model, self.n_ent, self.n_rel, self.d, self.l1 = model, int(n_ent), int(n_rel), int(d), bool(l1)
+        base = None if seed is None else int(seed)
+        rows = {"ent": n_ent, "rel": n_rel, "normal_vector": n_rel, "ent_transfer": n_ent, "rel_transfer": n_rel}
+        self.tables: Dict[str, torch.Tensor] = {}
+        for k, name in enumerate(("ent", "rel") + EXTRA_TABLES[model]):
+            self.tables[name] = init_embeddings(rows[name], d, device=device, seed=None if base is None else base + k)
+        self._ws: Optional[torch.Tensor] = None
+        self._ws_B = -1
+        self._loss = torch.empty(1, dtype=torch.float32, device=self.tables["ent"].device)
+
+    # the pointer arguments every ge_transx_* entry takes
+    def _ptrs(self):
+        t = self.tables
+        p = lambda name: t[name].data_ptr() if name in t else None
+        return (MODELS[self.model], int(self.l1), p("ent"), self.n_ent, p("rel"), self.n_rel, p("normal_vector"),
+                p("ent_transfer"), p("rel_transfer"), self.d)
+
+    def workspace(self, B: int) -> torch.Tensor:
+        if self._ws is None or self._ws_B != B:
+            nbytes = _lib.load().ge_transx_step_workspace_bytes(self.n_ent, self.n_rel, self.d, int(B))
+            if nbytes == 0:
+                raise RuntimeError("ge_transx_step_workspace_bytes failed")
+            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.tables["ent"].device)
+            self._ws_B = B
+        return self._ws
+
+    def score(self, triples: torch.Tensor) -> torch.Tensor:
+        """D of every (h, t, r) row, [B] fp32 (NaN where an id is out of range)."""
+        tb = _pairs(triples, "triples")
+        out = torch.empty(tb.shape[0], dtype=torch.float32, device=tb.device)
+        _lib.call("ge_transx_score", *self._ptrs(), tb.data_ptr(), tb.shape[0], out.data_ptr(), _stream())
+        return out
+
+    def step(self, pos: torch.Tensor, neg: torch.Tensor, lr: float, margin: float) -> torch.Tensor:
+        """One SGD step on sum max(D(pos) - D(neg) + margin, 0); returns that batch loss (device scalar, before
+        the step).  neg must keep pos's relation column (as getBatch's negatives do)."""
+        pb, nb = _pairs(pos, "pos"), _pairs(neg, "neg")
+        if pb.shape != nb.shape or pb.shape[0] == 0:
+            raise ValueError("pos and neg must be non-empty and of the same shape")
+        ws = self.workspace(pb.shape[0])
+        _lib.call("ge_transx_hinge_step", *self._ptrs(), pb.data_ptr(), nb.data_ptr(), pb.shape[0], float(margin),
+                  float(lr), self._loss.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+        return self._loss[0].clone()
+
+    def state_dict(self) -> Dict[str, object]:
+        return {"model": self.model, "l1": self.l1, "n_ent": self.n_ent, "n_rel": self.n_rel, "d": self.d,
+                **{k: v.detach().cpu().clone() for k, v in self.tables.items()}}
+
+    def load_state_dict(self, state: Dict[str, object]) -> None:
+        for key in ("model", "n_ent", "n_rel", "d"):
+            if state[key] != getattr(self, key):
+                raise ValueError(f"state_dict {key}={state[key]!r} does not match this model's {getattr(self, key)!r}")
+        self.l1 = bool(state.get("l1", self.l1))
+        for name, t in self.tables.items():
+            src = state[name]
+            if tuple(src.shape) != tuple(t.shape):
+                raise ValueError(f"state_dict table {name} has shape {tuple(src.shape)}, expected {tuple(t.shape)}")
+            t.copy_(src.to(device=t.device, dtype=torch.float32))
+
+    def trainer(self, triples, batch_size: int, *, margin: float = 1.0, learning_rate: float = 0.001,
+                seed: int = 0) -> "Trainer":
+        return Trainer(self, triples, batch_size, margin=margin, learning_rate=learning_rate, seed=seed)
+
+
+class Trainer:
+    """The reference's training loop (getBatch + train_step, transE.py:109-115) as one native call per run():
+    each step draws `batch_size` positives uniformly with replacement from `triples` and corrupts each with the
+    filtered Bernoulli rule (ent_lo = 0), then takes the hinge SGD step.  Step s of the run uses the Philox
+    counter (seed, s): ge_transx_draw_batch(.., seed, s, ..) reproduces any step's batch."""
+
+    def __init__(self, model: TransX, triples, batch_size: int, *, margin: float = 1.0, learning_rate: float = 0.001,
+                 seed: int = 0):
+        tri = np.asarray(triples.cpu().numpy() if isinstance(triples, torch.Tensor) else triples, dtype=np.int64)
+        if tri.ndim != 2 or tri.shape[1] != 3 or len(tri) == 0:
+            raise ValueError("triples must be a non-empty [T, 3] (h, t, r) array")
+        if tri[:, :2].min() < 0 or tri[:, :2].max() >= model.n_ent or tri[:, 2].min() < 0 or tri[:, 2].max() >= model.n_rel:
+            raise ValueError("triples hold an id outside the model's tables")
+        if batch_size <= 0:
+            raise ValueError("batch_size must be positive")
+        dev = model.tables["ent"].device
+        self.model, self.B, self.margin, self.lr, self.seed = model, int(batch_size), float(margin), float(learning_rate), int(seed)
+        self.triples = torch.as_tensor(tri.astype(np.int32)).to(dev).contiguous()
+        self.sampler = BernoulliSampler(tri, model.n_rel, model.n_ent, device=dev, ent_lo=0)
+        self.step_count = 0
+
+    def draw(self, step: int):
+        """The (pos, neg) batch the loop uses at `step`."""
+        s = self.sampler
+        pos = torch.empty(self.B, 3, dtype=torch.int32, device=self.triples.device)
+        neg = torch.empty_like(pos)
+        _lib.call("ge_transx_draw_batch", self.triples.data_ptr(), self.triples.shape[0], self.B, s.bh_key.data_ptr(),
+                  s.bh_ent.data_ptr(), s.bt_key.data_ptr(), s.bt_ent.data_ptr(), s.n_known, s.tail_threshold.data_ptr(),
+                  s.n_rel, s.n_ent, self.seed & (2**64 - 1), int(step) & (2**64 - 1), pos.data_ptr(), neg.data_ptr(),
+                  _stream())
+        return pos, neg
+
+    def run(self, n: int) -> torch.Tensor:
+        """n steps in one call; returns the [n] per-step batch losses (device)."""
+        m, s = self.model, self.sampler
+        losses = torch.empty(max(int(n), 0), dtype=torch.float32, device=self.triples.device)
+        if n <= 0:
+            return losses
+        ws = m.workspace(self.B)
+        _lib.call("ge_transx_train_steps", *m._ptrs(), self.triples.data_ptr(), self.triples.shape[0],
+                  s.bh_key.data_ptr(), s.bh_ent.data_ptr(), s.bt_key.data_ptr(), s.bt_ent.data_ptr(), s.n_known,
+                  s.tail_threshold.data_ptr(), self.seed & (2**64 - 1), self.step_count, int(n), self.B, self.margin,
+                  self.lr, losses.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+        self.step_count += int(n)
+        return losses

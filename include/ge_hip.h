@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define GE_VERSION 320 /* 0.3.2: + ge_rank_1vK_vs_loss (ranks against given losses: sharded candidate lists, the is_confident gate) */
+#define GE_VERSION 330 /* 0.3.3: + ge_transx_* (TransE / TransH / TransD scoring, hinge SGD step and native loop) */
 
 /* argument errors (negative, -errno style) */
 #define GE_EINVAL (-22)  /* bad dimension / null pointer / misaligned buffer */
@@ -192,6 +192,49 @@ int ge_bernoulli_corrupt_batch(const int32_t* pos, int64_t B, const int64_t* bh_
                                const int64_t* bt_key, const int32_t* bt_ent, int64_t n_known,
                                const uint32_t* tail_threshold, int32_t n_rel, int32_t ent_lo,
                                int32_t n_ent, uint64_t seed, uint64_t step, int32_t* neg, void* stream);
+
+/* --- TransE / TransH / TransD (transE.py, transH.py, transD.py).  Separate tables, row-major fp32:
+ * ent [n_ent,d] and rel [n_rel,d]; TransH adds normal [n_rel,d] (normal_vector); TransD adds ent_transfer
+ * [n_ent,d] and rel_transfer [n_rel,d].  A table the model does not have is passed as NULL (and ignored).
+ * Entity ids are rows of ent, [0, n_ent); relation ids rows of rel.  Triples are int32 [B,3] (h, t, r).
+ *   D = sum_k |h_p + r - t_p| (l1 != 0) or sum_k (h_p + r - t_p)^2 (l1 = 0), with the projection
+ *   TransE e;  TransH e - (e.n^) n^, n^ = n * rsqrt(max(n.n, 1e-12));  TransD e + (e.e_p) r_p.
+ * 1 <= d <= ge_transx_max_dim() (1024); d % 4 == 0 with 16-byte aligned tables takes the vectorised path. */
+#define GE_TRANSX_TRANSE 0
+#define GE_TRANSX_TRANSH 1
+#define GE_TRANSX_TRANSD 2
+int ge_transx_max_dim(void);
+/* out[i] = D of triple i ([B] fp32); NaN for a triple with an id out of range. */
+int ge_transx_score(int model, int l1, const float* ent, int64_t n_ent, const float* rel, int64_t n_rel,
+                    const float* normal, const float* ent_transfer, const float* rel_transfer, int32_t d,
+                    const int32_t* triples, int64_t B, float* out, void* stream);
+/* Workspace of one hinge step / of ge_transx_train_steps for B pairs (the same size serves both). */
+size_t ge_transx_step_workspace_bytes(int64_t n_ent, int64_t n_rel, int32_t d, int64_t B);
+/* One SGD step of loss = sum_i max(D(pos_i) - D(neg_i) + margin, 0) (a sum, not a mean) on every table of the
+ * model: gradients on the pre-step tables with TF's rules (a pair is active iff D+ - D- + margin >= 0,
+ * d|x|/dx = sign(x) with sign(0) = 0, the l2_normalize clamp differentiated on the branch max() takes),
+ * duplicate rows summed in slot order, then row -= lr * sum.  neg_i must keep pos_i's relation; a pair with
+ * an id out of range or neg_r != pos_r is skipped.  *loss (device, one float) = the batch loss before the step.
+ * Bitwise reproducible: no float atomics. */
+int ge_transx_hinge_step(int model, int l1, float* ent, int64_t n_ent, float* rel, int64_t n_rel, float* normal,
+                         float* ent_transfer, float* rel_transfer, int32_t d, const int32_t* pos, const int32_t* neg,
+                         int64_t B, float margin, float lr, float* loss, void* workspace, size_t workspace_bytes,
+                         void* stream);
+/* The batch draw of the native loop (init.cpp getBatch, 224-246): pos_i = triples[(w * T) >> 32] with w a
+ * Philox4x32-10 word keyed by (seed, step, i), then neg_i = the Bernoulli corruption of pos_i
+ * (ge_bernoulli_corrupt_batch with ent_lo = 0, n_ent entities, the same seed and step). */
+int ge_transx_draw_batch(const int32_t* triples, int64_t T, int64_t B, const int64_t* bh_key, const int32_t* bh_ent,
+                         const int64_t* bt_key, const int32_t* bt_ent, int64_t n_known, const uint32_t* tail_threshold,
+                         int32_t n_rel, int32_t n_ent, uint64_t seed, uint64_t step, int32_t* pos, int32_t* neg,
+                         void* stream);
+/* n_steps steps in one call: step s draws its batch as ge_transx_draw_batch(.., seed, first_step + s, ..) and runs
+ * ge_transx_hinge_step on it; losses[s] (device) = its batch loss.  No host synchronisation inside. */
+int ge_transx_train_steps(int model, int l1, float* ent, int64_t n_ent, float* rel, int64_t n_rel, float* normal,
+                          float* ent_transfer, float* rel_transfer, int32_t d, const int32_t* triples, int64_t T,
+                          const int64_t* bh_key, const int32_t* bh_ent, const int64_t* bt_key, const int32_t* bt_ent,
+                          int64_t n_known, const uint32_t* tail_threshold, uint64_t seed, uint64_t first_step,
+                          int64_t n_steps, int64_t B, float margin, float lr, float* losses, void* workspace,
+                          size_t workspace_bytes, void* stream);
 
 /* --- 1-vs-K candidate scoring (the inference loop of holE.py:564-569: fixed (head, relation)
  * against many tails; also K shared negatives per positive).  hr: [B,2] int32 (fixed entity,
