@@ -160,3 +160,81 @@ def test_malformed_input_raises_before_gpu(tmp_path, monkeypatch):
     with pytest.raises(ValueError):                           # 3 triples cannot fill 100 batches
         XT.main(["--data_dir", str(tmp_path)])
     assert calls == []
+
+
+def test_slot_keys_scheme():
+    """Slots 4i..4i+3 = pos h, pos t, neg h, neg t; slot 4B+i = E + r; an inactive pair's slots = E + R."""
+    E, R = 10, 3
+    pos, neg = np.array([[1, 2, 0], [3, 1, 2], [7, 7, 1]]), np.array([[1, 5, 0], [3, 1, 2], [4, 7, 1]])
+    keys, srt = TR.slot_keys(pos, neg, E, R, [True, False, True])
+    assert keys.tolist() == [1, 2, 1, 5, 13, 13, 13, 13, 7, 7, 4, 7, 10, 13, 11]
+    assert srt.tolist() == sorted(keys.tolist())
+    assert TR.run_of(srt, 7) == (5, 3) and TR.run_of(srt, 13) == (10, 5)
+
+
+@pytest.mark.parametrize("model", MODELS)
+@pytest.mark.parametrize("name", sorted(TR.LAYOUTS))
+@pytest.mark.parametrize("d", [7, 8])
+@pytest.mark.parametrize("l1", [True, False])
+def test_layout_batches_have_their_layout(model, name, d, l1):
+    """Each layout the GPU tests use puts its runs where it says, with the activity it says, and (TransE / TransD)
+    is exact: every value of the step is an integer, or a multiple of lr, below 2^24, so fp32 holds it."""
+    f = TR.layout_batch(model, name, d, l1)
+    spec = TR.LAYOUTS[name]
+    act = TR.active_mask(model, f["tabs"], f["pos"], f["neg"], f["margin"], l1)
+    assert act.sum() == sum(spec["counts"]) and len(act) == sum(spec["counts"]) + spec.get("inactive", 0)
+    z = TR.score(model, f["tabs"], f["pos"], l1) - TR.score(model, f["tabs"], f["neg"], l1) + f["margin"]
+    assert np.all(z[~act] == -1.0) and np.all(z[act] >= (1.0 if f["margin"] > 0 else 0.0))
+    _, srt = TR.slot_keys(f["pos"], f["neg"], f["E"], f["R"], act)
+    for key, start, length in f["expect"]:
+        assert TR.run_of(srt, key) == (start, length)
+    if model != "transh":
+        assert TR.exact_step_bound(model, f["tabs"], f["pos"], f["neg"], f["lr"], f["margin"], l1) < TR.FP32_EXACT
+        new, loss = TR.sgd_step(model, f["tabs"], f["pos"], f["neg"], f["lr"], f["margin"], l1)
+        assert np.float32(loss) == loss
+        for k in new:
+            assert np.array_equal(new[k].astype(np.float32), new[k]) and not np.array_equal(new[k], f["tabs"][k])
+
+
+def test_layouts_cut_where_they_say():
+    """The windows of the runs: whole, cut in two, straddling, four windows, meeting, ending at the last slot."""
+    win = lambda s, n: (s // TR.KWIN, (s + n - 1) // TR.KWIN)
+    spans = {name: [win(s, n) for _, s, n in spec["expect"]] for name, spec in TR.LAYOUTS.items()}
+    assert spans["run32_on_boundary"] == [(5, 5)] and spans["run33"] == [(5, 6)] and spans["straddle2"] == [(1, 2)]
+    assert spans["four_windows"] == [(13, 16)] and spans["two_cuts_meet"] == [(10, 11), (11, 12)]
+    assert spans["cut_before_sentinel"] == [(2, 3)] and spans["hot_entities"] == [(0, 1), (1, 2)]
+    f = TR.layout_batch("transe", "two_cuts_meet", 8)
+    assert 5 * len(f["pos"]) == 410                                        # relation 2 ends at the last slot
+    f = TR.layout_batch("transe", "cut_before_sentinel", 8)
+    assert 5 * sum(TR.LAYOUTS["cut_before_sentinel"]["counts"]) == 115    # relation 1 ends right before sentinels
+
+
+def test_exact_bound_rejects_what_fp32_cannot_hold():
+    f = TR.layout_batch("transd", "four_windows", 100, l1=False)          # a 100-slot hot row at d = 100, L2
+    args = (f["pos"], f["neg"], f["lr"], f["margin"], False)
+    assert TR.exact_step_bound("transd", f["tabs"], *args) > TR.FP32_EXACT
+    assert not TR.is_exact_step("transd", f["tabs"], *args)
+    g = TR.layout_batch("transd", "four_windows", 8, l1=False)
+    assert TR.is_exact_step("transd", g["tabs"], g["pos"], g["neg"], g["lr"], g["margin"], False)
+    half = {k: v + 0.5 for k, v in g["tabs"].items()}
+    for bad in ((half, g["lr"], g["margin"]), (g["tabs"], 0.01, g["margin"]), (g["tabs"], g["lr"], g["margin"] + 0.5)):
+        assert not TR.is_exact_step("transd", bad[0], g["pos"], g["neg"], bad[1], bad[2], False)
+    with pytest.raises(ValueError):
+        TR.exact_step_bound("transh", TR.exact_tables("transh", 5, 2, 4), g["pos"][:1] % 2, g["neg"][:1] % 2,
+                            1 / 64, 1.0)
+
+
+@pytest.mark.parametrize("model", MODELS)
+def test_magnitude_bounds_the_gradient(model):
+    rng = np.random.default_rng(6)
+    tabs = _tables(model, 12, 3, 5, rng)
+    pos = np.stack([rng.integers(0, 12, 30), rng.integers(0, 12, 30), rng.integers(0, 3, 30)], 1)
+    neg = pos.copy()
+    neg[:, 1] = rng.integers(0, 12, 30)
+    _, g = TR.hinge_grads(model, tabs, pos, neg, 2.0, True)
+    _, mag = TR.hinge_grads(model, tabs, pos, neg, 2.0, True, magnitude=True)
+    _, g1 = TR.hinge_grads(model, tabs, pos[:1], neg[:1], 2.0, True)
+    _, mag1 = TR.hinge_grads(model, tabs, pos[:1], neg[:1], 2.0, True, magnitude=True)
+    for k in g:
+        assert np.all(np.abs(g[k]) <= mag[k] + 1e-12) and mag[k].max() > np.abs(g[k]).max()
+        assert np.all(np.abs(g1[k]) <= mag1[k] + 1e-12)
