@@ -14,6 +14,7 @@
 // with a row stride of 33 floats so the 32 rows a half-wave reads per operand fall in 32 banks.
 #include "ge_common.h"
 #include "ge_rank_dev.h"
+#include "ge_launch.h"
 
 namespace ge {
 

@@ -2,59 +2,7 @@
 // Argument checks happen here, on the host, before any launch: a kernel that faults can take
 // the whole node down, so shapes, alignment and workspace sizes are validated up front.
 #include "ge_common.h"
-
-namespace ge {
-int complex_score_launch(const float*, int64_t, int32_t, const int32_t*, int64_t, float, int, float*, hipStream_t, int spectral = 0, float label = 0.f, float l2 = 0.f, const float* table_sumsq = nullptr, int64_t ld = 0);
-int complex_hinge_loss_launch(const float*, int64_t, int32_t, const int32_t*, const int32_t*, int64_t, float, float, float*, float*, hipStream_t, int spectral = 0);
-int complex_hinge_grad_launch(const float*, int64_t, int32_t, const int32_t*, const int32_t*, int64_t, float, float, float, float*, int32_t*, float*, hipStream_t, hipEvent_t = nullptr, hipEvent_t = nullptr, const int32_t* slot_item = nullptr, float* table_rw = nullptr, int spectral = 0, const int32_t* order = nullptr);
-int complex_max_dim();
-int select_rows_launch(const int32_t*, int64_t, int64_t, uint64_t, uint64_t, int32_t*, hipStream_t);
-int mean_pocket_launch(const float*, int64_t, float*, float*, int32_t*, hipStream_t);
-int copy_if_launch(const float*, float*, int64_t, const int32_t*, hipStream_t);
-int rank_max_dim();
-int complex_rank_1vK_launch(const float*, int64_t, int32_t, const int32_t*, int64_t, const int32_t*, const int32_t*, int64_t, float, int, const int32_t*, const uint16_t*, int32_t*, int32_t*, float*, float*, int, const void*, hipStream_t, int vs_loss = 0);
-int64_t rank_planes_bytes(int64_t, int32_t, int64_t);
-int known_cells_launch(int, const int64_t*, const int64_t*, int64_t, const int64_t*, const int64_t*, int64_t, const int64_t*, int64_t, int64_t, int32_t*, int32_t*, uint16_t*, hipStream_t);
-int rank_planes_launch(const float*, int64_t, int32_t, const int32_t*, int64_t, float, int, void*, hipStream_t);
-int hole_spectral_launch(float*, int64_t, int32_t, int, hipStream_t);
-int hole_score_launch(const float*, int64_t, int32_t, const int32_t*, int64_t, float, int, float*, hipStream_t);
-int hole_hinge_loss_launch(const float*, int64_t, int32_t, const int32_t*, const int32_t*, int64_t, float, float, float*, float*, hipStream_t);
-int hole_hinge_grad_launch(const float*, int64_t, int32_t, const int32_t*, const int32_t*, int64_t, float, float, float, float*, int32_t*, float*, hipStream_t, hipEvent_t = nullptr, hipEvent_t = nullptr);
-int hole_max_dim();
-int scatter_add_rows_launch(float*, int64_t, int32_t, const int32_t*, const float*, int64_t, hipStream_t, hipEvent_t = nullptr, hipEvent_t = nullptr);
-int gather_rows_launch(const float*, int64_t, int32_t, const int32_t*, int64_t, float*, hipStream_t);
-int corrupt_batch_launch(const int32_t*, int64_t, const int32_t*, int64_t, const int64_t*, int32_t, const int32_t*, uint64_t, uint64_t, int32_t, int32_t, int32_t*, hipStream_t);
-int complex_score_1vK_launch(const float*, int64_t, int32_t, const int32_t*, int64_t, const int32_t*, int64_t, float, int, int, float*, hipStream_t);
-int bernoulli_corrupt_launch(const int32_t*, int64_t, const int64_t*, const int32_t*, const int64_t*, const int32_t*, int64_t, const uint32_t*, int32_t, int32_t, int32_t, uint64_t, uint64_t, int32_t*, hipStream_t);
-int complex_logloss_grad_launch(const float*, int64_t, int32_t, const int32_t*, const float*, int64_t, float, float, float, const float*, float*, int32_t*, float*, hipStream_t, const int32_t* negs = nullptr, int64_t B = 0, float row_scale = 1.f, float neg_lr_eff = 0.f, hipEvent_t = nullptr, hipEvent_t = nullptr);
-int table_sumsq_launch(const float*, int64_t, float*, hipStream_t);
-int table_scale_launch(float*, int64_t, float, hipStream_t);
-size_t hinge_ws_bytes(int64_t, int32_t);
-size_t train_ws_bytes(int64_t, int32_t);
-int train_steps_run(float*, int64_t, int32_t, const int32_t*, int64_t, int64_t, int64_t, int64_t, const int32_t*, const int64_t*, int32_t, const int32_t*, uint64_t, uint64_t, int32_t, int32_t, float, float, float, float, float, int, float*, int, int32_t*, void*, size_t, void**, int, void*, hipStream_t);
-int train_prepare_run(const int32_t*, int64_t, int64_t, int64_t, int64_t, const int32_t*, int64_t, const int64_t*, int32_t, const int32_t*, uint64_t, uint64_t, int32_t, int32_t, int, int32_t*, hipStream_t);
-void train_prepared_layout(int64_t, int64_t*);
-size_t train_prepare_bytes(int64_t, int64_t);
-size_t train_logloss_ws_bytes(int64_t, int32_t, int32_t);
-int train_logloss_run(float*, int64_t, int32_t, const int32_t*, int64_t, int64_t, int64_t, int64_t, const int32_t*, const int64_t*, int32_t, const int32_t*, uint64_t, uint64_t, int32_t, int32_t, int32_t, float, float, float, float, float, float*, int, int32_t*, void*, size_t, void*, hipStream_t);
-size_t shard_plan_scratch_bytes(int64_t, int64_t);
-int shard_plan_launch(const int32_t*, const int32_t*, int64_t, int64_t, int64_t, int32_t, int32_t, int32_t*, int32_t*, int32_t*, int32_t*, int32_t*, void*, int, hipStream_t);
-int shard_grad_launch(float*, int32_t, const float*, const int32_t*, const int32_t*, const int32_t*, int32_t, int64_t, float, float, float, int, float*, int32_t*, float*, float*, const float* const*, int, hipStream_t, hipEvent_t, hipEvent_t);
-int shard_apply_launch(float*, int32_t, const int32_t*, int64_t, const int32_t*, const float*, int32_t, float*, hipStream_t, hipEvent_t, hipEvent_t);
-int64_t shard_owner_record_words(int64_t);
-size_t shard_owner_scratch_bytes(int64_t, int64_t);
-int shard_owner_plan_launch(const int32_t*, const int64_t*, int64_t, int64_t, int32_t, int32_t*, void*, hipStream_t);
-int shard_owner_apply_launch(float*, int32_t, const int32_t*, int64_t, const float*, hipStream_t);
-int pipeline_create(void**);
-int pipeline_reset(void*);
-int pipeline_destroy(void*);
-int transx_max_dim();
-size_t transx_ws_bytes(int64_t, int64_t, int32_t, int64_t);
-int transx_score_launch(int, int, const float*, int64_t, const float*, int64_t, const float*, const float*, const float*, int32_t, const int32_t*, int64_t, float*, hipStream_t);
-int transx_hinge_step_run(int, int, float*, int64_t, float*, int64_t, float*, float*, float*, int32_t, const int32_t*, const int32_t*, int64_t, float, float, float*, void*, size_t, hipStream_t);
-int transx_draw_launch(const int32_t*, int64_t, int64_t, const int64_t*, const int32_t*, const int64_t*, const int32_t*, int64_t, const uint32_t*, int32_t, int32_t, uint64_t, uint64_t, int32_t*, int32_t*, hipStream_t);
-int transx_train_steps_run(int, int, float*, int64_t, float*, int64_t, float*, float*, float*, int32_t, const int32_t*, int64_t, const int64_t*, const int32_t*, const int64_t*, const int32_t*, int64_t, const uint32_t*, uint64_t, uint64_t, int64_t, int64_t, float, float, float*, void*, size_t, hipStream_t);
-}  // namespace ge
+#include "ge_launch.h"
 
 using namespace ge;
 

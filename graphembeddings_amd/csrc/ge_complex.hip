@@ -16,6 +16,7 @@
 // identity for a trilinear form, (d s/d y_X) . x_X = s / scale_X: the backward pass through the
 // clip needs no reduction beyond the forward ones.
 #include "ge_complex_dev.h"
+#include "ge_launch.h"
 
 namespace ge {
 

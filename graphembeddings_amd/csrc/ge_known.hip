@@ -7,6 +7,7 @@
 //   scan    exclusive prefix sum over the tiles (one workgroup)
 //   fill    the same walk, cells written at their tile's cursor (order inside a tile is irrelevant to the counts)
 #include "ge_common.h"
+#include "ge_launch.h"
 
 namespace ge {
 namespace {

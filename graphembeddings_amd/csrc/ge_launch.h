@@ -1,0 +1,185 @@
+// ge_launch.h -- the host entry points one source of libge_hip.so defines and another calls: the one declaration of
+// each, included by the defining source too, so the compiler checks every definition against it.  Default arguments
+// live here and nowhere else.  Launchers return 0 or an error code (hipError_t, GE_E*).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+namespace ge {
+
+struct TileGeom;
+struct ShardOut;
+
+// ge_complex.hip: ComplEx scoring, hinge and log-loss steps, the row-sharded grad step, table reductions
+int complex_max_dim();
+int complex_score_launch(const float* table, int64_t N, int32_t d, const int32_t* triples, int64_t B, float max_norm,
+                         int apply_sigmoid, float* out, hipStream_t st, int spectral = 0, float label = 0.f, float l2 = 0.f,
+                         const float* table_sumsq = nullptr, int64_t ld = 0);
+int complex_hinge_loss_launch(const float* table, int64_t N, int32_t d, const int32_t* pos, const int32_t* neg, int64_t B,
+                              float margin, float max_norm, float* loss, float* sig_out, hipStream_t st, int spectral = 0);
+int complex_hinge_grad_launch(const float* rows, int64_t N, int32_t d, const int32_t* pos, const int32_t* neg, int64_t B,
+                              float margin, float lr, float max_norm, float* loss, int32_t* grad_idx, float* grad_val,
+                              hipStream_t st, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr,
+                              const int32_t* slot_item = nullptr, float* table_rw = nullptr, int spectral = 0,
+                              const int32_t* order = nullptr);
+int complex_logloss_grad_launch(const float* rows, int64_t N, int32_t d, const int32_t* triples, const float* labels,
+                                int64_t M, float lr, float max_norm, float l2, const float* table_sumsq, float* loss,
+                                int32_t* grad_idx, float* grad_val, hipStream_t st, const int32_t* negs = nullptr,
+                                int64_t B = 0, float row_scale = 1.f, float neg_lr_eff = 0.f, hipEvent_t ev_start = nullptr,
+                                hipEvent_t ev_stop = nullptr);
+int shard_hinge_grad_launch(float* shard, int32_t d, const float* staged, const int32_t* pos_src, const int32_t* neg_src,
+                            const int32_t* slot_item, int32_t R, int64_t B, float margin, float lr, float max_norm,
+                            float* loss, int32_t* grad_idx, float* grad_val, float* gsum, int spectral, hipStream_t st,
+                            hipEvent_t ev_start, hipEvent_t ev_stop, const int32_t* order, const float* const* peers,
+                            int n_peers);
+int table_sumsq_launch(const float* table, int64_t n, float* out, hipStream_t st);
+int table_scale_launch(float* table, int64_t n, float factor, hipStream_t st);
+
+// ge_hole.hip: HolE scoring and hinge steps
+int hole_score_launch(const float* table, int64_t N, int32_t d, const int32_t* triples, int64_t B, float max_norm,
+                      int apply_sigmoid, float* out, hipStream_t st);
+int hole_hinge_loss_launch(const float* table, int64_t N, int32_t d, const int32_t* pos, const int32_t* neg, int64_t B,
+                           float margin, float max_norm, float* loss, float* sig_out, hipStream_t st);
+int hole_hinge_grad_launch(const float* rows, int64_t N, int32_t d, const int32_t* pos, const int32_t* neg, int64_t B,
+                           float margin, float lr, float max_norm, float* loss, int32_t* grad_idx, float* grad_val,
+                           hipStream_t st, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
+
+// ge_spectral.hip: row-wise real DFT of a HolE table, in place
+int hole_spectral_launch(float* table, int64_t N, int32_t d, int inverse, hipStream_t st);
+
+// ge_rows.hip: row gather / scatter-add, samplers, pocket bookkeeping
+int scatter_add_rows_launch(float* table, int64_t N, int32_t d, const int32_t* idx, const float* val, int64_t R,
+                            hipStream_t st, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
+int gather_rows_launch(const float* table, int64_t N, int32_t d, const int32_t* idx, int64_t R, float* out, hipStream_t st);
+int corrupt_batch_launch(const int32_t* pos, int64_t B, const int32_t* id_to_type, int64_t N, const int64_t* type_offsets,
+                         int32_t n_types, const int32_t* type_ids, uint64_t seed, uint64_t step, int32_t padded_size,
+                         int32_t mode, int32_t* neg, hipStream_t st);
+int bernoulli_corrupt_launch(const int32_t* pos, int64_t B, const int64_t* bh_key, const int32_t* bh_ent,
+                             const int64_t* bt_key, const int32_t* bt_ent, int64_t n_known, const uint32_t* tail_threshold,
+                             int32_t n_rel, int32_t ent_lo, int32_t n_ent, uint64_t seed, uint64_t step, int32_t* neg,
+                             hipStream_t st);
+int select_rows_launch(const int32_t* valid, int64_t V, int64_t B, uint64_t seed, uint64_t counter, int32_t* out,
+                       hipStream_t st);
+int mean_pocket_launch(const float* loss, int64_t B, float* mean_out, float* best, int32_t* flag, hipStream_t st);
+int copy_if_launch(const float* src, float* dst, int64_t n, const int32_t* flag, hipStream_t st);
+
+// ge_1vk.hip: 1-vs-K candidate scoring
+int complex_score_1vK_launch(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* cand,
+                             int64_t K, float max_norm, int apply_sigmoid, int cand_is_head, float* out, hipStream_t st);
+
+// ge_rank.hip: link-prediction ranks for any embedding_dim % 8 == 0
+int rank_max_dim();
+int complex_rank_1vK_launch(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* true_id,
+                            const int32_t* cand, int64_t K, float max_norm, int cand_is_head, const int32_t* known_off,
+                            const uint16_t* known_rc, int32_t* raw_cnt, int32_t* skip_cnt, float* true_loss,
+                            float* scores_out, int spec, const void* planes_ws, hipStream_t st, int vs_loss = 0);
+
+// ge_rank_pipe.hip: the pipelined sweep (embedding_dim % 40, % 32 or % 24 == 0); GE_ENOTSUP for any other dim.
+// spec: the table is a spectral HolE table.  score_pipe_launch: ge_complex_score_1vK on the same sweep.
+int rank_pipe_launch(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* true_id,
+                     const int32_t* cand, int64_t K, float max_norm, int cand_is_head, const int32_t* known_off,
+                     const uint16_t* known_rc, int32_t* raw_cnt, int32_t* skip_cnt, float* true_loss,
+                     float* scores_out, int spec, const void* planes_ws, hipStream_t st, int vs_loss = 0);
+int score_pipe_launch(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* cand,
+                      int64_t K, float max_norm, int apply_sigmoid, int cand_is_head, float* out, hipStream_t st);
+
+// ge_rank_f16.hip: the split-precision sweep (embedding_dim % 8 == 0 in 56 ... 288, max_norm <= 8), ranks or scores.
+// planes_ws: the candidates' fp16 planes + entity -> position map (rank_planes_launch into rank_planes_bytes bytes,
+// 256-byte aligned) for the same (table, cand, max_norm, spec); NULL: built inside, in a stream-ordered allocation.
+int64_t rank_planes_bytes(int64_t N, int32_t d, int64_t K);
+int rank_planes_launch(const float* table, int64_t N, int32_t d, const int32_t* cand, int64_t K, float max_norm, int spec,
+                       void* planes_ws, hipStream_t st);
+int sweep_f16_launch(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* true_id,
+                     const int32_t* cand, int64_t K, float max_norm, int cand_is_head, const int32_t* known_off,
+                     const uint16_t* known_rc, int32_t* raw_cnt, int32_t* skip_cnt, float* true_loss,
+                     float* scores_out, int spec, int scores_only, int sweep_flags, const void* planes_ws, hipStream_t st);
+
+// ge_known.hip: the known-true cells of a ranking sweep as per-tile lists
+int known_cells_launch(int pass, const int64_t* key, const int64_t* ent, int64_t M, const int64_t* fixed, const int64_t* rel,
+                       int64_t B, const int64_t* pos_of, int64_t n_rows, int64_t n_cand, int32_t* tile_cnt, int32_t* off,
+                       uint16_t* rc, hipStream_t st);
+
+// ge_prep_big.hip: the multi-workgroup radix sort and the prepare stage of steps of more than one tile
+size_t sort_scratch_bytes(int64_t n, int64_t n_sub, int64_t P);
+unsigned long long* sort_scratch_keys(void* scratch);
+int sort_tiles_launch(void* scratch, int64_t n, int64_t n_sub, int64_t P, int64_t n_rows, hipStream_t st,
+                      const unsigned* limit, const unsigned long long** sorted);
+int items_launch(const unsigned long long* sorted, int64_t n, const TileGeom& G, int direct, int32_t* out, const ShardOut* so,
+                 hipStream_t st);
+int relation_order_launch(const int32_t* triples, int64_t T, int64_t first_row, int64_t B, int64_t s0, int64_t n, int64_t N,
+                          int32_t* out, int64_t stride, int64_t off_order, void* scratch, hipStream_t st);
+size_t prep_big_scratch_bytes(int64_t B, int64_t negs, int64_t n);
+int prepare_big_launch(const int32_t* triples, int64_t T, int64_t first_row, int64_t B, int64_t s0, int64_t n,
+                       const int32_t* id_to_type, int64_t N, const int64_t* type_offsets, int32_t n_types,
+                       const int32_t* type_ids, uint64_t seed, uint64_t global_step0, int32_t padded_size, int32_t mode,
+                       int direct, int32_t* out, void* scratch, hipStream_t st, int negs);
+
+// ge_train.hip: the native training loops, their prepare stage and pipeline handle, the row-sorted update
+int apply_items_launch(float* table, int d, const TileGeom& G, const int32_t* step_rec, const int32_t* gidx,
+                       const float* gval, int split, float* out2, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop,
+                       int det);
+size_t hinge_ws_bytes(int64_t B, int32_t d);
+size_t train_ws_bytes(int64_t B, int32_t d);
+int train_steps_run(float* table, int64_t N, int32_t d, const int32_t* triples, int64_t T, int64_t first_row, int64_t B,
+                    int64_t n_steps, const int32_t* id_to_type, const int64_t* type_offsets, int32_t n_types,
+                    const int32_t* type_ids, uint64_t seed, uint64_t global_step0, int32_t padded_size, int32_t mode,
+                    float margin, float lr0, float decay_steps, float decay_rate, float max_norm, int model, float* loss,
+                    int keep_all_losses, int32_t* neg_ws, void* workspace, size_t workspace_bytes, void** ev_pairs,
+                    int ev_kernel, void* pipe_handle, hipStream_t st);
+size_t train_logloss_ws_bytes(int64_t B, int32_t negs, int32_t d);
+int train_logloss_run(float* table, int64_t N, int32_t d, const int32_t* triples, int64_t T, int64_t first_row, int64_t B,
+                      int64_t n_steps, const int32_t* id_to_type, const int64_t* type_offsets, int32_t n_types,
+                      const int32_t* type_ids, uint64_t seed, uint64_t global_step0, int32_t padded_size, int32_t mode,
+                      int32_t negs, float l2, float lr0, float decay_steps, float decay_rate, float max_norm, float* loss,
+                      int keep_all_losses, int32_t* neg_ws, void* workspace, size_t workspace_bytes, void* pipe_handle,
+                      hipStream_t st);
+size_t train_prepare_bytes(int64_t B, int64_t n_steps);
+int train_prepare_run(const int32_t* triples, int64_t T, int64_t first_row, int64_t B, int64_t n_steps,
+                      const int32_t* id_to_type, int64_t N, const int64_t* type_offsets, int32_t n_types,
+                      const int32_t* type_ids, uint64_t seed, uint64_t global_step0, int32_t padded_size, int32_t mode,
+                      int direct, int32_t* out, hipStream_t st);
+void train_prepared_layout(int64_t B, int64_t* out);
+int pipeline_create(void** out);
+int pipeline_reset(void* h);
+int pipeline_destroy(void* h);
+
+// ge_shard.hip: the row-sharded step's requester and owner planners
+size_t shard_plan_scratch_bytes(int64_t B, int64_t S);
+int shard_plan_launch(const int32_t* pos, const int32_t* neg, int64_t S, int64_t B, int64_t N, int32_t G, int32_t rank,
+                      int32_t* records, int32_t* pos_src, int32_t* neg_src, int32_t* req_row, int32_t* counts,
+                      void* scratch, int peer, hipStream_t st);
+int shard_grad_launch(float* shard, int32_t d, const float* staged, const int32_t* pos_src, const int32_t* neg_src,
+                      const int32_t* record, int32_t R, int64_t B, float margin, float lr, float max_norm, int spectral,
+                      float* loss, int32_t* gidx, float* gval, float* gsum, const float* const* peers, int n_peers,
+                      hipStream_t st, hipEvent_t e0, hipEvent_t e1);
+int shard_apply_launch(float* shard, int32_t d, const int32_t* record, int64_t B, const int32_t* gidx, const float* gval,
+                       int32_t R, float* gsum, hipStream_t st, hipEvent_t e0, hipEvent_t e1);
+int64_t shard_owner_record_words(int64_t cap);
+size_t shard_owner_scratch_bytes(int64_t cap, int64_t S);
+int shard_owner_plan_launch(const int32_t* req_all, const int64_t* req_start, int64_t S, int64_t cap, int32_t rows_local,
+                            int32_t* records, void* scratch, hipStream_t st);
+int shard_owner_apply_launch(float* shard, int32_t d, const int32_t* record, int64_t cap, const float* recv, hipStream_t st);
+
+// ge_transx.hip: TransE / TransH / TransD scoring, hinge steps, sampler and native loop
+int transx_max_dim();
+size_t transx_ws_bytes(int64_t E, int64_t R, int32_t d, int64_t B);
+int transx_score_launch(int model, int l1, const float* ent, int64_t E, const float* rel, int64_t R, const float* normal,
+                        const float* ent_transfer, const float* rel_transfer, int32_t d, const int32_t* tri, int64_t B,
+                        float* out, hipStream_t st);
+int transx_hinge_step_run(int model, int l1, float* ent, int64_t E, float* rel, int64_t R, float* normal,
+                          float* ent_transfer, float* rel_transfer, int32_t d, const int32_t* pos, const int32_t* neg,
+                          int64_t B, float margin, float lr, float* loss, void* workspace, size_t workspace_bytes,
+                          hipStream_t st);
+int transx_draw_launch(const int32_t* triples, int64_t T, int64_t B, const int64_t* bh_key, const int32_t* bh_ent,
+                       const int64_t* bt_key, const int32_t* bt_ent, int64_t n_known, const uint32_t* tail_threshold,
+                       int32_t n_rel, int32_t n_ent, uint64_t seed, uint64_t step, int32_t* pos, int32_t* neg,
+                       hipStream_t st);
+int transx_train_steps_run(int model, int l1, float* ent, int64_t E, float* rel, int64_t R, float* normal,
+                           float* ent_transfer, float* rel_transfer, int32_t d, const int32_t* triples, int64_t T,
+                           const int64_t* bh_key, const int32_t* bh_ent, const int64_t* bt_key, const int32_t* bt_ent,
+                           int64_t n_known, const uint32_t* tail_threshold, uint64_t seed, uint64_t first_step,
+                           int64_t n_steps, int64_t B, float margin, float lr, float* losses, void* workspace,
+                           size_t workspace_bytes, hipStream_t st);
+
+}  // namespace ge

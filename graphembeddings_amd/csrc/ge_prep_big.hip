@@ -18,6 +18,7 @@
 // Everything is integer work off the training stream's critical path (the look-ahead pipeline runs it on
 // the side stream one chunk of steps ahead).
 #include "ge_prep.h"
+#include "ge_launch.h"
 #include <algorithm>
 
 namespace ge {
@@ -387,9 +388,9 @@ static unsigned* sort_scratch_limit(void* scratch, int64_t n, int64_t n_sub, int
 unsigned long long* sort_scratch_keys(void* scratch) { return reinterpret_cast<unsigned long long*>(scratch); }
 
 // stable LSD radix sort of the keys in scratch (as written by a key kernel) on their row field (< n_rows);
-// returns the array that holds the result
-const unsigned long long* sort_tiles_launch(void* scratch, int64_t n, int64_t n_sub, int64_t P, int64_t n_rows, hipStream_t st,
-                                            const unsigned* limit) {
+// *sorted: the array that holds the result
+int sort_tiles_launch(void* scratch, int64_t n, int64_t n_sub, int64_t P, int64_t n_rows, hipStream_t st,
+                      const unsigned* limit, const unsigned long long** sorted) {
   const SortBits sb = sort_bits_for(n_rows);
   const size_t keys_bytes = align_up_sz(sizeof(unsigned long long) * (size_t)n * (size_t)n_sub * (size_t)P, 256);
   unsigned long long* ka = reinterpret_cast<unsigned long long*>(scratch);
@@ -397,15 +398,17 @@ const unsigned long long* sort_tiles_launch(void* scratch, int64_t n, int64_t n_
   unsigned* hist = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(scratch) + 2 * keys_bytes);
   const dim3 grid((unsigned)n, (unsigned)n_sub), block(kPrepThreads);
   const size_t lds = sizeof(unsigned long long) * (size_t)P;      // the tile in digit order (128 KiB at P = 16,384)
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(prep_big_scatter_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          140 * 1024) != hipSuccess) return nullptr;
+  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(prep_big_scatter_kernel),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024);
+  if (e != hipSuccess) return (int)e;
   for (int pass = 0; pass < sb.n_pass; ++pass) {
     const int shift = 32 + pass * sb.bits;
     hipLaunchKernelGGL(prep_big_hist_kernel, grid, block, 0, st, ka, (int)P, (int)n_sub, shift, sb.bits, hist, limit);
     hipLaunchKernelGGL(prep_big_scatter_kernel, grid, block, lds, st, ka, kb, hist, (int)P, (int)n_sub, shift, sb.bits, limit);
     unsigned long long* t = ka; ka = kb; kb = t;
   }
-  return ka;
+  *sorted = ka;
+  return launch_status();
 }
 
 int items_launch(const unsigned long long* sorted, int64_t n, const TileGeom& G, int direct, int32_t* out, const ShardOut* so,
@@ -435,7 +438,9 @@ int relation_order_launch(const int32_t* triples, int64_t T, int64_t first_row, 
   if (hipMemsetAsync(limit, 0, sizeof(unsigned), st) != hipSuccess) return launch_status();
   hipLaunchKernelGGL(order_keys_kernel, dim3((unsigned)n, (unsigned)n_o), dim3(kPrepThreads), 0, st, triples, T, first_row, B,
                      s0, N, n_o, sort_scratch_keys(scratch), limit);
-  const unsigned long long* sorted = sort_tiles_launch(scratch, n, n_o, kOrderP, N + 1, st, limit);
+  const unsigned long long* sorted;
+  const int rc = sort_tiles_launch(scratch, n, n_o, kOrderP, N + 1, st, limit, &sorted);
+  if (rc) return rc;
   const int gy = (int)std::min<int64_t>((B + kPrepThreads - 1) / kPrepThreads, 64);
   hipLaunchKernelGGL(order_write_kernel, dim3((unsigned)n, (unsigned)gy), dim3(kPrepThreads), 0, st, sorted, n_o, B, stride,
                      off_order, out);
@@ -455,8 +460,10 @@ int prepare_big_launch(const int32_t* triples, int64_t T, int64_t first_row, int
   const dim3 grid((unsigned)n, (unsigned)L.n_sub), block(kPrepThreads);
   hipLaunchKernelGGL(prep_big_keys_kernel, grid, block, 0, st, triples, T, first_row, B, s0, id_to_type, N, type_offsets,
                      n_types, type_ids, seed, global_step0, padded_size, mode, direct, negs, out, sort_scratch_keys(scratch));
-  const unsigned long long* sorted = sort_tiles_launch(scratch, n, L.n_sub, L.P, N, st, nullptr);
-  const int rc = items_launch(sorted, n, geom_of(L), direct, out, nullptr, st);
+  const unsigned long long* sorted;
+  int rc = sort_tiles_launch(scratch, n, L.n_sub, L.P, N, st, nullptr, &sorted);
+  if (rc) return rc;
+  rc = items_launch(sorted, n, geom_of(L), direct, out, nullptr, st);
   if (rc || L.off_order < 0) return rc;
   return relation_order_launch(triples, T, first_row, B, s0, n, N, out, L.stride, L.off_order, scratch, st);
 }

@@ -21,6 +21,7 @@
 // LDS; a thread per row pop-counts it (raw), and the tile's (row, col) list of known-true candidates,
 // prepared by the host, is looked up in the same mask (filtered).
 #include "ge_rank_dev.h"
+#include "ge_launch.h"
 
 namespace ge {
 

@@ -32,6 +32,7 @@
 #include <type_traits>
 
 #include "ge_rank_dev.h"
+#include "ge_launch.h"
 
 #ifndef GE_PIPE_GRID_M
 #define GE_PIPE_GRID_M 2   // workgroups per CU (each CU holds one at a time): equal shares, two rounds

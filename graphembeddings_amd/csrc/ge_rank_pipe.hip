@@ -28,6 +28,7 @@
 #include <type_traits>
 
 #include "ge_rank_dev.h"
+#include "ge_launch.h"
 
 #ifndef GE_PIPE_GRID_M
 #define GE_PIPE_GRID_M 2   // workgroups per CU (each CU holds one at a time): equal shares, two rounds
@@ -551,8 +552,25 @@ int pipe_launch_cw(const float* table, int64_t N, int32_t d, const int32_t* hr, 
 
 }  // namespace
 
-int sweep_pipe_launch(const float*, int64_t, int32_t, const int32_t*, int64_t, const int32_t*, const int32_t*, int64_t, float,
-                      int, const int32_t*, const uint16_t*, int32_t*, int32_t*, float*, float*, int, int, int, const void*, hipStream_t);
+static int sweep_pipe_launch(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* true_id,
+                             const int32_t* cand, int64_t K, float max_norm, int cand_is_head, const int32_t* known_off,
+                             const uint16_t* known_rc, int32_t* raw_cnt, int32_t* skip_cnt, float* true_loss,
+                             float* scores_out, int spec, int scores_only, int sweep_flags, const void* planes_ws,
+                             hipStream_t st) {
+  {   // embedding_dim % 8 == 0 in 56 ... 288, max_norm <= 8: the split-precision sweep (ge_rank_f16.hip)
+    const int rc = sweep_f16_launch(table, N, d, hr, B, true_id, cand, K, max_norm, cand_is_head, known_off, known_rc, raw_cnt,
+                                    skip_cnt, true_loss, scores_out, spec, scores_only, sweep_flags, planes_ws, st);
+    if (rc != GE_ENOTSUP) return rc;
+  }
+#define GE_PIPE(CW)                                                                                                  \
+  return pipe_launch_cw<CW>(table, N, d, hr, B, true_id, cand, K, max_norm, cand_is_head, known_off, known_rc, raw_cnt, \
+                            skip_cnt, true_loss, scores_out, spec, scores_only, sweep_flags, st)
+  if (d % 40 == 0) GE_PIPE(40);
+  if (d % 32 == 0) GE_PIPE(32);
+  if (d % 24 == 0) GE_PIPE(24);
+#undef GE_PIPE
+  return GE_ENOTSUP;
+}
 
 int rank_pipe_launch(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* true_id,
                      const int32_t* cand, int64_t K, float max_norm, int cand_is_head, const int32_t* known_off,
@@ -567,25 +585,6 @@ int score_pipe_launch(const float* table, int64_t N, int32_t d, const int32_t* h
                       int64_t K, float max_norm, int apply_sigmoid, int cand_is_head, float* out, hipStream_t st) {
   return sweep_pipe_launch(table, N, d, hr, B, nullptr, cand, K, max_norm, cand_is_head, nullptr, nullptr, nullptr, nullptr,
                            nullptr, out, 0, 1, apply_sigmoid ? 1 : 0, nullptr, st);
-}
-
-int sweep_pipe_launch(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* true_id,
-                      const int32_t* cand, int64_t K, float max_norm, int cand_is_head, const int32_t* known_off,
-                      const uint16_t* known_rc, int32_t* raw_cnt, int32_t* skip_cnt, float* true_loss,
-                      float* scores_out, int spec, int scores_only, int sweep_flags, const void* planes_ws, hipStream_t st) {
-  {   // embedding_dim % 8 == 0 in 56 ... 288, max_norm <= 8: the split-precision sweep (ge_rank_f16.hip)
-    const int rc = sweep_f16_launch(table, N, d, hr, B, true_id, cand, K, max_norm, cand_is_head, known_off, known_rc, raw_cnt,
-                                    skip_cnt, true_loss, scores_out, spec, scores_only, sweep_flags, planes_ws, st);
-    if (rc != GE_ENOTSUP) return rc;
-  }
-#define GE_PIPE(CW)                                                                                                  \
-  return pipe_launch_cw<CW>(table, N, d, hr, B, true_id, cand, K, max_norm, cand_is_head, known_off, known_rc, raw_cnt, \
-                            skip_cnt, true_loss, scores_out, spec, scores_only, sweep_flags, st)
-  if (d % 40 == 0) GE_PIPE(40);
-  if (d % 32 == 0) GE_PIPE(32);
-  if (d % 24 == 0) GE_PIPE(24);
-#undef GE_PIPE
-  return GE_ENOTSUP;
 }
 
 }  // namespace ge

@@ -2,6 +2,7 @@
 // corruption sampler (holE.py:97-140 fused with the host resample of holE.py:343-347).
 #include "ge_common.h"
 #include "ge_bernoulli_dev.h"
+#include "ge_launch.h"
 
 namespace ge {
 

@@ -18,22 +18,9 @@
 // receive buffer) and sorted per step, give the work items that add the received gradient sums to the shard --
 // again one read-modify-write per distinct row, in a fixed order.
 #include "ge_prep.h"
+#include "ge_launch.h"
 
 namespace ge {
-
-int shard_hinge_grad_launch(float*, int32_t, const float*, const int32_t*, const int32_t*, const int32_t*, int32_t, int64_t,
-                            float, float, float, float*, int32_t*, float*, float*, int, hipStream_t, hipEvent_t, hipEvent_t,
-                            const int32_t*, const float* const*, int);
-int apply_items_launch(float*, int, const TileGeom&, const int32_t*, const int32_t*, const float*, int, float*, hipStream_t,
-                       hipEvent_t, hipEvent_t, int det);
-size_t sort_scratch_bytes(int64_t n, int64_t n_sub, int64_t P);
-unsigned long long* sort_scratch_keys(void* scratch);
-const unsigned long long* sort_tiles_launch(void* scratch, int64_t n, int64_t n_sub, int64_t P, int64_t n_rows, hipStream_t st,
-                                            const unsigned* limit = nullptr);
-int items_launch(const unsigned long long* sorted, int64_t n, const TileGeom& G, int direct, int32_t* out, const ShardOut* so,
-                 hipStream_t st);
-int relation_order_launch(const int32_t* triples, int64_t T, int64_t first_row, int64_t B, int64_t s0, int64_t n, int64_t N,
-                          int32_t* out, int64_t stride, int64_t off_order, void* scratch, hipStream_t st);
 
 // ---------------------------------------------------------------- requester: keys
 // grid (S, tiles).  neg must differ from pos in at most one of (head, tail) -- what ge_corrupt_batch produces;
@@ -142,10 +129,12 @@ int shard_plan_launch(const int32_t* pos, const int32_t* neg, int64_t S, int64_t
   if (e != hipSuccess) return (int)e;
   hipLaunchKernelGGL(shard_keys_kernel, grid, block, 0, st, pos, neg, B, N, G, rank, R, L, records, pos_src, neg_src,
                      sort_scratch_keys(scratch));
-  const unsigned long long* sorted = sort_tiles_launch(scratch, S, L.n_sub, L.P, (int64_t)R * (G + 1), st);
+  const unsigned long long* sorted;
+  int rc = sort_tiles_launch(scratch, S, L.n_sub, L.P, (int64_t)R * (G + 1), st, nullptr, &sorted);
+  if (rc) return rc;
   hipLaunchKernelGGL(shard_heads_kernel, grid, block, 0, st, sorted, (int)L.P, (int)L.n_sub, R, G, rank, tile_heads, counts);
   const ShardOut so{R, B, pos_src, neg_src, req_row, tile_heads, peer ? 1 : 0};
-  const int rc = items_launch(sorted, S, geom_of(L), /*direct=*/1, records, &so, st);
+  rc = items_launch(sorted, S, geom_of(L), /*direct=*/1, records, &so, st);
   if (rc || L.off_order < 0) return rc;
   return relation_order_launch(pos, 0, 0, B, 0, S, N, records, L.stride, L.off_order, scratch, st);
 }
@@ -178,7 +167,9 @@ int shard_owner_plan_launch(const int32_t* req_all, const int64_t* req_start, in
   const dim3 grid((unsigned)S, (unsigned)n_sub), block(kPrepThreads);
   hipLaunchKernelGGL(owner_keys_kernel, grid, block, 0, st, req_all, req_start, kOwnerP, n_sub, rows_local,
                      sort_scratch_keys(scratch));
-  const unsigned long long* sorted = sort_tiles_launch(scratch, S, n_sub, kOwnerP, rows_local, st);
+  const unsigned long long* sorted;
+  const int rc = sort_tiles_launch(scratch, S, n_sub, kOwnerP, rows_local, st, nullptr, &sorted);
+  if (rc) return rc;
   return items_launch(sorted, S, geom_plain(kOwnerP, n_sub), /*direct=*/0, records, nullptr, st);
 }
 

@@ -13,6 +13,7 @@
 // 40 k FMA at d = 200 -- the whole FB15k table is ~0.7 GFLOP, a few tens of microseconds, paid once
 // per ge_train_steps call (model 1) or once per training run (model 2, table kept spectral).
 #include "ge_common.h"
+#include "ge_launch.h"
 
 namespace ge {
 

@@ -26,17 +26,10 @@
 // where the previous one stopped finds its records already built.  Without a handle the launches go
 // to the caller's stream (one ~20 us launch per chunk of steps) and the library keeps no state at all.
 #include "ge_prep.h"
+#include "ge_launch.h"
 #include <cmath>
 
 namespace ge {
-
-int complex_hinge_grad_launch(const float*, int64_t, int32_t, const int32_t*, const int32_t*, int64_t, float, float, float, float*, int32_t*, float*, hipStream_t, hipEvent_t = nullptr, hipEvent_t = nullptr, const int32_t* slot_item = nullptr, float* table_rw = nullptr, int spectral = 0, const int32_t* order = nullptr);
-int hole_hinge_grad_launch(const float*, int64_t, int32_t, const int32_t*, const int32_t*, int64_t, float, float, float, float*, int32_t*, float*, hipStream_t, hipEvent_t = nullptr, hipEvent_t = nullptr);
-int scatter_add_rows_launch(float*, int64_t, int32_t, const int32_t*, const float*, int64_t, hipStream_t, hipEvent_t = nullptr, hipEvent_t = nullptr);
-int corrupt_batch_launch(const int32_t*, int64_t, const int32_t*, int64_t, const int64_t*, int32_t, const int32_t*, uint64_t, uint64_t, int32_t, int32_t, int32_t*, hipStream_t);
-int hole_spectral_launch(float*, int64_t, int32_t, int, hipStream_t);
-size_t prep_big_scratch_bytes(int64_t B, int64_t negs, int64_t n);
-int prepare_big_launch(const int32_t*, int64_t, int64_t, int64_t, int64_t, int64_t, const int32_t*, int64_t, const int64_t*, int32_t, const int32_t*, uint64_t, uint64_t, int32_t, int32_t, int, int32_t*, void*, hipStream_t, int);
 
 // grid (steps in the chunk, n_sub).  LDS: keys[P] (8 B) | hist[16 waves x 256 digits] | wtot[32].
 __global__ __launch_bounds__(kPrepThreads) void train_prepare_kernel(
@@ -629,7 +622,7 @@ size_t hinge_ws_bytes(int64_t B, int32_t d) {
   return align_up_sz(sizeof(int32_t) * 6 * (size_t)B, 256) + align_up_sz(sizeof(float) * 6 * (size_t)B * (size_t)d, 256);
 }
 
-bool train_fast_ok(int64_t B, int32_t d) { return B >= 1 && B <= (int64_t)1 << 24 && d <= 1024; }
+static bool train_fast_ok(int64_t B, int32_t d) { return B >= 1 && B <= (int64_t)1 << 24 && d <= 1024; }
 
 // steps prepared per launch: 32 at B <= 4096 (one record is ~1.2 MB there), fewer for large batches
 static int64_t prep_chunk_steps(int64_t B, int64_t negs = 0) {
@@ -968,10 +961,6 @@ size_t train_logloss_ws_bytes(int64_t B, int32_t negs, int32_t d) {
   return 256 + align_up_sz(sizeof(int32_t) * 3 * M, 256) + ring * region + 2 * prep_chunk_bytes(B, negs) +
          prep_big_scratch_bytes(B, negs, prep_chunk_steps(B, negs));
 }
-
-int complex_logloss_grad_launch(const float*, int64_t, int32_t, const int32_t*, const float*, int64_t, float, float, float, const float*, float*, int32_t*, float*, hipStream_t, const int32_t*, int64_t, float, float, hipEvent_t, hipEvent_t);
-int table_sumsq_launch(const float*, int64_t, float*, hipStream_t);
-int table_scale_launch(float*, int64_t, float, hipStream_t);
 
 int train_logloss_run(float* table, int64_t N, int32_t d, const int32_t* triples, int64_t T, int64_t first_row,
                       int64_t B, int64_t n_steps, const int32_t* id_to_type, const int64_t* type_offsets,

@@ -27,6 +27,7 @@
 
 #include "ge_common.h"
 #include "ge_bernoulli_dev.h"
+#include "ge_launch.h"
 
 namespace ge {
 

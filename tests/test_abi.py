@@ -15,6 +15,37 @@ def _declared():
     return sorted(set(re.findall(r"\b(ge_[a-z0-9_A-Z]+)\s*\(", src)))
 
 
+def _prototypes():
+    """{name: (return type, [argument types])} of every ge_* prototype in ge_hip.h; a pointer is "*"."""
+    src = open(os.path.join(ROOT, "include", "ge_hip.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    protos = {}
+    for ret, name, args in re.findall(r"^\s*([a-z_0-9]+)\s+(ge_[a-z0-9_A-Z]+)\s*\(([^)]*)\)\s*;", src, flags=re.M):
+        args = [a.strip() for a in args.split(",")] if args.strip() != "void" else []
+        # "const int32_t* pos" -> "*", "int64_t N" -> "int64_t"
+        protos[name] = (ret, ["*" if "*" in a else a.replace("const ", "").split()[0] for a in args])
+    return protos
+
+
+def test_ctypes_table_matches_header_prototypes():
+    """_lib.SYMBOLS passes every argument with the C type ge_hip.h gives it (a width mismatch would pass garbage)."""
+    from graphembeddings_amd import _lib
+    scalar = {"int": {ctypes.c_int, ctypes.c_int32}, "int32_t": {ctypes.c_int, ctypes.c_int32},
+              "int64_t": {ctypes.c_int64}, "uint64_t": {ctypes.c_uint64}, "uint32_t": {ctypes.c_uint32},
+              "size_t": {ctypes.c_size_t}, "float": {ctypes.c_float}}
+    protos = _prototypes()
+    assert set(protos) == set(_declared()), "prototype parser missed a declaration"
+    for name, (ret, args) in protos.items():
+        res, argtypes = _lib.SYMBOLS[name]
+        assert res in scalar[ret], f"{name}: returns {ret}, ctypes restype {res.__name__}"
+        assert len(argtypes) == len(args), f"{name}: {len(args)} arguments in ge_hip.h, {len(argtypes)} in SYMBOLS"
+        for i, (c, py) in enumerate(zip(args, argtypes)):
+            if c == "*":
+                assert py is ctypes.c_void_p or issubclass(py, ctypes._Pointer), f"{name} argument {i}: pointer"
+            else:
+                assert py in scalar[c], f"{name} argument {i}: {c} in ge_hip.h, {py.__name__} in SYMBOLS"
+
+
 def test_header_declares_expected_entry_points():
     names = _declared()
     for must in ("ge_complex_score", "ge_hole_score", "ge_complex_hinge_step", "ge_hole_hinge_step",
