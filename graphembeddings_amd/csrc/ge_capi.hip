@@ -301,6 +301,67 @@ int ge_transx_train_steps(int model, int l1, float* ent, int64_t n_ent, float* r
                                 margin, lr, losses, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
+// ---------------------------------------------------------------- TransR
+// tables present and 4-byte aligned, dimensions in range, entity and relation ids fit the sorts' 32-bit keys
+static inline int transr_tables_ok(const void* ent, int64_t E, const void* rel, const void* rel_matrix, int64_t R,
+                                   int32_t dE, int32_t dR) {
+  if (!ent || !rel || !rel_matrix || E <= 0 || R <= 0 || E >= ((int64_t)1 << 31) || R >= ((int64_t)1 << 31))
+    return GE_EINVAL;
+  if (dE <= 0 || dR <= 0) return GE_EINVAL;
+  if (dE > transr_max_dim() || dR > transr_max_dim()) return GE_ENOTSUP;
+  for (const void* p : {ent, rel, rel_matrix})
+    if (!aligned4(p)) return GE_EINVAL;
+  return 0;
+}
+// 4B entity slots and every sorted position fit an int32
+static inline bool transr_batch_ok(int64_t B) { return B > 0 && B <= ((int64_t)1 << 28); }
+static inline bool adam_ok(float b1, float b2, float eps, int64_t t, const void* m, const void* v) {
+  return b1 >= 0.f && b1 < 1.f && b2 >= 0.f && b2 < 1.f && eps >= 0.f && t >= 1 && m && v && aligned4(m) && aligned4(v);
+}
+
+int ge_transr_max_dim(void) { return transr_max_dim(); }
+
+int ge_transr_score(int l1, const float* ent, int64_t n_ent, const float* rel, const float* rel_matrix, int64_t n_rel,
+                    int32_t dim_e, int32_t dim_r, const int32_t* triples, int64_t B, float* out, void* stream) {
+  if (int rc = transr_tables_ok(ent, n_ent, rel, rel_matrix, n_rel, dim_e, dim_r)) return rc;
+  if (B < 0) return GE_EINVAL;
+  if (B > 0 && (!triples || !out || !aligned4(triples) || !aligned4(out))) return GE_EINVAL;
+  return transr_score_launch(l1, ent, n_ent, rel, rel_matrix, n_rel, dim_e, dim_r, triples, B, out, (hipStream_t)stream);
+}
+
+size_t ge_transr_step_workspace_bytes(int64_t n_ent, int64_t n_rel, int32_t dim_e, int32_t dim_r, int64_t B) {
+  if (n_ent <= 0 || n_rel <= 0 || n_ent >= ((int64_t)1 << 31) || n_rel >= ((int64_t)1 << 31)) return 0;
+  if (dim_e <= 0 || dim_r <= 0 || dim_e > transr_max_dim() || dim_r > transr_max_dim() || !transr_batch_ok(B)) return 0;
+  return transr_ws_bytes(n_ent, n_rel, dim_e, dim_r, B);
+}
+
+int ge_transr_adam_step(int l1, float* ent, int64_t n_ent, float* rel, float* rel_matrix, int64_t n_rel, int32_t dim_e,
+                        int32_t dim_r, float* m, float* v, const int32_t* pos, const int32_t* neg, int64_t B,
+                        float margin, float lr, float b1, float b2, float eps, int64_t t, float* loss, void* workspace,
+                        size_t workspace_bytes, void* stream) {
+  if (int rc = transr_tables_ok(ent, n_ent, rel, rel_matrix, n_rel, dim_e, dim_r)) return rc;
+  if (!transr_batch_ok(B) || !pos || !neg || !loss || !workspace || !adam_ok(b1, b2, eps, t, m, v)) return GE_EINVAL;
+  if (!aligned4(pos) || !aligned4(neg) || !aligned4(loss) || ((uintptr_t)workspace & 255)) return GE_EINVAL;
+  return transr_adam_step_run(l1, ent, n_ent, rel, rel_matrix, n_rel, dim_e, dim_r, m, v, pos, neg, B, margin, lr, b1,
+                              b2, eps, t, loss, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int ge_transr_train_steps(int l1, float* ent, int64_t n_ent, float* rel, float* rel_matrix, int64_t n_rel,
+                          int32_t dim_e, int32_t dim_r, float* m, float* v, const int32_t* triples, int64_t T,
+                          const int64_t* bh_key, const int32_t* bh_ent, const int64_t* bt_key, const int32_t* bt_ent,
+                          int64_t n_known, const uint32_t* tail_threshold, uint64_t seed, uint64_t first_step,
+                          int64_t n_steps, int64_t B, float margin, float lr, float b1, float b2, float eps,
+                          int64_t first_t, float* losses, void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = transr_tables_ok(ent, n_ent, rel, rel_matrix, n_rel, dim_e, dim_r)) return rc;
+  if (!transr_batch_ok(B) || n_steps < 0 || !losses || !workspace || ((uintptr_t)workspace & 255)) return GE_EINVAL;
+  if (!adam_ok(b1, b2, eps, first_t, m, v)) return GE_EINVAL;
+  if (!triples || T <= 0 || T > ((int64_t)1 << 32) || !tail_threshold) return GE_EINVAL;
+  if (n_known < 0 || (n_known > 0 && (!bh_key || !bh_ent || !bt_key || !bt_ent))) return GE_EINVAL;
+  return transr_train_steps_run(l1, ent, n_ent, rel, rel_matrix, n_rel, dim_e, dim_r, m, v, triples, T, bh_key, bh_ent,
+                                bt_key, bt_ent, n_known, tail_threshold, seed, first_step, n_steps, B, margin, lr, b1,
+                                b2, eps, first_t, losses, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
 int ge_complex_score_1vK(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B,
                          const int32_t* cand, int64_t K, float max_norm, int apply_sigmoid, int cand_is_head,
                          float* out, void* stream) {

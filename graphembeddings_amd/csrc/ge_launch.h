@@ -182,4 +182,20 @@ int transx_train_steps_run(int model, int l1, float* ent, int64_t E, float* rel,
                            int64_t n_steps, int64_t B, float margin, float lr, float* losses, void* workspace,
                            size_t workspace_bytes, hipStream_t st);
 
+// ge_transr.hip: TransR scoring, Adam steps and native loop
+int transr_max_dim();
+size_t transr_ws_bytes(int64_t E, int64_t R, int32_t dE, int32_t dR, int64_t B);
+int transr_score_launch(int l1, const float* ent, int64_t E, const float* rel, const float* rel_matrix, int64_t R,
+                        int32_t dE, int32_t dR, const int32_t* tri, int64_t B, float* out, hipStream_t st);
+int transr_adam_step_run(int l1, float* ent, int64_t E, float* rel, float* rel_matrix, int64_t R, int32_t dE,
+                         int32_t dR, float* m, float* v, const int32_t* pos, const int32_t* neg, int64_t B,
+                         float margin, float lr, float b1, float b2, float eps, int64_t t, float* loss,
+                         void* workspace, size_t workspace_bytes, hipStream_t st);
+int transr_train_steps_run(int l1, float* ent, int64_t E, float* rel, float* rel_matrix, int64_t R, int32_t dE,
+                           int32_t dR, float* m, float* v, const int32_t* triples, int64_t T, const int64_t* bh_key,
+                           const int32_t* bh_ent, const int64_t* bt_key, const int32_t* bt_ent, int64_t n_known,
+                           const uint32_t* tail_threshold, uint64_t seed, uint64_t first_step, int64_t n_steps,
+                           int64_t B, float margin, float lr, float b1, float b2, float eps, int64_t first_t,
+                           float* losses, void* workspace, size_t workspace_bytes, hipStream_t st);
+
 }  // namespace ge

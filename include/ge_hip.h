@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define GE_VERSION 330 /* 0.3.3: + ge_transx_* (TransE / TransH / TransD scoring, hinge SGD step and native loop) */
+#define GE_VERSION 340 /* 0.3.4: + ge_transr_* (TransR scoring, hinge Adam step and native loop) */
 
 /* argument errors (negative, -errno style) */
 #define GE_EINVAL (-22)  /* bad dimension / null pointer / misaligned buffer */
@@ -235,6 +235,41 @@ int ge_transx_train_steps(int model, int l1, float* ent, int64_t n_ent, float* r
                           int64_t n_known, const uint32_t* tail_threshold, uint64_t seed, uint64_t first_step,
                           int64_t n_steps, int64_t B, float margin, float lr, float* losses, void* workspace,
                           size_t workspace_bytes, void* stream);
+
+/* --- TransR (transR.py).  Row-major fp32 tables: ent [n_ent,dim_e], rel [n_rel,dim_r] and rel_matrix
+ * [n_rel, dim_r*dim_e], whose row r read as [dim_r][dim_e] is M_r.  Triples are int32 [B,3] (h, t, r).
+ *   u = M_r (h - t) + r (one mat-vec on the difference), D = sum_k |u_k| (l1 != 0) or sum_k u_k^2 (l1 = 0).
+ * 1 <= dim_e, dim_r <= ge_transr_max_dim() (256); dim_e and dim_r % 4 == 0 with 16-byte aligned buffers takes the
+ * vectorised path.  Adam state: m and v are two flat fp32 buffers of n_ent*dim_e + n_rel*dim_r + n_rel*dim_r*dim_e
+ * floats each, laid out [ent | rel | rel_matrix] in the tables' own row-major order; zero them before step t = 1. */
+int ge_transr_max_dim(void);
+/* out[i] = D of triple i ([B] fp32); NaN for a triple with an id out of range. */
+int ge_transr_score(int l1, const float* ent, int64_t n_ent, const float* rel, const float* rel_matrix, int64_t n_rel,
+                    int32_t dim_e, int32_t dim_r, const int32_t* triples, int64_t B, float* out, void* stream);
+/* Workspace of one Adam step / of ge_transr_train_steps for B pairs (the same size serves both). */
+size_t ge_transr_step_workspace_bytes(int64_t n_ent, int64_t n_rel, int32_t dim_e, int32_t dim_r, int64_t B);
+/* One step of tf.train.AdamOptimizer (transR.py:88) on loss = sum_i max(D(pos_i) - D(neg_i) + margin, 0), t >= 1
+ * the 1-based step.  Gradients on the pre-step tables with TF's rules (a pair is active iff D+ - D- + margin >= 0;
+ * d|x|/dx = sign(x) with sign(0) = 0); neg_i must keep pos_i's relation, a pair with an id out of range or
+ * neg_r != pos_r is skipped.  Duplicate rows are summed first (TF 1.x deduplicates IndexedSlices before its sparse
+ * Adam), so v receives (1-b2) (sum g)^2.  Then on EVERY element of the three tables, g = 0 where the batch did not
+ * touch the row:  m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2;  x -= lr_t m / (sqrt(v) + eps),  with
+ * lr_t = lr sqrt(1 - b2^t) / (1 - b1^t) computed in double from t (not a running fp32 product of b1 and b2).
+ * Needs 0 <= b1 < 1, 0 <= b2 < 1, eps >= 0.  *loss (device, one float) = the batch loss before the step.
+ * Bitwise reproducible: no float atomics. */
+int ge_transr_adam_step(int l1, float* ent, int64_t n_ent, float* rel, float* rel_matrix, int64_t n_rel, int32_t dim_e,
+                        int32_t dim_r, float* m, float* v, const int32_t* pos, const int32_t* neg, int64_t B,
+                        float margin, float lr, float b1, float b2, float eps, int64_t t, float* loss, void* workspace,
+                        size_t workspace_bytes, void* stream);
+/* n_steps Adam steps in one call: step s draws its batch as ge_transx_draw_batch(.., seed, first_step + s, ..) and
+ * runs ge_transr_adam_step on it with t = first_t + s; losses[s] (device) = its batch loss.  No host
+ * synchronisation inside. */
+int ge_transr_train_steps(int l1, float* ent, int64_t n_ent, float* rel, float* rel_matrix, int64_t n_rel,
+                          int32_t dim_e, int32_t dim_r, float* m, float* v, const int32_t* triples, int64_t T,
+                          const int64_t* bh_key, const int32_t* bh_ent, const int64_t* bt_key, const int32_t* bt_ent,
+                          int64_t n_known, const uint32_t* tail_threshold, uint64_t seed, uint64_t first_step,
+                          int64_t n_steps, int64_t B, float margin, float lr, float b1, float b2, float eps,
+                          int64_t first_t, float* losses, void* workspace, size_t workspace_bytes, void* stream);
 
 /* --- 1-vs-K candidate scoring (the inference loop of holE.py:564-569: fixed (head, relation)
  * against many tails; also K shared negatives per positive).  hr: [B,2] int32 (fixed entity,
