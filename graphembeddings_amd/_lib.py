@@ -89,6 +89,12 @@ SYMBOLS = {
                                       _f, _f, _i64, _p, _p, _sz, _p]),
     "ge_transr_train_steps": (C.c_int, [C.c_int, _p, _i64, _p, _p, _i64, _i32, _i32, _p, _p, _p, _i64, _p, _p, _p, _p,
                                         _i64, _p, _u64, _u64, _i64, _i64, _f, _f, _f, _f, _f, _i64, _p, _p, _sz, _p]),
+    "ge_transx_rank_workspace_bytes": (_sz, [C.c_int, _i64, _i64, _i32, _i64]),
+    "ge_transx_rank": (C.c_int, [C.c_int, C.c_int, _p, _i64, _p, _i64, _p, _p, _p, _i32, _p, _i64, C.c_int, _p, _p, _p,
+                                 _p, _p, _p, _p, _sz, _p]),
+    "ge_transr_rank_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32, _i64]),
+    "ge_transr_rank": (C.c_int, [C.c_int, _p, _i64, _p, _p, _i64, _i32, _i32, _p, _i64, C.c_int, _p, _p, _p, _p, _p, _p,
+                                 _p, _sz, _p]),
     "ge_event_create": (C.c_int, [C.POINTER(C.c_void_p)]),
     "ge_event_destroy": (C.c_int, [_p]),
     "ge_event_record": (C.c_int, [_p, _p]),

@@ -362,6 +362,65 @@ int ge_transr_train_steps(int l1, float* ent, int64_t n_ent, float* rel, float* 
                                 b2, eps, first_t, losses, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
+// ---------------------------------------------------------------- translation-model ranks
+// B rows of int32 counters, q rows of the workspace and the sweep's row-chunk grid all fit; the outputs are 4-byte
+// aligned; the known lists come as a pair
+static inline int rank_outputs_ok(int64_t B, const int32_t* triples, const int32_t* known_off, const uint16_t* known_rc,
+                                  const int32_t* n_before, const int32_t* n_known_before, const float* true_dist,
+                                  const float* scores_out, const void* workspace) {
+  if (B < 0 || B > ((int64_t)1 << 28)) return GE_EINVAL;
+  if ((known_off == nullptr) != (known_rc == nullptr)) return GE_EINVAL;
+  if (B == 0) return 0;
+  if (!triples || !n_before || !n_known_before || !true_dist || !workspace || ((uintptr_t)workspace & 255)) return GE_EINVAL;
+  for (const void* p : {(const void*)triples, (const void*)known_off, (const void*)n_before, (const void*)n_known_before,
+                        (const void*)true_dist, (const void*)scores_out})
+    if (p && !aligned4(p)) return GE_EINVAL;
+  return 0;
+}
+
+size_t ge_transx_rank_workspace_bytes(int model, int64_t n_ent, int64_t n_rel, int32_t d, int64_t B) {
+  if (model < GE_TRANSX_TRANSE || model > GE_TRANSX_TRANSD || n_ent <= 0 || n_rel <= 0 || d <= 0 ||
+      d > transx_max_dim() || B <= 0 || B > ((int64_t)1 << 28))
+    return 0;
+  return transx_rank_ws_bytes(model, n_ent, n_rel, d, B);
+}
+
+int ge_transx_rank(int model, int l1, const float* ent, int64_t n_ent, const float* rel, int64_t n_rel,
+                   const float* normal, const float* ent_transfer, const float* rel_transfer, int32_t d,
+                   const int32_t* triples, int64_t B, int cand_is_head, const int32_t* known_off,
+                   const uint16_t* known_rc, int32_t* n_before, int32_t* n_known_before, float* true_dist,
+                   float* scores_out, void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = transx_tables_ok(model, ent, n_ent, rel, n_rel, normal, ent_transfer, rel_transfer, d)) return rc;
+  if (int rc = rank_outputs_ok(B, triples, known_off, known_rc, n_before, n_known_before, true_dist, scores_out,
+                               workspace))
+    return rc;
+  if (B == 0) return 0;
+  return transx_rank_launch(model, l1, ent, n_ent, rel, n_rel, normal, ent_transfer, rel_transfer, d, triples, B,
+                            cand_is_head, known_off, known_rc, n_before, n_known_before, true_dist, scores_out, workspace,
+                            workspace_bytes, (hipStream_t)stream);
+}
+
+size_t ge_transr_rank_workspace_bytes(int64_t n_ent, int64_t n_rel, int32_t dim_e, int32_t dim_r, int64_t B) {
+  if (n_ent <= 0 || n_rel <= 0 || dim_e <= 0 || dim_r <= 0 || dim_e > transr_max_dim() || dim_r > transr_max_dim() ||
+      B <= 0 || B > ((int64_t)1 << 28))
+    return 0;
+  return transr_rank_ws_bytes(n_ent, n_rel, dim_r, B);
+}
+
+int ge_transr_rank(int l1, const float* ent, int64_t n_ent, const float* rel, const float* rel_matrix, int64_t n_rel,
+                   int32_t dim_e, int32_t dim_r, const int32_t* triples, int64_t B, int cand_is_head,
+                   const int32_t* known_off, const uint16_t* known_rc, int32_t* n_before, int32_t* n_known_before,
+                   float* true_dist, float* scores_out, void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = transr_tables_ok(ent, n_ent, rel, rel_matrix, n_rel, dim_e, dim_r)) return rc;
+  if (int rc = rank_outputs_ok(B, triples, known_off, known_rc, n_before, n_known_before, true_dist, scores_out,
+                               workspace))
+    return rc;
+  if (B == 0) return 0;
+  return transr_rank_launch(l1, ent, n_ent, rel, rel_matrix, n_rel, dim_e, dim_r, triples, B, cand_is_head, known_off,
+                            known_rc, n_before, n_known_before, true_dist, scores_out, workspace, workspace_bytes,
+                            (hipStream_t)stream);
+}
+
 int ge_complex_score_1vK(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B,
                          const int32_t* cand, int64_t K, float max_norm, int apply_sigmoid, int cand_is_head,
                          float* out, void* stream) {

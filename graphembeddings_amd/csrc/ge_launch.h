@@ -198,4 +198,18 @@ int transr_train_steps_run(int l1, float* ent, int64_t E, float* rel, float* rel
                            int64_t B, float margin, float lr, float b1, float b2, float eps, int64_t first_t,
                            float* losses, void* workspace, size_t workspace_bytes, hipStream_t st);
 
+// ge_transx_rank.hip: link-prediction ranks of TransE / TransH / TransD / TransR over every entity
+bool rank_vec4(const float* ent, int32_t d_ent, int32_t d_q);
+size_t transx_rank_ws_bytes(int model, int64_t E, int64_t R, int32_t d, int64_t B);
+size_t transr_rank_ws_bytes(int64_t E, int64_t R, int32_t dR, int64_t B);
+int transx_rank_launch(int model, int l1, const float* ent, int64_t E, const float* rel, int64_t R, const float* normal,
+                       const float* ent_transfer, const float* rel_transfer, int32_t d, const int32_t* tri, int64_t B,
+                       int cand_is_head, const int32_t* known_off, const uint16_t* known_rc, int32_t* n_before,
+                       int32_t* n_known_before, float* true_dist, float* scores_out, void* workspace,
+                       size_t workspace_bytes, hipStream_t st);
+int transr_rank_launch(int l1, const float* ent, int64_t E, const float* rel, const float* rel_matrix, int64_t R,
+                       int32_t dE, int32_t dR, const int32_t* tri, int64_t B, int cand_is_head, const int32_t* known_off,
+                       const uint16_t* known_rc, int32_t* n_before, int32_t* n_known_before, float* true_dist,
+                       float* scores_out, void* workspace, size_t workspace_bytes, hipStream_t st);
+
 }  // namespace ge

@@ -221,3 +221,82 @@ def evaluate_fb15k_style(embeddings: torch.Tensor, data, both_sides: bool = True
         print("raw MRR {raw_mrr:.6f} (mean rank {mean_raw_pos:.1f}); filtered MRR {filtered_mrr:.6f} "
               "(mean rank {mean_filtered_pos:.1f}); hits@1/3/10 {hits1:.2f} / {hits3:.2f} / {hits10:.2f} %".format(**out))
     return out
+
+
+# ------------------------------------------------------------------ translation models (TransE / H / D, TransR)
+def _translation_test(model, test) -> np.ndarray:
+    """The test rows as int64 [n,3] (h, t, r), ids checked against the model's tables on the host."""
+    t = np.asarray(test.cpu().numpy() if isinstance(test, torch.Tensor) else test)
+    if t.ndim != 2 or t.shape[1] != 3:
+        raise ValueError("test triples must have shape [n, 3] (head, tail, relation)")
+    if t.size and not np.issubdtype(t.dtype, np.integer):
+        raise ValueError("test triples must be integer ids")
+    t = t.astype(np.int64)
+    if len(t) and (t[:, :2].min() < 0 or t[:, :2].max() >= model.n_ent or t[:, 2].min() < 0 or t[:, 2].max() >= model.n_rel):
+        raise ValueError(f"a test triple holds an id outside [0, {model.n_ent}) entities / [0, {model.n_rel}) relations")
+    return t
+
+
+@torch.no_grad()
+def translation_ranks(model, test, known=None, side: str = "tail", batch: int = None):
+    """Raw and filtered rank of every test triple's true entity among ALL entities for a TransX or TransR model
+    (int64 arrays, in test order).  side="tail": every entity replaces the tail; "head": the head.  Order: ascending
+    by (D, entity id), as link_prediction_ranks.  known: an [n,3] array of triples to filter, or a KnownIndex built
+    for this side with n_rows = max(n_ent, n_rel) (None: filtered == raw).  The rows are grouped by relation for the
+    sweep (a stable sort on the host) and the ranks returned in the caller's order; a row's ranks do not depend on
+    the grouping.  batch: rows per native call (default 131072)."""
+    if side not in ("tail", "head"):
+        raise ValueError(f"side must be 'tail' or 'head', got {side!r}")
+    test = _translation_test(model, test)
+    dev = model.tables["ent"].device
+    E = model.n_ent
+    n_rows = max(E, model.n_rel)
+    index = known if isinstance(known, KnownIndex) else KnownIndex(known, n_rows, side, dev)
+    if index.n_rows != n_rows:
+        raise ValueError(f"the KnownIndex has n_rows={index.n_rows}, expected max(n_ent, n_rel) = {n_rows}")
+    if batch is None:
+        batch = 1 << 17
+    if batch <= 0:
+        raise ValueError("batch must be positive")
+    raw = np.empty(len(test), dtype=np.int64)
+    fil = np.empty(len(test), dtype=np.int64)
+    if len(test) == 0:
+        return raw, fil
+    order = np.argsort(test[:, 2], kind="stable")       # rows of one relation share the sweep's projection work
+    pos_of = torch.arange(n_rows, dtype=torch.int64, device=dev)   # every entity is a candidate, at its own id
+    pos_of[E:] = -1
+    fixed_col = 0 if side == "tail" else 1
+    for s in range(0, len(test), batch):
+        idx = order[s:s + batch]
+        chunk = torch.as_tensor(test[idx]).to(dev)
+        off, rc = index.cells(chunk[:, fixed_col], chunk[:, 2], pos_of, E)
+        nb, nk, _ = model.rank_counts(chunk, cand_is_head=(side == "head"), known_off=off, known_rc=rc)
+        nb, nk = nb.cpu().numpy().astype(np.int64), nk.cpu().numpy().astype(np.int64)
+        if (nb < 0).any() or (nk < 0).any():
+            raise ValueError("a test triple holds an id outside the model's tables")
+        raw[idx] = nb + 1
+        fil[idx] = nb + 1 - nk
+    return raw, fil
+
+
+def evaluate_translation(model, test, known=None, both_sides: bool = True, batch: int = None, verbose: bool = False) -> dict:
+    """Filtered link prediction of a TransX / TransR model over all entities: mrr_and_hits of the tail ranks (and the
+    head ranks with both_sides) plus `sweeps`, and per side `tail` / `head` dicts of the same numbers.  known: the
+    triples to filter (the Bordes et al. setting filters train + valid + test)."""
+    n_rows = max(model.n_ent, model.n_rel)
+    dev = model.tables["ent"].device
+    per, raw_all, fil_all = {}, [], []
+    for side in ("tail", "head") if both_sides else ("tail",):
+        idx = KnownIndex(None if known is None else np.asarray(known, dtype=np.int64), n_rows, side, dev)
+        raw, fil = translation_ranks(model, test, idx, side=side, batch=batch)
+        per[side] = mrr_and_hits(raw, fil)
+        raw_all.append(raw); fil_all.append(fil)
+    out = mrr_and_hits(np.concatenate(raw_all), np.concatenate(fil_all))
+    out["sweeps"] = int(sum(r.size for r in raw_all))
+    out.update(per)
+    if verbose:
+        for name, m in list(per.items()) + [("both", out)]:
+            print(f"{name}: raw MRR {m['raw_mrr']:.6f} (mean rank {m['mean_raw_pos']:.1f}); filtered MRR "
+                  f"{m['filtered_mrr']:.6f} (mean rank {m['mean_filtered_pos']:.1f}); hits@1/3/10 "
+                  f"{m['hits1']:.2f} / {m['hits3']:.2f} / {m['hits10']:.2f} %")
+    return out

@@ -15,7 +15,7 @@ import torch
 
 from . import _lib
 from .hole import BernoulliSampler, _stream, init_embeddings
-from .transx import _pairs, read_kg  # noqa: F401  (read_kg: the same *2id.txt reader)
+from .transx import _pairs, _rank_call, read_kg, read_triples  # noqa: F401  (the same *2id.txt readers)
 
 TABLES = ("ent", "rel", "rel_matrix")
 MAX_DIM = 256
@@ -104,6 +104,19 @@ class TransR:
                   self._loss.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
         self.t += 1
         return self._loss[0].clone()
+
+    def rank_counts(self, triples: torch.Tensor, cand_is_head: bool = False, known_off: torch.Tensor = None,
+                    known_rc: torch.Tensor = None, return_scores: bool = False):
+        """ge_transr_rank on the [B,3] rows as given: as TransX.rank_counts."""
+        tb = _pairs(triples, "triples")
+        return _rank_call("ge_transr_rank", self._ptrs(), _lib.load().ge_transr_rank_workspace_bytes(
+            self.n_ent, self.n_rel, self.dim_e, self.dim_r, max(tb.shape[0], 1)), self.n_ent, tb, cand_is_head,
+            known_off, known_rc, return_scores)
+
+    def ranks(self, test, known=None, side: str = "tail", batch: int = None):
+        """(raw, filtered) int64 rank arrays of the test triples over every entity: evaluate.translation_ranks."""
+        from .evaluate import translation_ranks
+        return translation_ranks(self, test, known, side=side, batch=batch)
 
     def state_dict(self) -> Dict[str, object]:
         return {"model": "transr", "l1": self.l1, "n_ent": self.n_ent, "n_rel": self.n_rel, "dim_e": self.dim_e,

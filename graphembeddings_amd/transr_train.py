@@ -11,6 +11,8 @@ import argparse
 import os
 import sys
 
+from .transx_train import add_eval_flags, check_eval_args, evaluate_to_json
+
 MAX_DIM = 256           # graphembeddings_amd.transr.MAX_DIM, kept here so that checking flags imports no torch
 
 
@@ -28,7 +30,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--margin", type=float, default=1.0)
     p.add_argument("--learning_rate", type=float, default=0.001)
     p.add_argument("--seed", type=int, default=0)
-    p.add_argument("--output_dir", default=".", help="where transr.pt is written")
+    p.add_argument("--output_dir", default=".", help="where transr.pt (and transr_test.json) is written")
+    add_eval_flags(p)
     return p
 
 
@@ -43,6 +46,7 @@ def check_args(a) -> None:
         raise ValueError("--learning_rate must be positive and --margin a number")
     if a.seed < 0:
         raise ValueError(f"--seed must be non-negative, got {a.seed}")
+    check_eval_args(a)
 
 
 def main(argv=None) -> int:
@@ -57,6 +61,8 @@ def main(argv=None) -> int:
     if not torch.cuda.is_available():
         raise RuntimeError("transr_train needs an MI355X: graphembeddings_amd has no CPU path")
     m = TR.TransR(E, R, a.hidden_size_e, a.hidden_size_r, l1=a.l1, seed=a.seed)
+    if a.load:
+        m.load_state_dict(torch.load(a.load, map_location="cpu"))
     tr = m.trainer(tri, B, margin=a.margin, learning_rate=a.learning_rate, seed=a.seed)
     for epoch in range(a.train_times):
         res = float(tr.run(a.nbatches).double().sum())
@@ -67,6 +73,8 @@ def main(argv=None) -> int:
     out = os.path.join(a.output_dir, "transr.pt")
     torch.save(m.state_dict(), out)
     print(f"saved {out}")
+    if a.test_file:
+        evaluate_to_json(m, a, E, R, tri, os.path.join(a.output_dir, "transr_test.json"))
     return 0
 
 

@@ -44,7 +44,13 @@ def read_kg(data_dir: str):
     write past its buffers (a partial last triple, more triples than declared, an id out of range) this raises."""
     R = _count(os.path.join(data_dir, "relation2id.txt"))
     E = _count(os.path.join(data_dir, "entity2id.txt"))
-    path = os.path.join(data_dir, "triple2id.txt")
+    return E, R, read_triples(os.path.join(data_dir, "triple2id.txt"), E, R)
+
+
+def read_triples(path: str, n_ent: int, n_rel: int) -> np.ndarray:
+    """int32 [T,3] (h, t, r) rows of one *2id.txt triple file (triple2id.txt, or a test / valid split in the same
+    format): a leading count, then `h t r` rows until the input ends, with read_kg's checks."""
+    E, R = n_ent, n_rel
     with open(path) as f:
         tok = f.read().split()
     if not tok:
@@ -65,7 +71,7 @@ def read_kg(data_dir: str):
         raise ValueError(f"{path}: entity id outside [0, {E})")
     if tri[:, 2].min() < 0 or tri[:, 2].max() >= R:
         raise ValueError(f"{path}: relation id outside [0, {R})")
-    return E, R, tri.astype(np.int32)
+    return tri.astype(np.int32)
 
 
 def _pairs(t: torch.Tensor, name: str) -> torch.Tensor:
@@ -73,6 +79,26 @@ def _pairs(t: torch.Tensor, name: str) -> torch.Tensor:
     if t.dim() != 2 or t.shape[1] != 3:
         raise ValueError(f"{name} must have shape [B, 3] (head, tail, relation)")
     return t.to(torch.int32).contiguous()
+
+
+def _rank_call(fn: str, ptrs, ws_bytes: int, n_ent: int, tb: torch.Tensor, cand_is_head: bool, known_off, known_rc,
+               return_scores: bool):
+    """One ge_transx_rank / ge_transr_rank call (ptrs: the model's table arguments)."""
+    B, dev = tb.shape[0], tb.device
+    if (known_off is None) != (known_rc is None):
+        raise ValueError("known_off and known_rc come together")
+    if ws_bytes == 0:
+        raise RuntimeError(f"{fn}_workspace_bytes failed")
+    nb = torch.empty(B, dtype=torch.int32, device=dev)
+    nk = torch.empty(B, dtype=torch.int32, device=dev)
+    td = torch.empty(B, dtype=torch.float32, device=dev)
+    sc = torch.empty((B, n_ent) if return_scores else (0,), dtype=torch.float32, device=dev)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    p = lambda t: None if t is None else t.data_ptr()
+    _lib.call(fn, *ptrs, tb.data_ptr(), B, int(bool(cand_is_head)), p(known_off), p(known_rc), nb.data_ptr(),
+              nk.data_ptr(), td.data_ptr(), sc.data_ptr() if return_scores else None, ws.data_ptr(), ws.numel(),
+              _stream())
+    return (nb, nk, td, sc) if return_scores else (nb, nk, td)
 
 
 class TransX:
@@ -131,6 +157,21 @@ class TransX:
         _lib.call("ge_transx_hinge_step", *self._ptrs(), pb.data_ptr(), nb.data_ptr(), pb.shape[0], float(margin),
                   float(lr), self._loss.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
         return self._loss[0].clone()
+
+    def rank_counts(self, triples: torch.Tensor, cand_is_head: bool = False, known_off: torch.Tensor = None,
+                    known_rc: torch.Tensor = None, return_scores: bool = False):
+        """ge_transx_rank on the [B,3] rows as given: (n_before, n_known_before, true_dist) device tensors, plus the
+        [B, n_ent] distances with return_scores (tests).  known_off / known_rc: ge_known_cells' lists for these rows
+        with pos_of = the identity (None: unfiltered).  Rows with an id out of range get -1 counts."""
+        tb = _pairs(triples, "triples")
+        return _rank_call("ge_transx_rank", self._ptrs(), _lib.load().ge_transx_rank_workspace_bytes(
+            MODELS[self.model], self.n_ent, self.n_rel, self.d, max(tb.shape[0], 1)), self.n_ent, tb, cand_is_head,
+            known_off, known_rc, return_scores)
+
+    def ranks(self, test, known=None, side: str = "tail", batch: int = None):
+        """(raw, filtered) int64 rank arrays of the test triples over every entity: evaluate.translation_ranks."""
+        from .evaluate import translation_ranks
+        return translation_ranks(self, test, known, side=side, batch=batch)
 
     def state_dict(self) -> Dict[str, object]:
         return {"model": self.model, "l1": self.l1, "n_ent": self.n_ent, "n_rel": self.n_rel, "d": self.d,

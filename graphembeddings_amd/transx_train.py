@@ -7,8 +7,45 @@ reference does, and saves the tables with torch.save (TF's model.vec checkpoint 
 from __future__ import annotations
 
 import argparse
+import json
 import os
 import sys
+
+FILTER_HELP = ("filtered evaluation (Bordes et al.): the filter is triple2id.txt + the --test_file + every --filter_file; "
+               "unlike the ComplEx evaluator, which filters train + valid as holE.py does")
+
+
+def add_eval_flags(p: argparse.ArgumentParser) -> None:
+    """--test_file / --filter_file / --load, shared by transx_train and transr_train."""
+    p.add_argument("--test_file", default=None,
+                   help="a *2id.txt file of test triples (leading count, then `h t r` rows) ranked after training over "
+                        "all entities, heads and tails; " + FILTER_HELP)
+    p.add_argument("--filter_file", action="append", default=[],
+                   help="a further *2id.txt file of known triples for the filter (repeatable; e.g. valid2id.txt)")
+    p.add_argument("--load", default=None, help="a saved state_dict to start from (with --train_times 0: evaluate only)")
+
+
+def check_eval_args(a) -> None:
+    if a.filter_file and not a.test_file:
+        raise ValueError("--filter_file needs --test_file")
+    for path in ([a.test_file] if a.test_file else []) + list(a.filter_file) + ([a.load] if a.load else []):
+        if not os.path.isfile(path):
+            raise ValueError(f"no such file: {path}")
+
+
+def evaluate_to_json(model, a, E: int, R: int, train, json_path: str) -> dict:
+    """Rank --test_file with the filter triple2id.txt + test + --filter_file; print the head, tail and both-sides
+    lines and write them to json_path."""
+    import numpy as np
+    from . import evaluate as EV
+    from .transx import read_triples
+    test = read_triples(a.test_file, E, R)
+    known = np.concatenate([train, test] + [read_triples(f, E, R) for f in a.filter_file], 0)
+    out = EV.evaluate_translation(model, test, known, both_sides=True, verbose=True)
+    with open(json_path, "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+    print(f"wrote {json_path}")
+    return out
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -25,7 +62,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--margin", type=float, default=1.0)
     p.add_argument("--learning_rate", type=float, default=0.001)
     p.add_argument("--seed", type=int, default=0)
-    p.add_argument("--output_dir", default=".", help="where <model>.pt is written")
+    p.add_argument("--output_dir", default=".", help="where <model>.pt (and <model>_test.json) is written")
+    add_eval_flags(p)
     return p
 
 
@@ -37,6 +75,7 @@ def check_args(a) -> None:
         raise ValueError("--nbatches must be positive and --train_times non-negative")
     if not a.learning_rate > 0 or a.margin != a.margin:
         raise ValueError("--learning_rate must be positive and --margin a number")
+    check_eval_args(a)
 
 
 def main(argv=None) -> int:
@@ -51,6 +90,8 @@ def main(argv=None) -> int:
     if not torch.cuda.is_available():
         raise RuntimeError("transx_train needs an MI355X: graphembeddings_amd has no CPU path")
     m = X.TransX(a.model, E, R, a.hidden_size, l1=a.l1, seed=a.seed)
+    if a.load:
+        m.load_state_dict(torch.load(a.load, map_location="cpu"))
     tr = m.trainer(tri, B, margin=a.margin, learning_rate=a.learning_rate, seed=a.seed)
     for epoch in range(a.train_times):
         res = float(tr.run(a.nbatches).double().sum())
@@ -61,6 +102,8 @@ def main(argv=None) -> int:
     out = os.path.join(a.output_dir, f"{a.model}.pt")
     torch.save(m.state_dict(), out)
     print(f"saved {out}")
+    if a.test_file:
+        evaluate_to_json(m, a, E, R, tri, os.path.join(a.output_dir, f"{a.model}_test.json"))
     return 0
 
 

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define GE_VERSION 340 /* 0.3.4: + ge_transr_* (TransR scoring, hinge Adam step and native loop) */
+#define GE_VERSION 350 /* 0.3.5: + ge_transx_rank / ge_transr_rank (link-prediction ranks of the translation models) */
 
 /* argument errors (negative, -errno style) */
 #define GE_EINVAL (-22)  /* bad dimension / null pointer / misaligned buffer */
@@ -270,6 +270,31 @@ int ge_transr_train_steps(int l1, float* ent, int64_t n_ent, float* rel, float* 
                           int64_t n_known, const uint32_t* tail_threshold, uint64_t seed, uint64_t first_step,
                           int64_t n_steps, int64_t B, float margin, float lr, float b1, float b2, float eps,
                           int64_t first_t, float* losses, void* workspace, size_t workspace_bytes, void* stream);
+
+/* --- link-prediction ranks of the translation models over EVERY entity, counted in the distance sweep (no [B, n_ent]
+ * matrix).  Row i = (h, t, r) of triples [B,3]: the candidates c in [0, n_ent) replace the tail (cand_is_head = 0,
+ * D_c = D(h, c, r)) or the head (D_c = D(c, t, r)), D as ge_transx_score / ge_transr_score state it, computed as
+ * sum_k term(q_k - P_c,k) with q = proj(h) + r (tail side) or proj(t) - r (head side) and P_c = proj(c):
+ *     n_before[i]       = #{c : D_c < D_true, or D_c == D_true and c < true}   (ascending (D, id); raw rank = 1 + it)
+ *     n_known_before[i] = how many of those c are listed in known_off / known_rc  (filtered rank = raw - it)
+ *     true_dist[i]      = D_true, computed by the same arithmetic as every D_c of the row (and of the filter pass)
+ * The known cells are ge_known_cells' lists for these rows with pos_of = the identity (candidate position = entity
+ * id); known_off = known_rc = NULL ranks unfiltered (n_known_before = 0).  A row with an id out of range gets
+ * n_before = n_known_before = -1 and true_dist NaN.  scores_out (nullable, tests) [B, n_ent] receives every D_c.
+ * A row's counts do not depend on the other rows of the call; rows grouped by relation share projection work.
+ * Integer counts only: two identical calls agree bitwise.  No host synchronisation inside; no CPU path. */
+size_t ge_transx_rank_workspace_bytes(int model, int64_t n_ent, int64_t n_rel, int32_t d, int64_t B);
+int ge_transx_rank(int model, int l1, const float* ent, int64_t n_ent, const float* rel, int64_t n_rel,
+                   const float* normal, const float* ent_transfer, const float* rel_transfer, int32_t d,
+                   const int32_t* triples, int64_t B, int cand_is_head, const int32_t* known_off,
+                   const uint16_t* known_rc, int32_t* n_before, int32_t* n_known_before, float* true_dist,
+                   float* scores_out, void* workspace, size_t workspace_bytes, void* stream);
+size_t ge_transr_rank_workspace_bytes(int64_t n_ent, int64_t n_rel, int32_t dim_e, int32_t dim_r, int64_t B);
+int ge_transr_rank(int l1, const float* ent, int64_t n_ent, const float* rel, const float* rel_matrix, int64_t n_rel,
+                   int32_t dim_e, int32_t dim_r, const int32_t* triples, int64_t B, int cand_is_head,
+                   const int32_t* known_off, const uint16_t* known_rc, int32_t* n_before, int32_t* n_known_before,
+                   float* true_dist, float* scores_out, void* workspace, size_t workspace_bytes, void* stream);
+
 
 /* --- 1-vs-K candidate scoring (the inference loop of holE.py:564-569: fixed (head, relation)
  * against many tails; also K shared negatives per positive).  hr: [B,2] int32 (fixed entity,
