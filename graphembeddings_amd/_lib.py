@@ -53,6 +53,10 @@ SYMBOLS = {
     "ge_rank_planes": (C.c_int, [_p, _i64, _i32, _p, _i64, _f, C.c_int, _p, _p]),
     "ge_rank_1vK_planes": (C.c_int, [_p, _i64, _i32, _p, _i64, _p, _p, _i64, _f, C.c_int, C.c_int, _p, _p, _p, _p, _p, _p, _p, _p]),
     "ge_rank_1vK_vs_loss": (C.c_int, [_p, _i64, _i32, _p, _i64, _p, _p, _p, _i64, _f, C.c_int, C.c_int, _p, _p, _p, _p, _p, _p]),
+    "ge_topk_max_k": (C.c_int, []),
+    "ge_topk_workspace_bytes": (_sz, [_i64, _i64, _i32]),
+    "ge_topk_1vK_planes": (C.c_int, [_p, _i64, _i32, _p, _i64, _p, _i64, _f, C.c_int, C.c_int, _p, _p, _i32, _p, _p, _p,
+                                     _p, _sz, _p]),
     "ge_train_workspace_bytes": (_sz, [_i64, _i32]),
     "ge_train_pipeline_create": (C.c_int, [C.POINTER(C.c_void_p)]),
     "ge_train_pipeline_reset": (C.c_int, [_p]),

@@ -483,6 +483,23 @@ int ge_rank_1vK_vs_loss(const float* table, int64_t N, int32_t d, const int32_t*
                                  /*vs_loss=*/1);
 }
 
+int ge_topk_max_k(void) { return topk_max_k(); }
+
+size_t ge_topk_workspace_bytes(int64_t B, int64_t K, int32_t k) { return topk_ws_bytes(B, K, k); }
+
+int ge_topk_1vK_planes(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* cand,
+                       int64_t K, float max_norm, int model, int cand_is_head, const int32_t* known_off,
+                       const uint16_t* known_rc, int32_t k, int32_t* out_id, float* out_loss, const void* planes,
+                       void* workspace, size_t workspace_bytes, void* stream) {
+  if (B < 0 || K < 1 || k < 1 || !ok_table(table, N, d) || !max_norm_ok(max_norm)) return GE_EINVAL;
+  if (model != GE_MODEL_COMPLEX && model != GE_MODEL_HOLE_SPECTRAL) return model == GE_MODEL_HOLE || model == GE_MODEL_HOLE_DIRECT ? GE_ENOTSUP : GE_EINVAL;
+  if (B > 0 && (!hr || !cand || !out_id || !out_loss)) return GE_EINVAL;
+  if ((known_off == nullptr) != (known_rc == nullptr)) return GE_EINVAL;
+  if (planes && (rank_planes_bytes(N, d, K) == 0 || reinterpret_cast<uintptr_t>(planes) % 256 != 0)) return GE_EINVAL;
+  return topk_f16_launch(table, N, d, hr, B, cand, K, max_norm, cand_is_head, known_off, known_rc, k, out_id, out_loss,
+                         model == GE_MODEL_HOLE_SPECTRAL, planes, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
 int ge_rank_1vK(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* true_id,
                 const int32_t* cand, int64_t K, float max_norm, int model, int cand_is_head, const int32_t* known_off,
                 const uint16_t* known_rc, int32_t* n_before, int32_t* n_known_before, float* true_loss,

@@ -94,6 +94,13 @@ int sweep_f16_launch(const float* table, int64_t N, int32_t d, const int32_t* hr
                      const int32_t* cand, int64_t K, float max_norm, int cand_is_head, const int32_t* known_off,
                      const uint16_t* known_rc, int32_t* raw_cnt, int32_t* skip_cnt, float* true_loss,
                      float* scores_out, int spec, int scores_only, int sweep_flags, const void* planes_ws, hipStream_t st);
+// the top-k sweep on the same planes (ge_topk_1vK_planes): k <= topk_max_k(), workspace of topk_ws_bytes(B, K, k)
+int topk_max_k();
+size_t topk_ws_bytes(int64_t B, int64_t K, int32_t k);
+int topk_f16_launch(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* cand, int64_t K,
+                    float max_norm, int cand_is_head, const int32_t* known_off, const uint16_t* known_rc, int32_t k,
+                    int32_t* out_id, float* out_loss, int spec, const void* planes_ws, void* workspace,
+                    size_t workspace_bytes, hipStream_t st);
 
 // ge_known.hip: the known-true cells of a ranking sweep as per-tile lists
 int known_cells_launch(int pass, const int64_t* key, const int64_t* ent, int64_t M, const int64_t* fixed, const int64_t* rel,

@@ -88,6 +88,107 @@ constexpr size_t h_lds_bytes() {
          sizeof(unsigned) * 8 * 64 + sizeof(int) * (4 * kRB + 4);
 }
 
+// ---- top-k (MODE 3, ge_topk_1vK): keys, pools, thresholds
+typedef unsigned long long u64;
+constexpr int kTopkMaxK = 128;
+constexpr u64 kNoKey = ~0ull;           // (also the padding of a partial list)
+// A candidate's key: (loss bits, entity id) as one unsigned 64-bit number.  Losses are sigmoids in [0, 1] (never NaN for a
+// candidate that survives), so the integer order of the keys is the reference heap's pop order (ascending loss, ties by
+// id); distinct candidates have distinct keys.
+__device__ __forceinline__ u64 topk_key(float e, int32_t id) { return ((u64)__float_as_uint(e) << 32) | (unsigned)id; }
+
+// per row of the block behind HLds: the current k-th best key, the pool's fill and the raw-score bound of that key
+template <int KKB>
+constexpr size_t topk_lds_bytes() { return h_lds_bytes<KKB>() + (sizeof(u64) + sizeof(int) + sizeof(float)) * kRB; }
+
+// (the sweep reads k, pool and part only -- n_split is gridDim.y, kp and cap follow from k: every kernel argument it
+// keeps live costs scalar registers the staging then spills)
+struct TopkArgs {
+  int k;              // 1 ... kTopkMaxK
+  int cap;            // pool entries per (row, split): topk_kp(k) + 128 <= 320 (one tile adds at most 128 to a row)
+  int n_split;        // workgroups per row block (gridDim.y), each over its own range of candidate tiles
+  u64* pool;          // [B][n_split][cap]
+  u64* part;          // [B][n_split][k] partial lists: each segment's k best, sorted, kNoKey-padded
+  int32_t* out_id;    // [B][k]
+  float* out_loss;    // [B][k]
+};
+
+// a pool past kp entries is cut back to k after the tile (>= 32 appends apart)
+__host__ __device__ constexpr int topk_kp(int k) { return (k + 95) / 64 * 64; }   // k + 32 rounded up: 64 for k <= 32, 192 for k = 128
+constexpr int kTopkLane = 5;            // pool entries per lane in a merge: cap = kp + 128 <= 320
+
+// the raw-score bound of a k-th best loss e: a candidate whose raw score lies above it has a loss > e (the bracket of
+// rank_f16_kernel's vs-loss mode, one-sided; infinite near saturation)
+__device__ __forceinline__ float topk_bound(float e) {
+  const float sa = 1.0f / (kQScale * kQScale);
+  const float ec = fminf(fmaxf(e, 1e-30f), 0.99999994f);
+  const float xs = logf(ec / (1.0f - ec));
+  const float gs = e * (1.0f - e);
+  const float wx = !(gs >= 1e-5f) ? __builtin_inff() : 1e-6f / gs + 4e-7f * fabsf(xs);
+  return xs / sa + wx / sa;
+}
+
+__device__ __forceinline__ u64 readlane64(u64 x, int l) {
+  const unsigned lo = __builtin_amdgcn_readlane((int)(unsigned)x, l);
+  const unsigned hi = __builtin_amdgcn_readlane((int)(unsigned)(x >> 32), l);
+  return ((u64)hi << 32) | lo;
+}
+
+// One wave: the first n (<= 320) keys of `pool`, entry m * 64 + lane in key[m], and each one's rank among them (the number
+// of smaller keys; kNoKey beyond n).  Every key is compared with every other: n^2 / 64 compares per lane, no scratch, no
+// LDS.
+__device__ __forceinline__ void topk_rank(const u64* pool, int n, int lane, u64 (&key)[kTopkLane], int (&rank)[kTopkLane]) {
+#pragma unroll
+  for (int m = 0; m < kTopkLane; ++m) {
+    const int i = m * 64 + lane;
+    key[m] = i < n ? pool[i] : kNoKey;
+    rank[m] = 0;
+  }
+#pragma unroll
+  for (int m2 = 0; m2 < kTopkLane; ++m2) {
+    const int lim = min(64, n - m2 * 64);
+    for (int l = 0; l < lim; ++l) {
+      const u64 kj = readlane64(key[m2], l);
+#pragma unroll
+      for (int m = 0; m < kTopkLane; ++m) rank[m] += kj < key[m] ? 1 : 0;
+    }
+  }
+}
+
+// One wave: keep the k best of a pool of n > k keys in its first k entries; returns the k-th best key (all lanes)
+__device__ __forceinline__ u64 topk_shrink(u64* pool, int n, int k, int lane) {
+  u64 key[kTopkLane];
+  int rank[kTopkLane];
+  topk_rank(pool, n, lane, key, rank);
+  u64 kth = kNoKey;
+#pragma unroll
+  for (int m = 0; m < kTopkLane; ++m) {
+    if (key[m] != kNoKey && rank[m] < k) pool[rank[m]] = key[m];
+    if (key[m] != kNoKey && rank[m] == k - 1) kth = key[m];
+  }
+  const u64 has = __ballot(kth != kNoKey);
+  return has ? readlane64(kth, __ffsll((long long)has) - 1) : kNoKey;
+}
+
+// One wave: the final list of a row -- the k best of n keys of `pool` into ids / losses (or keys), padded
+__device__ __forceinline__ void topk_emit(const u64* pool, int n, int k, int lane, int32_t* out_id, float* out_loss,
+                                          u64* out_key) {
+  u64 key[kTopkLane];
+  int rank[kTopkLane];
+  topk_rank(pool, n, lane, key, rank);
+#pragma unroll
+  for (int m = 0; m < kTopkLane; ++m) {
+    if (key[m] != kNoKey && rank[m] < k) {
+      if (out_key) out_key[rank[m]] = key[m];
+      else { out_id[rank[m]] = (int32_t)(unsigned)key[m]; out_loss[rank[m]] = __uint_as_float((unsigned)(key[m] >> 32)); }
+    }
+  }
+  for (int i = min(n, k) + lane; i < k; i += 64) {       // fewer eligible candidates than k
+    if (out_key) out_key[i] = kNoKey;
+    else { out_id[i] = -1; out_loss[i] = __builtin_inff(); }
+  }
+}
+
 struct HA { h8 ah[2], am[2]; };          // the Q operands of one k block of this wave's 64 rows
 struct HB { h8 bh, bm; };                // the candidate operands of one k block of this wave's 32 columns
 
@@ -188,6 +289,7 @@ __device__ __forceinline__ void h_mfma_loop(const HLds& lds, const _Float16* __r
 
 // MODE 0: ranks.  1: ranks, every loss computed exactly and stored too (tests).  2: no ranking at all -- the sweep
 // writes scores_out[B,K] (raw score, or its sigmoid when `sweep_flags` & 1): ge_complex_score_1vK on this pipeline.
+// 3: top-k (ge_topk_1vK, `tk`): the k first pops of the reference's heap per row, from the losses MODE 1 stores.
 template <int KKB, int MODE>
 __global__ __launch_bounds__(kBlk) void rank_f16_kernel(
     const float* __restrict__ table, int64_t N, int d, const int32_t* __restrict__ hr, int64_t B,
@@ -195,7 +297,7 @@ __global__ __launch_bounds__(kBlk) void rank_f16_kernel(
     int cand_is_head, const int32_t* __restrict__ known_off, const uint16_t* __restrict__ known_rc,
     int32_t* __restrict__ raw_cnt, int32_t* __restrict__ skip_cnt, float* true_loss,
     float* __restrict__ scores_out, int n_ct, int64_t n_tiles, int spec, int sweep_flags,
-    const int32_t* __restrict__ pos_of, const _Float16* __restrict__ planes) {
+    const int32_t* __restrict__ pos_of, const _Float16* __restrict__ planes, TopkArgs tk) {
   constexpr bool SCORES = MODE == 1;
   constexpr int kSA = HCfg<KKB>::kSA;
   constexpr int64_t kSliceHalves = (int64_t)KKB * 2 * kOpHalves;
@@ -216,6 +318,10 @@ __global__ __launch_bounds__(kBlk) void rank_f16_kernel(
   lds.tI = lds.extra + kRB;
   lds.tP = lds.tI + kRB;
   lds.next = lds.tP + kRB;
+  // MODE 3 only: behind HLds (topk_lds_bytes)
+  u64* tk_kth = reinterpret_cast<u64*>(lds.next + 4);           // (HLds ends on a multiple of 8 bytes)
+  int* tk_cnt = reinterpret_cast<int*>(tk_kth + kRB);
+  float* tk_hi = reinterpret_cast<float*>(tk_cnt + kRB);
   const int k = d >> 1;
 
   // This workgroup's share of the (row block, 128-candidate tile) list, row-block major -- walked so that every
@@ -224,7 +330,14 @@ __global__ __launch_bounds__(kBlk) void rank_f16_kernel(
   // few tiles of each other and the XCD's 4 MiB L2 serves all but the first of them; walked in list order the 32 CUs
   // sat at 32 different places of the candidate ring, the planes (13 MB) streamed through every L2 and 80 % of the
   // reads missed it (TCC_HIT / TCC_MISS: 20 % -> 93 % hits).
-  const int64_t share0 = n_tiles * blockIdx.x / gridDim.x, share1 = n_tiles * (blockIdx.x + 1) / gridDim.x;
+  // (MODE 3: workgroup = (row block, candidate range): n_split equal ranges of the row block's tiles, one each)
+  const int tk_s = MODE == 3 ? (int)blockIdx.y : 0;
+  const int64_t tk_rb = MODE == 3 ? (int64_t)blockIdx.x : 0;
+  const int tk_ns = MODE == 3 ? (int)gridDim.y : 1;            // (MODE 3: n_split, kp and cap from the grid and k)
+  const int tk_kp = topk_kp(tk.k), tk_cap = tk_kp + 128;
+  const int64_t share0 = MODE == 3 ? tk_rb * n_ct + (int64_t)n_ct * tk_s / tk_ns : n_tiles * blockIdx.x / gridDim.x;
+  const int64_t share1 = MODE == 3 ? tk_rb * n_ct + (int64_t)n_ct * (tk_s + 1) / tk_ns
+                                   : n_tiles * (blockIdx.x + 1) / gridDim.x;
   const int64_t first_end = min(share1, (share0 / n_ct + 1) * n_ct);
   for (int pass = 0; pass < 2; ++pass) {
   int64_t idx = pass ? share0 : first_end;
@@ -319,11 +432,16 @@ __global__ __launch_bounds__(kBlk) void rank_f16_kernel(
         lds.sA[qrow] = (bad || r >= B) ? __builtin_nanf("") : 1.0f / (kQScale * kQScale);
         lds.skip[qrow] = 0;
         lds.extra[qrow] = 0;
-        const int32_t tid = (MODE != 2 && r < B) ? true_id[r] : -1;
+        const int32_t tid = (MODE < 2 && r < B) ? true_id[r] : -1;
         lds.tI[qrow] = tid;
         // (sweep_flags & 2, ranking against GIVEN losses: the "true candidate" pass still runs -- the loop below has one
         // copy of the MFMA code -- on candidate 0's planes, and its result is replaced by the given loss)
         lds.tP[qrow] = (sweep_flags & 2) ? (r < B ? 0 : -1) : (tid >= 0 && tid < N) ? pos_of[tid] : -1;
+      }
+      if constexpr (MODE == 3) {
+        tk_kth[qrow] = kNoKey;                                   // (no list yet: every candidate of a good row survives)
+        tk_cnt[qrow] = 0;
+        tk_hi[qrow] = (bad || r >= B) ? __builtin_nanf("") : __builtin_inff();
       }
       if (t < 4) lds.next[t] = 2;                                // (blocks 0 and 1 of a slice go to its two waves up front)
     }
@@ -354,14 +472,16 @@ __global__ __launch_bounds__(kBlk) void rank_f16_kernel(
       if (lane == 0) v = atomicAdd(&lds.next[wn], 1);
       return __builtin_amdgcn_readfirstlane(v);
     };
-    int item = wm, item_next = take();
+    // (MODE 3: no counter -- wave (wm, wn) takes row half wm of slice wn of every tile, so it alone appends to and merges
+    // nothing but its own cells, and all waves pass the same number of barriers)
+    int item = wm, item_next = MODE == 3 ? wm + 2 : take();
     const int s0 = 4 * (ct0 + (item >> 1)) + wn;
     // ---- the first pass of the loop below (ranks): the true candidates -- a tile whose candidate rows are the block's 128
     // true entities (this wave: 32 of them, gathered by position), through the SAME copy of the MFMA loop as the sweep's
     // blocks (a second copy, fetched cold once per row block, took six tiles' time)
-    bool diag = MODE != 2;
+    bool diag = MODE < 2;
     unsigned cur = slice_src(s0);
-    if constexpr (MODE != 2) {
+    if constexpr (MODE < 2) {
       const int pos = lds.tP[wn * 32 + li];
       const int pc = pos < 0 ? 0 : pos;
       cur = (unsigned)(pc >> 5) * (unsigned)(kSliceHalves * 2) + (unsigned)((pc & 31) * 32 + lh * 16);
@@ -382,6 +502,18 @@ __global__ __launch_bounds__(kBlk) void rank_f16_kernel(
         // of the epilogue -- for the brackets -- waits for everything on that counter)
         kn0 = kn0_next; kn1 = kn1_next;
         known_of(ct0 + (item_next >> 1), kn0_next, kn1_next);
+      }
+      if constexpr (MODE == 3) {
+        // (top-k) this wave's known cells of the block -> its own bitmap, before the MFMA loop: nothing of the epilogue
+        // is live yet
+        if (known_off) {
+          lds.bm[lane] = 0u;
+          for (int32_t e = kn0 + lane; e < kn1; e += kWave) {
+            const unsigned rc = known_rc[e];
+            const int rl = rc >> 7, cl = rc & 127;
+            if ((rl >> 6) == wmi && (cl >> 5) == wn) atomicOr(&lds.bm[rl & 63], 1u << (cl & 31));
+          }
+        }
       }
       h_mfma_loop<KKB>(lds, planes, cur, nxt, Bq, acc, wmi, li, lh);     // leaves the next block's leading operands in Bq
       cur = nxt;
@@ -427,7 +559,7 @@ __global__ __launch_bounds__(kBlk) void rank_f16_kernel(
         continue;
       }
       item = item_next;
-      item_next = take();
+      item_next = MODE == 3 ? item + 2 : take();
       // the brackets of this lane's 32 rows, requested together (read score by score -- a wait on the LDS queue in front
       // of every compare sequence -- the epilogue took 200 cycles per score; held in registers across the MFMA loop
       // they are spilled)
@@ -440,6 +572,60 @@ __global__ __launch_bounds__(kBlk) void rank_f16_kernel(
       }
       // epilogue: C layout of the 32x32 f32 MFMA: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5).  A candidate
       // beyond K or with a bad id has NaN planes, a row beyond B a NaN bracket: no bit is set.
+      if constexpr (MODE == 3) {
+        // Top-k epilogue.  Per row: a pool of candidate keys in global memory (tk.pool), its fill, the k-th best key so
+        // far and that key's raw-score bound (LDS).  A score above the bound cannot enter the list (one compare); the
+        // few below it take the exact loss of MODE 1 -- rank_sigmoid(acc * 2^-16), bit for bit -- and, when their key beats
+        // the k-th best and they are no known-true cell, are appended.  After the tile, pools past kp entries are cut
+        // back to their k best and the bound tightens.
+        __syncthreads();                                         // the merges after the previous tile are done
+        u64* const pbase = tk.pool + (m0 * tk_ns + tk_s) * (int64_t)tk_cap;   // row rl's pool: pbase + rl * pstride
+        const int pstride = tk_ns * tk_cap;
+        static_for<0, 2>([&](auto tc) {                          // one 32-row half at a time (registers)
+          constexpr int tm = decltype(tc)::value;
+          float hv[16];
+#pragma unroll
+          for (int q = 0; q < 16; ++q) hv[q] = tk_hi[wmi * 64 + tm * 32 + (q & 3) + 8 * (q >> 2) + 4 * lh];
+          unsigned I = 0;                                        // bit 15 - q: the score passed the bound
+#pragma unroll
+          for (int q = 0; q < 16; ++q) I = (I << 1) | (acc[tm][q] <= hv[q] ? 1u : 0u);
+          if (I) {
+            const int32_t cid = col < K ? cand[col] : -1;        // (beyond K: NaN planes, never below a bound)
+            static_for<0, 4>([&](auto gc) {                      // 4 scores per outer test (most groups are empty)
+              constexpr int g4 = decltype(gc)::value;
+              if (I & (0xf000u >> (4 * g4))) {
+                static_for<0, 4>([&](auto kc) {
+                  constexpr int q = 4 * g4 + decltype(kc)::value, R32 = (q & 3) + 8 * (q >> 2);
+                  if (I & (0x8000u >> q)) {
+                    const int rl = wmi * 64 + tm * 32 + R32 + 4 * lh;
+                    if (!known_off || !((lds.bm[rl & 63] >> li) & 1u)) {
+                      const u64 key = topk_key(rank_sigmoid(acc[tm][q] * (1.0f / (kQScale * kQScale))), cid);
+                      if (key < tk_kth[rl]) {
+                        const int slot = atomicAdd(&tk_cnt[rl], 1);  // < cap: <= kp before the tile, <= 128 cells per tile
+                        pbase[rl * pstride + slot] = key;
+                      }
+                    }
+                  }
+                });
+              }
+            });
+          }
+        });
+        __syncthreads();                                         // the tile's appends are in
+        for (int j = 0; j < kRB / 8; ++j) {                      // wave w merges rows 16 w ... 16 w + 15
+          const int rl = w * (kRB / 8) + j;
+          const int n = __builtin_amdgcn_readfirstlane(tk_cnt[rl]);
+          if (n > tk_kp) {
+            const u64 kth = topk_shrink(pbase + rl * pstride, n, tk.k, lane);
+            if (lane == 0) {
+              tk_cnt[rl] = tk.k;
+              tk_kth[rl] = kth;
+              tk_hi[rl] = topk_bound(__uint_as_float((unsigned)(kth >> 32)));
+            }
+          }
+        }
+        continue;
+      }
       if constexpr (MODE == 2) {                                 // scores only: 32 consecutive floats of a row per half-wave
 #pragma unroll
         for (int tm = 0; tm < 2; ++tm)
@@ -517,7 +703,19 @@ __global__ __launch_bounds__(kBlk) void rank_f16_kernel(
       }
     }
     __syncthreads();
-    if constexpr (MODE != 2) {
+    if constexpr (MODE == 3) {
+      // the segment's list of each row, sorted and kNoKey-padded, for topk_merge_kernel
+      for (int j = 0; j < kRB / 8; ++j) {
+        const int rl = w * (kRB / 8) + j;
+        const int64_t row = m0 + rl;
+        if (row >= B) break;
+        const int n = __builtin_amdgcn_readfirstlane(tk_cnt[rl]);
+        // (rows with an id out of range have an empty pool; topk_merge_kernel gives them -1 / NaN)
+        topk_emit(tk.pool + (row * tk_ns + tk_s) * (int64_t)tk_cap, n, tk.k, lane, nullptr, nullptr,
+                  tk.part + (row * tk_ns + tk_s) * (int64_t)tk.k);
+      }
+    }
+    if constexpr (MODE < 2) {
       if (lane < 32) {
 #pragma unroll
         for (int hm = 0; hm < 2; ++hm)
@@ -608,6 +806,51 @@ __global__ void rank_pos_kernel(const int32_t* __restrict__ cand, int64_t K, int
   }
 }
 
+// The second step of a top-k: per row (one wave), the n_split partial lists -- each sorted, kNoKey-padded -- into the
+// final k ids and losses (one list: a copy).  Only keys below the running k-th best are taken (a prefix of each list);
+// the row's first pool collects them and is cut back to k whenever the next list might not fit.
+__global__ __launch_bounds__(256) void topk_merge_kernel(const int32_t* __restrict__ hr, int64_t B, int64_t N, TopkArgs tk) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= B) return;
+  const int k = tk.k;
+  int32_t* oid = tk.out_id + row * k;
+  float* ol = tk.out_loss + row * k;
+  const int32_t fid = hr[2 * row], rid = hr[2 * row + 1];
+  if (fid < 0 || fid >= N || rid < 0 || rid >= N) {
+    for (int i = lane; i < k; i += 64) { oid[i] = -1; ol[i] = __builtin_nanf(""); }
+    return;
+  }
+  if (tk.n_split == 1) {
+    const u64* L = tk.part + row * (int64_t)k;
+    for (int i = lane; i < k; i += 64) {
+      const u64 key = L[i];
+      oid[i] = key == kNoKey ? -1 : (int32_t)(unsigned)key;
+      ol[i] = key == kNoKey ? __builtin_inff() : __uint_as_float((unsigned)(key >> 32));
+    }
+    return;
+  }
+  u64* pool = tk.pool + row * tk.n_split * (int64_t)tk.cap;
+  int n = 0;
+  u64 kth = kNoKey;
+  for (int s = 0; s < tk.n_split; ++s) {
+    const u64* L = tk.part + (row * tk.n_split + s) * (int64_t)k;
+    const u64 a = lane < k ? L[lane] : kNoKey, b = lane + 64 < k ? L[lane + 64] : kNoKey;
+    const int ns = __popcll(__ballot(a < kth)) + __popcll(__ballot(b < kth));
+    if (ns == 0) continue;
+    if (n + ns > tk.cap) {                                   // (after the cut n = k, and k + ns <= 2 k <= cap)
+      kth = topk_shrink(pool, n, k, lane);
+      n = k;
+      __threadfence_block();
+    }
+    if (lane < ns) pool[n + lane] = a;
+    if (lane + 64 < ns) pool[n + 64 + lane] = b;
+    n += ns;
+    __threadfence_block();
+  }
+  topk_emit(pool, n, k, lane, oid, ol, nullptr);
+}
+
 int f16_cu_count() {
   int dev = 0, cus = 0;
   if (hipGetDevice(&dev) != hipSuccess) return 256;
@@ -637,7 +880,7 @@ int f16_launch_kkb(const float* table, int64_t N, int32_t d, const int32_t* hr, 
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kBlk), h_lds_bytes<KKB>(), st, table, N, d, hr, B, true_id, cand, K,
                        max_norm, cand_is_head, known_off, known_rc, raw_cnt, skip_cnt, true_loss, scores_out, (int)n_ct,
-                       n_tiles, spec, sweep_flags, pos_of, planes);
+                       n_tiles, spec, sweep_flags, pos_of, planes, TopkArgs{});
     return launch_status();
   };
   if (scores_only) return go(rank_f16_kernel<KKB, 2>);
@@ -654,6 +897,20 @@ int f16_launch_kkb(const float* table, int64_t N, int32_t d, const int32_t* hr, 
     case 14: CALL(14); case 15: CALL(15); case 16: CALL(16); case 17: CALL(17); case 18: CALL(18);    \
     default: return GE_ENOTSUP;                                                                       \
   }
+
+// ---- top-k: workgroups per row block.  With fewer than 256 row blocks (one workgroup per CU of the MI355X) the row
+// blocks' candidates are cut into ranges until there are about 256 workgroups (one query against 1.2 M candidates: 256
+// ranges of 37 tiles); the partial lists meet in topk_merge_kernel.  A function of (B, K) alone, so that the workspace is.
+int64_t topk_splits(int64_t B, int64_t K) {
+  const int64_t n_rb = (B + kRB - 1) / kRB, n_ct = (K + kRB - 1) / kRB;
+  if (n_rb >= 256) return 1;
+  return std::max<int64_t>(1, std::min<int64_t>(n_ct, (256 + n_rb - 1) / n_rb));
+}
+
+int64_t topk_ws_rows(int64_t n_rb, int64_t K, int32_t k) {      // bytes for n_rb full row blocks
+  const int64_t ns = topk_splits(n_rb * kRB, K);
+  return n_rb * kRB * ns * (topk_kp(k) + 128 + k) * (int64_t)sizeof(u64);
+}
 
 // bytes of the candidate planes of a K-candidate sweep over an N-row table (0: embedding_dim has no split-precision sweep)
 int64_t rank_planes_bytes(int64_t N, int32_t d, int64_t K) {
@@ -713,6 +970,82 @@ int sweep_f16_launch(const float* table, int64_t N, int32_t d, const int32_t* hr
 #undef GE_CALL
   };
   int rc = run();
+  if (own) {
+    const hipError_t e = hipFreeAsync(own, st);
+    if (rc == 0 && e != hipSuccess) rc = (int)e;
+  }
+  return rc;
+}
+
+int topk_max_k() { return kTopkMaxK; }
+
+// Workspace of a top-k over B rows and K candidates: the pools, [B][n_split][kp + 128] keys, and the partial lists,
+// [B][n_split][k].  Taken as the largest need of any B' <= B (the ranges shrink as B grows), so that the
+// size is monotone in B, K and k.
+size_t topk_ws_bytes(int64_t B, int64_t K, int32_t k) {
+  if (B <= 0 || K <= 0 || k < 1 || k > kTopkMaxK) return 0;
+  const int64_t n_rb = (B + kRB - 1) / kRB;
+  int64_t need = topk_ws_rows(n_rb, K, k);
+  for (int64_t r = 1; r < std::min<int64_t>(n_rb, 256); ++r) need = std::max(need, topk_ws_rows(r, K, k));
+  return (size_t)need + 256;
+}
+
+// The top-k sweep (rank_f16_kernel MODE 3, grid row blocks x candidate ranges), then the merge of the partial lists.  The same planes
+// and Q staging as the rank sweep, so the losses are MODE 1's.
+int topk_f16_launch(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* cand, int64_t K,
+                    float max_norm, int cand_is_head, const int32_t* known_off, const uint16_t* known_rc, int32_t k,
+                    int32_t* out_id, float* out_loss, int spec, const void* planes_ws, void* workspace,
+                    size_t workspace_bytes, hipStream_t st) {
+  if (!f16_dim_ok(d, max_norm) || rank_planes_bytes(N, d, K) == 0) return GE_ENOTSUP;
+  if (k < 1) return GE_EINVAL;
+  if (k > kTopkMaxK) return GE_ENOTSUP;
+  if (B == 0) return 0;
+  if (!workspace || reinterpret_cast<uintptr_t>(workspace) % 256 != 0) return GE_EINVAL;
+  if (workspace_bytes < topk_ws_bytes(B, K, k)) return GE_ENOMEM;
+  static_assert(topk_lds_bytes<18>() <= 160 * 1024, "LDS of the largest top-k instantiation");
+  const int64_t n_rb = (B + kRB - 1) / kRB, n_ct = (K + kRB - 1) / kRB;
+  if (n_ct > INT32_MAX / 8) return GE_ENOTSUP;
+  if (4 * n_ct * (int64_t)((d + 15) / 16) * 2 * kOpHalves * 2 >= ((int64_t)1 << 32)) return GE_ENOTSUP;
+  const int64_t ns = topk_splits(B, K);
+  if (n_rb * ns > INT32_MAX) return GE_ENOTSUP;
+  TopkArgs tk;
+  tk.k = k;
+  tk.cap = topk_kp(k) + 128;
+  tk.n_split = (int)ns;
+  tk.pool = reinterpret_cast<u64*>(workspace);
+  tk.part = tk.pool + B * ns * tk.cap;
+  tk.out_id = out_id;
+  tk.out_loss = out_loss;
+  void* own = nullptr;
+  if (!planes_ws) {
+    hipError_t e = hipMallocAsync(&own, (size_t)rank_planes_bytes(N, d, K), st);
+    if (e != hipSuccess) return (int)e;
+    const int rc = rank_planes_launch(table, N, d, cand, K, max_norm, spec, own, st);
+    if (rc != 0) { (void)hipFreeAsync(own, st); return rc; }
+    planes_ws = own;
+  }
+  const int32_t* pos_of = reinterpret_cast<const int32_t*>(planes_ws);
+  const _Float16* planes = reinterpret_cast<const _Float16*>(reinterpret_cast<const char*>(planes_ws) + pos_bytes(N));
+  auto run = [&]() -> int {
+#define GE_CALL(KKB)                                                                                                  \
+  {                                                                                                                   \
+    auto kern = rank_f16_kernel<KKB, 3>;                                                                              \
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, \
+                                       160 * 1024);                                                                   \
+    if (e != hipSuccess) return (int)e;                                                                               \
+    hipLaunchKernelGGL(kern, dim3((unsigned)n_rb, (unsigned)ns), dim3(kBlk), topk_lds_bytes<KKB>(), st, table, N, d, hr, B,   \
+                       nullptr, cand, K, max_norm, cand_is_head, known_off, known_rc, nullptr, nullptr, nullptr,      \
+                       nullptr, (int)n_ct, n_rb * n_ct, spec, 0, pos_of, planes, tk);                                 \
+    return launch_status();                                                                                           \
+  }
+    GE_KKB_SWITCH(d, GE_CALL)
+#undef GE_CALL
+  };
+  int rc = run();
+  if (rc == 0) {
+    hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, hr, B, N, tk);
+    rc = launch_status();
+  }
   if (own) {
     const hipError_t e = hipFreeAsync(own, st);
     if (rc == 0 && e != hipSuccess) rc = (int)e;

@@ -223,6 +223,213 @@ def evaluate_fb15k_style(embeddings: torch.Tensor, data, both_sides: bool = True
     return out
 
 
+# ------------------------------------------------------------------ top-k prediction
+def _split_f16_ok(d: int, max_norm: float) -> bool:
+    """embedding_dim has the split-precision sweep (the fused top-k's range)."""
+    return d % 8 == 0 and 56 <= d <= 288 and max_norm <= 8.0
+
+
+def _known_cells_rc(off: torch.Tensor, rc: torch.Tensor, n_cand: int):
+    """(rows, columns) int64 of the per-tile known-cell lists of KnownIndex.cells."""
+    dev = off.device
+    n_ct = (n_cand + 127) // 128
+    tiles = torch.repeat_interleave(torch.arange(off.numel() - 1, device=dev), (off[1:] - off[:-1]).to(torch.int64))
+    rcv = rc[:tiles.numel()].to(torch.int64)
+    return (tiles // n_ct) * 128 + rcv // 128, (tiles % n_ct) * 128 + rcv % 128
+
+
+def _topk_of_losses(losses: torch.Tensor, cand64: torch.Tensor, k: int, known=None):
+    """The first k pops of the reference's heap from a [b, K] loss matrix: a stable sort by loss of the candidates in id
+    order, i.e. ascending (loss, id).  Known cells are skipped; padding -1 / +inf, rows with NaN losses -1 / NaN."""
+    L = losses.clone()
+    if known is not None and known[0].numel():
+        L[known[0], known[1]] = float("inf")
+    by_id = torch.argsort(cand64)
+    vals, order = torch.sort(L[:, by_id], dim=1, stable=True)
+    kk = min(k, L.shape[1])
+    vals, ids = vals[:, :kk].contiguous(), cand64[by_id][order[:, :kk]]
+    if kk < k:
+        vals = torch.cat([vals, torch.full((L.shape[0], k - kk), float("inf"), device=L.device)], 1)
+        ids = torch.cat([ids, torch.full((L.shape[0], k - kk), -1, dtype=torch.int64, device=L.device)], 1)
+    ids[vals == float("inf")] = -1
+    bad = torch.isnan(L).any(1)
+    vals[bad] = float("nan")
+    ids[bad] = -1
+    return ids, vals
+
+
+@torch.no_grad()
+def predict_links(embeddings: torch.Tensor, queries, candidates, k: int, known_triples=None, side: str = "tail",
+                  model: str = "complex", batch: int = None, fused: bool = None, planes=None, max_norm: float = 1.0):
+    """Top-k link prediction: for every query (fixed entity, relation) the first k pops of the reference's heap
+    (holE.py:427-469) over `candidates` -- ascending loss E = sigmoid(score), ties by entity id.  side="tail" predicts
+    (fixed, ?, relation), "head" (?, fixed, relation).  known_triples (an [n,3] array or a KnownIndex for this side):
+    known-true candidates are skipped, as the reference's filtered ranks skip them.
+    Returns (ids int64 [n,k], losses float32 [n,k]) numpy arrays, rows in the queries' order; a row with fewer eligible
+    candidates is padded with -1 / +inf.
+    fused (default: whenever embedding_dim has the split-precision sweep, % 8 == 0 in 56 ... 288): the list is selected
+    inside the candidate sweep (hole.topk_candidates) and no [n, K] matrix exists; k > hole.topk_max_k() takes the same
+    sweep's losses (rank_candidates' scores) in chunks of 1024 rows, sorted on the device.  fused=False: the losses of
+    score_candidates, sorted the same way in chunks of 1024 rows.
+    model: "complex", "hole" (a real-valued HolE table: a copy is transformed once) or "hole_spectral"; HolE needs the
+    fused sweep.  planes: hole.RankPlanes of (embeddings, candidates) shared between calls.  The copy model="hole" makes
+    is new on every call, so planes cannot be built for it: with HolE and planes, transform the table once
+    (hole.hole_to_spectral), build the planes with model="hole_spectral" and pass that table and model here."""
+    assert side in ("tail", "head")
+    if model not in ("complex", "hole", "hole_spectral"):
+        raise ValueError(f"unknown model {model!r}")
+    k = int(k)
+    if k < 1:
+        raise ValueError("k must be >= 1")
+    dev = embeddings.device
+    N, d = embeddings.shape
+    can_fuse = _split_f16_ok(d, max_norm)
+    if fused is None:
+        fused = can_fuse
+    if fused and not can_fuse:
+        raise ValueError("the fused top-k needs embedding_dim % 8 == 0 in 56 ... 288 and max_norm <= 8")
+    if model != "complex":
+        if not fused:
+            raise ValueError("HolE prediction needs the fused sweep: embedding_dim % 8 == 0 in 56 ... 288")
+        if model == "hole":
+            if planes is not None:
+                raise ValueError("planes with model='hole': build them for a hole_to_spectral table and pass that "
+                                 "table with model='hole_spectral'")
+            embeddings = H.hole_to_spectral(embeddings.detach().clone())
+        model = "hole_spectral"
+    q = np.asarray(queries, dtype=np.int64).reshape(-1, 2)
+    cand_np = np.asarray(candidates, dtype=np.int64).reshape(-1)
+    if cand_np.size == 0:
+        raise ValueError("candidates must not be empty")
+    if cand_np.min() < 0 or cand_np.max() >= N or np.unique(cand_np).size != cand_np.size:
+        raise ValueError("candidates must be distinct table rows")
+    if q.size and (q.min() < 0 or q.max() >= N):
+        raise ValueError("a query id is outside the table")
+    cand = torch.as_tensor(cand_np.astype(np.int32)).to(dev)
+    cand64 = cand.to(torch.int64)
+    K = cand.numel()
+    pos_of = torch.full((N,), -1, dtype=torch.int64, device=dev)
+    pos_of[cand64] = torch.arange(K, device=dev)
+    index = None
+    if known_triples is not None:
+        index = known_triples if isinstance(known_triples, KnownIndex) else KnownIndex(known_triples, N, side, dev)
+    if fused and planes is None:
+        planes = H.RankPlanes(embeddings, cand, max_norm=max_norm, model=model)
+    if planes is not None:
+        if planes.cand.numel() != K or not bool(torch.equal(planes.cand.to(dev), cand)):
+            raise ValueError("`planes` were built for another candidate list")
+        cand = planes.cand
+    in_kernel = fused and k <= H.topk_max_k()
+    if batch is None:
+        batch = 1 << 17 if in_kernel else 1024
+    if not in_kernel:
+        batch = min(batch, 1024)                 # a [batch, K] loss matrix exists per chunk
+    ids_all, loss_all = [], []
+    for s0 in range(0, len(q), batch):
+        chunk = torch.as_tensor(q[s0:s0 + batch]).to(dev)
+        fixed, rel = chunk[:, 0], chunk[:, 1]
+        hr = torch.stack([fixed, rel], 1).to(torch.int32)
+        off = rc = None
+        if index is not None:
+            off, rc = index.cells(fixed, rel, pos_of, K)
+        if in_kernel:
+            ids, losses = H.topk_candidates(embeddings, hr, cand, k, known_off=off, known_rc=rc, cand_is_head=(side == "head"),
+                                            max_norm=max_norm, model=model, planes=planes)
+            ids = ids.to(torch.int64)
+        else:
+            if fused:                            # the fused sweep's own losses (MODE 1 of the rank kernel)
+                tid = cand[:1].expand(hr.shape[0]).contiguous()
+                losses = H.rank_candidates(embeddings, hr, tid, cand, cand_is_head=(side == "head"), max_norm=max_norm,
+                                           return_scores=True, model=model, planes=planes)[-1]
+            else:
+                losses = H.score_candidates(embeddings, hr, cand, cand_is_head=(side == "head"), max_norm=max_norm)
+            ids, losses = _topk_of_losses(losses, cand64, k, _known_cells_rc(off, rc, K) if off is not None else None)
+        ids_all.append(ids.cpu().numpy())
+        loss_all.append(losses.cpu().numpy())
+    if not ids_all:
+        return np.zeros((0, k), dtype=np.int64), np.zeros((0, k), dtype=np.float32)
+    return np.concatenate(ids_all).astype(np.int64), np.concatenate(loss_all).astype(np.float32)
+
+
+def inference_lines(head: int, relation: int, pop_ids, pop_losses, in_sample_set) -> list:
+    """The lines of the reference's inference_results.tsv (holE.py:451-453) for one query's pops, in pop order:
+    'loss, head, tail, relation, in_sample' with in_sample = the tail completes a known (train / valid) triple."""
+    return ['{:.6f}\t{}\t{}\t{}\t{}\n'.format(float(l), int(head), int(t), int(relation), int(t) in in_sample_set)
+            for t, l in zip(pop_ids, pop_losses)]
+
+
+@torch.no_grad()
+def predict_inference_results(embeddings: torch.Tensor, data, predict_k: int, infer_threshold: float, path: str,
+                              model: str = "complex", log=print) -> dict:
+    """The prediction output of the reference's --infer (holE.py:427-469) for the distinct (head, relation) pairs of the
+    test triples, in order of first appearance, over every entity row: for each query whose lowest loss is below
+    infer_threshold (is_confident, holE.py:436-438), every pop up to and including the predict_k-th filtered pop --
+    known-true (train / valid) pops interleaved with in_sample = True -- as the reference's lines, written to `path`
+    (truncated first; the reference appends to ./inference_results.tsv).
+    Exact: the filtered top-k gives the k-th filtered pop; its raw position m (rank_candidates_vs_loss, or the stored
+    scores off the fused range) gives the raw top-m that holds every line."""
+    R, N = data.relation_count, data.entity_count
+    cand = np.arange(R, N, dtype=np.int64)
+    test = np.asarray(data.test_array, dtype=np.int64)
+    hr_all = test[:, [0, 2]]
+    _, first = np.unique(hr_all, axis=0, return_index=True)
+    queries = hr_all[np.sort(first)]
+    parts = [a for a in (data.triples, data.validation_triples) if a is not None]
+    known = np.concatenate(parts, 0) if parts else None
+    if model == "hole":
+        embeddings, model = H.hole_to_spectral(embeddings.detach().clone()), "hole_spectral"
+    dev = embeddings.device
+    fused = _split_f16_ok(embeddings.shape[1], 1.0)
+    planes = H.RankPlanes(embeddings, torch.as_tensor(cand).to(dev), model=model) if fused else None
+    kw = dict(model=model, fused=fused, planes=planes)
+    K = int(predict_k)
+    fid, floss = predict_links(embeddings, queries, cand, K, known_triples=KnownIndex(known, N, "tail", dev), **kw)
+    # m = raw position of the K-th filtered pop (every pop when fewer than K candidates are eligible)
+    m = np.full(len(queries), len(cand), dtype=np.int64)
+    rows = np.nonzero(fid[:, K - 1] >= 0)[0]
+    if rows.size:
+        hr = torch.as_tensor(queries[rows]).to(dev).to(torch.int32)
+        ref_id = torch.as_tensor(fid[rows, K - 1]).to(dev)
+        ref_loss = torch.as_tensor(floss[rows, K - 1]).to(dev)
+        if fused:
+            nb, _ = H.rank_candidates_vs_loss(embeddings, hr, ref_id, ref_loss, planes.cand, model=model, planes=planes)
+            m[rows] = nb.cpu().numpy().astype(np.int64) + 1
+        else:
+            c64 = torch.as_tensor(cand).to(dev)
+            for s0 in range(0, rows.size, 1024):
+                sc = H.score_candidates(embeddings, hr[s0:s0 + 1024], c64)
+                rl, ri = ref_loss[s0:s0 + 1024, None], ref_id[s0:s0 + 1024, None]
+                m[rows[s0:s0 + 1024]] = (((sc < rl) | ((sc == rl) & (c64[None, :] < ri))).sum(1) + 1).cpu().numpy()
+    # the raw pops: rows sorted by m and cut into chunks, each predicted with its own longest m -- up to 16384 rows
+    # while that fits the fused kernel, 1024 rows (the fallback's [rows, K] losses) beyond it
+    raw_id = [None] * len(queries)
+    raw_loss = [None] * len(queries)
+    order = np.argsort(m, kind="stable")
+    kmax = H.topk_max_k()
+    s0 = 0
+    while s0 < order.size:
+        rows_c = 1 << 14 if m[order[s0]] <= kmax else 1024
+        chunk = order[s0:s0 + rows_c]
+        if m[chunk[-1]] > kmax and m[chunk[0]] <= kmax:      # (the fused chunk ends where m passes kmax)
+            chunk = chunk[m[chunk] <= kmax]
+        ids, ls = predict_links(embeddings, queries[chunk], cand, int(m[chunk[-1]]), **kw)
+        for j, i in enumerate(chunk):
+            raw_id[i], raw_loss[i] = ids[j, :m[i]], ls[j, :m[i]]
+        s0 += chunk.size
+    n_conf = n_lines = 0
+    with open(path, "w") as out:
+        for i, (h, r) in enumerate(queries):
+            if not raw_loss[i][0] < infer_threshold:       # is_confident: the lowest loss of the sweep (holE.py:438)
+                continue
+            n_conf += 1
+            lines = inference_lines(h, r, raw_id[i], raw_loss[i], data.true_triples[int(h)][int(r)])
+            out.writelines(lines)
+            n_lines += len(lines)
+    log(f"top-{K} prediction: {len(queries)} queries, {n_conf} confident (lowest loss < {infer_threshold}), "
+        f"{n_lines} lines written to {path}")
+    return {"queries": int(len(queries)), "confident": int(n_conf), "lines": int(n_lines)}
+
+
 # ------------------------------------------------------------------ translation models (TransE / H / D, TransR)
 def _translation_test(model, test) -> np.ndarray:
     """The test rows as int64 [n,3] (h, t, r), ids checked against the model's tables on the host."""

@@ -440,6 +440,69 @@ def rank_candidates_vs_loss(embeddings: torch.Tensor, fixed_and_relation: torch.
     return n_before, n_known
 
 
+def topk_max_k() -> int:
+    """Largest k the fused top-k sweep (ge_topk_1vK_planes) takes."""
+    return int(_lib.load().ge_topk_max_k())
+
+
+def topk_candidates(embeddings: torch.Tensor, fixed_and_relation: torch.Tensor, candidates: torch.Tensor, k: int, *,
+                    known_off: Optional[torch.Tensor] = None, known_rc: Optional[torch.Tensor] = None,
+                    cand_is_head: bool = False, max_norm: float = 1.0, model: str = "complex",
+                    planes: Optional[RankPlanes] = None):
+    """The first k pops of the reference's heap (holE.py:427-469: ascending loss, ties by entity id) per query row
+    (fixed entity, relation) among `candidates`, on the split-precision sweep (ge_topk_1vK_planes) -- no [B,K] matrix.
+    With known_off / known_rc (as rank_candidates takes them) known-true candidates are skipped.  Returns
+    (ids int32 [B,k], losses float32 [B,k]); a row with fewer eligible candidates is padded with -1 / +inf, a row whose
+    ids are out of range is -1 / NaN.  The losses are bit-equal to rank_candidates(..., return_scores=True)'s.
+    embedding_dim % 8 == 0 in 56 ... 288, max_norm <= 8, 1 <= k <= topk_max_k(); otherwise GeError (GE_ENOTSUP)."""
+    if model not in ("complex", "hole_spectral"):
+        raise ValueError("topk_candidates: model must be 'complex' or 'hole_spectral' (transform a real HolE table first)")
+    emb = _table(embeddings)
+    for name, t in (("fixed_and_relation", fixed_and_relation), ("candidates", candidates)):
+        _need_cuda(t, name)
+    hr = fixed_and_relation.to(torch.int32).contiguous()
+    cand = candidates.to(torch.int32).contiguous().view(-1)
+    if hr.dim() != 2 or hr.shape[1] != 2:
+        raise ValueError("fixed_and_relation must be [B,2] (entity, relation)")
+    B, K, N = hr.shape[0], cand.numel(), emb.shape[0]
+    k = int(k)
+    if k < 1:
+        raise ValueError("k must be >= 1")
+    if K < 1:
+        raise ValueError("candidates must not be empty")
+    if bool(((cand < 0) | (cand >= N)).any()):
+        raise ValueError("a candidate id is outside the table")
+    if torch.unique(cand).numel() != K:
+        raise ValueError("candidates must be distinct")
+    if B and bool(((hr < 0) | (hr >= N)).any()):
+        raise ValueError("a fixed entity or relation id is outside the table")
+    if (known_off is None) != (known_rc is None):
+        raise ValueError("known_off and known_rc come together")
+    if known_off is not None:
+        n_tiles = ((B + 127) // 128) * ((K + 127) // 128)
+        if known_off.dtype != torch.int32 or known_off.numel() != n_tiles + 1 or known_rc.dtype != torch.int16:
+            raise ValueError("known_off must be int32 [tiles+1], known_rc int16 (row%128 << 7 | col%128)")
+    pl = None
+    if planes is not None and planes.buffer is not None:
+        same = planes.key == (emb.data_ptr(), emb.shape[0], emb.shape[1], planes.cand.data_ptr(), K, float(max_norm), model)
+        if same and cand.data_ptr() != planes.cand.data_ptr():
+            same = bool(torch.equal(planes.cand, cand))
+        if not same:
+            raise ValueError("topk_candidates: `planes` were built for another table / candidate list / max_norm / model")
+        cand, pl = planes.cand, planes.buffer.data_ptr()
+    ids = torch.empty(B, k, dtype=torch.int32, device=emb.device)
+    losses = torch.empty(B, k, dtype=torch.float32, device=emb.device)
+    if B == 0:
+        return ids, losses
+    nbytes = int(_lib.load().ge_topk_workspace_bytes(B, K, k))
+    ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=emb.device)
+    _lib.call("ge_topk_1vK_planes", emb.data_ptr(), N, emb.shape[1], hr.data_ptr(), B, cand.data_ptr(), K, max_norm,
+              _MODELS[model], int(cand_is_head), known_off.data_ptr() if known_off is not None else None,
+              known_rc.data_ptr() if known_rc is not None else None, k, ids.data_ptr(), losses.data_ptr(), pl,
+              ws.data_ptr(), ws.numel(), _stream())
+    return ids, losses
+
+
 def confident_rows(embeddings: torch.Tensor, fixed_and_relation: torch.Tensor, candidates: torch.Tensor, infer_threshold: float,
                    **kw) -> torch.Tensor:
     """is_confident of holE.py:436-438 for every row of a sweep: min over the candidates of the loss < infer_threshold,

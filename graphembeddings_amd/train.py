@@ -51,6 +51,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('--save_embeddings', action='store_true', help='Output the embeddings to stdout.')
     p.add_argument('--infer', action='store_true', help='Link-prediction evaluation from the latest checkpoint.')
     p.add_argument('--infer_threshold', type=float, default=0.05, help='Max loss to save triples')
+    p.add_argument('--predict_k', type=int, default=0,
+                   help='With --infer: also write <output_dir>/inference_results.tsv, every pop up to the K-th filtered '
+                        'prediction of each confident (head, relation) test query (0: no predictions).')
     p.add_argument('--min_mentions', type=int, default=50000,
                    help='The minimum number of mentions for an entity to be a viable candidate in inference.')
     # extensions
@@ -226,12 +229,22 @@ def infer_triples(FLAGS, log=print) -> dict:
     emb, _ = load_checkpoint(FLAGS.output_dir)
     # --model hole: the checkpoint holds the real-valued table; ranks use the HolE score (README.md:42), not ComplEx
     # positions are recorded for confident sweeps only: lowest loss < --infer_threshold (holE.py:436-438, 464-466, 616)
-    return E.evaluate_fb15k_style(emb, data, both_sides=True, model=FLAGS.model, infer_threshold=FLAGS.infer_threshold)
+    out = E.evaluate_fb15k_style(emb, data, both_sides=True, model=FLAGS.model, infer_threshold=FLAGS.infer_threshold)
+    if FLAGS.predict_k > 0:
+        # the reference's prediction lines (holE.py:445-456), into the output directory (truncated), not appended to ./
+        E.predict_inference_results(emb, data, FLAGS.predict_k, FLAGS.infer_threshold,
+                                    os.path.join(FLAGS.output_dir, 'inference_results.tsv'), model=FLAGS.model, log=log)
+    return out
 
 
 def main(argv=None):
     FLAGS, _unparsed = build_parser().parse_known_args(argv)
     world = int(os.environ.get('WORLD_SIZE', '1'))
+    if FLAGS.predict_k < 0:
+        raise SystemExit('--predict_k must be >= 0')
+    if FLAGS.predict_k and (FLAGS.gpus > 1 or world > 1):
+        raise SystemExit('--predict_k runs on one GPU: top-k prediction over a row-sharded table is not implemented '
+                         '(drop --gpus or --predict_k)')
     if FLAGS.gpus > 1 and 'WORLD_SIZE' not in os.environ and not FLAGS.save_embeddings:
         # no launcher: this process (which has not touched the GPU) becomes the parent of --gpus ranks of itself
         from . import launch

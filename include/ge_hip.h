@@ -10,7 +10,7 @@
  * that make it usable from a GPU training loop: every entry point returns an int status
  * (0 = ok, <0 = -errno style argument error, >0 = hipError_t), takes the hipStream_t it must
  * enqueue on (as void*), never synchronises, allocates no device memory of its own -- with ONE exception,
- * stated where it applies: ge_rank_1vK / ge_complex_rank_1vK / ge_rank_1vK_vs_loss without a `planes` buffer and
+ * stated where it applies: ge_rank_1vK / ge_complex_rank_1vK / ge_rank_1vK_vs_loss / ge_topk_1vK_planes without a `planes` buffer and
  * ge_complex_score_1vK on large sweeps build the candidates' fp16 planes in a stream-ordered allocation
  * (hipMallocAsync / hipFreeAsync on `stream`, nothing outlives the call; pass ge_rank_planes' buffer to avoid it) --
  * and keeps no global state (the only state is inside the explicit ge_train_pipeline handle, see ge_train_steps).
@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define GE_VERSION 350 /* 0.3.5: + ge_transx_rank / ge_transr_rank (link-prediction ranks of the translation models) */
+#define GE_VERSION 360 /* 0.3.6: + ge_topk_1vK_planes (top-k tail / head prediction of ComplEx and HolE) */
 
 /* argument errors (negative, -errno style) */
 #define GE_EINVAL (-22)  /* bad dimension / null pointer / misaligned buffer */
@@ -369,6 +369,31 @@ int ge_rank_1vK_vs_loss(const float* table, int64_t N, int32_t d, const int32_t*
                         const float* ref_loss, const int32_t* cand, int64_t K, float max_norm, int model, int cand_is_head,
                         const int32_t* known_off, const uint16_t* known_rc, int32_t* n_before, int32_t* n_known_before,
                         const void* planes, void* stream);
+
+/* --- top-k prediction straight out of the split-precision sweep: for query row i = hr[i] = (fixed entity, relation) over
+ * the K candidates `cand` (distinct entity rows; cand_is_head = 0: the candidate is the tail, 1: the head), the first k
+ * pops of the reference's heap (holE.py:427-469): ascending (E_ic, cand_c) with E = sigmoid(score), ties by entity id
+ * (the tuple order of holE.py:434, as ge_rank_1vK ranks).
+ *     out_id[i*k + j], out_loss[i*k + j]   the j-th pop: its entity id and its loss
+ * Filtered (known_off / known_rc exactly as ge_rank_1vK takes them): known-true candidates are skipped -- the first k
+ * filtered pops.  The losses, and so the order, are bit-equal to the ones ge_rank_1vK_planes stores in scores_out for the
+ * same cells (the same MFMA loop over the same planes, then rank_sigmoid(acc * 2^-16)): the ranks of the returned
+ * candidates agree with ge_rank_1vK's by construction.
+ * A row with fewer than k eligible candidates is padded with id -1, loss +inf; a row whose fixed entity or relation is
+ * outside [0, N) gets id -1, loss NaN in every slot.
+ * Scope: GE_MODEL_COMPLEX and GE_MODEL_HOLE_SPECTRAL (a real-valued HolE table is GE_ENOTSUP: transform a copy), the
+ * split-precision range (embedding_dim % 8 == 0 in 56 ... 288, max_norm <= 8), 1 <= k <= ge_topk_max_k() (128);
+ * otherwise GE_ENOTSUP.  k < 1, K < 1 or a null pointer: GE_EINVAL.
+ * Memory: no [B,K] matrix; the caller passes `workspace` (256-byte aligned) of ge_topk_workspace_bytes(B, K, k) bytes
+ * (GE_ENOMEM when smaller) -- per row a pool of candidate keys, and partial lists when few rows leave the GPU idle and
+ * the candidates are cut into ranges.  `planes`: ge_rank_planes' buffer for (table, cand, max_norm, model), or NULL --
+ * then built per call in a stream-ordered allocation, as ge_rank_1vK_planes does. */
+int ge_topk_max_k(void);
+size_t ge_topk_workspace_bytes(int64_t B, int64_t K, int32_t k);
+int ge_topk_1vK_planes(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* cand,
+                       int64_t K, float max_norm, int model, int cand_is_head, const int32_t* known_off,
+                       const uint16_t* known_rc, int32_t k, int32_t* out_id, float* out_loss, const void* planes,
+                       void* workspace, size_t workspace_bytes, void* stream);
 
 /* --- the known_off / known_rc lists of ge_rank_1vK from a sorted index of the known-true triples (the filter of
  * holE.py:454-463, built by the reference as a dict of sets, holE.py:413-422).  known_key [M] ascending = fixed entity *
