@@ -6,7 +6,6 @@
 
 using namespace ge;
 
-static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 static inline bool ok_table(const void* t, int64_t N, int32_t d) { return t != nullptr && N > 0 && d > 0; }
 static inline bool max_norm_ok(float m) { return m > 0.f; }
 
@@ -246,6 +245,13 @@ static inline int transx_tables_ok(int model, const void* ent, int64_t E, const 
   return 0;
 }
 static inline bool transx_batch_ok(int64_t B) { return B > 0 && B <= ((int64_t)1 << 31) / 5 - 1; }
+// the triples and Bernoulli tables a draw reads: T rows fit its 32-bit row pick, the four arrays are there when
+// n_known > 0
+static inline bool sampler_ok(const int32_t* triples, int64_t T, const uint32_t* tail_threshold, int64_t n_known,
+                              const int64_t* bh_key, const int32_t* bh_ent, const int64_t* bt_key, const int32_t* bt_ent) {
+  return triples && T > 0 && T <= ((int64_t)1 << 32) && tail_threshold && n_known >= 0 &&
+         (n_known == 0 || (bh_key && bh_ent && bt_key && bt_ent));
+}
 
 int ge_transx_max_dim(void) { return transx_max_dim(); }
 
@@ -279,9 +285,8 @@ int ge_transx_draw_batch(const int32_t* triples, int64_t T, int64_t B, const int
                          const int64_t* bt_key, const int32_t* bt_ent, int64_t n_known, const uint32_t* tail_threshold,
                          int32_t n_rel, int32_t n_ent, uint64_t seed, uint64_t step, int32_t* pos, int32_t* neg,
                          void* stream) {
-  if (!triples || T <= 0 || T > ((int64_t)1 << 32) || B < 0 || !tail_threshold || n_rel <= 0 || n_ent <= 0) return GE_EINVAL;
-  if (n_known < 0 || (n_known > 0 && (!bh_key || !bh_ent || !bt_key || !bt_ent))) return GE_EINVAL;
-  if (B > 0 && (!pos || !neg)) return GE_EINVAL;
+  if (!sampler_ok(triples, T, tail_threshold, n_known, bh_key, bh_ent, bt_key, bt_ent)) return GE_EINVAL;
+  if (B < 0 || n_rel <= 0 || n_ent <= 0 || (B > 0 && (!pos || !neg))) return GE_EINVAL;
   return transx_draw_launch(triples, T, B, bh_key, bh_ent, bt_key, bt_ent, n_known, tail_threshold, n_rel, n_ent, seed,
                             step, pos, neg, (hipStream_t)stream);
 }
@@ -294,8 +299,7 @@ int ge_transx_train_steps(int model, int l1, float* ent, int64_t n_ent, float* r
                           size_t workspace_bytes, void* stream) {
   if (int rc = transx_tables_ok(model, ent, n_ent, rel, n_rel, normal, ent_transfer, rel_transfer, d)) return rc;
   if (!transx_batch_ok(B) || n_steps < 0 || !losses || !workspace || ((uintptr_t)workspace & 255)) return GE_EINVAL;
-  if (!triples || T <= 0 || T > ((int64_t)1 << 32) || !tail_threshold) return GE_EINVAL;
-  if (n_known < 0 || (n_known > 0 && (!bh_key || !bh_ent || !bt_key || !bt_ent))) return GE_EINVAL;
+  if (!sampler_ok(triples, T, tail_threshold, n_known, bh_key, bh_ent, bt_key, bt_ent)) return GE_EINVAL;
   return transx_train_steps_run(model, l1, ent, n_ent, rel, n_rel, normal, ent_transfer, rel_transfer, d, triples, T,
                                 bh_key, bh_ent, bt_key, bt_ent, n_known, tail_threshold, seed, first_step, n_steps, B,
                                 margin, lr, losses, workspace, workspace_bytes, (hipStream_t)stream);
@@ -355,8 +359,7 @@ int ge_transr_train_steps(int l1, float* ent, int64_t n_ent, float* rel, float* 
   if (int rc = transr_tables_ok(ent, n_ent, rel, rel_matrix, n_rel, dim_e, dim_r)) return rc;
   if (!transr_batch_ok(B) || n_steps < 0 || !losses || !workspace || ((uintptr_t)workspace & 255)) return GE_EINVAL;
   if (!adam_ok(b1, b2, eps, first_t, m, v)) return GE_EINVAL;
-  if (!triples || T <= 0 || T > ((int64_t)1 << 32) || !tail_threshold) return GE_EINVAL;
-  if (n_known < 0 || (n_known > 0 && (!bh_key || !bh_ent || !bt_key || !bt_ent))) return GE_EINVAL;
+  if (!sampler_ok(triples, T, tail_threshold, n_known, bh_key, bh_ent, bt_key, bt_ent)) return GE_EINVAL;
   return transr_train_steps_run(l1, ent, n_ent, rel, rel_matrix, n_rel, dim_e, dim_r, m, v, triples, T, bh_key, bh_ent,
                                 bt_key, bt_ent, n_known, tail_threshold, seed, first_step, n_steps, B, margin, lr, b1,
                                 b2, eps, first_t, losses, workspace, workspace_bytes, (hipStream_t)stream);

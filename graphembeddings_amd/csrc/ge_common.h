@@ -4,6 +4,8 @@
 #include <hip/hip_ext.h>
 #include <stdint.h>
 
+#include <initializer_list>
+
 #include "../../include/ge_hip.h"
 
 namespace ge {
@@ -75,6 +77,22 @@ inline int grid_for(int64_t units, int units_per_block) {
 inline int launch_status() {
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : (int)e;
+}
+
+// host-side workspace layout: v rounded up to a multiple of a
+inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// bits of a radix-sort key that holds every value in [0, n] (a sentinel n included), at most 32
+inline unsigned sort_key_bits(int64_t n) {
+  unsigned b = 1;
+  while (b < 32 && ((uint64_t)1 << b) <= (uint64_t)n) ++b;
+  return b;
+}
+
+// every pointer 16-byte aligned (a null one counts as aligned): the float4 paths' test
+inline bool aligned16(std::initializer_list<const void*> ptrs) {
+  for (const void* p : ptrs) if ((uintptr_t)p & 15) return false;
+  return true;
 }
 
 // Philox4x32-10, the sampler's stream (stated in oracle/hole_oracle.py).

@@ -182,6 +182,20 @@ int transx_draw_launch(const int32_t* triples, int64_t T, int64_t B, const int64
                        const int64_t* bt_key, const int32_t* bt_ent, int64_t n_known, const uint32_t* tail_threshold,
                        int32_t n_rel, int32_t n_ent, uint64_t seed, uint64_t step, int32_t* pos, int32_t* neg,
                        hipStream_t st);
+// The native loop of transx_train_steps_run and transr_train_steps_run: for s in [0, n_steps), draw step
+// first_step + s's batch into pos / neg, then run step(s) on it; stops at the first nonzero code.
+template <class Step>
+int draw_then_step(const int32_t* triples, int64_t T, int64_t B, const int64_t* bh_key, const int32_t* bh_ent,
+                   const int64_t* bt_key, const int32_t* bt_ent, int64_t n_known, const uint32_t* tail_threshold,
+                   int32_t n_rel, int32_t n_ent, uint64_t seed, uint64_t first_step, int64_t n_steps, int32_t* pos,
+                   int32_t* neg, hipStream_t st, Step step) {
+  for (int64_t s = 0; s < n_steps; ++s) {
+    int rc = transx_draw_launch(triples, T, B, bh_key, bh_ent, bt_key, bt_ent, n_known, tail_threshold, n_rel, n_ent,
+                                seed, first_step + (uint64_t)s, pos, neg, st);
+    if (rc || (rc = step(s))) return rc;
+  }
+  return 0;
+}
 int transx_train_steps_run(int model, int l1, float* ent, int64_t E, float* rel, int64_t R, float* normal,
                            float* ent_transfer, float* rel_transfer, int32_t d, const int32_t* triples, int64_t T,
                            const int64_t* bh_key, const int32_t* bh_ent, const int64_t* bt_key, const int32_t* bt_ent,

@@ -374,12 +374,10 @@ __global__ __launch_bounds__(kPrepThreads) void order_write_kernel(
 }
 
 // ---------------------------------------------------------------- host
-static inline size_t align_up_sz(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 // scratch of one sort over n steps of n_sub tiles of P keys: two key arrays (ping-pong) + the digit counts of one pass
 size_t sort_scratch_bytes(int64_t n, int64_t n_sub, int64_t P) {
-  const size_t keys = align_up_sz(sizeof(unsigned long long) * (size_t)n * (size_t)n_sub * (size_t)P, 256);
-  const size_t hist = align_up_sz(sizeof(unsigned) * (size_t)n * kMaxRadix * (size_t)n_sub, 256);
+  const size_t keys = align_up(sizeof(unsigned long long) * (size_t)n * (size_t)n_sub * (size_t)P, 256);
+  const size_t hist = align_up(sizeof(unsigned) * (size_t)n * kMaxRadix * (size_t)n_sub, 256);
   return 2 * keys + hist + 256;        // + the `limit` word of a sort whose key kernel reports its largest row field
 }
 static unsigned* sort_scratch_limit(void* scratch, int64_t n, int64_t n_sub, int64_t P) {
@@ -392,7 +390,7 @@ unsigned long long* sort_scratch_keys(void* scratch) { return reinterpret_cast<u
 int sort_tiles_launch(void* scratch, int64_t n, int64_t n_sub, int64_t P, int64_t n_rows, hipStream_t st,
                       const unsigned* limit, const unsigned long long** sorted) {
   const SortBits sb = sort_bits_for(n_rows);
-  const size_t keys_bytes = align_up_sz(sizeof(unsigned long long) * (size_t)n * (size_t)n_sub * (size_t)P, 256);
+  const size_t keys_bytes = align_up(sizeof(unsigned long long) * (size_t)n * (size_t)n_sub * (size_t)P, 256);
   unsigned long long* ka = reinterpret_cast<unsigned long long*>(scratch);
   unsigned long long* kb = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(scratch) + keys_bytes);
   unsigned* hist = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(scratch) + 2 * keys_bytes);

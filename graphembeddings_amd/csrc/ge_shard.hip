@@ -110,12 +110,10 @@ __global__ __launch_bounds__(kPrepThreads) void owner_keys_kernel(
   }
 }
 
-static inline size_t align_up_sz(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 // ---------------------------------------------------------------- host
 size_t shard_plan_scratch_bytes(int64_t B, int64_t S) {
   const PrepLayout L = prep_layout(B);
-  return sort_scratch_bytes(S, L.n_sub, L.P) + align_up_sz(sizeof(int32_t) * (size_t)S * (size_t)L.n_sub, 256);
+  return sort_scratch_bytes(S, L.n_sub, L.P) + align_up(sizeof(int32_t) * (size_t)S * (size_t)L.n_sub, 256);
 }
 
 int shard_plan_launch(const int32_t* pos, const int32_t* neg, int64_t S, int64_t B, int64_t N, int32_t G, int32_t rank,

@@ -616,10 +616,8 @@ static int apply_sorted_launch(float* table, int d, const PrepLayout& L, const i
   return apply_items_launch(table, d, geom_of(L), step_rec, gidx, gval, 0x7FFFFFFF, nullptr, st, ev_start, ev_stop, det);
 }
 
-static inline size_t align_up_sz(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 size_t hinge_ws_bytes(int64_t B, int32_t d) {
-  return align_up_sz(sizeof(int32_t) * 6 * (size_t)B, 256) + align_up_sz(sizeof(float) * 6 * (size_t)B * (size_t)d, 256);
+  return align_up(sizeof(int32_t) * 6 * (size_t)B, 256) + align_up(sizeof(float) * 6 * (size_t)B * (size_t)d, 256);
 }
 
 static bool train_fast_ok(int64_t B, int32_t d) { return B >= 1 && B <= (int64_t)1 << 24 && d <= 1024; }
@@ -642,7 +640,7 @@ static int64_t prep_chunk_steps(int64_t B, int64_t negs = 0) {
 // round again (normally 4 steps later, > the 32 MB of L2 in between) its lines have been evicted and the
 // stores take the fast path.
 static size_t grad_region_bytes(int64_t B, int32_t d) {
-  return align_up_sz(sizeof(float) * 6 * (size_t)B * (size_t)d, 256);
+  return align_up(sizeof(float) * 6 * (size_t)B * (size_t)d, 256);
 }
 static int grad_ring(int64_t B, int32_t d) {
   const size_t reg = grad_region_bytes(B, d);
@@ -655,10 +653,10 @@ static int grad_ring(int64_t B, int32_t d) {
   return (int)r;
 }
 static size_t train_grad_bytes(int64_t B, int32_t d) {
-  return align_up_sz(sizeof(int32_t) * 6 * (size_t)B, 256) + (size_t)grad_ring(B, d) * grad_region_bytes(B, d);
+  return align_up(sizeof(int32_t) * 6 * (size_t)B, 256) + (size_t)grad_ring(B, d) * grad_region_bytes(B, d);
 }
 static size_t prep_chunk_bytes(int64_t B, int64_t negs = 0) {
-  return align_up_sz(sizeof(int32_t) * (size_t)prep_chunk_steps(B, negs) * (size_t)prep_layout(B, negs).stride, 256);
+  return align_up(sizeof(int32_t) * (size_t)prep_chunk_steps(B, negs) * (size_t)prep_layout(B, negs).stride, 256);
 }
 size_t train_ws_bytes(int64_t B, int32_t d) {
   if (!train_fast_ok(B, d)) return hinge_ws_bytes(B, d);
@@ -879,7 +877,7 @@ int train_steps_run(float* table, int64_t N, int32_t d, const int32_t* triples, 
   const bool hole_direct = (model == GE_MODEL_HOLE && (d & 1)) || model == GE_MODEL_HOLE_DIRECT;
   if (transform) { int rc = hole_spectral_launch(table, N, d, /*inverse=*/0, st); if (rc) return rc; }
   int32_t* gidx = reinterpret_cast<int32_t*>(workspace);
-  float* gval0 = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + align_up_sz(sizeof(int32_t) * 6 * (size_t)B, 256));
+  float* gval0 = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + align_up(sizeof(int32_t) * 6 * (size_t)B, 256));
   const bool fast = train_fast_ok(B, d) && workspace_bytes >= train_ws_bytes(B, d);
   const int ring = fast ? grad_ring(B, d) : 1;
   const size_t region_floats = grad_region_bytes(B, d) / sizeof(float);
@@ -954,11 +952,11 @@ int train_steps_run(float* table, int64_t N, int32_t d, const int32_t* triples, 
 // vector the caller keeps (all of them with keep_all_losses, else the last).
 size_t train_logloss_ws_bytes(int64_t B, int32_t negs, int32_t d) {
   const size_t M = (size_t)(1 + negs) * (size_t)B;
-  const size_t region = align_up_sz(sizeof(float) * 3 * M * (size_t)d, 256);
+  const size_t region = align_up(sizeof(float) * 3 * M * (size_t)d, 256);
   size_t ring = ((size_t)64 << 20) / region + 1;
   if (ring < 2) ring = 2;
   if (ring > 8) ring = 8;
-  return 256 + align_up_sz(sizeof(int32_t) * 3 * M, 256) + ring * region + 2 * prep_chunk_bytes(B, negs) +
+  return 256 + align_up(sizeof(int32_t) * 3 * M, 256) + ring * region + 2 * prep_chunk_bytes(B, negs) +
          prep_big_scratch_bytes(B, negs, prep_chunk_steps(B, negs));
 }
 
@@ -971,14 +969,14 @@ int train_logloss_run(float* table, int64_t N, int32_t d, const int32_t* triples
   if (n_steps <= 0) return 0;
   if (workspace_bytes < train_logloss_ws_bytes(B, negs, d)) return GE_ENOMEM;
   const size_t M = (size_t)(1 + negs) * (size_t)B;
-  const size_t region = align_up_sz(sizeof(float) * 3 * M * (size_t)d, 256);
+  const size_t region = align_up(sizeof(float) * 3 * M * (size_t)d, 256);
   size_t ring = ((size_t)64 << 20) / region + 1;
   if (ring < 2) ring = 2;
   if (ring > 8) ring = 8;
   char* w = reinterpret_cast<char*>(workspace);
   float* sumsq = reinterpret_cast<float*>(w);
   int32_t* gidx = reinterpret_cast<int32_t*>(w + 256);
-  char* gval0 = w + 256 + align_up_sz(sizeof(int32_t) * 3 * M, 256);
+  char* gval0 = w + 256 + align_up(sizeof(int32_t) * 3 * M, 256);
   int32_t* prep_base = reinterpret_cast<int32_t*>(gval0 + ring * region);
   const StepIdentity ident{triples, T, first_row, B, id_to_type, N, type_offsets, n_types, type_ids, seed, global_step0,
                            padded_size, mode, d, 0, negs, workspace};
@@ -1039,14 +1037,14 @@ int train_logloss_run(float* table, int64_t N, int32_t d, const int32_t* triples
 // prepared records of `n_steps` consecutive steps into a caller buffer (tests, tools): the same launch
 // ge_train_steps uses.  For B > 4096 the buffer also holds the multi-tile sort's scratch, behind the records.
 size_t train_prepare_bytes(int64_t B, int64_t n_steps) {
-  return align_up_sz(sizeof(int32_t) * (size_t)n_steps * (size_t)prep_layout(B).stride, 256) + prep_big_scratch_bytes(B, 0, n_steps);
+  return align_up(sizeof(int32_t) * (size_t)n_steps * (size_t)prep_layout(B).stride, 256) + prep_big_scratch_bytes(B, 0, n_steps);
 }
 int train_prepare_run(const int32_t* triples, int64_t T, int64_t first_row, int64_t B, int64_t n_steps,
                       const int32_t* id_to_type, int64_t N, const int64_t* type_offsets, int32_t n_types,
                       const int32_t* type_ids, uint64_t seed, uint64_t global_step0, int32_t padded_size,
                       int32_t mode, int direct, int32_t* out, hipStream_t st) {
   if (n_steps == 0) return 0;
-  void* scratch = reinterpret_cast<char*>(out) + align_up_sz(sizeof(int32_t) * (size_t)n_steps * (size_t)prep_layout(B).stride, 256);
+  void* scratch = reinterpret_cast<char*>(out) + align_up(sizeof(int32_t) * (size_t)n_steps * (size_t)prep_layout(B).stride, 256);
   return prepare_launch(triples, T, norm_row(first_row, T, B), B, 0, n_steps, id_to_type, N, type_offsets, n_types,
                         type_ids, seed, global_step0, padded_size, mode, direct ? 1 : 0, out, scratch, st);
 }

@@ -362,12 +362,6 @@ __global__ __launch_bounds__(kBlock) void transr_adam_kernel(AdamArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------- host side
-static inline size_t tr_al(size_t v) { return (v + 255) / 256 * 256; }
-static inline unsigned tr_key_bits(int64_t n) {               // the sentinel n must fit
-  unsigned b = 1;
-  while (b < 32 && ((uint64_t)1 << b) <= (uint64_t)n) ++b;
-  return b;
-}
 static inline int64_t max_chunks(int64_t R, int64_t B) { return (B + kChunk - 1) / kChunk + (R < B ? R : B); }
 
 struct TrWs {
@@ -384,16 +378,16 @@ struct TrWs {
 static int tr_ws_layout(int64_t E, int64_t R, int32_t dE, int32_t dR, int64_t B, void* base, TrWs& w) {
   size_t sb_r = 0, sb_e = 0;
   hipError_t e = rocprim::radix_sort_pairs(nullptr, sb_r, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr,
-                                           (uint32_t*)nullptr, (size_t)B, 0u, tr_key_bits(R));
+                                           (uint32_t*)nullptr, (size_t)B, 0u, sort_key_bits(R));
   if (e != hipSuccess) return (int)e;
   e = rocprim::radix_sort_pairs(nullptr, sb_e, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr,
-                                (uint32_t*)nullptr, (size_t)(4 * B), 0u, tr_key_bits(E));
+                                (uint32_t*)nullptr, (size_t)(4 * B), 0u, sort_key_bits(E));
   if (e != hipSuccess) return (int)e;
   w.pstride = (int64_t)dR * dE + dR;
   w.nchunk_max = max_chunks(R, B);
   char* p = (char*)base;
   size_t off = 0;
-  auto take = [&](size_t bytes) { char* q = p ? p + off : nullptr; off += tr_al(bytes); return q; };
+  auto take = [&](size_t bytes) { char* q = p ? p + off : nullptr; off += align_up(bytes, 256); return q; };
   w.rkeys_in = (uint32_t*)take(B * 4); w.rkeys_out = (uint32_t*)take(B * 4);
   w.rpairs_in = (uint32_t*)take(B * 4); w.rpairs_out = (uint32_t*)take(B * 4);
   w.ekeys_in = (uint32_t*)take(16 * B); w.ekeys_out = (uint32_t*)take(16 * B);
@@ -436,11 +430,6 @@ static float adam_lr_t(float lr, float b1, float b2, int64_t t) {
   return (float)((double)lr * std::sqrt(1.0 - p2) / (1.0 - p1));
 }
 
-static bool aligned16(std::initializer_list<const void*> ptrs) {
-  for (const void* p : ptrs) if ((uintptr_t)p & 15) return false;
-  return true;
-}
-
 template <bool L1, int VEC>
 static int launch_chunks(const ChunkArgs& ca, int64_t grid, size_t lds, hipStream_t st) {
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(transr_chunk_kernel<L1, VEC>),
@@ -460,7 +449,7 @@ static int tr_step_core(int l1, float* ent, int64_t E, float* rel, float* mat, i
   if (rc) return rc;
   size_t sb = w.sort_bytes;
   hipError_t e = rocprim::radix_sort_pairs(w.sort_tmp, sb, w.rkeys_in, w.rkeys_out, w.rpairs_in, w.rpairs_out,
-                                           (size_t)B, 0u, tr_key_bits(R), st);
+                                           (size_t)B, 0u, sort_key_bits(R), st);
   if (e != hipSuccess) return (int)e;
   hipLaunchKernelGGL(transr_plan_kernel, dim3(1), dim3(kPlanBlock), 0, st, w.rkeys_out, B, R, w.chunk_pos, w.chunk_n,
                      w.chunk_rel, w.nchunks, w.rfirst, w.rcount);
@@ -474,7 +463,7 @@ static int tr_step_core(int l1, float* ent, int64_t E, float* rel, float* mat, i
   if (rc) return rc;
   sb = w.sort_bytes;
   e = rocprim::radix_sort_pairs(w.sort_tmp, sb, w.ekeys_in, w.ekeys_out, w.eslots_in, w.eslots_out, (size_t)(4 * B),
-                                0u, tr_key_bits(E), st);
+                                0u, sort_key_bits(E), st);
   if (e != hipSuccess) return (int)e;
   hipLaunchKernelGGL(transr_emap_kernel, dim3(grid_for(4 * B, kBlock)), dim3(kBlock), 0, st, w.ekeys_out, 4 * B, E,
                      w.estart, w.eend);
@@ -524,15 +513,11 @@ int transr_train_steps_run(int l1, float* ent, int64_t E, float* rel, float* rel
   int rc = tr_ws_layout(E, R, dE, dR, B, workspace, w);
   if (rc) return rc;
   if (workspace_bytes < w.total) return GE_ENOMEM;
-  for (int64_t s = 0; s < n_steps; ++s) {
-    rc = transx_draw_launch(triples, T, B, bh_key, bh_ent, bt_key, bt_ent, n_known, tail_threshold, (int32_t)R,
-                            (int32_t)E, seed, first_step + (uint64_t)s, w.pos, w.neg, st);
-    if (rc) return rc;
-    rc = tr_step_core(l1, ent, E, rel, rel_matrix, R, dE, dR, m, v, w.pos, w.neg, B, margin, lr, b1, b2, eps,
-                      first_t + s, losses + s, w, st);
-    if (rc) return rc;
-  }
-  return 0;
+  return draw_then_step(triples, T, B, bh_key, bh_ent, bt_key, bt_ent, n_known, tail_threshold, (int32_t)R, (int32_t)E,
+                        seed, first_step, n_steps, w.pos, w.neg, st, [&](int64_t s) {
+    return tr_step_core(l1, ent, E, rel, rel_matrix, R, dE, dR, m, v, w.pos, w.neg, B, margin, lr, b1, b2, eps,
+                        first_t + s, losses + s, w, st);
+  });
 }
 
 }  // namespace ge

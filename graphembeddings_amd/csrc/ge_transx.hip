@@ -422,12 +422,7 @@ __global__ __launch_bounds__(kBlock) void transx_draw_kernel(
 
 // ------------------------------------------------------------------------------------------- host side
 static inline int lpt_for(int nvec) { return nvec <= 8 ? 8 : nvec <= 16 ? 16 : nvec <= 32 ? 32 : 64; }
-static inline size_t al(size_t v) { return (v + 255) / 256 * 256; }
-static inline unsigned key_bits(int64_t E, int64_t R) {
-  unsigned b = 1;
-  while (b < 32 && ((uint64_t)1 << b) <= (uint64_t)(E + R)) ++b;    // the sentinel E + R must fit
-  return b;
-}
+static inline unsigned key_bits(int64_t E, int64_t R) { return sort_key_bits(E + R); }   // the sentinel E + R
 
 struct TxWs {
   uint32_t *keys_in, *keys_out, *slots_in, *slots_out;
@@ -445,7 +440,7 @@ static int ws_layout(int64_t E, int64_t R, int32_t d, int64_t B, void* base, TxW
   if (e != hipSuccess) return (int)e;
   char* p = (char*)base;
   size_t off = 0;
-  auto take = [&](size_t bytes) { char* q = p ? p + off : nullptr; off += al(bytes); return q; };
+  auto take = [&](size_t bytes) { char* q = p ? p + off : nullptr; off += align_up(bytes, 256); return q; };
   w.keys_in = (uint32_t*)take(n * 4); w.keys_out = (uint32_t*)take(n * 4);
   w.slots_in = (uint32_t*)take(n * 4); w.slots_out = (uint32_t*)take(n * 4);
   w.hinge = (float*)take(B * 4);
@@ -500,12 +495,6 @@ static void dispatch_mn(int model, int l1, A... args) {
   else { if (l1) go(ID{}, T{}); else go(ID{}, F{}); }
 }
 
-static bool vec4_ok(int d, std::initializer_list<const void*> ptrs) {
-  if (d % 4) return false;
-  for (const void* p : ptrs) if (p && ((uintptr_t)p & 15)) return false;
-  return true;
-}
-
 // ent2 / rel2 as the kernels take them, from the model's named tables
 static void extra_tables(int model, const float* normal, const float* ent_transfer, const float* rel_transfer,
                          const float*& ent2, const float*& rel2) {
@@ -519,7 +508,7 @@ int transx_score_launch(int model, int l1, const float* ent, int64_t E, const fl
   if (B == 0) return 0;
   const float *ent2, *rel2;
   extra_tables(model, normal, ent_transfer, rel_transfer, ent2, rel2);
-  const bool v4 = vec4_ok(d, {ent, rel, ent2, rel2});
+  const bool v4 = d % 4 == 0 && aligned16({ent, rel, ent2, rel2});
   const int nvec = v4 ? d / 4 : d, lpt = lpt_for(nvec);
   const int grid = grid_for((B + kWave / lpt - 1) / (kWave / lpt), kBlock / kWave);
   if (v4) dispatch_mn<true, 4>(model, l1, lpt, grid, st, ent, rel, ent2, rel2, E, R, (int)d, tri, B, out);
@@ -531,7 +520,7 @@ int transx_score_launch(int model, int l1, const float* ent, int64_t E, const fl
 static int step_core(int model, int l1, float* ent, int64_t E, float* rel, int64_t R, float* ent2, float* rel2,
                      int32_t d, const int32_t* pos, const int32_t* neg, int64_t B, float margin, float lr, float* loss,
                      TxWs& w, hipStream_t st) {
-  const bool v4 = vec4_ok(d, {ent, rel, ent2, rel2, w.g0, w.g1, w.part});
+  const bool v4 = d % 4 == 0 && aligned16({ent, rel, ent2, rel2, w.g0, w.g1, w.part});
   const int nvec = v4 ? d / 4 : d, lpt = lpt_for(nvec);
   const int grid = grid_for((B + kWave / lpt - 1) / (kWave / lpt), kBlock / kWave);
   if (v4) dispatch_mn<false, 4>(model, l1, lpt, grid, st, ent, rel, ent2, rel2, E, R, (int)d, pos, neg, B, margin, w);
@@ -592,14 +581,10 @@ int transx_train_steps_run(int model, int l1, float* ent, int64_t E, float* rel,
   if (workspace_bytes < w.total) return GE_ENOMEM;
   const float *e2, *r2;
   extra_tables(model, normal, ent_transfer, rel_transfer, e2, r2);
-  for (int64_t s = 0; s < n_steps; ++s) {
-    rc = transx_draw_launch(triples, T, B, bh_key, bh_ent, bt_key, bt_ent, n_known, tail_threshold, (int32_t)R,
-                            (int32_t)E, seed, first_step + (uint64_t)s, w.pos, w.neg, st);
-    if (rc) return rc;
-    rc = step_core(model, l1, ent, E, rel, R, (float*)e2, (float*)r2, d, w.pos, w.neg, B, margin, lr, losses + s, w, st);
-    if (rc) return rc;
-  }
-  return 0;
+  return draw_then_step(triples, T, B, bh_key, bh_ent, bt_key, bt_ent, n_known, tail_threshold, (int32_t)R, (int32_t)E,
+                        seed, first_step, n_steps, w.pos, w.neg, st, [&](int64_t s) {
+    return step_core(model, l1, ent, E, rel, R, (float*)e2, (float*)r2, d, w.pos, w.neg, B, margin, lr, losses + s, w, st);
+  });
 }
 
 }  // namespace ge

@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from . import hole as H
+from .transx import ids_outside
 
 
 def mrr_and_hits(raw_ranks, filtered_ranks) -> dict:
@@ -439,7 +440,7 @@ def _translation_test(model, test) -> np.ndarray:
     if t.size and not np.issubdtype(t.dtype, np.integer):
         raise ValueError("test triples must be integer ids")
     t = t.astype(np.int64)
-    if len(t) and (t[:, :2].min() < 0 or t[:, :2].max() >= model.n_ent or t[:, 2].min() < 0 or t[:, 2].max() >= model.n_rel):
+    if ids_outside(t, model.n_ent, model.n_rel):
         raise ValueError(f"a test triple holds an id outside [0, {model.n_ent}) entities / [0, {model.n_rel}) relations")
     return t
 

@@ -37,6 +37,15 @@ def _count(path: str) -> int:
     return n
 
 
+def ids_outside(tri: np.ndarray, n_ent: int, n_rel: int) -> Optional[str]:
+    """"entity" or "relation" when an id of the [n,3] (h, t, r) rows lies outside [0, n_ent) / [0, n_rel), else None."""
+    if len(tri) and (tri[:, :2].min() < 0 or tri[:, :2].max() >= n_ent):
+        return "entity"
+    if len(tri) and (tri[:, 2].min() < 0 or tri[:, 2].max() >= n_rel):
+        return "relation"
+    return None
+
+
 def read_kg(data_dir: str):
     """(entity_total, relation_total, triples int32 [T,3] as (h, t, r)) from relation2id.txt, entity2id.txt and
     triple2id.txt (init.cpp:47-86).  Each file begins with its count; the triples follow as `h t r` rows and are
@@ -67,11 +76,12 @@ def read_triples(path: str, n_ent: int, n_rel: int) -> np.ndarray:
         raise ValueError(f"{path}: no triples")
     if len(tri) > declared:
         raise ValueError(f"{path}: {len(tri)} triples but the file declares {declared}")
-    if tri[:, :2].min() < 0 or tri[:, :2].max() >= E:
-        raise ValueError(f"{path}: entity id outside [0, {E})")
-    if tri[:, 2].min() < 0 or tri[:, 2].max() >= R:
-        raise ValueError(f"{path}: relation id outside [0, {R})")
+    bad = ids_outside(tri, E, R)
+    if bad:
+        raise ValueError(f"{path}: {bad} id outside [0, {E if bad == 'entity' else R})")
     return tri.astype(np.int32)
+
+
 
 
 def _pairs(t: torch.Tensor, name: str) -> torch.Tensor:
@@ -81,29 +91,148 @@ def _pairs(t: torch.Tensor, name: str) -> torch.Tensor:
     return t.to(torch.int32).contiguous()
 
 
-def _rank_call(fn: str, ptrs, ws_bytes: int, n_ent: int, tb: torch.Tensor, cand_is_head: bool, known_off, known_rc,
-               return_scores: bool):
-    """One ge_transx_rank / ge_transr_rank call (ptrs: the model's table arguments)."""
-    B, dev = tb.shape[0], tb.device
-    if (known_off is None) != (known_rc is None):
-        raise ValueError("known_off and known_rc come together")
-    if ws_bytes == 0:
-        raise RuntimeError(f"{fn}_workspace_bytes failed")
-    nb = torch.empty(B, dtype=torch.int32, device=dev)
-    nk = torch.empty(B, dtype=torch.int32, device=dev)
-    td = torch.empty(B, dtype=torch.float32, device=dev)
-    sc = torch.empty((B, n_ent) if return_scores else (0,), dtype=torch.float32, device=dev)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    p = lambda t: None if t is None else t.data_ptr()
-    _lib.call(fn, *ptrs, tb.data_ptr(), B, int(bool(cand_is_head)), p(known_off), p(known_rc), nb.data_ptr(),
-              nk.data_ptr(), td.data_ptr(), sc.data_ptr() if return_scores else None, ws.data_ptr(), ws.numel(),
-              _stream())
-    return (nb, nk, td, sc) if return_scores else (nb, nk, td)
+class Trainer:
+    """The reference's training loop (getBatch + train_step, transE.py:109-115) as one native call per run():
+    each step draws `batch_size` positives uniformly with replacement from `triples` and corrupts each with the
+    filtered Bernoulli rule (ent_lo = 0), then takes the model's step.  Step s of the run uses the Philox counter
+    (seed, s): ge_transx_draw_batch(.., seed, s, ..) reproduces any step's batch."""
+
+    def __init__(self, model: TransX, triples, batch_size: int, *, margin: float = 1.0, learning_rate: float = 0.001,
+                 seed: int = 0):
+        tri = np.asarray(triples.cpu().numpy() if isinstance(triples, torch.Tensor) else triples, dtype=np.int64)
+        if tri.ndim != 2 or tri.shape[1] != 3 or len(tri) == 0:
+            raise ValueError("triples must be a non-empty [T, 3] (h, t, r) array")
+        if ids_outside(tri, model.n_ent, model.n_rel):
+            raise ValueError("triples hold an id outside the model's tables")
+        if batch_size <= 0:
+            raise ValueError("batch_size must be positive")
+        dev = model.tables["ent"].device
+        self.model, self.B, self.margin, self.lr, self.seed = model, int(batch_size), float(margin), float(learning_rate), int(seed)
+        self.triples = torch.as_tensor(tri.astype(np.int32)).to(dev).contiguous()
+        self.sampler = BernoulliSampler(tri, model.n_rel, model.n_ent, device=dev, ent_lo=0)
+        self.step_count = 0
+
+    def _sampler_args(self):
+        """The triples and sampler arguments of a *_train_steps call, from `triples` to `tail_threshold`."""
+        s = self.sampler
+        return (self.triples.data_ptr(), self.triples.shape[0], s.bh_key.data_ptr(), s.bh_ent.data_ptr(),
+                s.bt_key.data_ptr(), s.bt_ent.data_ptr(), s.n_known, s.tail_threshold.data_ptr())
+
+    def draw(self, step: int):
+        """The (pos, neg) batch the loop uses at `step`."""
+        pos = torch.empty(self.B, 3, dtype=torch.int32, device=self.triples.device)
+        neg = torch.empty_like(pos)
+        a = self._sampler_args()                        # ge_transx_draw_batch takes B after (triples, T)
+        _lib.call("ge_transx_draw_batch", *a[:2], self.B, *a[2:], self.sampler.n_rel, self.sampler.n_ent,
+                  self.seed & (2**64 - 1), int(step) & (2**64 - 1), pos.data_ptr(), neg.data_ptr(), _stream())
+        return pos, neg
+
+    def run(self, n: int) -> torch.Tensor:
+        """n steps in one call (the model's _train_steps); returns the [n] per-step batch losses (device)."""
+        losses = torch.empty(max(int(n), 0), dtype=torch.float32, device=self.triples.device)
+        if n <= 0:
+            return losses
+        self.model._train_steps(self, int(n), losses, self.model.workspace(self.B))
+        self.step_count += int(n)
+        return losses
 
 
-class TransX:
+class _Model:
+    """What TransX and TransR share: named tables, the cached step workspace, scoring, ranks, the Trainer and the
+    state-dict checks.  A subclass sets PREFIX (its ge_* entry points), _trainer and _state_tensors(), and supplies
+    _ptrs() (the table arguments every entry takes), _ws_bytes(kind, B) and _train_steps(trainer, n, losses, ws)."""
+    PREFIX = ""
+    _trainer = Trainer
+
+    def _init_tables(self, shapes, seed: Optional[int], device) -> None:
+        """One table per (name, shape), drawn with seed base + k for the k-th (None: unseeded)."""
+        base = None if seed is None else int(seed)
+        self.tables: Dict[str, torch.Tensor] = {
+            name: init_embeddings(*shape, device=device, seed=None if base is None else base + k)
+            for k, (name, shape) in enumerate(shapes)}
+        self._ws: Optional[torch.Tensor] = None
+        self._ws_B = -1
+        self._loss = torch.empty(1, dtype=torch.float32, device=self.tables["ent"].device)
+
+    def workspace(self, B: int) -> torch.Tensor:
+        if self._ws is None or self._ws_B != B:
+            nbytes = self._ws_bytes("step", int(B))
+            if nbytes == 0:
+                raise RuntimeError(f"{self.PREFIX}_step_workspace_bytes failed")
+            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.tables["ent"].device)
+            self._ws_B = B
+        return self._ws
+
+    def score(self, triples: torch.Tensor) -> torch.Tensor:
+        """D of every (h, t, r) row, [B] fp32 (NaN where an id is out of range)."""
+        tb = _pairs(triples, "triples")
+        out = torch.empty(tb.shape[0], dtype=torch.float32, device=tb.device)
+        _lib.call(self.PREFIX + "_score", *self._ptrs(), tb.data_ptr(), tb.shape[0], out.data_ptr(), _stream())
+        return out
+
+    def _step_batch(self, pos: torch.Tensor, neg: torch.Tensor):
+        """(pos, neg, workspace) of one step, the pairs checked."""
+        pb, nb = _pairs(pos, "pos"), _pairs(neg, "neg")
+        if pb.shape != nb.shape or pb.shape[0] == 0:
+            raise ValueError("pos and neg must be non-empty and of the same shape")
+        return pb, nb, self.workspace(pb.shape[0])
+
+    def rank_counts(self, triples: torch.Tensor, cand_is_head: bool = False, known_off: torch.Tensor = None,
+                    known_rc: torch.Tensor = None, return_scores: bool = False):
+        """ge_transx_rank / ge_transr_rank on the [B,3] rows as given: (n_before, n_known_before, true_dist) device
+        tensors, plus the [B, n_ent] distances with return_scores (tests).  known_off / known_rc: ge_known_cells'
+        lists for these rows with pos_of = the identity (None: unfiltered).  Rows with an id out of range get -1
+        counts."""
+        tb = _pairs(triples, "triples")
+        B, dev = tb.shape[0], tb.device
+        ws_bytes = self._ws_bytes("rank", max(B, 1))
+        if (known_off is None) != (known_rc is None):
+            raise ValueError("known_off and known_rc come together")
+        if ws_bytes == 0:
+            raise RuntimeError(f"{self.PREFIX}_rank_workspace_bytes failed")
+        nb = torch.empty(B, dtype=torch.int32, device=dev)
+        nk = torch.empty(B, dtype=torch.int32, device=dev)
+        td = torch.empty(B, dtype=torch.float32, device=dev)
+        sc = torch.empty((B, self.n_ent) if return_scores else (0,), dtype=torch.float32, device=dev)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        p = lambda t: None if t is None else t.data_ptr()
+        _lib.call(self.PREFIX + "_rank", *self._ptrs(), tb.data_ptr(), B, int(bool(cand_is_head)), p(known_off),
+                  p(known_rc), nb.data_ptr(), nk.data_ptr(), td.data_ptr(), sc.data_ptr() if return_scores else None,
+                  ws.data_ptr(), ws.numel(), _stream())
+        return (nb, nk, td, sc) if return_scores else (nb, nk, td)
+
+    def ranks(self, test, known=None, side: str = "tail", batch: int = None):
+        """(raw, filtered) int64 rank arrays of the test triples over every entity: evaluate.translation_ranks."""
+        from .evaluate import translation_ranks
+        return translation_ranks(self, test, known, side=side, batch=batch)
+
+    def trainer(self, triples, batch_size: int, *, margin: float = 1.0, learning_rate: float = 0.001,
+                seed: int = 0) -> Trainer:
+        return self._trainer(self, triples, batch_size, margin=margin, learning_rate=learning_rate, seed=seed)
+
+    def _state_tensors(self) -> Dict[str, torch.Tensor]:
+        return self.tables
+
+    def _check_state(self, state: Dict[str, object], keys, what: str) -> None:
+        """The sizes in `keys` and the shape of every tensor, checked before anything is copied."""
+        for key in keys:
+            if state[key] != getattr(self, key):
+                raise ValueError(f"state_dict {key}={state[key]!r} does not match this model's {getattr(self, key)!r}")
+        for name, t in self._state_tensors().items():
+            src = state[name]
+            if tuple(src.shape) != tuple(t.shape):
+                raise ValueError(f"state_dict {what} {name} has shape {tuple(src.shape)}, expected {tuple(t.shape)}")
+
+    def _copy_state(self, state: Dict[str, object]) -> None:
+        self.l1 = bool(state.get("l1", self.l1))
+        for name, t in self._state_tensors().items():
+            t.copy_(state[name].to(device=t.device, dtype=torch.float32))
+
+
+class TransX(_Model):
     """The tables of one translation model.  `model` in {"transe", "transh", "transd"}; `l1` selects the L1
     distance (the reference's L1_flag), else the squared L2 one."""
+    PREFIX = "ge_transx"
 
     def __init__(self, model: str, n_ent: int, n_rel: int, d: int, l1: bool = True, seed: Optional[int] = 0,
                  device="cuda"):
@@ -115,14 +244,8 @@ class TransX:
         if not 1 <= d <= 1024:
             raise ValueError(f"d must lie in [1, 1024], got {d}")
         self.model, self.n_ent, self.n_rel, self.d, self.l1 = model, int(n_ent), int(n_rel), int(d), bool(l1)
-        base = None if seed is None else int(seed)
         rows = {"ent": n_ent, "rel": n_rel, "normal_vector": n_rel, "ent_transfer": n_ent, "rel_transfer": n_rel}
-        self.tables: Dict[str, torch.Tensor] = {}
-        for k, name in enumerate(("ent", "rel") + EXTRA_TABLES[model]):
-            self.tables[name] = init_embeddings(rows[name], d, device=device, seed=None if base is None else base + k)
-        self._ws: Optional[torch.Tensor] = None
-        self._ws_B = -1
-        self._loss = torch.empty(1, dtype=torch.float32, device=self.tables["ent"].device)
+        self._init_tables([(name, (rows[name], d)) for name in ("ent", "rel") + EXTRA_TABLES[model]], seed, device)
 
     # the pointer arguments every ge_transx_* entry takes
     def _ptrs(self):
@@ -131,110 +254,26 @@ class TransX:
         return (MODELS[self.model], int(self.l1), p("ent"), self.n_ent, p("rel"), self.n_rel, p("normal_vector"),
                 p("ent_transfer"), p("rel_transfer"), self.d)
 
-    def workspace(self, B: int) -> torch.Tensor:
-        if self._ws is None or self._ws_B != B:
-            nbytes = _lib.load().ge_transx_step_workspace_bytes(self.n_ent, self.n_rel, self.d, int(B))
-            if nbytes == 0:
-                raise RuntimeError("ge_transx_step_workspace_bytes failed")
-            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.tables["ent"].device)
-            self._ws_B = B
-        return self._ws
-
-    def score(self, triples: torch.Tensor) -> torch.Tensor:
-        """D of every (h, t, r) row, [B] fp32 (NaN where an id is out of range)."""
-        tb = _pairs(triples, "triples")
-        out = torch.empty(tb.shape[0], dtype=torch.float32, device=tb.device)
-        _lib.call("ge_transx_score", *self._ptrs(), tb.data_ptr(), tb.shape[0], out.data_ptr(), _stream())
-        return out
+    def _ws_bytes(self, kind: str, B: int) -> int:
+        lead = (MODELS[self.model],) if kind == "rank" else ()
+        return getattr(_lib.load(), f"ge_transx_{kind}_workspace_bytes")(*lead, self.n_ent, self.n_rel, self.d, B)
 
     def step(self, pos: torch.Tensor, neg: torch.Tensor, lr: float, margin: float) -> torch.Tensor:
         """One SGD step on sum max(D(pos) - D(neg) + margin, 0); returns that batch loss (device scalar, before
         the step).  neg must keep pos's relation column (as getBatch's negatives do)."""
-        pb, nb = _pairs(pos, "pos"), _pairs(neg, "neg")
-        if pb.shape != nb.shape or pb.shape[0] == 0:
-            raise ValueError("pos and neg must be non-empty and of the same shape")
-        ws = self.workspace(pb.shape[0])
+        pb, nb, ws = self._step_batch(pos, neg)
         _lib.call("ge_transx_hinge_step", *self._ptrs(), pb.data_ptr(), nb.data_ptr(), pb.shape[0], float(margin),
                   float(lr), self._loss.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
         return self._loss[0].clone()
 
-    def rank_counts(self, triples: torch.Tensor, cand_is_head: bool = False, known_off: torch.Tensor = None,
-                    known_rc: torch.Tensor = None, return_scores: bool = False):
-        """ge_transx_rank on the [B,3] rows as given: (n_before, n_known_before, true_dist) device tensors, plus the
-        [B, n_ent] distances with return_scores (tests).  known_off / known_rc: ge_known_cells' lists for these rows
-        with pos_of = the identity (None: unfiltered).  Rows with an id out of range get -1 counts."""
-        tb = _pairs(triples, "triples")
-        return _rank_call("ge_transx_rank", self._ptrs(), _lib.load().ge_transx_rank_workspace_bytes(
-            MODELS[self.model], self.n_ent, self.n_rel, self.d, max(tb.shape[0], 1)), self.n_ent, tb, cand_is_head,
-            known_off, known_rc, return_scores)
-
-    def ranks(self, test, known=None, side: str = "tail", batch: int = None):
-        """(raw, filtered) int64 rank arrays of the test triples over every entity: evaluate.translation_ranks."""
-        from .evaluate import translation_ranks
-        return translation_ranks(self, test, known, side=side, batch=batch)
+    def _train_steps(self, tr: Trainer, n: int, losses: torch.Tensor, ws: torch.Tensor) -> None:
+        _lib.call("ge_transx_train_steps", *self._ptrs(), *tr._sampler_args(), tr.seed & (2**64 - 1), tr.step_count, n,
+                  tr.B, tr.margin, tr.lr, losses.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
 
     def state_dict(self) -> Dict[str, object]:
         return {"model": self.model, "l1": self.l1, "n_ent": self.n_ent, "n_rel": self.n_rel, "d": self.d,
                 **{k: v.detach().cpu().clone() for k, v in self.tables.items()}}
 
     def load_state_dict(self, state: Dict[str, object]) -> None:
-        for key in ("model", "n_ent", "n_rel", "d"):
-            if state[key] != getattr(self, key):
-                raise ValueError(f"state_dict {key}={state[key]!r} does not match this model's {getattr(self, key)!r}")
-        self.l1 = bool(state.get("l1", self.l1))
-        for name, t in self.tables.items():
-            src = state[name]
-            if tuple(src.shape) != tuple(t.shape):
-                raise ValueError(f"state_dict table {name} has shape {tuple(src.shape)}, expected {tuple(t.shape)}")
-            t.copy_(src.to(device=t.device, dtype=torch.float32))
-
-    def trainer(self, triples, batch_size: int, *, margin: float = 1.0, learning_rate: float = 0.001,
-                seed: int = 0) -> "Trainer":
-        return Trainer(self, triples, batch_size, margin=margin, learning_rate=learning_rate, seed=seed)
-
-
-class Trainer:
-    """The reference's training loop (getBatch + train_step, transE.py:109-115) as one native call per run():
-    each step draws `batch_size` positives uniformly with replacement from `triples` and corrupts each with the
-    filtered Bernoulli rule (ent_lo = 0), then takes the hinge SGD step.  Step s of the run uses the Philox
-    counter (seed, s): ge_transx_draw_batch(.., seed, s, ..) reproduces any step's batch."""
-
-    def __init__(self, model: TransX, triples, batch_size: int, *, margin: float = 1.0, learning_rate: float = 0.001,
-                 seed: int = 0):
-        tri = np.asarray(triples.cpu().numpy() if isinstance(triples, torch.Tensor) else triples, dtype=np.int64)
-        if tri.ndim != 2 or tri.shape[1] != 3 or len(tri) == 0:
-            raise ValueError("triples must be a non-empty [T, 3] (h, t, r) array")
-        if tri[:, :2].min() < 0 or tri[:, :2].max() >= model.n_ent or tri[:, 2].min() < 0 or tri[:, 2].max() >= model.n_rel:
-            raise ValueError("triples hold an id outside the model's tables")
-        if batch_size <= 0:
-            raise ValueError("batch_size must be positive")
-        dev = model.tables["ent"].device
-        self.model, self.B, self.margin, self.lr, self.seed = model, int(batch_size), float(margin), float(learning_rate), int(seed)
-        self.triples = torch.as_tensor(tri.astype(np.int32)).to(dev).contiguous()
-        self.sampler = BernoulliSampler(tri, model.n_rel, model.n_ent, device=dev, ent_lo=0)
-        self.step_count = 0
-
-    def draw(self, step: int):
-        """The (pos, neg) batch the loop uses at `step`."""
-        s = self.sampler
-        pos = torch.empty(self.B, 3, dtype=torch.int32, device=self.triples.device)
-        neg = torch.empty_like(pos)
-        _lib.call("ge_transx_draw_batch", self.triples.data_ptr(), self.triples.shape[0], self.B, s.bh_key.data_ptr(),
-                  s.bh_ent.data_ptr(), s.bt_key.data_ptr(), s.bt_ent.data_ptr(), s.n_known, s.tail_threshold.data_ptr(),
-                  s.n_rel, s.n_ent, self.seed & (2**64 - 1), int(step) & (2**64 - 1), pos.data_ptr(), neg.data_ptr(),
-                  _stream())
-        return pos, neg
-
-    def run(self, n: int) -> torch.Tensor:
-        """n steps in one call; returns the [n] per-step batch losses (device)."""
-        m, s = self.model, self.sampler
-        losses = torch.empty(max(int(n), 0), dtype=torch.float32, device=self.triples.device)
-        if n <= 0:
-            return losses
-        ws = m.workspace(self.B)
-        _lib.call("ge_transx_train_steps", *m._ptrs(), self.triples.data_ptr(), self.triples.shape[0],
-                  s.bh_key.data_ptr(), s.bh_ent.data_ptr(), s.bt_key.data_ptr(), s.bt_ent.data_ptr(), s.n_known,
-                  s.tail_threshold.data_ptr(), self.seed & (2**64 - 1), self.step_count, int(n), self.B, self.margin,
-                  self.lr, losses.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
-        self.step_count += int(n)
-        return losses
+        self._check_state(state, ("model", "n_ent", "n_rel", "d"), "table")
+        self._copy_state(state)

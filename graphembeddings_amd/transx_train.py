@@ -3,6 +3,7 @@
 Reads relation2id.txt, entity2id.txt and triple2id.txt from --data_dir, trains for --train_times epochs of
 --nbatches batches of triples // nbatches pairs (Config, transE.py:12-21), prints each epoch's summed loss as the
 reference does, and saves the tables with torch.save (TF's model.vec checkpoint format is not reproduced).
+The flags, checks and run() both translation drivers share live here; transr_train adds TransR's own.
 """
 from __future__ import annotations
 
@@ -15,14 +16,35 @@ FILTER_HELP = ("filtered evaluation (Bordes et al.): the filter is triple2id.txt
                "unlike the ComplEx evaluator, which filters train + valid as holE.py does")
 
 
-def add_eval_flags(p: argparse.ArgumentParser) -> None:
-    """--test_file / --filter_file / --load, shared by transx_train and transr_train."""
+def add_common_flags(p: argparse.ArgumentParser, dims, out: str) -> None:
+    """The flags of transx_train and transr_train, with the model's int size flags `dims` (default 100) after
+    --l1 / --l2; `out` names the files written."""
+    p.add_argument("--data_dir", default="./data/", help="directory of the three *2id.txt files")
+    g = p.add_mutually_exclusive_group()
+    g.add_argument("--l1", dest="l1", action="store_true", help="L1 distance (Config.L1_flag = True, the default)")
+    g.add_argument("--l2", dest="l1", action="store_false", help="squared L2 distance")
+    p.set_defaults(l1=True)
+    for flag in dims:
+        p.add_argument(f"--{flag}", type=int, default=100)
+    p.add_argument("--nbatches", type=int, default=100)
+    p.add_argument("--train_times", type=int, default=3000)
+    p.add_argument("--margin", type=float, default=1.0)
+    p.add_argument("--learning_rate", type=float, default=0.001)
+    p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--output_dir", default=".", help=f"where {out}.pt (and {out}_test.json) is written")
     p.add_argument("--test_file", default=None,
                    help="a *2id.txt file of test triples (leading count, then `h t r` rows) ranked after training over "
                         "all entities, heads and tails; " + FILTER_HELP)
     p.add_argument("--filter_file", action="append", default=[],
                    help="a further *2id.txt file of known triples for the filter (repeatable; e.g. valid2id.txt)")
     p.add_argument("--load", default=None, help="a saved state_dict to start from (with --train_times 0: evaluate only)")
+
+
+def check_training_args(a) -> None:
+    if a.nbatches <= 0 or a.train_times < 0:
+        raise ValueError("--nbatches must be positive and --train_times non-negative")
+    if not a.learning_rate > 0 or a.margin != a.margin:
+        raise ValueError("--learning_rate must be positive and --margin a number")
 
 
 def check_eval_args(a) -> None:
@@ -33,63 +55,19 @@ def check_eval_args(a) -> None:
             raise ValueError(f"no such file: {path}")
 
 
-def evaluate_to_json(model, a, E: int, R: int, train, json_path: str) -> dict:
-    """Rank --test_file with the filter triple2id.txt + test + --filter_file; print the head, tail and both-sides
-    lines and write them to json_path."""
+def run(a, driver: str, make_model, name: str) -> int:
+    """Everything after the flags are checked: read --data_dir, build make_model(E, R), --load, train, save
+    <name>.pt and, with --test_file, rank it (heads and tails, printed) into <name>_test.json."""
     import numpy as np
-    from . import evaluate as EV
-    from .transx import read_triples
-    test = read_triples(a.test_file, E, R)
-    known = np.concatenate([train, test] + [read_triples(f, E, R) for f in a.filter_file], 0)
-    out = EV.evaluate_translation(model, test, known, both_sides=True, verbose=True)
-    with open(json_path, "w") as f:
-        json.dump(out, f, indent=1, sort_keys=True)
-    print(f"wrote {json_path}")
-    return out
-
-
-def build_parser() -> argparse.ArgumentParser:
-    p = argparse.ArgumentParser(prog="python -m graphembeddings_amd.transx_train", description=__doc__.splitlines()[0])
-    p.add_argument("--model", choices=("transe", "transh", "transd"), default="transe")
-    p.add_argument("--data_dir", default="./data/", help="directory of the three *2id.txt files")
-    g = p.add_mutually_exclusive_group()
-    g.add_argument("--l1", dest="l1", action="store_true", help="L1 distance (Config.L1_flag = True, the default)")
-    g.add_argument("--l2", dest="l1", action="store_false", help="squared L2 distance")
-    p.set_defaults(l1=True)
-    p.add_argument("--hidden_size", type=int, default=100)
-    p.add_argument("--nbatches", type=int, default=100)
-    p.add_argument("--train_times", type=int, default=3000)
-    p.add_argument("--margin", type=float, default=1.0)
-    p.add_argument("--learning_rate", type=float, default=0.001)
-    p.add_argument("--seed", type=int, default=0)
-    p.add_argument("--output_dir", default=".", help="where <model>.pt (and <model>_test.json) is written")
-    add_eval_flags(p)
-    return p
-
-
-def check_args(a) -> None:
-    """Everything that can be wrong with the flags, before any GPU call."""
-    if not 1 <= a.hidden_size <= 1024:
-        raise ValueError(f"--hidden_size must lie in [1, 1024], got {a.hidden_size}")
-    if a.nbatches <= 0 or a.train_times < 0:
-        raise ValueError("--nbatches must be positive and --train_times non-negative")
-    if not a.learning_rate > 0 or a.margin != a.margin:
-        raise ValueError("--learning_rate must be positive and --margin a number")
-    check_eval_args(a)
-
-
-def main(argv=None) -> int:
-    a = build_parser().parse_args(argv)
-    check_args(a)
-    from . import transx as X
-    E, R, tri = X.read_kg(a.data_dir)
+    from .transx import read_kg, read_triples
+    E, R, tri = read_kg(a.data_dir)
     B = len(tri) // a.nbatches        # config.batch_size = getTripleTotal() / nbatches
     if B <= 0:
         raise ValueError(f"{len(tri)} triples cannot fill {a.nbatches} batches")
     import torch
     if not torch.cuda.is_available():
-        raise RuntimeError("transx_train needs an MI355X: graphembeddings_amd has no CPU path")
-    m = X.TransX(a.model, E, R, a.hidden_size, l1=a.l1, seed=a.seed)
+        raise RuntimeError(f"{driver} needs an MI355X: graphembeddings_amd has no CPU path")
+    m = make_model(E, R)
     if a.load:
         m.load_state_dict(torch.load(a.load, map_location="cpu"))
     tr = m.trainer(tri, B, margin=a.margin, learning_rate=a.learning_rate, seed=a.seed)
@@ -99,12 +77,41 @@ def main(argv=None) -> int:
         print(res)
         sys.stdout.flush()
     os.makedirs(a.output_dir, exist_ok=True)
-    out = os.path.join(a.output_dir, f"{a.model}.pt")
+    out = os.path.join(a.output_dir, f"{name}.pt")
     torch.save(m.state_dict(), out)
     print(f"saved {out}")
-    if a.test_file:
-        evaluate_to_json(m, a, E, R, tri, os.path.join(a.output_dir, f"{a.model}_test.json"))
+    if a.test_file:                  # filter: triple2id.txt + test + --filter_file
+        from .evaluate import evaluate_translation
+        test = read_triples(a.test_file, E, R)
+        known = np.concatenate([tri, test] + [read_triples(f, E, R) for f in a.filter_file], 0)
+        res = evaluate_translation(m, test, known, both_sides=True, verbose=True)
+        json_path = os.path.join(a.output_dir, f"{name}_test.json")
+        with open(json_path, "w") as f:
+            json.dump(res, f, indent=1, sort_keys=True)
+        print(f"wrote {json_path}")
     return 0
+
+
+def build_parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(prog="python -m graphembeddings_amd.transx_train", description=__doc__.splitlines()[0])
+    p.add_argument("--model", choices=("transe", "transh", "transd"), default="transe")
+    add_common_flags(p, ("hidden_size",), "<model>")
+    return p
+
+
+def check_args(a) -> None:
+    """Everything that can be wrong with the flags, before any GPU call."""
+    if not 1 <= a.hidden_size <= 1024:
+        raise ValueError(f"--hidden_size must lie in [1, 1024], got {a.hidden_size}")
+    check_training_args(a)
+    check_eval_args(a)
+
+
+def main(argv=None) -> int:
+    a = build_parser().parse_args(argv)
+    check_args(a)
+    from .transx import TransX
+    return run(a, "transx_train", lambda E, R: TransX(a.model, E, R, a.hidden_size, l1=a.l1, seed=a.seed), a.model)
 
 
 if __name__ == "__main__":

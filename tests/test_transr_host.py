@@ -161,3 +161,19 @@ def test_malformed_input_raises_before_gpu(tmp_path, monkeypatch):
     with pytest.raises(ValueError):                             # 3 triples cannot fill 100 batches
         XRT.main(["--data_dir", str(tmp_path)])
     assert calls == []
+
+
+def test_load_state_dict_that_raises_leaves_the_model_untouched():
+    """Every shape (and t) is checked before anything is copied: a wrong-shaped later tensor raises with the tables,
+    m, v and t intact."""
+    m = XR.TransR(10, 3, 8, 4, device="cpu")
+    m.m.fill_(0.5); m.v.fill_(0.25); m.t = 3
+    before = {k: v.clone() for k, v in list(m.tables.items()) + [("m", m.m), ("v", m.v)]}
+    good = XR.TransR(10, 3, 8, 4, seed=7, device="cpu").state_dict()
+    for key, bad in (("rel_matrix", torch.zeros(3, 31)), ("v", torch.zeros(5)), ("t", -1)):
+        state = dict(good, l1=False, **{key: bad})
+        with pytest.raises(ValueError):
+            m.load_state_dict(state)
+        assert m.l1 is True and m.t == 3
+        for k, v in list(m.tables.items()) + [("m", m.m), ("v", m.v)]:
+            assert torch.equal(v, before[k]), (key, k)

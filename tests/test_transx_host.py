@@ -238,3 +238,17 @@ def test_magnitude_bounds_the_gradient(model):
     for k in g:
         assert np.all(np.abs(g[k]) <= mag[k] + 1e-12) and mag[k].max() > np.abs(g[k]).max()
         assert np.all(np.abs(g1[k]) <= mag1[k] + 1e-12)
+
+
+def test_load_state_dict_that_raises_leaves_the_model_untouched():
+    """Every shape is checked before anything is copied: a wrong-shaped later table raises with `ent` still intact."""
+    m = X.TransX("transd", 10, 3, 8, device="cpu")
+    before = {k: v.clone() for k, v in m.tables.items()}
+    state = X.TransX("transd", 10, 3, 8, seed=7, device="cpu").state_dict()
+    state["l1"] = False
+    state["rel_transfer"] = torch.zeros(3, 9)
+    with pytest.raises(ValueError, match="rel_transfer"):
+        m.load_state_dict(state)
+    assert m.l1 is True
+    for k, v in m.tables.items():
+        assert torch.equal(v, before[k]), k
