@@ -424,6 +424,58 @@ int ge_transr_rank(int l1, const float* ent, int64_t n_ent, const float* rel, co
                             (hipStream_t)stream);
 }
 
+// the top-k's outputs: B in range, k in [1, max_k], every buffer present and aligned; the known lists come as a pair
+static inline int topk_outputs_ok(int64_t B, const int32_t* queries, const int32_t* known_off, const uint16_t* known_rc,
+                                  int32_t k, const int32_t* out_id, const float* out_dist, const void* workspace) {
+  if (B < 0 || B > ((int64_t)1 << 28) || k < 1 || k > transx_topk_max_k()) return GE_EINVAL;
+  if ((known_off == nullptr) != (known_rc == nullptr)) return GE_EINVAL;
+  if (B == 0) return 0;
+  if (!queries || !out_id || !out_dist || !workspace || ((uintptr_t)workspace & 255)) return GE_EINVAL;
+  for (const void* p : {(const void*)queries, (const void*)known_off, (const void*)out_id, (const void*)out_dist})
+    if (p && !aligned4(p)) return GE_EINVAL;
+  return 0;
+}
+
+int ge_transx_topk_max_k(void) { return transx_topk_max_k(); }
+
+size_t ge_transx_topk_workspace_bytes(int model, int64_t n_ent, int64_t n_rel, int32_t d, int64_t B, int32_t k) {
+  if (model < GE_TRANSX_TRANSE || model > GE_TRANSX_TRANSD || n_ent <= 0 || n_rel <= 0 || d <= 0 ||
+      d > transx_max_dim() || B <= 0 || B > ((int64_t)1 << 28))
+    return 0;
+  return transx_topk_ws_bytes(model, n_ent, n_rel, d, B, k);
+}
+
+int ge_transx_topk(int model, int l1, const float* ent, int64_t n_ent, const float* rel, int64_t n_rel,
+                   const float* normal, const float* ent_transfer, const float* rel_transfer, int32_t d,
+                   const int32_t* queries, int64_t B, int cand_is_head, const int32_t* known_off,
+                   const uint16_t* known_rc, int32_t k, int32_t* out_id, float* out_dist, void* workspace,
+                   size_t workspace_bytes, void* stream) {
+  if (int rc = transx_tables_ok(model, ent, n_ent, rel, n_rel, normal, ent_transfer, rel_transfer, d)) return rc;
+  if (int rc = topk_outputs_ok(B, queries, known_off, known_rc, k, out_id, out_dist, workspace)) return rc;
+  if (B == 0) return 0;
+  return transx_topk_launch(model, l1, ent, n_ent, rel, n_rel, normal, ent_transfer, rel_transfer, d, queries, B,
+                            cand_is_head, known_off, known_rc, k, out_id, out_dist, workspace, workspace_bytes,
+                            (hipStream_t)stream);
+}
+
+size_t ge_transr_topk_workspace_bytes(int64_t n_ent, int64_t n_rel, int32_t dim_e, int32_t dim_r, int64_t B, int32_t k) {
+  if (n_ent <= 0 || n_rel <= 0 || dim_e <= 0 || dim_r <= 0 || dim_e > transr_max_dim() || dim_r > transr_max_dim() ||
+      B <= 0 || B > ((int64_t)1 << 28))
+    return 0;
+  return transr_topk_ws_bytes(n_ent, n_rel, dim_r, B, k);
+}
+
+int ge_transr_topk(int l1, const float* ent, int64_t n_ent, const float* rel, const float* rel_matrix, int64_t n_rel,
+                   int32_t dim_e, int32_t dim_r, const int32_t* queries, int64_t B, int cand_is_head,
+                   const int32_t* known_off, const uint16_t* known_rc, int32_t k, int32_t* out_id, float* out_dist,
+                   void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = transr_tables_ok(ent, n_ent, rel, rel_matrix, n_rel, dim_e, dim_r)) return rc;
+  if (int rc = topk_outputs_ok(B, queries, known_off, known_rc, k, out_id, out_dist, workspace)) return rc;
+  if (B == 0) return 0;
+  return transr_topk_launch(l1, ent, n_ent, rel, rel_matrix, n_rel, dim_e, dim_r, queries, B, cand_is_head, known_off,
+                            known_rc, k, out_id, out_dist, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
 int ge_complex_score_1vK(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B,
                          const int32_t* cand, int64_t K, float max_norm, int apply_sigmoid, int cand_is_head,
                          float* out, void* stream) {

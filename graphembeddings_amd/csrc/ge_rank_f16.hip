@@ -33,6 +33,7 @@
 
 #include "ge_rank_dev.h"
 #include "ge_launch.h"
+#include "ge_topk_dev.h"
 
 #ifndef GE_PIPE_GRID_M
 #define GE_PIPE_GRID_M 2   // workgroups per CU (each CU holds one at a time): equal shares, two rounds
@@ -88,14 +89,10 @@ constexpr size_t h_lds_bytes() {
          sizeof(unsigned) * 8 * 64 + sizeof(int) * (4 * kRB + 4);
 }
 
-// ---- top-k (MODE 3, ge_topk_1vK): keys, pools, thresholds
-typedef unsigned long long u64;
+// ---- top-k (MODE 3, ge_topk_1vK): keys, pools, thresholds (keys, rank / cut / emit: ge_topk_dev.h)
 constexpr int kTopkMaxK = 128;
-constexpr u64 kNoKey = ~0ull;           // (also the padding of a partial list)
-// A candidate's key: (loss bits, entity id) as one unsigned 64-bit number.  Losses are sigmoids in [0, 1] (never NaN for a
-// candidate that survives), so the integer order of the keys is the reference heap's pop order (ascending loss, ties by
-// id); distinct candidates have distinct keys.
-__device__ __forceinline__ u64 topk_key(float e, int32_t id) { return ((u64)__float_as_uint(e) << 32) | (unsigned)id; }
+// Losses are sigmoids in [0, 1] (never NaN for a candidate that survives), so the integer order of topk_key's keys is the
+// reference heap's pop order (ascending loss, ties by id).
 
 // per row of the block behind HLds: the current k-th best key, the pool's fill and the raw-score bound of that key
 template <int KKB>
@@ -113,8 +110,6 @@ struct TopkArgs {
   float* out_loss;    // [B][k]
 };
 
-// a pool past kp entries is cut back to k after the tile (>= 32 appends apart)
-__host__ __device__ constexpr int topk_kp(int k) { return (k + 95) / 64 * 64; }   // k + 32 rounded up: 64 for k <= 32, 192 for k = 128
 constexpr int kTopkLane = 5;            // pool entries per lane in a merge: cap = kp + 128 <= 320
 
 // the raw-score bound of a k-th best loss e: a candidate whose raw score lies above it has a loss > e (the bracket of
@@ -126,67 +121,6 @@ __device__ __forceinline__ float topk_bound(float e) {
   const float gs = e * (1.0f - e);
   const float wx = !(gs >= 1e-5f) ? __builtin_inff() : 1e-6f / gs + 4e-7f * fabsf(xs);
   return xs / sa + wx / sa;
-}
-
-__device__ __forceinline__ u64 readlane64(u64 x, int l) {
-  const unsigned lo = __builtin_amdgcn_readlane((int)(unsigned)x, l);
-  const unsigned hi = __builtin_amdgcn_readlane((int)(unsigned)(x >> 32), l);
-  return ((u64)hi << 32) | lo;
-}
-
-// One wave: the first n (<= 320) keys of `pool`, entry m * 64 + lane in key[m], and each one's rank among them (the number
-// of smaller keys; kNoKey beyond n).  Every key is compared with every other: n^2 / 64 compares per lane, no scratch, no
-// LDS.
-__device__ __forceinline__ void topk_rank(const u64* pool, int n, int lane, u64 (&key)[kTopkLane], int (&rank)[kTopkLane]) {
-#pragma unroll
-  for (int m = 0; m < kTopkLane; ++m) {
-    const int i = m * 64 + lane;
-    key[m] = i < n ? pool[i] : kNoKey;
-    rank[m] = 0;
-  }
-#pragma unroll
-  for (int m2 = 0; m2 < kTopkLane; ++m2) {
-    const int lim = min(64, n - m2 * 64);
-    for (int l = 0; l < lim; ++l) {
-      const u64 kj = readlane64(key[m2], l);
-#pragma unroll
-      for (int m = 0; m < kTopkLane; ++m) rank[m] += kj < key[m] ? 1 : 0;
-    }
-  }
-}
-
-// One wave: keep the k best of a pool of n > k keys in its first k entries; returns the k-th best key (all lanes)
-__device__ __forceinline__ u64 topk_shrink(u64* pool, int n, int k, int lane) {
-  u64 key[kTopkLane];
-  int rank[kTopkLane];
-  topk_rank(pool, n, lane, key, rank);
-  u64 kth = kNoKey;
-#pragma unroll
-  for (int m = 0; m < kTopkLane; ++m) {
-    if (key[m] != kNoKey && rank[m] < k) pool[rank[m]] = key[m];
-    if (key[m] != kNoKey && rank[m] == k - 1) kth = key[m];
-  }
-  const u64 has = __ballot(kth != kNoKey);
-  return has ? readlane64(kth, __ffsll((long long)has) - 1) : kNoKey;
-}
-
-// One wave: the final list of a row -- the k best of n keys of `pool` into ids / losses (or keys), padded
-__device__ __forceinline__ void topk_emit(const u64* pool, int n, int k, int lane, int32_t* out_id, float* out_loss,
-                                          u64* out_key) {
-  u64 key[kTopkLane];
-  int rank[kTopkLane];
-  topk_rank(pool, n, lane, key, rank);
-#pragma unroll
-  for (int m = 0; m < kTopkLane; ++m) {
-    if (key[m] != kNoKey && rank[m] < k) {
-      if (out_key) out_key[rank[m]] = key[m];
-      else { out_id[rank[m]] = (int32_t)(unsigned)key[m]; out_loss[rank[m]] = __uint_as_float((unsigned)(key[m] >> 32)); }
-    }
-  }
-  for (int i = min(n, k) + lane; i < k; i += 64) {       // fewer eligible candidates than k
-    if (out_key) out_key[i] = kNoKey;
-    else { out_id[i] = -1; out_loss[i] = __builtin_inff(); }
-  }
 }
 
 struct HA { h8 ah[2], am[2]; };          // the Q operands of one k block of this wave's 64 rows
@@ -616,7 +550,7 @@ __global__ __launch_bounds__(kBlk) void rank_f16_kernel(
           const int rl = w * (kRB / 8) + j;
           const int n = __builtin_amdgcn_readfirstlane(tk_cnt[rl]);
           if (n > tk_kp) {
-            const u64 kth = topk_shrink(pbase + rl * pstride, n, tk.k, lane);
+            const u64 kth = topk_shrink<kTopkLane>(pbase + rl * pstride, n, tk.k, lane);
             if (lane == 0) {
               tk_cnt[rl] = tk.k;
               tk_kth[rl] = kth;
@@ -711,7 +645,7 @@ __global__ __launch_bounds__(kBlk) void rank_f16_kernel(
         if (row >= B) break;
         const int n = __builtin_amdgcn_readfirstlane(tk_cnt[rl]);
         // (rows with an id out of range have an empty pool; topk_merge_kernel gives them -1 / NaN)
-        topk_emit(tk.pool + (row * tk_ns + tk_s) * (int64_t)tk_cap, n, tk.k, lane, nullptr, nullptr,
+        topk_emit<kTopkLane>(tk.pool + (row * tk_ns + tk_s) * (int64_t)tk_cap, n, tk.k, lane, nullptr, nullptr,
                   tk.part + (row * tk_ns + tk_s) * (int64_t)tk.k);
       }
     }
@@ -839,7 +773,7 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const int32_t* __restri
     const int ns = __popcll(__ballot(a < kth)) + __popcll(__ballot(b < kth));
     if (ns == 0) continue;
     if (n + ns > tk.cap) {                                   // (after the cut n = k, and k + ns <= 2 k <= cap)
-      kth = topk_shrink(pool, n, k, lane);
+      kth = topk_shrink<kTopkLane>(pool, n, k, lane);
       n = k;
       __threadfence_block();
     }
@@ -848,7 +782,7 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const int32_t* __restri
     n += ns;
     __threadfence_block();
   }
-  topk_emit(pool, n, k, lane, oid, ol, nullptr);
+  topk_emit<kTopkLane>(pool, n, k, lane, oid, ol, nullptr);
 }
 
 int f16_cu_count() {

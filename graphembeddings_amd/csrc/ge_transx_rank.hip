@@ -21,8 +21,14 @@
 //          (scalar loads).  Per row: ballot + popcount of the before-test, summed over the workgroup's four waves in
 //          LDS, one integer atomic per row and workgroup.
 //   filter one thread per known cell: recompute D with the row's operands, integer atomic when it ranks before.
+// Top-k (ge_transx_topk / ge_transr_topk): the same prep, a row kernel for (fixed, relation)
+// queries, topk_sweep_kernel (the rank sweep's grid and distance loop, GE_SWEEP_DISTS; per row a pool of keys cut back
+// to k as the bound tightens) and rounds of topk_merge_kernel over the candidate ranges' sorted lists.
 #include "ge_common.h"
 #include "ge_launch.h"
+#include "ge_topk_dev.h"
+
+#include <algorithm>
 
 namespace ge {
 namespace {
@@ -127,9 +133,63 @@ __global__ __launch_bounds__(kBlock) void rank_row_kernel(RankTables T, const in
   n_known[i] = ok ? 0 : -1;
 }
 
-// The sweep.  blockIdx.x: rows [x * kRows, +kRows); candidate blocks of 256 strided by gridDim.y.  Consecutive rows of
-// one relation form a segment that shares the lane's projection scalar.  VEC: entity components per load (4 needs
+// The distances of one lane's candidate cc (a real row: a padding lane passes E - 1) to the rows [row0, row0 + nrows)
+// of a sweep workgroup: declares and fills float acc[kRows], acc[j] for row j.  The rank sweep and the top-k sweep
+// share this one distance loop.  It is a macro, not a function, so that the rank sweep's code stays what it was
+// (hipcc -O3 schedules and allocates a forceinline function or a lambda epilogue differently: the listings differ).
+// Names it reads from the kernel: MODEL, L1, VEC, T, q, rel_of, row0, nrows, cc, dE, dq.  Consecutive rows of one
+// relation form a segment that shares the lane's projection scalar.  VEC: entity components per load (4 needs
 // dE % 4 == 0, dq % 4 == 0 and a 16-byte aligned ent).
+#define GE_SWEEP_DISTS \
+  const float* e = T.ent + cc * dE;                                                                \
+  float acc[kRows];                                                                                \
+  _Pragma("unroll")                                                                                \
+  for (int j = 0; j < kRows; ++j) acc[j] = 0.f;                                                    \
+  for (int s = 0; s < nrows;) {                                                                    \
+    const int64_t r = rel_of[row0 + s];                                                            \
+    int s1 = s + 1;                                                                                \
+    if constexpr (MODEL != kTransE)                                                                \
+      while (s1 < nrows && rel_of[row0 + s1] == r) ++s1;                                           \
+    else                                                                                           \
+      s1 = nrows;                                                                                  \
+    const float a = proj_scalar<MODEL>(T, cc, r);                                                  \
+    for (int k = 0; k < dq; k += VEC) {                                                            \
+      float p[VEC];                                                                                \
+      if constexpr (MODEL == kTransR) {                                                            \
+        const float* m = T.aux + r * (int64_t)dq * dE + (int64_t)k * dE;                           \
+        _Pragma("unroll")                                                                          \
+        for (int v = 0; v < VEC; ++v) p[v] = 0.f;                                                  \
+        for (int jj = 0; jj < dE; jj += VEC) {                                                     \
+          float x[VEC];                                                                            \
+          load_vec<VEC>(e + jj, x);                                                                \
+          _Pragma("unroll")                                                                        \
+          for (int v = 0; v < VEC; ++v)                                                            \
+            _Pragma("unroll")                                                                      \
+            for (int z = 0; z < VEC; ++z) p[v] = fmaf(m[(int64_t)v * dE + jj + z], x[z], p[v]);    \
+        }                                                                                          \
+      } else {                                                                                     \
+        load_vec<VEC>(e + k, p);                                                                   \
+        if constexpr (MODEL == kTransH) {                                                          \
+          _Pragma("unroll")                                                                        \
+          for (int v = 0; v < VEC; ++v) p[v] = fmaf(-a, T.aux[r * dq + k + v], p[v]);              \
+        } else if constexpr (MODEL == kTransD) {                                                   \
+          _Pragma("unroll")                                                                        \
+          for (int v = 0; v < VEC; ++v) p[v] = fmaf(a, T.aux[r * dq + k + v], p[v]);               \
+        }                                                                                          \
+      }                                                                                            \
+      _Pragma("unroll")                                                                            \
+      for (int j = 0; j < kRows; ++j) {                                                            \
+        if (j >= s && j < s1) {                                                                    \
+          const float* qj = q + (row0 + j) * dq + k;                                               \
+          _Pragma("unroll")                                                                        \
+          for (int v = 0; v < VEC; ++v) acc[j] = dist_acc(L1, acc[j], qj[v] - p[v]);               \
+        }                                                                                          \
+      }                                                                                            \
+    }                                                                                              \
+    s = s1;                                                                                        \
+  }
+
+// The rank sweep.  blockIdx.x: rows [x * kRows, +kRows); candidate blocks of 256 strided by gridDim.y.
 template <int MODEL, bool L1, int VEC>
 __global__ __launch_bounds__(kBlock) void rank_sweep_kernel(RankTables T, const float* __restrict__ q,
                                                             const int32_t* __restrict__ rel_of,
@@ -154,53 +214,7 @@ __global__ __launch_bounds__(kBlock) void rank_sweep_kernel(RankTables T, const 
     const int64_t c = cb * kBlock + threadIdx.x;
     const bool valid = c < T.E;
     const int64_t cc = valid ? c : T.E - 1;            // a padding lane reads a real row; its result is dropped
-    const float* e = T.ent + cc * dE;
-    float acc[kRows];
-#pragma unroll
-    for (int j = 0; j < kRows; ++j) acc[j] = 0.f;
-    for (int s = 0; s < nrows;) {                       // segments of equal relation (uniform)
-      const int64_t r = rel_of[row0 + s];
-      int s1 = s + 1;
-      if constexpr (MODEL != kTransE)
-        while (s1 < nrows && rel_of[row0 + s1] == r) ++s1;
-      else
-        s1 = nrows;
-      const float a = proj_scalar<MODEL>(T, cc, r);
-      for (int k = 0; k < dq; k += VEC) {
-        float p[VEC];
-        if constexpr (MODEL == kTransR) {
-          const float* m = T.aux + r * (int64_t)dq * dE + (int64_t)k * dE;
-#pragma unroll
-          for (int v = 0; v < VEC; ++v) p[v] = 0.f;
-          for (int jj = 0; jj < dE; jj += VEC) {
-            float x[VEC];
-            load_vec<VEC>(e + jj, x);
-#pragma unroll
-            for (int v = 0; v < VEC; ++v)
-#pragma unroll
-              for (int z = 0; z < VEC; ++z) p[v] = fmaf(m[(int64_t)v * dE + jj + z], x[z], p[v]);
-          }
-        } else {
-          load_vec<VEC>(e + k, p);
-          if constexpr (MODEL == kTransH) {
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) p[v] = fmaf(-a, T.aux[r * dq + k + v], p[v]);
-          } else if constexpr (MODEL == kTransD) {
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) p[v] = fmaf(a, T.aux[r * dq + k + v], p[v]);
-          }
-        }
-#pragma unroll
-        for (int j = 0; j < kRows; ++j) {
-          if (j >= s && j < s1) {
-            const float* qj = q + (row0 + j) * dq + k;
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) acc[j] = dist_acc(L1, acc[j], qj[v] - p[v]);
-          }
-        }
-      }
-      s = s1;
-    }
+    GE_SWEEP_DISTS
 #pragma unroll
     for (int j = 0; j < kRows; ++j) {
       if (j < nrows) {
@@ -247,6 +261,182 @@ __global__ __launch_bounds__(kBlock) void rank_filter_kernel(RankTables T, const
     const float D = dist_one<MODEL, L1>(T, q + row * T.dq, col, rel_of[row]);
     if (D < dt || (D == dt && col < tid[row])) atomicAdd(&n_known[row], 1);
   }
+}
+
+// ---- top-k (ge_transx_topk / ge_transr_topk): per query row (fixed f, relation r) the first k candidates c in
+// ascending (D_c, c), D_c the rank sweep's own value (GE_SWEEP_DISTS), known cells skipped.  D is a sum of |u| or u^2
+// from +0, never negative or -0.0, so topk_key's integer order is that order.
+constexpr int kTopkMaxK = 128;
+constexpr int kTopkLanes = 7;            // pool entries per lane: cap = kp + 256 <= 448 (a candidate block adds <= 256)
+constexpr int kMergeFan = 16;            // partial lists per merge wave
+
+struct TopkWs {
+  int k, kp, cap;       // kp = topk_kp(k): a pool past kp keys is cut back to k; cap = kp + 256
+  u64* pool;            // [B][n_split][cap]
+  u64* part;            // [B][n_split][k]: each (row chunk, candidate range)'s k best, sorted, kNoKey-padded
+  int32_t* bad;         // [B]: an id out of range, or a NaN distance of a candidate that is not known
+};
+
+// One thread per query row: q (as rank_row_kernel forms it), the sanitised relation and the row's flag.
+template <int MODEL>
+__global__ __launch_bounds__(kBlock) void topk_row_kernel(RankTables T, const int32_t* __restrict__ qr, int64_t B,
+                                                          int head, float* __restrict__ q, int32_t* __restrict__ rel_of,
+                                                          int32_t* __restrict__ bad) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B) return;
+  int32_t f = qr[2 * i], r = qr[2 * i + 1];
+  const bool ok = f >= 0 && f < T.E && r >= 0 && r < T.R;
+  if (!ok) f = r = 0;
+  float* qi = q + i * T.dq;
+  const float a = proj_scalar<MODEL>(T, f, r);
+  for (int k = 0; k < T.dq; ++k) {
+    const float p = proj_elem<MODEL>(T, f, r, a, k), rk = T.rel[(int64_t)r * T.dq + k];
+    qi[k] = head ? p - rk : p + rk;
+  }
+  rel_of[i] = r;
+  bad[i] = ok ? 0 : 1;
+}
+
+// The top-k sweep: the rank sweep's grid and distance loop.  Per row of the workgroup a pool of keys in the workspace,
+// its fill and its k-th best key in LDS.  A lane appends its candidate when the key beats the row's k-th best and the
+// cell is not known (ballot + prefix count, one LDS atomic per wave and row); after each block of 256 candidates the
+// pools past kp keys are cut back to k (one wave per row).  Known cells: a bitmap of the block's rows x candidates,
+// built from ge_known_cells' lists of the (at most two) 128 x 128 tiles the block covers.
+template <int MODEL, bool L1, int VEC>
+__global__ __launch_bounds__(kBlock) void topk_sweep_kernel(RankTables T, const float* __restrict__ q,
+                                                            const int32_t* __restrict__ rel_of, int64_t B,
+                                                            const int32_t* __restrict__ known_off,
+                                                            const uint16_t* __restrict__ known_rc, TopkWs W) {
+  __shared__ u64 kth[kRows];
+  __shared__ int fill[kRows];
+  __shared__ uint32_t bm[kRows][kBlock / 32];
+  const int64_t row0 = (int64_t)blockIdx.x * kRows;
+  const int nrows = (int)(B - row0 < kRows ? B - row0 : kRows);
+  const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x >> 6;
+  const int64_t ns = gridDim.y, pstride = ns * W.cap;
+  u64* const pool0 = W.pool + (row0 * ns + blockIdx.y) * W.cap;          // row j's pool: pool0 + j * pstride
+  const int64_t n_ct = (T.E + kTile - 1) / kTile, rtile = row0 / kTile;
+  const int rsub = (int)(row0 % kTile);
+  if (threadIdx.x < kRows) {
+    kth[threadIdx.x] = kNoKey;
+    fill[threadIdx.x] = 0;
+  }
+  unsigned nan_rows = 0;                                 // bit j: a NaN distance in row j (wave-uniform)
+  const int dE = T.dE, dq = T.dq;
+  __syncthreads();
+  for (int64_t cb = blockIdx.y; cb * kBlock < T.E; cb += gridDim.y) {
+    const int64_t c = cb * kBlock + threadIdx.x;
+    const bool valid = c < T.E;
+    const int64_t cc = valid ? c : T.E - 1;            // a padding lane reads a real row; its result is dropped
+    if (known_off) {
+      if (threadIdx.x < kRows * kBlock / 32) (&bm[0][0])[threadIdx.x] = 0u;
+      __syncthreads();
+      for (int h = 0; h < 2 && 2 * cb + h < n_ct; ++h) {
+        const int64_t tile = rtile * n_ct + 2 * cb + h;
+        const int32_t x1 = known_off[tile + 1];
+        for (int32_t x = known_off[tile] + threadIdx.x; x < x1; x += kBlock) {
+          const int cell = known_rc[x], rl = (cell >> 7) - rsub, cl = (cell & 127) + kTile * h;
+          if (rl >= 0 && rl < kRows) atomicOr(&bm[rl][cl >> 5], 1u << (cl & 31));
+        }
+      }
+      __syncthreads();
+    }
+    GE_SWEEP_DISTS
+#pragma unroll
+    for (int j = 0; j < kRows; ++j) {
+      if (j < nrows) {
+        const bool known = known_off && ((bm[j][threadIdx.x >> 5] >> (threadIdx.x & 31)) & 1u);
+        const float D = acc[j];
+        if (__ballot(valid && !known && D != D)) nan_rows |= 1u << j;
+        const u64 key = topk_key(D, (int32_t)c);
+        const bool take = valid && !known && D < __builtin_inff() && key < kth[j];
+        const u64 m = __ballot(take);
+        if (m) {
+          int base = 0;
+          if (lane == 0) base = atomicAdd(&fill[j], __popcll(m));
+          base = __shfl(base, 0);
+          const int below = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+          if (take) pool0[j * pstride + base + below] = key;          // < cap: <= kp before the block, <= 256 in it
+        }
+      }
+    }
+    __syncthreads();                                     // the block's appends are in
+    for (int jj = 0; jj < kRows / 4; ++jj) {             // wave w cuts rows 4 w ... 4 w + 3
+      const int rl = w * (kRows / 4) + jj;
+      const int n = __builtin_amdgcn_readfirstlane(fill[rl]);
+      if (n > W.kp) {
+        const u64 t = topk_shrink<kTopkLanes>(pool0 + rl * pstride, n, W.k, lane);
+        if (lane == 0) {
+          fill[rl] = W.k;
+          kth[rl] = t;
+        }
+      }
+    }
+    __syncthreads();
+  }
+  if (lane == 0 && nan_rows) {
+    for (int j = 0; j < nrows; ++j)
+      if ((nan_rows >> j) & 1u) W.bad[row0 + j] = 1;
+  }
+  for (int jj = 0; jj < kRows / 4; ++jj) {               // each row's list of this candidate range, sorted and padded
+    const int rl = w * (kRows / 4) + jj;
+    if (rl >= nrows) break;
+    const int n = __builtin_amdgcn_readfirstlane(fill[rl]);
+    topk_emit<kTopkLanes>(pool0 + rl * pstride, n, W.k, lane, nullptr, nullptr,
+                          W.part + ((row0 + rl) * ns + blockIdx.y) * W.k);
+  }
+}
+
+// One wave per (row, group of up to kMergeFan partial lists): the group's lists -- each sorted, kNoKey-padded -- into
+// one (out), or, in the last round (out_id set, one group per row), into the row's ids and distances: -1 / NaN for a
+// flagged row, padding -1 / +inf.  Only keys below the running k-th best are taken (a prefix of each list); the pool
+// collects them and is cut back to k whenever the next list might not fit (cap >= 2 k).
+__global__ __launch_bounds__(kBlock) void topk_merge_kernel(const u64* __restrict__ in, int n_in, u64* __restrict__ out,
+                                                            int64_t B, TopkWs W, int32_t* __restrict__ out_id,
+                                                            float* __restrict__ out_dist) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int n_out = (n_in + kMergeFan - 1) / kMergeFan, k = W.k;
+  const int64_t wv = (int64_t)blockIdx.x * (kBlock / kWave) + (threadIdx.x >> 6);
+  if (wv >= B * n_out) return;
+  const int64_t row = wv / n_out;
+  const int g0 = (int)(wv % n_out) * kMergeFan, ng = min(kMergeFan, n_in - g0);
+  const u64* L0 = in + (row * n_in + g0) * (int64_t)k;
+  if (out_id && W.bad[row]) {
+    for (int i = lane; i < k; i += kWave) { out_id[row * k + i] = -1; out_dist[row * k + i] = __builtin_nanf(""); }
+    return;
+  }
+  if (ng == 1) {
+    for (int i = lane; i < k; i += kWave) {
+      const u64 key = L0[i];
+      if (out_id) {
+        out_id[row * k + i] = key == kNoKey ? -1 : (int32_t)(unsigned)key;
+        out_dist[row * k + i] = key == kNoKey ? __builtin_inff() : __uint_as_float((unsigned)(key >> 32));
+      } else {
+        out[wv * k + i] = key;
+      }
+    }
+    return;
+  }
+  u64* pool = W.pool + wv * (int64_t)W.cap;
+  int n = 0;
+  u64 kth = kNoKey;
+  for (int s = 0; s < ng; ++s) {
+    const u64* L = L0 + s * (int64_t)k;
+    const u64 a = lane < k ? L[lane] : kNoKey, b = lane + 64 < k ? L[lane + 64] : kNoKey;
+    const int na = __popcll(__ballot(a < kth)), nb = __popcll(__ballot(b < kth));
+    if (na + nb == 0) continue;
+    if (n + na + nb > W.cap) {                           // (after the cut n = k, and k + na + nb <= 2 k <= cap)
+      kth = topk_shrink<kTopkLanes>(pool, n, k, lane);
+      n = k;
+      __threadfence_block();
+    }
+    if (lane < na) pool[n + lane] = a;                   // (a list is sorted: the taken keys are its prefix)
+    if (lane < nb) pool[n + na + lane] = b;
+    n += na + nb;
+    __threadfence_block();
+  }
+  if (out_id) topk_emit<kTopkLanes>(pool, n, k, lane, out_id + row * k, out_dist + row * k, nullptr);
+  else topk_emit<kTopkLanes>(pool, n, k, lane, nullptr, nullptr, out + wv * k);
 }
 
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -299,6 +489,107 @@ int run(RankTables T, const float* normal, const int32_t* tri, int64_t B, int he
   return launch_status();
 }
 
+// ---- the top-k's host side
+// candidate ranges per 16-row chunk: about one round of resident workgroups (kMaxBlocks) over the grid, at most one
+// range per candidate block.  A function of (B, E) alone, so that the workspace is.
+int64_t topk_ranges(int64_t B, int64_t E) {
+  const int64_t n_chunks = (B + kRows - 1) / kRows, n_cb = (E + kBlock - 1) / kBlock;
+  int64_t ns = (kMaxBlocks + n_chunks - 1) / n_chunks;
+  return ns < 1 ? 1 : (ns > n_cb ? n_cb : ns);
+}
+
+// workspace: q [B, dq] | rel_of [B] | bad [B] | n^ [R, d] (TransH) or A [E] (TransD) | pools [B][ns][cap] |
+// partial lists [B][ns][k] | the first merge round's lists [B][ceil(ns / kMergeFan)][k]
+struct TopkLayout {
+  size_t q, rel_of, bad, aux, pool, part, part2, total;
+};
+
+TopkLayout topk_layout(int model, int64_t E, int64_t R, int dq, int64_t B, int k) {
+  const int64_t ns = topk_ranges(B, E), cap = topk_kp(k) + kBlock;
+  TopkLayout L;
+  L.q = 0;
+  L.rel_of = L.q + align256(sizeof(float) * (size_t)B * dq);
+  L.bad = L.rel_of + align256(sizeof(int32_t) * (size_t)B);
+  L.aux = L.bad + align256(sizeof(int32_t) * (size_t)B);
+  L.pool = L.aux + (model == kTransH ? align256(sizeof(float) * (size_t)R * dq)
+                                     : model == kTransD ? align256(sizeof(float) * (size_t)E) : 0);
+  L.part = L.pool + align256(sizeof(u64) * (size_t)(B * ns * cap));
+  L.part2 = L.part + align256(sizeof(u64) * (size_t)(B * ns * k));
+  L.total = L.part2 + align256(sizeof(u64) * (size_t)(B * ((ns + kMergeFan - 1) / kMergeFan) * k));
+  return L;
+}
+
+// the largest layout of any B' <= B (the ranges shrink as B grows), so that the size is monotone in B, E and k
+size_t topk_ws_bytes(int model, int64_t E, int64_t R, int dq, int64_t B, int32_t k) {
+  if (B <= 0 || E <= 0 || k < 1 || k > kTopkMaxK) return 0;
+  const int64_t n_chunks = (B + kRows - 1) / kRows;
+  size_t need = topk_layout(model, E, R, dq, B, k).total;
+  for (int64_t ch = 1; ch < n_chunks && ch <= kMaxBlocks; ++ch)
+    need = std::max(need, topk_layout(model, E, R, dq, ch * kRows, k).total);
+  return need;
+}
+
+template <int MODEL, bool L1>
+int run_topk(RankTables T, const float* normal, const int32_t* qr, int64_t B, int head, const int32_t* known_off,
+             const uint16_t* known_rc, int k, int32_t* out_id, float* out_dist, void* ws, hipStream_t st) {
+  const TopkLayout L = topk_layout(MODEL, T.E, T.R, T.dq, B, k);
+  char* p = (char*)ws;
+  float* q = (float*)(p + L.q);
+  int32_t* rel_of = (int32_t*)(p + L.rel_of);
+  TopkWs W;
+  W.k = k;
+  W.kp = topk_kp(k);
+  W.cap = W.kp + kBlock;
+  W.bad = (int32_t*)(p + L.bad);
+  W.pool = (u64*)(p + L.pool);
+  W.part = (u64*)(p + L.part);
+  u64* part2 = (u64*)(p + L.part2);
+  if constexpr (MODEL == kTransH) {
+    float* nhat = (float*)(p + L.aux);
+    hipLaunchKernelGGL(rank_nhat_kernel, dim3((unsigned)((T.R + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, normal,
+                       T.R, T.dq, nhat);
+    T.aux = nhat;
+  }
+  if constexpr (MODEL == kTransD) {
+    float* A = (float*)(p + L.aux);
+    hipLaunchKernelGGL(rank_transfer_dot_kernel, dim3((unsigned)((T.E + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
+                       T.ent, T.ent2, T.E, T.dE, A);
+    T.A = A;
+  }
+  hipLaunchKernelGGL((topk_row_kernel<MODEL>), dim3((unsigned)((B + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, T, qr,
+                     B, head, q, rel_of, W.bad);
+  const int64_t n_chunks = (B + kRows - 1) / kRows, ns = topk_ranges(B, T.E);
+  const dim3 grid((unsigned)n_chunks, (unsigned)ns);
+  if (rank_vec4(T.ent, T.dE, T.dq))
+    hipLaunchKernelGGL((topk_sweep_kernel<MODEL, L1, 4>), grid, dim3(kBlock), 0, st, T, q, rel_of, B, known_off,
+                       known_rc, W);
+  else
+    hipLaunchKernelGGL((topk_sweep_kernel<MODEL, L1, 1>), grid, dim3(kBlock), 0, st, T, q, rel_of, B, known_off,
+                       known_rc, W);
+  // merge rounds: groups of kMergeFan lists, until one group per row is left; that round writes ids / distances
+  u64* lists[2] = {W.part, part2};                      // a round reads one and writes the other
+  int cur = 0;
+  for (int64_t n = ns;;) {
+    const int64_t n_out = (n + kMergeFan - 1) / kMergeFan, waves = B * n_out;
+    const dim3 mg((unsigned)((waves + kBlock / kWave - 1) / (kBlock / kWave)));
+    const bool last = n_out == 1;
+    hipLaunchKernelGGL(topk_merge_kernel, mg, dim3(kBlock), 0, st, lists[cur], (int)n, last ? nullptr : lists[cur ^ 1],
+                       B, W, last ? out_id : nullptr, last ? out_dist : nullptr);
+    if (last) break;
+    cur ^= 1;
+    n = n_out;
+  }
+  return launch_status();
+}
+
+template <int MODEL>
+int run_topk_l(int l1, RankTables T, const float* normal, const int32_t* qr, int64_t B, int head,
+               const int32_t* known_off, const uint16_t* known_rc, int k, int32_t* out_id, float* out_dist, void* ws,
+               hipStream_t st) {
+  return l1 ? run_topk<MODEL, true>(T, normal, qr, B, head, known_off, known_rc, k, out_id, out_dist, ws, st)
+            : run_topk<MODEL, false>(T, normal, qr, B, head, known_off, known_rc, k, out_id, out_dist, ws, st);
+}
+
 template <int MODEL>
 int run_l(int l1, RankTables T, const float* normal, const int32_t* tri, int64_t B, int head, const int32_t* known_off,
           const uint16_t* known_rc, int32_t* n_before, int32_t* n_known, float* true_dist, float* scores, void* ws,
@@ -348,6 +639,48 @@ int transr_rank_launch(int l1, const float* ent, int64_t E, const float* rel, co
   RankTables T{ent, rel, rel_matrix, nullptr, nullptr, E, R, dE, dR};
   return run_l<kTransR>(l1, T, nullptr, tri, B, cand_is_head ? 1 : 0, known_off, known_rc, n_before, n_known_before,
                         true_dist, scores_out, workspace, st);
+}
+
+int transx_topk_max_k() { return kTopkMaxK; }
+
+size_t transx_topk_ws_bytes(int model, int64_t E, int64_t R, int32_t d, int64_t B, int32_t k) {
+  return topk_ws_bytes(model, E, R, d, B, k);
+}
+
+size_t transr_topk_ws_bytes(int64_t E, int64_t R, int32_t dR, int64_t B, int32_t k) {
+  return topk_ws_bytes(kTransR, E, R, dR, B, k);
+}
+
+int transx_topk_launch(int model, int l1, const float* ent, int64_t E, const float* rel, int64_t R, const float* normal,
+                       const float* ent_transfer, const float* rel_transfer, int32_t d, const int32_t* queries,
+                       int64_t B, int cand_is_head, const int32_t* known_off, const uint16_t* known_rc, int32_t k,
+                       int32_t* out_id, float* out_dist, void* workspace, size_t workspace_bytes, hipStream_t st) {
+  if (workspace_bytes < topk_ws_bytes(model, E, R, d, B, k)) return GE_ENOMEM;
+  RankTables T{ent, rel, nullptr, nullptr, nullptr, E, R, d, d};
+  const int head = cand_is_head ? 1 : 0;
+  switch (model) {
+    case kTransE:
+      return run_topk_l<kTransE>(l1, T, nullptr, queries, B, head, known_off, known_rc, k, out_id, out_dist, workspace,
+                                 st);
+    case kTransH:
+      return run_topk_l<kTransH>(l1, T, normal, queries, B, head, known_off, known_rc, k, out_id, out_dist, workspace,
+                                 st);
+    default:
+      T.aux = rel_transfer;
+      T.ent2 = ent_transfer;
+      return run_topk_l<kTransD>(l1, T, nullptr, queries, B, head, known_off, known_rc, k, out_id, out_dist, workspace,
+                                 st);
+  }
+}
+
+int transr_topk_launch(int l1, const float* ent, int64_t E, const float* rel, const float* rel_matrix, int64_t R,
+                       int32_t dE, int32_t dR, const int32_t* queries, int64_t B, int cand_is_head,
+                       const int32_t* known_off, const uint16_t* known_rc, int32_t k, int32_t* out_id, float* out_dist,
+                       void* workspace, size_t workspace_bytes, hipStream_t st) {
+  if (workspace_bytes < topk_ws_bytes(kTransR, E, R, dR, B, k)) return GE_ENOMEM;
+  RankTables T{ent, rel, rel_matrix, nullptr, nullptr, E, R, dE, dR};
+  return run_topk_l<kTransR>(l1, T, nullptr, queries, B, cand_is_head ? 1 : 0, known_off, known_rc, k, out_id, out_dist,
+                             workspace, st);
 }
 
 }  // namespace ge

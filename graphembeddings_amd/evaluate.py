@@ -445,6 +445,25 @@ def _translation_test(model, test) -> np.ndarray:
     return t
 
 
+def _translation_sweep_setup(model, rel, known, side: str):
+    """What a translation-model sweep over every entity needs, for translation_ranks and predict_translation: the
+    rows' order (a stable sort by relation: rows of one relation share the sweep's projection work), the KnownIndex of
+    `known` (an [n,3] array, None, or a KnownIndex with n_rows = max(n_ent, n_rel)) and pos_of (every entity is a
+    candidate at its own id)."""
+    if side not in ("tail", "head"):
+        raise ValueError(f"side must be 'tail' or 'head', got {side!r}")
+    dev = model.tables["ent"].device
+    E = model.n_ent
+    n_rows = max(E, model.n_rel)
+    index = known if isinstance(known, KnownIndex) else KnownIndex(known, n_rows, side, dev)
+    if index.n_rows != n_rows:
+        raise ValueError(f"the KnownIndex has n_rows={index.n_rows}, expected max(n_ent, n_rel) = {n_rows}")
+    order = np.argsort(np.asarray(rel), kind="stable")
+    pos_of = torch.arange(n_rows, dtype=torch.int64, device=dev)
+    pos_of[E:] = -1
+    return order, index, pos_of
+
+
 @torch.no_grad()
 def translation_ranks(model, test, known=None, side: str = "tail", batch: int = None):
     """Raw and filtered rank of every test triple's true entity among ALL entities for a TransX or TransR model
@@ -453,15 +472,9 @@ def translation_ranks(model, test, known=None, side: str = "tail", batch: int = 
     for this side with n_rows = max(n_ent, n_rel) (None: filtered == raw).  The rows are grouped by relation for the
     sweep (a stable sort on the host) and the ranks returned in the caller's order; a row's ranks do not depend on
     the grouping.  batch: rows per native call (default 131072)."""
-    if side not in ("tail", "head"):
-        raise ValueError(f"side must be 'tail' or 'head', got {side!r}")
     test = _translation_test(model, test)
-    dev = model.tables["ent"].device
-    E = model.n_ent
-    n_rows = max(E, model.n_rel)
-    index = known if isinstance(known, KnownIndex) else KnownIndex(known, n_rows, side, dev)
-    if index.n_rows != n_rows:
-        raise ValueError(f"the KnownIndex has n_rows={index.n_rows}, expected max(n_ent, n_rel) = {n_rows}")
+    order, index, pos_of = _translation_sweep_setup(model, test[:, 2], known, side)
+    E, dev = model.n_ent, model.tables["ent"].device
     if batch is None:
         batch = 1 << 17
     if batch <= 0:
@@ -470,9 +483,6 @@ def translation_ranks(model, test, known=None, side: str = "tail", batch: int = 
     fil = np.empty(len(test), dtype=np.int64)
     if len(test) == 0:
         return raw, fil
-    order = np.argsort(test[:, 2], kind="stable")       # rows of one relation share the sweep's projection work
-    pos_of = torch.arange(n_rows, dtype=torch.int64, device=dev)   # every entity is a candidate, at its own id
-    pos_of[E:] = -1
     fixed_col = 0 if side == "tail" else 1
     for s in range(0, len(test), batch):
         idx = order[s:s + batch]
@@ -508,3 +518,107 @@ def evaluate_translation(model, test, known=None, both_sides: bool = True, batch
                   f"{m['filtered_mrr']:.6f} (mean rank {m['mean_filtered_pos']:.1f}); hits@1/3/10 "
                   f"{m['hits1']:.2f} / {m['hits3']:.2f} / {m['hits10']:.2f} %")
     return out
+
+
+def _translation_queries(model, queries) -> np.ndarray:
+    """The query rows as int64 [n,2] (fixed entity, relation), ids checked against the model's tables on the host."""
+    q = np.asarray(queries.cpu().numpy() if isinstance(queries, torch.Tensor) else queries)
+    if q.size == 0:
+        return np.zeros((0, 2), dtype=np.int64)
+    if q.ndim != 2 or q.shape[1] != 2:
+        raise ValueError("queries must have shape [n, 2] (fixed entity, relation)")
+    if not np.issubdtype(q.dtype, np.integer):
+        raise ValueError("queries must be integer ids")
+    q = q.astype(np.int64)
+    if q[:, 0].min() < 0 or q[:, 0].max() >= model.n_ent or q[:, 1].min() < 0 or q[:, 1].max() >= model.n_rel:
+        raise ValueError(f"a query holds an id outside [0, {model.n_ent}) entities / [0, {model.n_rel}) relations")
+    return q
+
+
+@torch.no_grad()
+def predict_translation(model, queries, k: int, known=None, side: str = "tail", batch: int = None, fused: bool = None):
+    """Top-k link prediction of a TransX / TransR model over ALL entities: for every query (fixed f, relation r) the
+    first k entities c in ascending (D, c), D = D(f, c, r) (side="tail") or D(c, f, r) ("head") -- the rank sweep's own
+    distance, so the filtered rank (translation_ranks, same `known`) of the j-th candidate is j + 1.  known: an [m,3]
+    array or a KnownIndex with n_rows = max(n_ent, n_rel); known-true candidates are skipped.
+    Returns (ids int64 [n,k], dist float32 [n,k]) numpy arrays in the queries' order; padding -1 / +inf (+inf distances
+    are padding too); a row with a NaN distance at a candidate that is not known is -1 / NaN.
+    The rows are grouped by relation for the sweep.  fused (default: k <= transx.topk_max_k()): the list is selected
+    inside the sweep (topk_candidates), no [n, n_ent] matrix exists.  k > max_k or fused=False: the rank sweep's stored
+    distances (rank_counts(return_scores=True)) in chunks of <= 1024 rows, sorted stably on the device -- the same
+    arrays where both routes apply.  batch: rows per native call."""
+    from .transx import topk_max_k
+    k = int(k)
+    if k < 1:
+        raise ValueError("k must be >= 1")
+    q = _translation_queries(model, queries)
+    order, index, pos_of = _translation_sweep_setup(model, q[:, 1], known, side)
+    E, dev = model.n_ent, model.tables["ent"].device
+    in_kernel = fused is not False and k <= topk_max_k()
+    if batch is None:
+        batch = 1 << 15 if in_kernel else 1024
+    if batch <= 0:
+        raise ValueError("batch must be positive")
+    if not in_kernel:
+        batch = min(batch, 1024)                 # a [batch, n_ent] distance matrix exists per chunk
+    ids_out = np.empty((len(q), k), dtype=np.int64)
+    dist_out = np.empty((len(q), k), dtype=np.float32)
+    filtered = index.key.numel() > 0
+    head = side == "head"
+    for s0 in range(0, len(q), batch):
+        idx = order[s0:s0 + batch]
+        chunk = torch.as_tensor(q[idx]).to(dev)
+        off = rc = None
+        if filtered:
+            off, rc = index.cells(chunk[:, 0], chunk[:, 1], pos_of, E)
+        if in_kernel:
+            ids, dist = model.topk_candidates(chunk, k, cand_is_head=head, known_off=off, known_rc=rc)
+        else:
+            # rows (f, any valid target, r): the target's counts are discarded, the distances are the row's
+            zero = torch.zeros_like(chunk[:, 0])
+            tri = torch.stack([zero, chunk[:, 0], chunk[:, 1]] if head else [chunk[:, 0], zero, chunk[:, 1]], 1)
+            dist_all = model.rank_counts(tri, cand_is_head=head, return_scores=True)[-1]
+            cells = _known_cells_rc(off, rc, E) if off is not None else None
+            ids, dist = _topk_of_losses(dist_all, torch.arange(E, device=dev), k, cells)
+        ids_out[idx] = ids.to(torch.int64).cpu().numpy()
+        dist_out[idx] = dist.cpu().numpy()
+    return ids_out, dist_out
+
+
+def distinct_pairs(a) -> np.ndarray:
+    """The distinct rows of an [n,2] array, in order of first appearance."""
+    a = np.asarray(a, dtype=np.int64).reshape(-1, 2)
+    if len(a) == 0:
+        return a
+    _, first = np.unique(a, axis=0, return_index=True)
+    return a[np.sort(first)]
+
+
+def translation_predict_lines(side: str, queries, ids, dist, test_triples) -> list:
+    """The lines of a driver's <name>_predict.tsv for one side: per returned candidate, in order,
+    'side, fixed, relation, position (1-based), entity, distance (%.9g: round-trips fp32), in_test' with in_test = 1
+    when the completed triple is a test triple.  Padding (id -1) is not written."""
+    tset = {tuple(int(x) for x in t) for t in np.asarray(test_triples, dtype=np.int64).reshape(-1, 3)}
+    lines = []
+    for (f, r), row_ids, row_d in zip(np.asarray(queries, dtype=np.int64), np.asarray(ids), np.asarray(dist)):
+        for j, (c, D) in enumerate(zip(row_ids, row_d)):
+            if c < 0:
+                continue
+            tri = (int(f), int(c), int(r)) if side == "tail" else (int(c), int(f), int(r))
+            lines.append("%s\t%d\t%d\t%d\t%d\t%.9g\t%d\n" % (side, f, r, j + 1, c, float(D), tri in tset))
+    return lines
+
+
+def write_translation_predictions(model, test, known, k: int, path: str) -> int:
+    """The driver's top-k prediction file: tails for the distinct (h, r) pairs of the test triples, then heads for the
+    distinct (t, r) pairs, each in order of first appearance, filtered by `known`; returns the number of lines."""
+    test = np.asarray(test, dtype=np.int64).reshape(-1, 3)
+    n = 0
+    with open(path, "w") as out:
+        for side, cols in (("tail", [0, 2]), ("head", [1, 2])):
+            queries = distinct_pairs(test[:, cols])
+            ids, dist = predict_translation(model, queries, k, known, side=side)
+            lines = translation_predict_lines(side, queries, ids, dist, test)
+            out.writelines(lines)
+            n += len(lines)
+    return n

@@ -73,9 +73,9 @@ class TransR(_Model):
         return (int(self.l1), t["ent"].data_ptr(), self.n_ent, t["rel"].data_ptr(), t["rel_matrix"].data_ptr(),
                 self.n_rel, self.dim_e, self.dim_r)
 
-    def _ws_bytes(self, kind: str, B: int) -> int:
+    def _ws_bytes(self, kind: str, B: int, *extra) -> int:
         return getattr(_lib.load(), f"ge_transr_{kind}_workspace_bytes")(self.n_ent, self.n_rel, self.dim_e,
-                                                                          self.dim_r, B)
+                                                                          self.dim_r, B, *extra)
 
     def moments(self, name: str):
         """(m, v) of one table, as views shaped like it."""

@@ -84,6 +84,11 @@ def read_triples(path: str, n_ent: int, n_rel: int) -> np.ndarray:
 
 
 
+def topk_max_k() -> int:
+    """Largest k the fused top-k of the translation models (ge_transx_topk / ge_transr_topk) takes."""
+    return int(_lib.load().ge_transx_topk_max_k())
+
+
 def _pairs(t: torch.Tensor, name: str) -> torch.Tensor:
     _need_cuda(t, name)
     if t.dim() != 2 or t.shape[1] != 3:
@@ -138,9 +143,9 @@ class Trainer:
 
 
 class _Model:
-    """What TransX and TransR share: named tables, the cached step workspace, scoring, ranks, the Trainer and the
-    state-dict checks.  A subclass sets PREFIX (its ge_* entry points), _trainer and _state_tensors(), and supplies
-    _ptrs() (the table arguments every entry takes), _ws_bytes(kind, B) and _train_steps(trainer, n, losses, ws)."""
+    """What TransX and TransR share: named tables, the cached step workspace, scoring, ranks, top-k prediction, the
+    Trainer and the state-dict checks.  A subclass sets PREFIX (its ge_* entry points), _trainer and _state_tensors(), and supplies
+    _ptrs() (the table arguments every entry takes), _ws_bytes(kind, B, *extra) and _train_steps(trainer, n, losses, ws)."""
     PREFIX = ""
     _trainer = Trainer
 
@@ -201,6 +206,40 @@ class _Model:
                   ws.data_ptr(), ws.numel(), _stream())
         return (nb, nk, td, sc) if return_scores else (nb, nk, td)
 
+    def topk_candidates(self, queries: torch.Tensor, k: int, cand_is_head: bool = False, known_off: torch.Tensor = None,
+                        known_rc: torch.Tensor = None):
+        """ge_transx_topk / ge_transr_topk on the [B,2] (fixed, relation) rows as given: (ids int32 [B,k], dist fp32
+        [B,k]) device tensors, the first k entities in ascending (D, id), D the rank sweep's own distance.  known_off /
+        known_rc: ge_known_cells' lists for these rows with pos_of = the identity (None: unfiltered); known cells are
+        skipped.  Padding -1 / +inf; a row with an id out of range or a NaN distance is -1 / NaN."""
+        _need_cuda(queries, "queries")
+        qb = queries.to(torch.int32).contiguous()
+        if qb.dim() != 2 or qb.shape[1] != 2:
+            raise ValueError("queries must have shape [B, 2] (fixed entity, relation)")
+        k = int(k)
+        if not 1 <= k <= topk_max_k():
+            raise ValueError(f"k must lie in [1, {topk_max_k()}], got {k}")
+        if (known_off is None) != (known_rc is None):
+            raise ValueError("known_off and known_rc come together")
+        B, dev = qb.shape[0], qb.device
+        ids = torch.empty(B, k, dtype=torch.int32, device=dev)
+        dist = torch.empty(B, k, dtype=torch.float32, device=dev)
+        if B == 0:
+            return ids, dist
+        nbytes = self._ws_bytes("topk", B, k)
+        if nbytes == 0:
+            raise RuntimeError(f"{self.PREFIX}_topk_workspace_bytes failed")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        p = lambda t: None if t is None else t.data_ptr()
+        _lib.call(self.PREFIX + "_topk", *self._ptrs(), qb.data_ptr(), B, int(bool(cand_is_head)), p(known_off),
+                  p(known_rc), k, ids.data_ptr(), dist.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+        return ids, dist
+
+    def predict(self, queries, k: int, known=None, side: str = "tail", batch: int = None, fused: bool = None):
+        """Top-k tail (or head) prediction over every entity: evaluate.predict_translation."""
+        from .evaluate import predict_translation
+        return predict_translation(self, queries, k, known, side=side, batch=batch, fused=fused)
+
     def ranks(self, test, known=None, side: str = "tail", batch: int = None):
         """(raw, filtered) int64 rank arrays of the test triples over every entity: evaluate.translation_ranks."""
         from .evaluate import translation_ranks
@@ -254,9 +293,9 @@ class TransX(_Model):
         return (MODELS[self.model], int(self.l1), p("ent"), self.n_ent, p("rel"), self.n_rel, p("normal_vector"),
                 p("ent_transfer"), p("rel_transfer"), self.d)
 
-    def _ws_bytes(self, kind: str, B: int) -> int:
-        lead = (MODELS[self.model],) if kind == "rank" else ()
-        return getattr(_lib.load(), f"ge_transx_{kind}_workspace_bytes")(*lead, self.n_ent, self.n_rel, self.d, B)
+    def _ws_bytes(self, kind: str, B: int, *extra) -> int:
+        lead = (MODELS[self.model],) if kind in ("rank", "topk") else ()
+        return getattr(_lib.load(), f"ge_transx_{kind}_workspace_bytes")(*lead, self.n_ent, self.n_rel, self.d, B, *extra)
 
     def step(self, pos: torch.Tensor, neg: torch.Tensor, lr: float, margin: float) -> torch.Tensor:
         """One SGD step on sum max(D(pos) - D(neg) + margin, 0); returns that batch loss (device scalar, before

@@ -38,6 +38,11 @@ def add_common_flags(p: argparse.ArgumentParser, dims, out: str) -> None:
     p.add_argument("--filter_file", action="append", default=[],
                    help="a further *2id.txt file of known triples for the filter (repeatable; e.g. valid2id.txt)")
     p.add_argument("--load", default=None, help="a saved state_dict to start from (with --train_times 0: evaluate only)")
+    p.add_argument("--predict_k", type=int, default=None,
+                   help=f"after the evaluation write {out}_predict.tsv: the top K tails of every distinct (h, r) of the "
+                        "--test_file, then the top K heads of every distinct (t, r), over all entities.  Lines: side, "
+                        "fixed, relation, position, entity, distance, in_test.  Its filter is triple2id.txt + every "
+                        "--filter_file but NOT the test file (unlike the ranking filter), so held-out answers can appear")
 
 
 def check_training_args(a) -> None:
@@ -50,6 +55,11 @@ def check_training_args(a) -> None:
 def check_eval_args(a) -> None:
     if a.filter_file and not a.test_file:
         raise ValueError("--filter_file needs --test_file")
+    if a.predict_k is not None:
+        if not a.test_file:
+            raise ValueError("--predict_k needs --test_file")
+        if a.predict_k < 1:
+            raise ValueError(f"--predict_k must be >= 1, got {a.predict_k}")
     for path in ([a.test_file] if a.test_file else []) + list(a.filter_file) + ([a.load] if a.load else []):
         if not os.path.isfile(path):
             raise ValueError(f"no such file: {path}")
@@ -57,7 +67,8 @@ def check_eval_args(a) -> None:
 
 def run(a, driver: str, make_model, name: str) -> int:
     """Everything after the flags are checked: read --data_dir, build make_model(E, R), --load, train, save
-    <name>.pt and, with --test_file, rank it (heads and tails, printed) into <name>_test.json."""
+    <name>.pt and, with --test_file, rank it (heads and tails, printed) into <name>_test.json; with --predict_k, write
+    <name>_predict.tsv."""
     import numpy as np
     from .transx import read_kg, read_triples
     E, R, tri = read_kg(a.data_dir)
@@ -81,14 +92,19 @@ def run(a, driver: str, make_model, name: str) -> int:
     torch.save(m.state_dict(), out)
     print(f"saved {out}")
     if a.test_file:                  # filter: triple2id.txt + test + --filter_file
-        from .evaluate import evaluate_translation
+        from .evaluate import evaluate_translation, write_translation_predictions
         test = read_triples(a.test_file, E, R)
-        known = np.concatenate([tri, test] + [read_triples(f, E, R) for f in a.filter_file], 0)
+        extra = [read_triples(f, E, R) for f in a.filter_file]
+        known = np.concatenate([tri, test] + extra, 0)
         res = evaluate_translation(m, test, known, both_sides=True, verbose=True)
         json_path = os.path.join(a.output_dir, f"{name}_test.json")
         with open(json_path, "w") as f:
             json.dump(res, f, indent=1, sort_keys=True)
         print(f"wrote {json_path}")
+        if a.predict_k is not None:  # filter: triple2id.txt + --filter_file, not the test file
+            tsv = os.path.join(a.output_dir, f"{name}_predict.tsv")
+            n = write_translation_predictions(m, test, np.concatenate([tri] + extra, 0), a.predict_k, tsv)
+            print(f"wrote {tsv} ({n} lines)")
     return 0
 
 

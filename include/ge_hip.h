@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define GE_VERSION 360 /* 0.3.6: + ge_topk_1vK_planes (top-k tail / head prediction of ComplEx and HolE) */
+#define GE_VERSION 370 /* 0.3.7: + ge_transx_topk / ge_transr_topk (top-k prediction of the translation models) */
 
 /* argument errors (negative, -errno style) */
 #define GE_EINVAL (-22)  /* bad dimension / null pointer / misaligned buffer */
@@ -294,6 +294,33 @@ int ge_transr_rank(int l1, const float* ent, int64_t n_ent, const float* rel, co
                    int32_t dim_e, int32_t dim_r, const int32_t* triples, int64_t B, int cand_is_head,
                    const int32_t* known_off, const uint16_t* known_rc, int32_t* n_before, int32_t* n_known_before,
                    float* true_dist, float* scores_out, void* workspace, size_t workspace_bytes, void* stream);
+
+
+/* --- top-k tail / head prediction of the translation models over EVERY entity, selected inside the rank sweep (no
+ * [B, n_ent] matrix).  Query row i = queries[2i], queries[2i+1] = (fixed f, relation r); every entity c is a candidate:
+ * D_c = D(f, c, r) (cand_is_head = 0) or D(c, f, r), the SAME value ge_transx_rank / ge_transr_rank compute for that
+ * cell (one distance loop: bit-equal to what their scores_out stores for a row with the same (fixed, relation)).
+ *     out_id[i*k + j], out_dist[i*k + j]   the j-th candidate in ascending (D, entity id)
+ * Filtered (known_off / known_rc as ge_transx_rank takes them, pos_of = the identity): known cells are skipped, so with
+ * the same known set the filtered rank of the j-th candidate is j + 1.  Padding: id -1, distance +inf (fewer eligible
+ * candidates than k; +inf distances count as padding).  A row with an id out of range, or with a NaN distance at a
+ * candidate that is not known, gets id -1, distance NaN in every slot.  A row's result does not depend on the other rows
+ * of the call; two identical calls agree bitwise.  1 <= k <= ge_transx_topk_max_k() (128), else GE_EINVAL.
+ * Memory: the caller passes `workspace` (256-byte aligned) of the *_topk_workspace_bytes bytes (GE_ENOMEM when
+ * smaller; 0 for k outside [1, max_k] or bad sizes): per row a pool of candidate keys and the partial lists of the
+ * candidate ranges.  No host synchronisation inside; nothing allocated. */
+int ge_transx_topk_max_k(void);
+size_t ge_transx_topk_workspace_bytes(int model, int64_t n_ent, int64_t n_rel, int32_t d, int64_t B, int32_t k);
+int ge_transx_topk(int model, int l1, const float* ent, int64_t n_ent, const float* rel, int64_t n_rel,
+                   const float* normal, const float* ent_transfer, const float* rel_transfer, int32_t d,
+                   const int32_t* queries, int64_t B, int cand_is_head, const int32_t* known_off,
+                   const uint16_t* known_rc, int32_t k, int32_t* out_id, float* out_dist, void* workspace,
+                   size_t workspace_bytes, void* stream);
+size_t ge_transr_topk_workspace_bytes(int64_t n_ent, int64_t n_rel, int32_t dim_e, int32_t dim_r, int64_t B, int32_t k);
+int ge_transr_topk(int l1, const float* ent, int64_t n_ent, const float* rel, const float* rel_matrix, int64_t n_rel,
+                   int32_t dim_e, int32_t dim_r, const int32_t* queries, int64_t B, int cand_is_head,
+                   const int32_t* known_off, const uint16_t* known_rc, int32_t k, int32_t* out_id, float* out_dist,
+                   void* workspace, size_t workspace_bytes, void* stream);
 
 
 /* --- 1-vs-K candidate scoring (the inference loop of holE.py:564-569: fixed (head, relation)
