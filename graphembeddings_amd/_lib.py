@@ -99,6 +99,13 @@ SYMBOLS = {
     "ge_transr_rank_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32, _i64]),
     "ge_transr_rank": (C.c_int, [C.c_int, _p, _i64, _p, _p, _i64, _i32, _i32, _p, _i64, C.c_int, _p, _p, _p, _p, _p, _p,
                                  _p, _sz, _p]),
+    "ge_neighbor_max_k": (C.c_int, []),
+    "ge_neighbor_max_dim": (C.c_int, []),
+    "ge_neighbor_planes_bytes": (_i64, [_i64, _i32]),
+    "ge_neighbor_planes": (C.c_int, [_p, _i64, _i32, _p, _i64, _p, _p]),
+    "ge_neighbor_workspace_bytes": (_sz, [_i64, _i64, _i32]),
+    "ge_neighbor_dists": (C.c_int, [_p, _i64, _i32, _p, _i64, _p, _i64, C.c_int, _p, _p, _p]),
+    "ge_neighbor_topk": (C.c_int, [_p, _i64, _i32, _p, _i64, _p, _i64, _i32, C.c_int, C.c_int, _p, _p, _p, _p, _sz, _p]),
     "ge_transx_topk_max_k": (C.c_int, []),
     "ge_transx_topk_workspace_bytes": (_sz, [C.c_int, _i64, _i64, _i32, _i64, _i32]),
     "ge_transx_topk": (C.c_int, [C.c_int, C.c_int, _p, _i64, _p, _i64, _p, _p, _p, _i32, _p, _i64, C.c_int, _p, _p, _i32,

@@ -476,6 +476,56 @@ int ge_transr_topk(int l1, const float* ent, int64_t n_ent, const float* rel, co
                             known_rc, k, out_id, out_dist, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
+static inline int neighbor_args_ok(const float* table, int64_t N, int32_t d, const int32_t* queries, int64_t B,
+                                   const int32_t* cand, int64_t K, int metric, const void* planes) {
+  if (!ok_table(table, N, d) || B < 0 || B > ((int64_t)1 << 28) || K <= 0 || K > INT32_MAX) return GE_EINVAL;
+  if (metric != GE_METRIC_COSINE && metric != GE_METRIC_EUCLIDEAN) return GE_EINVAL;
+  if (d > neighbor_max_dim()) return GE_ENOTSUP;
+  if (!cand || !planes || ((uintptr_t)planes & 255) || !aligned4(table) || !aligned4(cand)) return GE_EINVAL;
+  if (B > 0 && (!queries || !aligned4(queries))) return GE_EINVAL;
+  return 0;
+}
+
+int ge_neighbor_max_k(void) { return neighbor_max_k(); }
+int ge_neighbor_max_dim(void) { return neighbor_max_dim(); }
+int64_t ge_neighbor_planes_bytes(int64_t K, int32_t d) { return neighbor_planes_bytes(K, d); }
+
+int ge_neighbor_planes(const float* table, int64_t N, int32_t d, const int32_t* cand, int64_t K, void* planes,
+                       void* stream) {
+  if (!ok_table(table, N, d) || K <= 0 || K > INT32_MAX || !cand || !planes) return GE_EINVAL;
+  if (d > neighbor_max_dim()) return GE_ENOTSUP;
+  if (((uintptr_t)planes & 255) || !aligned4(table) || !aligned4(cand)) return GE_EINVAL;
+  if (neighbor_planes_bytes(K, d) == 0) return GE_ENOTSUP;
+  return neighbor_planes_launch(table, N, d, cand, K, planes, (hipStream_t)stream);
+}
+
+size_t ge_neighbor_workspace_bytes(int64_t B, int64_t K, int32_t k) {
+  if (B <= 0 || B > ((int64_t)1 << 28) || K <= 0 || K > INT32_MAX) return 0;
+  return neighbor_ws_bytes(B, K, k);
+}
+
+int ge_neighbor_dists(const float* table, int64_t N, int32_t d, const int32_t* queries, int64_t B, const int32_t* cand,
+                      int64_t K, int metric, const void* planes, float* out, void* stream) {
+  if (int rc = neighbor_args_ok(table, N, d, queries, B, cand, K, metric, planes)) return rc;
+  if (B == 0) return 0;
+  if (!out || !aligned4(out)) return GE_EINVAL;
+  return neighbor_dists_launch(table, N, d, queries, B, cand, K, metric, planes, out, (hipStream_t)stream);
+}
+
+int ge_neighbor_topk(const float* table, int64_t N, int32_t d, const int32_t* queries, int64_t B, const int32_t* cand,
+                     int64_t K, int32_t k, int metric, int exclude_self, const void* planes, int32_t* out_id,
+                     float* out_dist, void* workspace, size_t workspace_bytes, void* stream) {
+  if (k < 1) return GE_EINVAL;
+  if (int rc = neighbor_args_ok(table, N, d, queries, B, cand, K, metric, planes)) return rc;
+  if (k > neighbor_max_k()) return GE_ENOTSUP;
+  if (B == 0) return 0;
+  if (!out_id || !out_dist || !aligned4(out_id) || !aligned4(out_dist)) return GE_EINVAL;
+  if (!workspace || ((uintptr_t)workspace & 255)) return GE_EINVAL;
+  if (workspace_bytes < neighbor_ws_bytes(B, K, k)) return GE_ENOMEM;
+  return neighbor_topk_launch(table, N, d, queries, B, cand, K, k, metric, exclude_self, planes, out_id, out_dist,
+                              workspace, workspace_bytes, (hipStream_t)stream);
+}
+
 int ge_complex_score_1vK(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B,
                          const int32_t* cand, int64_t K, float max_norm, int apply_sigmoid, int cand_is_head,
                          float* out, void* stream) {

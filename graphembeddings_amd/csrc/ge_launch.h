@@ -101,6 +101,20 @@ int topk_f16_launch(const float* table, int64_t N, int32_t d, const int32_t* hr,
                     float max_norm, int cand_is_head, const int32_t* known_off, const uint16_t* known_rc, int32_t k,
                     int32_t* out_id, float* out_loss, int spec, const void* planes_ws, void* workspace,
                     size_t workspace_bytes, hipStream_t st);
+int64_t topk_splits(int64_t B, int64_t K);
+
+// ge_neighbors.hip: nearest-neighbour search (cosine / Euclidean) on the split-precision sweep; embedding_dim 1 ... 288
+int neighbor_max_k();
+int neighbor_max_dim();
+int64_t neighbor_planes_bytes(int64_t K, int32_t d);
+int neighbor_planes_launch(const float* table, int64_t N, int32_t d, const int32_t* cand, int64_t K, void* planes_ws,
+                           hipStream_t st);
+size_t neighbor_ws_bytes(int64_t B, int64_t K, int32_t k);
+int neighbor_dists_launch(const float* table, int64_t N, int32_t d, const int32_t* queries, int64_t B,
+                          const int32_t* cand, int64_t K, int metric, const void* planes_ws, float* out, hipStream_t st);
+int neighbor_topk_launch(const float* table, int64_t N, int32_t d, const int32_t* queries, int64_t B,
+                         const int32_t* cand, int64_t K, int32_t k, int metric, int exclude_self, const void* planes_ws,
+                         int32_t* out_id, float* out_dist, void* workspace, size_t workspace_bytes, hipStream_t st);
 
 // ge_known.hip: the known-true cells of a ranking sweep as per-tile lists
 int known_cells_launch(int pass, const int64_t* key, const int64_t* ent, int64_t M, const int64_t* fixed, const int64_t* rel,

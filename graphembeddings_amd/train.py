@@ -54,6 +54,13 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('--predict_k', type=int, default=0,
                    help='With --infer: also write <output_dir>/inference_results.tsv, every pop up to the K-th filtered '
                         'prediction of each confident (head, relation) test query (0: no predictions).')
+    p.add_argument('--neighbors', type=int, default=0,
+                   help='Write <output_dir>/neighbors.tsv from the checkpoint: the K nearest entities of every entity '
+                        'row (no training).  Lines: query, query_name, position, neighbor, neighbor_name, distance.')
+    p.add_argument('--neighbors_of', type=str, default=None,
+                   help='With --neighbors: a file of entity indices, one per line, to list instead of every entity.')
+    p.add_argument('--neighbors_metric', choices=['cosine', 'euclidean'], default='cosine',
+                   help='With --neighbors: the distance (cosine: 1 - cos of the rows, as the reference demo ranks).')
     p.add_argument('--min_mentions', type=int, default=50000,
                    help='The minimum number of mentions for an entity to be a viable candidate in inference.')
     # extensions
@@ -237,9 +244,63 @@ def infer_triples(FLAGS, log=print) -> dict:
     return out
 
 
+def check_neighbor_flags(FLAGS, world: int = 1) -> None:
+    """--neighbors is a mode of its own, on one GPU, like --save_embeddings: refused with training-only or other modes."""
+    if FLAGS.neighbors < 0:
+        raise SystemExit('--neighbors must be >= 0')
+    if not FLAGS.neighbors:
+        if FLAGS.neighbors_of is not None:
+            raise SystemExit('--neighbors_of needs --neighbors K')
+        return
+    if FLAGS.gpus > 1 or world > 1:
+        raise SystemExit('--neighbors runs on one GPU (drop --gpus)')
+    if FLAGS.infer or FLAGS.save_embeddings:
+        raise SystemExit('--neighbors is a mode of its own: drop --infer / --save_embeddings')
+    if FLAGS.neighbors_of is not None and not os.path.isfile(FLAGS.neighbors_of):
+        raise SystemExit(f'--neighbors_of: no such file: {FLAGS.neighbors_of}')
+
+
+def read_neighbors_of(path: str, entity_count: int) -> np.ndarray:
+    """The entity indices of a --neighbors_of file, one per line (blank lines skipped), checked against the table."""
+    ids = []
+    with open(path) as f:
+        for n, line in enumerate(f, 1):
+            line = line.strip()
+            if not line:
+                continue
+            try:
+                ids.append(int(line))
+            except ValueError:
+                raise SystemExit(f'{path}:{n}: not an entity index: {line!r}')
+    a = np.asarray(ids, dtype=np.int64)
+    if a.size and (a.min() < 0 or a.max() >= entity_count):
+        raise SystemExit(f'{path}: entity indices must lie in [0, {entity_count})')
+    return a
+
+
+def write_neighbors(FLAGS, log=print) -> int:
+    """--neighbors K: the K nearest entity rows of every entity row (or of --neighbors_of's) by --neighbors_metric, over
+    the checkpoint's table as stored, into <output_dir>/neighbors.tsv.  Candidates: the entity rows
+    [relation_count, entity_count); a query's own row is not its neighbour."""
+    from . import neighbors as NB
+    data = D.init_inference_data(FLAGS.data_dir, min_mentions=None)
+    emb, _ = load_checkpoint(FLAGS.output_dir)
+    R, E = data.relation_count, data.entity_count
+    queries = np.arange(R, E) if FLAGS.neighbors_of is None else read_neighbors_of(FLAGS.neighbors_of, E)
+    path = os.path.join(FLAGS.output_dir, 'neighbors.tsv')
+    n = NB.write_neighbors(path, emb.contiguous(), queries, FLAGS.neighbors, candidates=np.arange(R, E),
+                           metric=FLAGS.neighbors_metric, names=data.id_to_metadata)
+    log(f'wrote {path} ({n} lines)')
+    return n
+
+
 def main(argv=None):
     FLAGS, _unparsed = build_parser().parse_known_args(argv)
     world = int(os.environ.get('WORLD_SIZE', '1'))
+    check_neighbor_flags(FLAGS, world)
+    if FLAGS.neighbors:
+        write_neighbors(FLAGS)
+        return
     if FLAGS.predict_k < 0:
         raise SystemExit('--predict_k must be >= 0')
     if FLAGS.predict_k and (FLAGS.gpus > 1 or world > 1):

@@ -43,6 +43,11 @@ def add_common_flags(p: argparse.ArgumentParser, dims, out: str) -> None:
                         "--test_file, then the top K heads of every distinct (t, r), over all entities.  Lines: side, "
                         "fixed, relation, position, entity, distance, in_test.  Its filter is triple2id.txt + every "
                         "--filter_file but NOT the test file (unlike the ranking filter), so held-out answers can appear")
+    p.add_argument("--neighbors_k", type=int, default=None,
+                   help=f"after saving write {out}_neighbors.tsv: the K nearest entities of every entity by the `ent` "
+                        "table (lines: query, position, neighbor, distance)")
+    p.add_argument("--neighbors_metric", choices=("cosine", "euclidean"), default="cosine",
+                   help="the distance of --neighbors_k")
 
 
 def check_training_args(a) -> None:
@@ -60,6 +65,9 @@ def check_eval_args(a) -> None:
             raise ValueError("--predict_k needs --test_file")
         if a.predict_k < 1:
             raise ValueError(f"--predict_k must be >= 1, got {a.predict_k}")
+    neighbors_k = getattr(a, "neighbors_k", None)       # (a Namespace built without the flag: none)
+    if neighbors_k is not None and neighbors_k < 1:
+        raise ValueError(f"--neighbors_k must be >= 1, got {neighbors_k}")
     for path in ([a.test_file] if a.test_file else []) + list(a.filter_file) + ([a.load] if a.load else []):
         if not os.path.isfile(path):
             raise ValueError(f"no such file: {path}")
@@ -67,8 +75,8 @@ def check_eval_args(a) -> None:
 
 def run(a, driver: str, make_model, name: str) -> int:
     """Everything after the flags are checked: read --data_dir, build make_model(E, R), --load, train, save
-    <name>.pt and, with --test_file, rank it (heads and tails, printed) into <name>_test.json; with --predict_k, write
-    <name>_predict.tsv."""
+    <name>.pt (with --neighbors_k, <name>_neighbors.tsv) and, with --test_file, rank it (heads and tails, printed)
+    into <name>_test.json; with --predict_k, write <name>_predict.tsv."""
     import numpy as np
     from .transx import read_kg, read_triples
     E, R, tri = read_kg(a.data_dir)
@@ -91,6 +99,11 @@ def run(a, driver: str, make_model, name: str) -> int:
     out = os.path.join(a.output_dir, f"{name}.pt")
     torch.save(m.state_dict(), out)
     print(f"saved {out}")
+    if getattr(a, "neighbors_k", None) is not None:
+        from .neighbors import write_neighbors
+        tsv = os.path.join(a.output_dir, f"{name}_neighbors.tsv")
+        n = write_neighbors(tsv, m.tables["ent"].contiguous(), np.arange(E), a.neighbors_k, metric=a.neighbors_metric)
+        print(f"wrote {tsv} ({n} lines)")
     if a.test_file:                  # filter: triple2id.txt + test + --filter_file
         from .evaluate import evaluate_translation, write_translation_predictions
         test = read_triples(a.test_file, E, R)

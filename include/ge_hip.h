@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define GE_VERSION 370 /* 0.3.7: + ge_transx_topk / ge_transr_topk (top-k prediction of the translation models) */
+#define GE_VERSION 380 /* 0.3.8: + ge_neighbor_* (cosine / Euclidean nearest-neighbour entity search) */
 
 /* argument errors (negative, -errno style) */
 #define GE_EINVAL (-22)  /* bad dimension / null pointer / misaligned buffer */
@@ -53,6 +53,10 @@ extern "C" {
  * order (one more launch per step), so that every row of the table is bitwise reproducible run to run whatever the ids'
  * distribution.  Off by default: it costs a launch per step (measured: DESIGN.md section 5). */
 #define GE_STEP_DETERMINISTIC 0x100
+
+/* ge_neighbor_dists / ge_neighbor_topk metrics */
+#define GE_METRIC_COSINE 0    /* D = max(0, 1 - cos) */
+#define GE_METRIC_EUCLIDEAN 1 /* D = sqrt(max(0, |q|^2 + |c|^2 - 2 |q| |c| cos)) */
 
 int ge_version(void);
 
@@ -321,6 +325,37 @@ int ge_transr_topk(int l1, const float* ent, int64_t n_ent, const float* rel, co
                    int32_t dim_e, int32_t dim_r, const int32_t* queries, int64_t B, int cand_is_head,
                    const int32_t* known_off, const uint16_t* known_rc, int32_t k, int32_t* out_id, float* out_dist,
                    void* workspace, size_t workspace_bytes, void* stream);
+
+/* --- nearest-neighbour entity search: for query rows q = table[queries[i]] and the K candidate rows cand (distinct, in
+ * [0, N)) of a float32 table [N, d] used as stored, the candidates in ascending (D, row id) with
+ *     u_x = x / |x| (0 for a zero row),  cos = u_q . u_c
+ *     GE_METRIC_COSINE     D = max(0, 1 - cos)
+ *     GE_METRIC_EUCLIDEAN  D = sqrt(max(0, |q|^2 + |c|^2 - 2 |q| |c| cos))
+ * D is never negative and never -0.  cos is formed by f16 MFMAs on 22-bit operands (unit rows * 2^8 as fp16 high
+ * halves and remainders) accumulated in fp32; every distance is one fixed fp32 expression of it, the same in both calls.
+ *   ge_neighbor_planes_bytes  bytes of the candidates' planes + norms (0: d outside 1 ... ge_neighbor_max_dim() (288)
+ *                             or more candidates than the sweep addresses)
+ *   ge_neighbor_planes        fills them (256-byte aligned); valid until the table or cand change
+ *   ge_neighbor_dists         out[i*K + c] = D of query i and candidate cand[c], every cell (NaN for a query id outside
+ *                             [0, N)): tests, and k > ge_neighbor_max_k()
+ *   ge_neighbor_topk          out_id[i*k + j], out_dist[i*k + j]: the j-th candidate of query i, no [B, K] matrix.
+ *                             exclude_self: the candidate equal to the query's row is skipped.  Padding -1 / +inf; a
+ *                             query id outside [0, N), or a NaN D at an eligible candidate, gives -1 / NaN in every
+ *                             slot.  The lists are the first k of ge_neighbor_dists' values by (D, id), bit for bit.
+ * 1 <= k <= ge_neighbor_max_k() (128); d > 288 or k > 128: GE_ENOTSUP.  Bad sizes, metric, null or misaligned
+ * pointers: GE_EINVAL.  Workspace (256-byte aligned) below ge_neighbor_workspace_bytes(B, K, k), which is monotone in
+ * every argument: GE_ENOMEM.  No host synchronisation, nothing allocated; two identical calls agree bitwise. */
+int ge_neighbor_max_k(void);
+int ge_neighbor_max_dim(void);
+int64_t ge_neighbor_planes_bytes(int64_t K, int32_t d);
+int ge_neighbor_planes(const float* table, int64_t N, int32_t d, const int32_t* cand, int64_t K, void* planes,
+                       void* stream);
+size_t ge_neighbor_workspace_bytes(int64_t B, int64_t K, int32_t k);
+int ge_neighbor_dists(const float* table, int64_t N, int32_t d, const int32_t* queries, int64_t B, const int32_t* cand,
+                      int64_t K, int metric, const void* planes, float* out, void* stream);
+int ge_neighbor_topk(const float* table, int64_t N, int32_t d, const int32_t* queries, int64_t B, const int32_t* cand,
+                     int64_t K, int32_t k, int metric, int exclude_self, const void* planes, int32_t* out_id,
+                     float* out_dist, void* workspace, size_t workspace_bytes, void* stream);
 
 
 /* --- 1-vs-K candidate scoring (the inference loop of holE.py:564-569: fixed (head, relation)
