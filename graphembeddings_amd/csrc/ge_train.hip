@@ -423,6 +423,45 @@ __global__ __launch_bounds__(kHotBlock) void hot_rows_kernel(
   }
 }
 
+// The k-th live slot of an item: the lowest set bit of the (wave-uniform) liveness mask, which is then cleared -- s_ff1 and
+// two scalar instructions, no vector work.
+__device__ __forceinline__ int next_live_slot(uint32_t& mask) {
+  const int b = __builtin_ctz(mask);
+  mask &= mask - 1u;
+  return b;
+}
+
+// One dense group of the one-tile update: the rows of the next W live slots of `m` (all that are left when fewer) are
+// requested together, then added in ascending slot order.  A row register that got no row holds +0.0f and is added
+// all the same, which keeps the group free of branches and of values carried from one group to the next; acc starts
+// at +0.0f and a sum is -0.0f only when both terms are, so acc + 0.0f == acc to the bit.
+template <int W, int NR, class LoadRow>
+__device__ __forceinline__ void add_live_rows(uint32_t& m, float (&acc)[NR], LoadRow load_row) {
+  float v[W][NR];
+#pragma unroll
+  for (int q = 0; q < W; ++q) {
+    if (m) load_row(next_live_slot(m), v[q]);
+    else {
+#pragma unroll
+      for (int r = 0; r < NR; ++r) v[q][r] = 0.f;
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < W; ++q)
+#pragma unroll
+    for (int r = 0; r < NR; ++r) acc[r] += v[q][r];
+}
+
+// an item's live rows in dense groups of RW; items of up to 4 live rows (two in three) take a group of 4
+template <int RW, int NR, class LoadRow>
+__device__ __forceinline__ void add_live_item(uint32_t m, float (&acc)[NR], LoadRow load_row) {
+  constexpr int RS = RW < 4 ? RW : 4;
+  while (m) {
+    if (RW > RS && __builtin_popcount(m) > RS) add_live_rows<RW>(m, acc, load_row);
+    else add_live_rows<RS>(m, acc, load_row);
+  }
+}
+
 // The same work item for steps of several tiles (large batches, the row-sharded step), where the kernel is a few hundred
 // thousand short waves whose time is their chain of dependent memory round trips, not their bytes:
 //  * the item header comes on the scalar path (s_load: one item per wave, so it is wave-uniform);
@@ -436,14 +475,29 @@ __global__ __launch_bounds__(kHotBlock) void hot_rows_kernel(
 // keep the column-per-lane layout: float atomics run at full rate only on 256 contiguous bytes per instruction
 // (16-byte lanes there: 80 us).
 // Summation order and arithmetic are the old kernel's: 0 + g_0 + g_1 + ... in slot order, then row + sum.
-template <int VW, int NJ, bool DET = false>
+// All of the figures above belong to steps of several tiles, where the kernel is bound by how many waves are resident:
+// RW = 0, the instantiations of those steps and of the row-sharded callers, is that code unchanged.
+// A ONE-TILE step (B <= 4096: ~2,450 working waves on 1,024 SIMDs, one resident round) lasts as long as its longest
+// item, and a sixth of its items list 13-16 slots (the pieces of ~120 hot rows): four dependent groups of 4 rows each.
+// Its instantiations (RW > 0) walk the SET BITS of the liveness mask, so a group is dense (16 listed, 7 live slots: one
+// group of 8), and hold RW rows in flight, in both branches.  Measurements of that shape: DESIGN.md 9(j).
+// row registers a lane holds in flight in the one-tile instantiations (16 rows of d <= 256).  Measured: d = 200 with
+// 16-byte lanes (<4, 1>) only; the other widths (d > 256: 8, 4 or 2 rows; unaligned or odd d) follow the same rule
+// unmeasured -- they compile without spills (profiles/r11_onetile_rows_resource_usage.txt).
+constexpr int kOneTileRowRegs = 64;
+constexpr int one_tile_rows(int regs_per_row) {
+  const int r = kOneTileRowRegs / regs_per_row;
+  return r > kItemCap ? kItemCap : (r < 2 ? 2 : r);
+}
+
+template <int VW, int NJ, bool DET = false, int RW = 0>
 __global__ __launch_bounds__(kBlock) void apply_rows_kernel(
     float* __restrict__ table, int d, const int32_t* __restrict__ sub0, int64_t sub_stride, int off_items,
     int off_islots, const int32_t* __restrict__ grad_idx, const float* grad_val, int split,
     float* __restrict__ out2) {
   typedef const __attribute__((address_space(4))) int32_t* kptr_t;
-  // row registers a lane: 16 (4 rows of 200 columns in flight per wave; 8 and 16 rows in flight were slower -- 45 / 51 us
-  // against 41: more waves per SIMD hide more than more rows per wave)
+  // row registers a lane when RW == 0: 16 (4 rows of 200 columns in flight per wave; at 65,536 pairs 8 and 16 rows in
+  // flight were slower -- 45 / 51 us against 41: more waves per SIMD hide more than more rows per wave)
   constexpr int RG0 = 16 / (VW * NJ);
   constexpr int RG = RG0 > kItemCap ? kItemCap : (RG0 < 2 ? 2 : RG0);
   const int lane = threadIdx.x & (kWave - 1);
@@ -463,6 +517,7 @@ __global__ __launch_bounds__(kBlock) void apply_rows_kernel(
     const int cnt = cm & 0x3FFFFFFF;
     const bool multi = (cm >> 30) & 1;
     const bool away = row >= split;
+    auto live_cap = [](int n) -> uint32_t { return n < kItemCap ? (1u << n) - 1u : (1u << kItemCap) - 1u; };   // listed slots only
     float* dst = away ? out2 + (int64_t)(row - split) * d : table + (int64_t)row * d;
     if (multi) {
       // a hot row (> 16 slots: several items): its partial sum is ADDED with float atomics, and those run at full rate
@@ -476,6 +531,13 @@ __global__ __launch_bounds__(kBlock) void apply_rows_kernel(
       float a[ND];
 #pragma unroll
       for (int j = 0; j < ND; ++j) a[j] = 0.f;
+      if constexpr (RW > 0) {
+        add_live_item<RW>((uint32_t)lv & live_cap(cnt), a, [&](int b, float (&r)[ND]) {
+          const float* src = grad_val + (int64_t)__builtin_amdgcn_readlane(slot_v, b) * d;
+#pragma unroll
+          for (int j = 0; j < ND; ++j) { const int c = lane + kWave * j; r[j] = src[c < d ? c : 0]; }
+        });
+      } else {
       for (int o = 0; o < cnt; o += 4) {
         float v[4][ND];
 #pragma unroll
@@ -491,6 +553,7 @@ __global__ __launch_bounds__(kBlock) void apply_rows_kernel(
 #pragma unroll
             for (int j = 0; j < ND; ++j) a[j] += v[q][j];
           }
+      }
       }
       float* parked = const_cast<float*>(grad_val) + (int64_t)__builtin_amdgcn_readlane(slot_v, 0) * d;
 #pragma unroll
@@ -517,6 +580,28 @@ __global__ __launch_bounds__(kBlock) void apply_rows_kernel(
       for (int e = 0; e < VW; ++e) acc[j][e] = 0.f;
     unsigned long long live = 0ull;
     bool have_live = false;
+    if constexpr (RW > 0) {
+      const bool act_v = slot_v >= 0 && (!grad_idx || grad_idx[slot_v] >= 0);   // pair was hinge-active
+      live = __ballot(act_v) & live_cap(cnt);
+      float sum[NJ * VW];
+#pragma unroll
+      for (int r = 0; r < NJ * VW; ++r) sum[r] = 0.f;
+      add_live_item<RW>((uint32_t)live, sum, [&](int b, float (&r)[NJ * VW]) {
+        // (scalar row base + unsigned 32-bit lane offset: no address registers per row)
+        const char* src = reinterpret_cast<const char*>(grad_val + (int64_t)__builtin_amdgcn_readlane(slot_v, b) * d);
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+          float w[VW];
+          load_vec<VW>(reinterpret_cast<const float*>(src + (uint32_t)col[j] * 4u), w);
+#pragma unroll
+          for (int e = 0; e < VW; ++e) r[j * VW + e] = w[e];
+        }
+      });
+#pragma unroll
+      for (int j = 0; j < NJ; ++j)
+#pragma unroll
+        for (int e = 0; e < VW; ++e) acc[j][e] = sum[j * VW + e];
+    } else
     for (int o = 0; o < cnt; o += RG) {
       float v[RG][NJ][VW];
       if (!have_live) {
@@ -560,7 +645,7 @@ int apply_items_launch(float* table, int d, const TileGeom& G, const int32_t* st
                        int det) {
   const int grid = grid_for(G.P, kBlock / kWave);  // at most P items per tile
   const int nj = (d + kWave - 1) / kWave;
-  const dim3 g((unsigned)grid, (unsigned)G.n_sub);   // (one tile: 1024 workgroups instead of 2048 measured the same, 512 slower)
+  const dim3 g((unsigned)grid, (unsigned)G.n_sub);   // (one tile, 4 rows in flight, round 4: 1024 workgroups instead of 2048 measured the same, 512 slower)
   // the ordered pass behind either update kernel (det): heads are looked for 64 items a workgroup
   auto hot = [&]() -> int {
     const dim3 gh((unsigned)((G.P + kWave - 1) / kWave), (unsigned)G.n_sub);   // one 64-item window a workgroup (windows past the tile's items return at once)
@@ -589,8 +674,22 @@ int apply_items_launch(float* table, int d, const TileGeom& G, const int32_t* st
     // of the item loop.  Update kernel 35.3-36.0 -> 33.4-33.7 us, 15 -> 11 us with no pair hinge-active (alternated on one
     // box, `profiles/r04_ab_gridx.log`; 1024 workgroups a tile: 34.8-34.9, 384: 33.3-33.5).
     const dim3 g((unsigned)(G.n_sub > 1 ? grid_for((G.P + 7) / 8, kBlock / kWave) : grid), (unsigned)G.n_sub);
+    // one-tile steps of the training loops (not the row-sharded callers, which keep the code above): dense groups of
+    // one_tile_rows() rows in flight on the same grid of one wave per key (DESIGN.md 9(j) has the other grids' numbers)
+    const bool one_tile = G.n_sub == 1 && out2 == nullptr;
 #define LR(VW, NJ)                                                                                                       \
     {                                                                                                                    \
+      if (one_tile) {                                                                                                    \
+        constexpr int RW = one_tile_rows(VW * NJ);                                                                       \
+        if (det) {                                                                                                       \
+          hipExtLaunchKernelGGL((apply_rows_kernel<VW, NJ, true, RW>), g, dim3(kBlock), 0, st, ev_start, ev_stop, 0, table, d, \
+                                step_rec + G.off_sub, G.sub_stride, G.off_items, G.off_islots, gidx, gval, split, out2); \
+          return hot();                                                                                                  \
+        }                                                                                                                \
+        hipExtLaunchKernelGGL((apply_rows_kernel<VW, NJ, false, RW>), g, dim3(kBlock), 0, st, ev_start, ev_stop, 0, table, d, \
+                              step_rec + G.off_sub, G.sub_stride, G.off_items, G.off_islots, gidx, gval, split, out2);   \
+        return launch_status();                                                                                          \
+      }                                                                                                                  \
       if (det) {                                                                                                         \
         hipExtLaunchKernelGGL((apply_rows_kernel<VW, NJ, true>), g, dim3(kBlock), 0, st, ev_start, ev_stop, 0, table, d, \
                               step_rec + G.off_sub, G.sub_stride, G.off_items, G.off_islots, gidx, gval, split, out2);   \
