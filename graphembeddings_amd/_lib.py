@@ -99,6 +99,12 @@ SYMBOLS = {
     "ge_transr_rank_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32, _i64]),
     "ge_transr_rank": (C.c_int, [C.c_int, _p, _i64, _p, _p, _i64, _i32, _i32, _p, _i64, C.c_int, _p, _p, _p, _p, _p, _p,
                                  _p, _sz, _p]),
+    "ge_transx_relation_rank_workspace_bytes": (_sz, [C.c_int, _i64, _i64, _i32, _i64]),
+    "ge_transx_relation_rank": (C.c_int, [C.c_int, C.c_int, _p, _i64, _p, _i64, _p, _p, _p, _i32, _p, _i64, _p, _p, _p,
+                                          _p, _p, _p, _p, _sz, _p]),
+    "ge_transr_relation_rank_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32, _i64]),
+    "ge_transr_relation_rank": (C.c_int, [C.c_int, _p, _i64, _p, _p, _i64, _i32, _i32, _p, _i64, _p, _p, _p, _p, _p, _p,
+                                          _p, _sz, _p]),
     "ge_neighbor_max_k": (C.c_int, []),
     "ge_neighbor_max_dim": (C.c_int, []),
     "ge_neighbor_planes_bytes": (_i64, [_i64, _i32]),

@@ -424,6 +424,51 @@ int ge_transr_rank(int l1, const float* ent, int64_t n_ent, const float* rel, co
                             (hipStream_t)stream);
 }
 
+// ---------------------------------------------------------------- translation-model relation prediction
+size_t ge_transx_relation_rank_workspace_bytes(int model, int64_t n_ent, int64_t n_rel, int32_t d, int64_t B) {
+  if (model < GE_TRANSX_TRANSE || model > GE_TRANSX_TRANSD || n_ent <= 0 || n_rel <= 0 ||
+      n_ent + n_rel >= ((int64_t)1 << 31) || d <= 0 || d > transx_max_dim() || B <= 0 || B > ((int64_t)1 << 28))
+    return 0;
+  return transx_relrank_ws_bytes(model, n_rel, d, B);
+}
+
+int ge_transx_relation_rank(int model, int l1, const float* ent, int64_t n_ent, const float* rel, int64_t n_rel,
+                            const float* normal, const float* ent_transfer, const float* rel_transfer, int32_t d,
+                            const int32_t* triples, int64_t B, const int32_t* known_off, const uint16_t* known_rc,
+                            int32_t* n_before, int32_t* n_known_before, float* true_dist, float* scores_out,
+                            void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = transx_tables_ok(model, ent, n_ent, rel, n_rel, normal, ent_transfer, rel_transfer, d)) return rc;
+  if (int rc = rank_outputs_ok(B, triples, known_off, known_rc, n_before, n_known_before, true_dist, scores_out,
+                               workspace))
+    return rc;
+  if (B == 0) return 0;
+  return transx_relrank_launch(model, l1, ent, n_ent, rel, n_rel, normal, ent_transfer, rel_transfer, d, triples, B,
+                               known_off, known_rc, n_before, n_known_before, true_dist, scores_out, workspace,
+                               workspace_bytes, (hipStream_t)stream);
+}
+
+size_t ge_transr_relation_rank_workspace_bytes(int64_t n_ent, int64_t n_rel, int32_t dim_e, int32_t dim_r, int64_t B) {
+  if (n_ent <= 0 || n_rel <= 0 || n_ent >= ((int64_t)1 << 31) || n_rel >= ((int64_t)1 << 31) || dim_e <= 0 ||
+      dim_r <= 0 || dim_e > transr_max_dim() || dim_r > transr_max_dim() || B <= 0 || B > ((int64_t)1 << 28))
+    return 0;
+  return transr_relrank_ws_bytes(n_rel, dim_e, B);
+}
+
+int ge_transr_relation_rank(int l1, const float* ent, int64_t n_ent, const float* rel, const float* rel_matrix,
+                            int64_t n_rel, int32_t dim_e, int32_t dim_r, const int32_t* triples, int64_t B,
+                            const int32_t* known_off, const uint16_t* known_rc, int32_t* n_before,
+                            int32_t* n_known_before, float* true_dist, float* scores_out, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+  if (int rc = transr_tables_ok(ent, n_ent, rel, rel_matrix, n_rel, dim_e, dim_r)) return rc;
+  if (int rc = rank_outputs_ok(B, triples, known_off, known_rc, n_before, n_known_before, true_dist, scores_out,
+                               workspace))
+    return rc;
+  if (B == 0) return 0;
+  return transr_relrank_launch(l1, ent, n_ent, rel, rel_matrix, n_rel, dim_e, dim_r, triples, B, known_off, known_rc,
+                               n_before, n_known_before, true_dist, scores_out, workspace, workspace_bytes,
+                               (hipStream_t)stream);
+}
+
 // the top-k's outputs: B in range, k in [1, max_k], every buffer present and aligned; the known lists come as a pair
 static inline int topk_outputs_ok(int64_t B, const int32_t* queries, const int32_t* known_off, const uint16_t* known_rc,
                                   int32_t k, const int32_t* out_id, const float* out_dist, const void* workspace) {

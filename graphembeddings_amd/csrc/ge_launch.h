@@ -259,4 +259,17 @@ int transr_topk_launch(int l1, const float* ent, int64_t E, const float* rel, co
                        const int32_t* known_off, const uint16_t* known_rc, int32_t k, int32_t* out_id, float* out_dist,
                        void* workspace, size_t workspace_bytes, hipStream_t st);
 
+// ge_transx_relrank.hip: relation prediction (h, ?, t) of TransE / TransH / TransD / TransR over every relation
+size_t transx_relrank_ws_bytes(int model, int64_t R, int32_t d, int64_t B);
+size_t transr_relrank_ws_bytes(int64_t R, int32_t dE, int64_t B);
+int transx_relrank_launch(int model, int l1, const float* ent, int64_t E, const float* rel, int64_t R,
+                          const float* normal, const float* ent_transfer, const float* rel_transfer, int32_t d,
+                          const int32_t* tri, int64_t B, const int32_t* known_off, const uint16_t* known_rc,
+                          int32_t* n_before, int32_t* n_known_before, float* true_dist, float* scores_out,
+                          void* workspace, size_t workspace_bytes, hipStream_t st);
+int transr_relrank_launch(int l1, const float* ent, int64_t E, const float* rel, const float* rel_matrix, int64_t R,
+                          int32_t dE, int32_t dR, const int32_t* tri, int64_t B, const int32_t* known_off,
+                          const uint16_t* known_rc, int32_t* n_before, int32_t* n_known_before, float* true_dist,
+                          float* scores_out, void* workspace, size_t workspace_bytes, hipStream_t st);
+
 }  // namespace ge

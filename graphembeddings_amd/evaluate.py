@@ -32,7 +32,9 @@ def mrr_and_hits(raw_ranks, filtered_ranks) -> dict:
 
 class KnownIndex:
     """Known-true triples as a device-side sorted index: key = fixed entity * n_rows + relation -> the entities
-    that complete a known triple (tails for side="tail", heads for "head")."""
+    that complete a known triple (tails for side="tail", heads for "head").  side="relation": key = head * n_rows +
+    tail -> the relations that link the pair (n_rows must hold every entity and relation id); cells(h, t, pos_of,
+    n_rel) then lists the known relations of (h, ?, t) rows."""
 
     def __init__(self, known_triples, n_rows: int, side: str, device):
         self.n_rows = int(n_rows)
@@ -41,13 +43,17 @@ class KnownIndex:
             self.ent = torch.empty(0, dtype=torch.int64, device=device)
             return
         k = torch.as_tensor(np.asarray(known_triples, dtype=np.int64)).to(device)
-        fixed, other = (k[:, 0], k[:, 1]) if side == "tail" else (k[:, 1], k[:, 0])
+        if side == "relation":              # (head, tail) -> relation
+            fixed, second, other = k[:, 0], k[:, 1], k[:, 2]
+        else:
+            fixed, other = (k[:, 0], k[:, 1]) if side == "tail" else (k[:, 1], k[:, 0])
+            second = k[:, 2]
         # a set, like the reference's dict of sets (holE.py:413-422), sorted by (fixed, relation, other)
         if self.n_rows ** 3 < 2 ** 63:      # one radix sort of the triple packed into an int64
-            packed = torch.unique_consecutive(torch.sort((fixed * self.n_rows + k[:, 2]) * self.n_rows + other)[0])
+            packed = torch.unique_consecutive(torch.sort((fixed * self.n_rows + second) * self.n_rows + other)[0])
             self.key, self.ent = (packed // self.n_rows).contiguous(), (packed % self.n_rows).contiguous()
         else:
-            pairs = torch.unique(torch.stack([fixed * self.n_rows + k[:, 2], other], 1), dim=0)
+            pairs = torch.unique(torch.stack([fixed * self.n_rows + second, other], 1), dim=0)
             self.key, self.ent = pairs[:, 0].contiguous(), pairs[:, 1].contiguous()
 
     def cells(self, fixed: torch.Tensor, rel: torch.Tensor, pos_of: torch.Tensor, n_cand: int):
@@ -497,10 +503,12 @@ def translation_ranks(model, test, known=None, side: str = "tail", batch: int = 
     return raw, fil
 
 
-def evaluate_translation(model, test, known=None, both_sides: bool = True, batch: int = None, verbose: bool = False) -> dict:
+def evaluate_translation(model, test, known=None, both_sides: bool = True, batch: int = None, verbose: bool = False,
+                         relations: bool = False) -> dict:
     """Filtered link prediction of a TransX / TransR model over all entities: mrr_and_hits of the tail ranks (and the
     head ranks with both_sides) plus `sweeps`, and per side `tail` / `head` dicts of the same numbers.  known: the
-    triples to filter (the Bordes et al. setting filters train + valid + test)."""
+    triples to filter (the Bordes et al. setting filters train + valid + test).  relations: add a `relation` dict, the
+    same numbers for the relation ranks (translation_relation_ranks); the other entries do not change."""
     n_rows = max(model.n_ent, model.n_rel)
     dev = model.tables["ent"].device
     per, raw_all, fil_all = {}, [], []
@@ -511,6 +519,8 @@ def evaluate_translation(model, test, known=None, both_sides: bool = True, batch
         raw_all.append(raw); fil_all.append(fil)
     out = mrr_and_hits(np.concatenate(raw_all), np.concatenate(fil_all))
     out["sweeps"] = int(sum(r.size for r in raw_all))
+    if relations:
+        per["relation"] = mrr_and_hits(*translation_relation_ranks(model, test, known, batch=batch))
     out.update(per)
     if verbose:
         for name, m in list(per.items()) + [("both", out)]:
@@ -583,6 +593,155 @@ def predict_translation(model, queries, k: int, known=None, side: str = "tail", 
         ids_out[idx] = ids.to(torch.int64).cpu().numpy()
         dist_out[idx] = dist.cpu().numpy()
     return ids_out, dist_out
+
+
+# ------------------------------------------------------------------ relation prediction (h, ?, t)
+def _relation_sweep_setup(model, known):
+    """The KnownIndex(side="relation") of `known` (an [n,3] array, None, or such an index with n_rows =
+    max(n_ent, n_rel)) and pos_of (every relation is a candidate at its own id)."""
+    dev = model.tables["ent"].device
+    n_rows = max(model.n_ent, model.n_rel)
+    index = known if isinstance(known, KnownIndex) else KnownIndex(known, n_rows, "relation", dev)
+    if index.n_rows != n_rows:
+        raise ValueError(f"the KnownIndex has n_rows={index.n_rows}, expected max(n_ent, n_rel) = {n_rows}")
+    pos_of = torch.arange(n_rows, dtype=torch.int64, device=dev)
+    pos_of[model.n_rel:] = -1
+    return index, pos_of
+
+
+@torch.no_grad()
+def translation_relation_ranks(model, test, known=None, batch: int = None):
+    """Raw and filtered rank of every test triple's relation among ALL relations for a TransX or TransR model (int64
+    arrays, in test order): the candidates c replace the relation, D_c = D(h, t, c), order ascending by (D, relation
+    id).  known: an [n,3] array of triples to filter, or a KnownIndex(side="relation") with n_rows = max(n_ent, n_rel)
+    (None: filtered == raw).  batch: rows per native call (default 131072)."""
+    test = _translation_test(model, test)
+    index, pos_of = _relation_sweep_setup(model, known)
+    dev = model.tables["ent"].device
+    if batch is None:
+        batch = 1 << 17
+    if batch <= 0:
+        raise ValueError("batch must be positive")
+    raw = np.empty(len(test), dtype=np.int64)
+    fil = np.empty(len(test), dtype=np.int64)
+    filtered = index.key.numel() > 0
+    for s in range(0, len(test), batch):
+        chunk = torch.as_tensor(test[s:s + batch]).to(dev)
+        off = rc = None
+        if filtered:
+            off, rc = index.cells(chunk[:, 0], chunk[:, 1], pos_of, model.n_rel)
+        nb, nk, _ = model.relation_rank_counts(chunk, known_off=off, known_rc=rc)
+        nb, nk = nb.cpu().numpy().astype(np.int64), nk.cpu().numpy().astype(np.int64)
+        if (nb < 0).any() or (nk < 0).any():
+            raise ValueError("a test triple holds an id outside the model's tables")
+        raw[s:s + batch] = nb + 1
+        fil[s:s + batch] = nb + 1 - nk
+    return raw, fil
+
+
+def _entity_pairs(n_ent: int, pairs) -> np.ndarray:
+    """The (h, t) rows as int64 [n,2], ids checked against [0, n_ent) on the host."""
+    q = np.asarray(pairs.cpu().numpy() if isinstance(pairs, torch.Tensor) else pairs)
+    if q.size == 0:
+        return np.zeros((0, 2), dtype=np.int64)
+    if q.ndim != 2 or q.shape[1] != 2:
+        raise ValueError("pairs must have shape [n, 2] (head, tail)")
+    if not np.issubdtype(q.dtype, np.integer):
+        raise ValueError("pairs must be integer ids")
+    q = q.astype(np.int64)
+    if q.min() < 0 or q.max() >= n_ent:
+        raise ValueError(f"a pair holds an id outside [0, {n_ent}) entities")
+    return q
+
+
+@torch.no_grad()
+def predict_translation_relations(model, pairs, k: int, known=None, batch: int = None):
+    """Top-k relation prediction of a TransX / TransR model: for every pair (h, t) the first k relations c in ascending
+    (D, c), D = D(h, t, c) -- the relation sweep's own stored distance, so the filtered rank
+    (translation_relation_ranks, same `known`) of the j-th entry is j + 1.  known: an [m,3] array or a
+    KnownIndex(side="relation") with n_rows = max(n_ent, n_rel); known relations of the pair are skipped.
+    Returns (ids int64 [n,k], dist float32 [n,k]) numpy arrays in the pairs' order; padding -1 / +inf.  The stored
+    distances (relation_rank_counts(return_scores=True)) are sorted stably on the device in chunks of <= 1024 rows
+    (batch: rows per chunk, at most 1024)."""
+    k = int(k)
+    if k < 1:
+        raise ValueError("k must be >= 1")
+    q = _entity_pairs(model.n_ent, pairs)
+    index, pos_of = _relation_sweep_setup(model, known)
+    R, dev = model.n_rel, model.tables["ent"].device
+    if batch is None:
+        batch = 1024
+    if batch <= 0:
+        raise ValueError("batch must be positive")
+    batch = min(batch, 1024)                     # a [batch, n_rel] distance matrix is sorted per chunk
+    ids_out = np.empty((len(q), k), dtype=np.int64)
+    dist_out = np.empty((len(q), k), dtype=np.float32)
+    filtered = index.key.numel() > 0
+    for s0 in range(0, len(q), batch):
+        chunk = torch.as_tensor(q[s0:s0 + batch]).to(dev)
+        cells = None
+        if filtered:
+            cells = _known_cells_rc(*index.cells(chunk[:, 0], chunk[:, 1], pos_of, R), R)
+        # rows (h, t, any valid relation): the target's counts are discarded, the distances are the row's
+        tri = torch.cat([chunk, torch.zeros_like(chunk[:, :1])], 1)
+        dist_all = model.relation_rank_counts(tri, return_scores=True)[-1]
+        ids, dist = _topk_of_losses(dist_all, torch.arange(R, device=dev), k, cells)
+        ids_out[s0:s0 + batch] = ids.to(torch.int64).cpu().numpy()
+        dist_out[s0:s0 + batch] = dist.cpu().numpy()
+    return ids_out, dist_out
+
+
+def translation_relation_lines(pairs, ids, dist, test_triples) -> list:
+    """The lines of a driver's <name>_predict_relations.tsv: per returned relation, in order,
+    'head, tail, position (1-based), relation, distance (%.9g: round-trips fp32), in_test' with in_test = 1 when
+    (head, tail, relation) is a test triple.  Padding (id -1) is not written."""
+    tset = {tuple(int(x) for x in t) for t in np.asarray(test_triples, dtype=np.int64).reshape(-1, 3)}
+    lines = []
+    for (h, t), row_ids, row_d in zip(np.asarray(pairs, dtype=np.int64), np.asarray(ids), np.asarray(dist)):
+        for j, (c, D) in enumerate(zip(row_ids, row_d)):
+            if c >= 0:
+                lines.append("%d\t%d\t%d\t%d\t%.9g\t%d\n" % (h, t, j + 1, c, float(D), (int(h), int(t), int(c)) in tset))
+    return lines
+
+
+def write_translation_relation_predictions(model, test, known, k: int, path: str) -> int:
+    """The driver's top-k relation file: for the distinct (h, t) pairs of the test triples, in order of first
+    appearance, the k best relations filtered by `known`; returns the number of lines."""
+    test = np.asarray(test, dtype=np.int64).reshape(-1, 3)
+    pairs = distinct_pairs(test[:, :2])
+    ids, dist = predict_translation_relations(model, pairs, k, known)
+    lines = translation_relation_lines(pairs, ids, dist, test)
+    with open(path, "w") as out:
+        out.writelines(lines)
+    return len(lines)
+
+
+def _relation_as_head(triples):
+    """(h, t, r) rows as (r, t, h): ComplEx's Re sum h r conj(t) and HolE's sum_{k,i} r_k h_i t_{i+k} are symmetric
+    under h <-> r, so the relation of (h, ?, t) is the head of (?, t, h) in the same table."""
+    if triples is None or isinstance(triples, KnownIndex):
+        return triples
+    t = np.asarray(triples, dtype=np.int64).reshape(-1, 3)
+    return t[:, [2, 1, 0]]
+
+
+def relation_ranks(embeddings: torch.Tensor, test, relation_count: int, known_triples=None, model: str = "complex", **kw):
+    """Raw and filtered rank of every test triple's relation among the relation rows [0, relation_count) of a ComplEx
+    or HolE table: link_prediction_ranks' head-side sweep on the triples with head and relation exchanged (the scores
+    are symmetric under h <-> r).  known_triples: an [n,3] (h, t, r) array, or a KnownIndex(side="head") built from
+    triples exchanged the same way.  Further keywords go to link_prediction_ranks."""
+    return link_prediction_ranks(embeddings, _relation_as_head(test), np.arange(int(relation_count), dtype=np.int32),
+                                 _relation_as_head(known_triples), side="head", model=model, **kw)
+
+
+def predict_relations(embeddings: torch.Tensor, pairs, relation_count: int, k: int, known_triples=None,
+                      model: str = "complex", **kw):
+    """Top-k relation prediction of a ComplEx or HolE table for (h, t) pairs: predict_links' head-side sweep over the
+    relation rows [0, relation_count) with the query (fixed = t, relation = h).  Returns (ids int64 [n,k], losses
+    float32 [n,k]); known relations of the pair are skipped; padding -1 / +inf."""
+    q = _entity_pairs(embeddings.shape[0], pairs)
+    return predict_links(embeddings, q[:, [1, 0]], np.arange(int(relation_count), dtype=np.int64), k,
+                         _relation_as_head(known_triples), side="head", model=model, **kw)
 
 
 def distinct_pairs(a) -> np.ndarray:

@@ -54,6 +54,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('--predict_k', type=int, default=0,
                    help='With --infer: also write <output_dir>/inference_results.tsv, every pop up to the K-th filtered '
                         'prediction of each confident (head, relation) test query (0: no predictions).')
+    p.add_argument('--relation_ranks', action='store_true',
+                   help='With --infer: also rank every test triple\'s relation among all relation rows, (h, ?, t), '
+                        'filtered by train + valid; prints the line and returns it as the `relation` block.  One GPU.')
     p.add_argument('--neighbors', type=int, default=0,
                    help='Write <output_dir>/neighbors.tsv from the checkpoint: the K nearest entities of every entity '
                         'row (no training).  Lines: query, query_name, position, neighbor, neighbor_name, distance.')
@@ -241,6 +244,14 @@ def infer_triples(FLAGS, log=print) -> dict:
         # the reference's prediction lines (holE.py:445-456), into the output directory (truncated), not appended to ./
         E.predict_inference_results(emb, data, FLAGS.predict_k, FLAGS.infer_threshold,
                                     os.path.join(FLAGS.output_dir, 'inference_results.tsv'), model=FLAGS.model, log=log)
+    if getattr(FLAGS, 'relation_ranks', False):
+        # (h, ?, t): the head-side sweep over the relation rows on the triples with head and relation exchanged
+        parts = [a for a in (data.triples, data.validation_triples) if a is not None]
+        raw, fil = E.relation_ranks(emb, data.test_array, data.relation_count, np.concatenate(parts, 0) if parts else None,
+                                    model=FLAGS.model)
+        out['relation'] = rel = E.mrr_and_hits(raw, fil)
+        log('relation: raw MRR {raw_mrr:.6f} (mean rank {mean_raw_pos:.1f}); filtered MRR {filtered_mrr:.6f} '
+            '(mean rank {mean_filtered_pos:.1f}); hits@1/3/10 {hits1:.2f} / {hits3:.2f} / {hits10:.2f} %'.format(**rel))
     return out
 
 
@@ -306,6 +317,10 @@ def main(argv=None):
     if FLAGS.predict_k and (FLAGS.gpus > 1 or world > 1):
         raise SystemExit('--predict_k runs on one GPU: top-k prediction over a row-sharded table is not implemented '
                          '(drop --gpus or --predict_k)')
+    if FLAGS.relation_ranks and not FLAGS.infer:
+        raise SystemExit('--relation_ranks needs --infer')
+    if FLAGS.relation_ranks and (FLAGS.gpus > 1 or world > 1):
+        raise SystemExit('--relation_ranks runs on one GPU (drop --gpus)')
     if FLAGS.gpus > 1 and 'WORLD_SIZE' not in os.environ and not FLAGS.save_embeddings:
         # no launcher: this process (which has not touched the GPU) becomes the parent of --gpus ranks of itself
         from . import launch

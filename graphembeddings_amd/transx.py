@@ -235,6 +235,42 @@ class _Model:
                   p(known_rc), k, ids.data_ptr(), dist.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
         return ids, dist
 
+    def relation_rank_counts(self, triples: torch.Tensor, known_off: torch.Tensor = None, known_rc: torch.Tensor = None,
+                             return_scores: bool = False):
+        """ge_transx_relation_rank / ge_transr_relation_rank on the [B,3] (h, t, r) rows as given: every relation c is
+        a candidate with D_c = D(h, t, c).  Returns (n_before, n_known_before, true_dist) device tensors, plus the
+        [B, n_rel] distances with return_scores.  known_off / known_rc: ge_known_cells' lists for these rows (fixed = h,
+        rel = t against a KnownIndex(side="relation")) with pos_of = the identity over [0, n_rel) (None: unfiltered).
+        Rows with an id out of range get -1 counts and a NaN distance."""
+        tb = _pairs(triples, "triples")
+        B, dev = tb.shape[0], tb.device
+        if (known_off is None) != (known_rc is None):
+            raise ValueError("known_off and known_rc come together")
+        ws_bytes = self._ws_bytes("relation_rank", max(B, 1))
+        if ws_bytes == 0:
+            raise RuntimeError(f"{self.PREFIX}_relation_rank_workspace_bytes failed")
+        nb = torch.empty(B, dtype=torch.int32, device=dev)
+        nk = torch.empty(B, dtype=torch.int32, device=dev)
+        td = torch.empty(B, dtype=torch.float32, device=dev)
+        sc = torch.empty((B, self.n_rel) if return_scores else (0,), dtype=torch.float32, device=dev)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        p = lambda t: None if t is None else t.data_ptr()
+        _lib.call(self.PREFIX + "_relation_rank", *self._ptrs(), tb.data_ptr(), B, p(known_off), p(known_rc),
+                  nb.data_ptr(), nk.data_ptr(), td.data_ptr(), sc.data_ptr() if return_scores else None, ws.data_ptr(),
+                  ws.numel(), _stream())
+        return (nb, nk, td, sc) if return_scores else (nb, nk, td)
+
+    def relation_ranks(self, test, known=None, batch: int = None):
+        """(raw, filtered) int64 rank arrays of the test triples' relations over every relation:
+        evaluate.translation_relation_ranks."""
+        from .evaluate import translation_relation_ranks
+        return translation_relation_ranks(self, test, known, batch=batch)
+
+    def predict_relations(self, pairs, k: int, known=None, batch: int = None):
+        """Top-k relation prediction for (h, t) pairs: evaluate.predict_translation_relations."""
+        from .evaluate import predict_translation_relations
+        return predict_translation_relations(self, pairs, k, known, batch=batch)
+
     def predict(self, queries, k: int, known=None, side: str = "tail", batch: int = None, fused: bool = None):
         """Top-k tail (or head) prediction over every entity: evaluate.predict_translation."""
         from .evaluate import predict_translation
@@ -294,7 +330,7 @@ class TransX(_Model):
                 p("ent_transfer"), p("rel_transfer"), self.d)
 
     def _ws_bytes(self, kind: str, B: int, *extra) -> int:
-        lead = (MODELS[self.model],) if kind in ("rank", "topk") else ()
+        lead = (MODELS[self.model],) if kind in ("rank", "topk", "relation_rank") else ()
         return getattr(_lib.load(), f"ge_transx_{kind}_workspace_bytes")(*lead, self.n_ent, self.n_rel, self.d, B, *extra)
 
     def step(self, pos: torch.Tensor, neg: torch.Tensor, lr: float, margin: float) -> torch.Tensor:

@@ -43,6 +43,13 @@ def add_common_flags(p: argparse.ArgumentParser, dims, out: str) -> None:
                         "--test_file, then the top K heads of every distinct (t, r), over all entities.  Lines: side, "
                         "fixed, relation, position, entity, distance, in_test.  Its filter is triple2id.txt + every "
                         "--filter_file but NOT the test file (unlike the ranking filter), so held-out answers can appear")
+    p.add_argument("--relation_ranks", action="store_true",
+                   help=f"with --test_file: also rank every test triple's relation among all relations (h, ?, t), same "
+                        f"filter; adds a `relation` block to {out}_test.json and prints its line")
+    p.add_argument("--predict_relations_k", type=int, default=None,
+                   help=f"after the evaluation write {out}_predict_relations.tsv: the top K relations of every distinct "
+                        "(h, t) of the --test_file.  Lines: head, tail, position, relation, distance, in_test.  Filter as "
+                        "--predict_k: triple2id.txt + every --filter_file, not the test file")
     p.add_argument("--neighbors_k", type=int, default=None,
                    help=f"after saving write {out}_neighbors.tsv: the K nearest entities of every entity by the `ent` "
                         "table (lines: query, position, neighbor, distance)")
@@ -65,6 +72,14 @@ def check_eval_args(a) -> None:
             raise ValueError("--predict_k needs --test_file")
         if a.predict_k < 1:
             raise ValueError(f"--predict_k must be >= 1, got {a.predict_k}")
+    if getattr(a, "relation_ranks", False) and not a.test_file:
+        raise ValueError("--relation_ranks needs --test_file")
+    rel_k = getattr(a, "predict_relations_k", None)     # (a Namespace built without the flag: none)
+    if rel_k is not None:
+        if not a.test_file:
+            raise ValueError("--predict_relations_k needs --test_file")
+        if rel_k < 1:
+            raise ValueError(f"--predict_relations_k must be >= 1, got {rel_k}")
     neighbors_k = getattr(a, "neighbors_k", None)       # (a Namespace built without the flag: none)
     if neighbors_k is not None and neighbors_k < 1:
         raise ValueError(f"--neighbors_k must be >= 1, got {neighbors_k}")
@@ -76,7 +91,8 @@ def check_eval_args(a) -> None:
 def run(a, driver: str, make_model, name: str) -> int:
     """Everything after the flags are checked: read --data_dir, build make_model(E, R), --load, train, save
     <name>.pt (with --neighbors_k, <name>_neighbors.tsv) and, with --test_file, rank it (heads and tails, printed)
-    into <name>_test.json; with --predict_k, write <name>_predict.tsv."""
+    into <name>_test.json (with --relation_ranks, relations too); with --predict_k, write <name>_predict.tsv; with
+    --predict_relations_k, <name>_predict_relations.tsv."""
     import numpy as np
     from .transx import read_kg, read_triples
     E, R, tri = read_kg(a.data_dir)
@@ -105,11 +121,13 @@ def run(a, driver: str, make_model, name: str) -> int:
         n = write_neighbors(tsv, m.tables["ent"].contiguous(), np.arange(E), a.neighbors_k, metric=a.neighbors_metric)
         print(f"wrote {tsv} ({n} lines)")
     if a.test_file:                  # filter: triple2id.txt + test + --filter_file
-        from .evaluate import evaluate_translation, write_translation_predictions
+        from .evaluate import (evaluate_translation, write_translation_predictions,
+                               write_translation_relation_predictions)
         test = read_triples(a.test_file, E, R)
         extra = [read_triples(f, E, R) for f in a.filter_file]
         known = np.concatenate([tri, test] + extra, 0)
-        res = evaluate_translation(m, test, known, both_sides=True, verbose=True)
+        res = evaluate_translation(m, test, known, both_sides=True, verbose=True,
+                                   relations=bool(getattr(a, "relation_ranks", False)))
         json_path = os.path.join(a.output_dir, f"{name}_test.json")
         with open(json_path, "w") as f:
             json.dump(res, f, indent=1, sort_keys=True)
@@ -117,6 +135,11 @@ def run(a, driver: str, make_model, name: str) -> int:
         if a.predict_k is not None:  # filter: triple2id.txt + --filter_file, not the test file
             tsv = os.path.join(a.output_dir, f"{name}_predict.tsv")
             n = write_translation_predictions(m, test, np.concatenate([tri] + extra, 0), a.predict_k, tsv)
+            print(f"wrote {tsv} ({n} lines)")
+        if getattr(a, "predict_relations_k", None) is not None:
+            tsv = os.path.join(a.output_dir, f"{name}_predict_relations.tsv")
+            n = write_translation_relation_predictions(m, test, np.concatenate([tri] + extra, 0),
+                                                       a.predict_relations_k, tsv)
             print(f"wrote {tsv} ({n} lines)")
     return 0
 

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define GE_VERSION 380 /* 0.3.8: + ge_neighbor_* (cosine / Euclidean nearest-neighbour entity search) */
+#define GE_VERSION 390 /* 0.3.9: + ge_transx_relation_rank / ge_transr_relation_rank (relation prediction (h, ?, t)) */
 
 /* argument errors (negative, -errno style) */
 #define GE_EINVAL (-22)  /* bad dimension / null pointer / misaligned buffer */
@@ -299,6 +299,37 @@ int ge_transr_rank(int l1, const float* ent, int64_t n_ent, const float* rel, co
                    const int32_t* known_off, const uint16_t* known_rc, int32_t* n_before, int32_t* n_known_before,
                    float* true_dist, float* scores_out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* --- relation prediction (h, ?, t) of the translation models: ranks of a triple's relation among EVERY relation.
+ * Row i = (h, t, r) of triples [B,3]: every c in [0, n_rel) is a candidate with D_c = D(h, t, c).  The arithmetic is
+ * fixed: the row's difference is taken once, w = e_h - e_t (one rounding per component), and the projection applied to
+ * it:  TransE u_k = w_k + r_c,k;  TransH a = n^_c . w, u_k = fmaf(-a, n^_c,k, w_k) + r_c,k (n^ normalised with the
+ * 1e-12 clamp, as ge_transx_score does);  TransD s = e_h . p_h - e_t . p_t (once per row), u_k = fmaf(s, rp_c,k, w_k)
+ * + r_c,k;  TransR u_k = (M_c w)_k + r_c,k;  D = sum_k |u_k| or sum_k u_k^2, k in order, every dot and sum a
+ * sequential fmaf chain in index order.  This equals ge_transx_score / ge_transr_score of (h, t, c) up to rounding.
+ *     n_before[i]       = #{c : D_c < D_r, or D_c == D_r and c < r}   (ascending (D, relation id); raw rank = 1 + it)
+ *     n_known_before[i] = how many of those c are listed in known_off / known_rc   (filtered rank = raw - it)
+ *     true_dist[i]      = D_r
+ *     scores_out        nullable, [B, n_rel]: every D_c (NaN in a row with an id out of range)
+ * Every D_c is computed once and stored (in the workspace, or in scores_out when given); the counts, true_dist and the
+ * filter read the stored values.  known_off / known_rc: ge_known_cells' tile lists for these rows with pos_of = the
+ * identity over [0, n_rel) and n_cand = n_rel (fixed = h, rel = t against an index keyed h * n_rows + t that holds the
+ * relations); NULL ranks unfiltered.  A row with an id out of range gets n_before = n_known_before = -1, true_dist
+ * NaN.  A row's result does not depend on the other rows of the call; two identical calls agree bitwise.
+ * Dims: 1 <= d <= ge_transx_max_dim(); TransR dims up to ge_transr_max_dim().  The caller passes `workspace`
+ * (256-byte aligned) of *_relation_rank_workspace_bytes bytes (0 for bad sizes; GE_ENOMEM when smaller): a fixed chunk
+ * of rows is processed at a time.  No host synchronisation inside; nothing allocated; no CPU path. */
+size_t ge_transx_relation_rank_workspace_bytes(int model, int64_t n_ent, int64_t n_rel, int32_t d, int64_t B);
+int ge_transx_relation_rank(int model, int l1, const float* ent, int64_t n_ent, const float* rel, int64_t n_rel,
+                            const float* normal, const float* ent_transfer, const float* rel_transfer, int32_t d,
+                            const int32_t* triples, int64_t B, const int32_t* known_off, const uint16_t* known_rc,
+                            int32_t* n_before, int32_t* n_known_before, float* true_dist, float* scores_out,
+                            void* workspace, size_t workspace_bytes, void* stream);
+size_t ge_transr_relation_rank_workspace_bytes(int64_t n_ent, int64_t n_rel, int32_t dim_e, int32_t dim_r, int64_t B);
+int ge_transr_relation_rank(int l1, const float* ent, int64_t n_ent, const float* rel, const float* rel_matrix,
+                            int64_t n_rel, int32_t dim_e, int32_t dim_r, const int32_t* triples, int64_t B,
+                            const int32_t* known_off, const uint16_t* known_rc, int32_t* n_before,
+                            int32_t* n_known_before, float* true_dist, float* scores_out, void* workspace,
+                            size_t workspace_bytes, void* stream);
 
 /* --- top-k tail / head prediction of the translation models over EVERY entity, selected inside the rank sweep (no
  * [B, n_ent] matrix).  Query row i = queries[2i], queries[2i+1] = (fixed f, relation r); every entity c is a candidate:
