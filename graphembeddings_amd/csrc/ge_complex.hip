@@ -703,6 +703,30 @@ __global__ __launch_bounds__(kBlock) void complex_logloss_grad_kernel(
 #pragma unroll
         for (int v = 0; v < VEC; ++v) { x[X].re[it][v] *= row_scale; x[X].im[it][v] *= row_scale; }
     }
+    // The dense factor of this objective can grow the table without bound (the reference's defaults: x -9.24 a step).
+    // Past elements of 2^42 the un-clipped score and, past row norms of 2^64, the sum of squares overflow fp32, and
+    // inf * 0 turned every row such a triple names into NaN.  A clipped row depends on its direction only, so a row
+    // with an element above 2^30 is read as row * 2^-e (largest element near 2^15: still far outside the unit ball,
+    // every intermediate in range): the forward pass is unchanged and d/d(row) = 2^-e * d/d(row * 2^-e).  Rows up to
+    // 2^30 take the arithmetic they always took, bit for bit.
+    float down[3];
+#pragma unroll
+    for (int X = 0; X < 3; ++X) {
+      float m = 0.f;
+#pragma unroll
+      for (int it = 0; it < NITER; ++it)
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) m = fmaxf(m, fmaxf(fabsf(x[X].re[it][v]), fabsf(x[X].im[it][v])));
+#pragma unroll
+      for (int o = LPT / 2; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, kWave));
+      down[X] = (m > 0x1p30f && m <= 3.4028234e38f) ? ldexpf(1.f, 15 - ilogbf(m)) : 1.f;
+      if (down[X] != 1.f) {
+#pragma unroll
+        for (int it = 0; it < NITER; ++it)
+#pragma unroll
+          for (int v = 0; v < VEC; ++v) { x[X].re[it][v] *= down[X]; x[X].im[it][v] *= down[X]; }
+      }
+    }
     const SideFwd f = side_forward<false, VEC, LPT, NITER>(x[0], x[1], x[2], max_norm, false, 1.f);
     const float z = -y * f.s;                                            // holE.py:195
     const float softplus = z > 0.f ? z + log1pf(expf(-z)) : log1pf(expf(z));
@@ -713,7 +737,8 @@ __global__ __launch_bounds__(kBlock) void complex_logloss_grad_kernel(
       const int64_t slot = g * 3 + X;
       if (live && sub == 0) grad_idx[slot] = bad ? -1 : p[X];
       if (!live || bad) continue;
-      const RowCoef kc = row_coef(coef, f, X, max_norm, neg_lr_eff);
+      RowCoef kc = row_coef(coef, f, X, max_norm, neg_lr_eff);
+      if (down[X] != 1.f) { kc.alpha *= down[X]; kc.beta *= down[X]; }
       float* gp = grad_val + slot * d;
 #pragma unroll
       for (int it = 0; it < NITER; ++it) {

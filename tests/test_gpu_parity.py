@@ -1133,8 +1133,10 @@ def test_native_logloss_loop_matches_oracle_over_twenty_dependent_steps(H, B, K,
 
 def test_native_logloss_loop_survives_the_reference_default_l2(H):
     """holE.py's own defaults (lr 0.1, batch 512, l2 0.1) make the dense factor 1 - lr*M*l2 = -9.24: the table
-    changes sign and grows ~9x per step.  The carried scalar is re-materialised when it leaves its range; the
-    loop must follow the oracle as long as fp32 holds (6 steps: ~6e5 growth)."""
+    changes sign and grows ~9x per step.  Over these 6 steps the carried scalar reaches 9.24^6 = 6e5 and stays inside
+    its range, so this covers a negative, growing scalar materialised once, at the end of the call; the loop must follow
+    the oracle as long as fp32 holds.  The scalar leaving its range in the middle of a run is
+    test_gpu_logloss_k.py::test_scalar_leaves_its_range_mid_run."""
     from graphembeddings_amd import data as D
     fb = D.fb15k_shape()
     names, id_to_type, offsets, ids = fb.type_arrays()
