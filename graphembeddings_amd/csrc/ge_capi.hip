@@ -38,6 +38,7 @@ int ge_complex_logloss(const float* table, int64_t N, int32_t d, const int32_t* 
   if (B < 0 || !ok_table(table, N, d) || !max_norm_ok(max_norm)) return GE_EINVAL;
   if (B == 0) return 0;
   if (!triples || !out || !workspace) return GE_EINVAL;
+  if (reinterpret_cast<uintptr_t>(workspace) % 256 != 0) return GE_EINVAL;
   if (workspace_bytes < 256) return GE_ENOMEM;
   float* sumsq = reinterpret_cast<float*>(workspace);
   int rc = table_sumsq_launch(table, N * (int64_t)d, sumsq, (hipStream_t)stream);
@@ -87,7 +88,7 @@ int ge_validation_tick(const float* table, int64_t N, int32_t d, const int32_t* 
                        void* stream) {
   if (B <= 0 || V <= 0 || !ok_table(table, N, d) || !max_norm_ok(max_norm) || model < 0 || model > 2) return GE_EINVAL;
   if (!valid || !id_to_type || !type_offsets || !type_ids || !workspace || !mean_out || !best) return GE_EINVAL;
-  if (reinterpret_cast<uintptr_t>(workspace) % 16 != 0) return GE_EINVAL;
+  if (reinterpret_cast<uintptr_t>(workspace) % 256 != 0) return GE_EINVAL;
   if (workspace_bytes < ge_validation_workspace_bytes(B)) return GE_ENOMEM;
   hipStream_t st = (hipStream_t)stream;
   int32_t* pos = (int32_t*)workspace;                 // [B,3] | neg [B,3] | loss [B] | flag
@@ -119,7 +120,7 @@ int ge_validation_tick_logloss(const float* table, int64_t N, int32_t d, const i
                                float* mean_out, float* best, float* pocket, void* stream) {
   if (B <= 0 || V <= 0 || negative_ratio < 1 || !ok_table(table, N, d) || !max_norm_ok(max_norm)) return GE_EINVAL;
   if (!valid || !id_to_type || !type_offsets || !type_ids || !workspace || !mean_out || !best) return GE_EINVAL;
-  if (reinterpret_cast<uintptr_t>(workspace) % 16 != 0) return GE_EINVAL;
+  if (reinterpret_cast<uintptr_t>(workspace) % 256 != 0) return GE_EINVAL;
   if (workspace_bytes < ge_validation_logloss_workspace_bytes(B, negative_ratio)) return GE_ENOMEM;
   hipStream_t st = (hipStream_t)stream;
   const int64_t K = negative_ratio, M = (1 + K) * B;
@@ -758,6 +759,7 @@ int ge_shard_plan(const int32_t* pos, const int32_t* neg, int64_t S, int64_t B, 
   if (peer_mapped && (G > 8 || ((N + G - 1) / G) * (G + 1) >= ((int64_t)1 << 30))) return GE_EINVAL;
   if (S == 0) return 0;
   if (!pos || !neg || !records || !pos_src || !neg_src || !req_row || !counts || !workspace) return GE_EINVAL;
+  if (reinterpret_cast<uintptr_t>(workspace) % 256 != 0) return GE_EINVAL;
   if (workspace_bytes < shard_plan_scratch_bytes(B, S)) return GE_ENOMEM;
   return shard_plan_launch(pos, neg, S, B, N, G, rank, records, pos_src, neg_src, req_row, counts, workspace, peer_mapped, (hipStream_t)stream);
 }
@@ -795,6 +797,7 @@ int ge_shard_owner_plan(const int32_t* req_all, const int64_t* req_start, int64_
   if (S < 0 || cap < 0 || rows_local <= 0 || rows_local >= ((int64_t)1 << 31) || cap >= ((int64_t)1 << 30)) return GE_EINVAL;
   if (S == 0 || cap == 0) return 0;
   if (!req_all || !req_start || !records || !workspace) return GE_EINVAL;
+  if (reinterpret_cast<uintptr_t>(workspace) % 256 != 0) return GE_EINVAL;
   if (workspace_bytes < shard_owner_scratch_bytes(cap, S)) return GE_ENOMEM;
   return shard_owner_plan_launch(req_all, req_start, S, cap, (int32_t)rows_local, records, workspace, (hipStream_t)stream);
 }
@@ -810,7 +813,7 @@ int ge_shard_owner_apply(float* shard, int64_t rows_local, int32_t d, const int3
 // workspace: [sumsq: 256 B][grad_idx: 3M int32, 256-B padded][grad_val: 3M*d fp32]
 size_t ge_logloss_step_workspace_bytes(int64_t M, int32_t d) {
   if (M <= 0 || d <= 0) return 0;
-  return 256 + align_up(sizeof(int32_t) * 3 * (size_t)M, 256) + sizeof(float) * 3 * (size_t)M * (size_t)d;
+  return 256 + align_up(sizeof(int32_t) * 3 * (size_t)M, 256) + align_up(sizeof(float) * 3 * (size_t)M * (size_t)d, 256);
 }
 
 int ge_complex_logloss_step(float* table, int64_t N, int32_t d, const int32_t* triples, const float* labels,

@@ -759,23 +759,41 @@ __global__ __launch_bounds__(kBlock) void complex_logloss_grad_kernel(
   }
 }
 
-// sum of squares of the whole table (tf.nn.l2_loss * 2) -> out[0]; out must be zeroed before.
-__global__ __launch_bounds__(kBlock) void table_sumsq_kernel(const float* __restrict__ t, int64_t n,
-                                                              float* __restrict__ out) {
-  float acc = 0.f;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const float v = t[i];
-    acc += v * v;
+// sum of squares of the whole table (tf.nn.l2_loss * 2) -> out[0], in a FIXED order: block b leaves its partial sum in
+// out[2 + b] (out is the 256-byte scratch every caller reserves: kSumsqBlocks <= 62 partials), a second launch adds
+// the partials by index.  No float atomics: the value is the same bits run to run, whatever the scratch held before.
+constexpr int kSumsqBlocks = 60, kSumsqThreads = 1024;
+__global__ __launch_bounds__(kSumsqThreads) void table_sumsq_kernel(const float* __restrict__ t, int64_t n,
+                                                                     float* __restrict__ out) {
+  // few blocks, so each thread keeps four 16-byte loads in flight (a table that is not 16-byte aligned goes by floats)
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x, tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t n4 = (reinterpret_cast<uintptr_t>(t) & 15) == 0 ? n / 4 : 0;
+  const float4* __restrict__ t4 = reinterpret_cast<const float4*>(t);
+  auto sq = [](const float4& v) { return (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w); };
+  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+  int64_t i = tid;
+  for (; i + 3 * stride < n4; i += 4 * stride) {
+    const float4 v0 = t4[i], v1 = t4[i + stride], v2 = t4[i + 2 * stride], v3 = t4[i + 3 * stride];
+    a0 += sq(v0); a1 += sq(v1); a2 += sq(v2); a3 += sq(v3);
   }
+  for (; i < n4; i += stride) a0 += sq(t4[i]);
+  for (int64_t j = 4 * n4 + tid; j < n; j += stride) { const float v = t[j]; a1 += v * v; }
+  float acc = (a0 + a1) + (a2 + a3);
   acc = group_sum<kWave>(acc);
-  __shared__ float part[kBlock / kWave];
+  __shared__ float part[kSumsqThreads / kWave];
   if ((threadIdx.x & (kWave - 1)) == 0) part[threadIdx.x >> 6] = acc;
   __syncthreads();
   if (threadIdx.x == 0) {
     float s = 0.f;
-    for (int w = 0; w < kBlock / kWave; ++w) s += part[w];
-    atomic_add_f32(out, s);
+    for (int w = 0; w < kSumsqThreads / kWave; ++w) s += part[w];
+    out[2 + blockIdx.x] = s;
   }
+}
+__global__ void table_sumsq_finish_kernel(float* __restrict__ out, int n_blocks) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  float s = 0.f;
+  for (int b = 0; b < n_blocks; ++b) s += out[2 + b];
+  out[0] = s;
 }
 
 // table *= factor : the dense part of the SGD step, (1 - lr * M * l2)
@@ -787,12 +805,13 @@ __global__ __launch_bounds__(kBlock) void table_scale_kernel(float* __restrict__
 // ---------------------------------------------------------------- dispatch
 struct Shape { int vec, lpt, niter; };
 
-static bool pick_shape(int d, const void* base, int max_niter, Shape& s) {
+// ld: floats between two rows (0: dense rows); vector loads need every row, not only the first, on their boundary
+static bool pick_shape(int d, const void* base, int max_niter, Shape& s, int64_t ld = 0) {
   if (d <= 0 || (d & 1)) return false;
   const int k = d / 2;
   int vec = (k % 4 == 0) ? 4 : (k % 2 == 0) ? 2 : 1;
   const uintptr_t a = reinterpret_cast<uintptr_t>(base);
-  while (vec > 1 && (a % (vec * 4)) != 0) vec >>= 1;
+  while (vec > 1 && ((a % (vec * 4)) != 0 || ld % vec != 0)) vec >>= 1;
   const int nvec = k / vec;
   int lpt = 16;
   while (lpt < 64 && lpt < nvec) lpt <<= 1;
@@ -837,8 +856,9 @@ int complex_score_launch(const float* table, int64_t N, int32_t d, const int32_t
                          float l2, const float* table_sumsq, int64_t ld) {
   Shape s;
   if (ld <= 0) ld = d;
-  if (!pick_shape(d, table, 2, s)) return (d <= 0 || (d & 1)) ? GE_EINVAL : GE_ENOTSUP;
-  if (ld < d || (s.vec > 1 && ld % s.vec != 0)) return GE_EINVAL;
+  if (ld < d) return GE_EINVAL;
+  // a row pitch that is no multiple of the vector width takes narrower loads (GE_ENOTSUP where the narrow kernels end)
+  if (!pick_shape(d, table, 2, s, ld)) return (d <= 0 || (d & 1)) ? GE_EINVAL : GE_ENOTSUP;
   if (B == 0) return 0;
   const int gpb = (kBlock / kWave) * (kWave / s.lpt);
   const int grid = grid_for(B, gpb);
@@ -948,9 +968,11 @@ int complex_logloss_grad_launch(const float* rows, int64_t N, int32_t d, const i
 }
 
 int table_sumsq_launch(const float* table, int64_t n, float* out, hipStream_t st) {
-  hipError_t e = hipMemsetAsync(out, 0, sizeof(float), st);
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(table_sumsq_kernel, dim3(grid_for(n, kBlock * 8)), dim3(kBlock), 0, st, table, n, out);
+  static_assert((2 + kSumsqBlocks) * sizeof(float) <= 256, "the partial sums live in the callers' 256-byte scratch");
+  int grid = grid_for(n, kSumsqThreads * 8);
+  if (grid > kSumsqBlocks) grid = kSumsqBlocks;
+  hipLaunchKernelGGL(table_sumsq_kernel, dim3(grid), dim3(kSumsqThreads), 0, st, table, n, out);
+  hipLaunchKernelGGL(table_sumsq_finish_kernel, dim3(1), dim3(kWave), 0, st, out, grid);
   return launch_status();
 }
 

@@ -27,7 +27,9 @@
 // to the caller's stream (one ~20 us launch per chunk of steps) and the library keeps no state at all.
 #include "ge_prep.h"
 #include "ge_launch.h"
+#include <algorithm>
 #include <cmath>
+#include <utility>
 
 namespace ge {
 
@@ -757,10 +759,34 @@ static size_t train_grad_bytes(int64_t B, int32_t d) {
 static size_t prep_chunk_bytes(int64_t B, int64_t negs = 0) {
   return align_up(sizeof(int32_t) * (size_t)prep_chunk_steps(B, negs) * (size_t)prep_layout(B, negs).stride, 256);
 }
-size_t train_ws_bytes(int64_t B, int32_t d) {
-  if (!train_fast_ok(B, d)) return hinge_ws_bytes(B, d);
+// The layout of a batch size b is cut from two step functions that only fall as b grows (steps prepared per chunk, regions
+// in the gradient ring), so the bytes it needs drop where one of them steps down.  A workspace size must not: a caller
+// that sizes for its largest batch must be able to run every smaller one.  need(b) rises between two drops, so the
+// largest need of any batch <= B is need(B) or the need of the last batch in front of a drop: those are visited here.
+template <class Need, class Step>
+static size_t largest_need_up_to(int64_t B, Need need, Step step) {
+  size_t best = need(B);
+  int64_t b = 1;
+  while (b < B) {
+    const auto v = step(b);
+    if (step(B) == v) break;
+    int64_t lo = b, hi = B;                              // step(lo) == v != step(hi)
+    while (hi - lo > 1) { const int64_t mid = lo + (hi - lo) / 2; if (step(mid) == v) lo = mid; else hi = mid; }
+    best = std::max(best, need(lo));
+    b = hi;
+  }
+  return best;
+}
+
+static size_t train_layout_bytes(int64_t B, int32_t d) {
   // two chunk buffers + (B > 4096) the key arrays of the multi-tile sort of ONE prepare sequence
   return train_grad_bytes(B, d) + 2 * prep_chunk_bytes(B) + prep_big_scratch_bytes(B, 0, prep_chunk_steps(B));
+}
+size_t train_ws_bytes(int64_t B, int32_t d) {
+  if (!train_fast_ok(B, d)) return hinge_ws_bytes(B, d);
+  // what this batch size's layout takes, and no less than any smaller batch's (ge_train_workspace_bytes is monotone in B)
+  return largest_need_up_to(B, [&](int64_t b) { return train_layout_bytes(b, d); },
+                            [&](int64_t b) { return std::make_pair(prep_chunk_steps(b), (int64_t)grad_ring(b, d)); });
 }
 
 static size_t prep_lds_bytes(const PrepLayout& L) {
@@ -1049,14 +1075,24 @@ int train_steps_run(float* table, int64_t N, int32_t d, const int32_t* triples, 
 // pass) at the end of the call, or earlier if |g| leaves [2^-40, 2^40] or a factor is exactly 0.
 // l2_loss(table) enters only the reported loss values: it is summed (one read pass) for the steps whose loss
 // vector the caller keeps (all of them with keep_all_losses, else the last).
-size_t train_logloss_ws_bytes(int64_t B, int32_t negs, int32_t d) {
+static size_t logloss_ring(int64_t B, int32_t negs, int32_t d) {
   const size_t M = (size_t)(1 + negs) * (size_t)B;
   const size_t region = align_up(sizeof(float) * 3 * M * (size_t)d, 256);
   size_t ring = ((size_t)64 << 20) / region + 1;
   if (ring < 2) ring = 2;
   if (ring > 8) ring = 8;
-  return 256 + align_up(sizeof(int32_t) * 3 * M, 256) + ring * region + 2 * prep_chunk_bytes(B, negs) +
+  return ring;
+}
+static size_t train_logloss_layout_bytes(int64_t B, int32_t negs, int32_t d) {
+  const size_t M = (size_t)(1 + negs) * (size_t)B;
+  const size_t region = align_up(sizeof(float) * 3 * M * (size_t)d, 256);
+  return 256 + align_up(sizeof(int32_t) * 3 * M, 256) + logloss_ring(B, negs, d) * region + 2 * prep_chunk_bytes(B, negs) +
          prep_big_scratch_bytes(B, negs, prep_chunk_steps(B, negs));
+}
+size_t train_logloss_ws_bytes(int64_t B, int32_t negs, int32_t d) {
+  // monotone in B, as train_ws_bytes is
+  return largest_need_up_to(B, [&](int64_t b) { return train_logloss_layout_bytes(b, negs, d); },
+                            [&](int64_t b) { return std::make_pair(prep_chunk_steps(b, negs), (int64_t)logloss_ring(b, negs, d)); });
 }
 
 int train_logloss_run(float* table, int64_t N, int32_t d, const int32_t* triples, int64_t T, int64_t first_row,

@@ -69,13 +69,15 @@ int ge_max_dim(void);
 int ge_complex_score(const float* table, int64_t N, int32_t d, const int32_t* triples, int64_t B,
                      float max_norm, int apply_sigmoid, float* out, void* stream);
 /* The same on a table whose rows are `ld` >= d floats apart (row i at table + i * ld; the reference's table is dense,
- * ld = d).  Exists to measure padded row layouts (800-byte rows straddle 64-byte sectors; profiles/r03_padded_rows.txt). */
+ * ld = d).  Exists to measure padded row layouts (800-byte rows straddle 64-byte sectors; profiles/r03_padded_rows.txt).
+ * Any ld >= d is taken: a pitch that is no multiple of 4 (or 2) floats is read with narrower loads (GE_ENOTSUP above
+ * d = 256, where the narrow kernels end). */
 int ge_complex_score_strided(const float* table, int64_t N, int32_t d, int64_t ld, const int32_t* triples, int64_t B,
                              float max_norm, int apply_sigmoid, float* out, void* stream);
 
 /* --- evaluate_triples(triple_batch, embeddings, label) in --log_loss mode (holE.py:194-196), forward only:
  * out[i] = log(1 + exp(-label * score_i)) + l2 * sum(table^2) / 2 (tf.nn.l2_loss of the WHOLE table).
- * workspace: >= 256 bytes of device scratch (the table's sum of squares). */
+ * workspace: >= 256 bytes of device scratch (the table's sum of squares), 256-byte aligned (else GE_EINVAL). */
 int ge_complex_logloss(const float* table, int64_t N, int32_t d, const int32_t* triples, int64_t B, float label,
                        float l2, float max_norm, float* out, void* workspace, size_t workspace_bytes, void* stream);
 
@@ -109,7 +111,7 @@ int ge_hinge_loss(const float* table, int64_t N, int32_t d, const int32_t* pos, 
  * ge_hinge_loss; its mean -> *mean_out (device); and the reference's "pocket": if the mean is below *best (device
  * scalar, start it at 2.0 as holE.py:336 does) then *best = mean and, when pocket is not NULL, pocket <- table.
  * The host reads the means whenever it likes (e.g. once per epoch) and knows from them which tick the pocket
- * holds.  workspace: >= ge_validation_workspace_bytes(B), 16-byte aligned. */
+ * holds.  workspace: >= ge_validation_workspace_bytes(B) (else GE_ENOMEM), 256-byte aligned (else GE_EINVAL). */
 size_t ge_validation_workspace_bytes(int64_t B);
 int ge_validation_tick(const float* table, int64_t N, int32_t d, const int32_t* valid, int64_t V, int64_t B,
                        const int32_t* id_to_type, const int64_t* type_offsets, int32_t n_types, const int32_t* type_ids,
@@ -118,7 +120,8 @@ int ge_validation_tick(const float* table, int64_t N, int32_t d, const int32_t* 
                        void* stream);
 /* The same tick for --log_loss (holE.py:194-196, 206-220 evaluated on a validation batch): the batch with label +1,
  * negative_ratio corrupted batches (ge_corrupt_batch with step = counter * negative_ratio + k) with label -1, every
- * loss = log(1 + exp(-y s)) + l2 * sum(table^2) / 2; mean over the (1 + negative_ratio) * B values, pocket as above. */
+ * loss = log(1 + exp(-y s)) + l2 * sum(table^2) / 2; mean over the (1 + negative_ratio) * B values, pocket and
+ * workspace rules as above (ge_validation_logloss_workspace_bytes(B, negative_ratio) bytes). */
 size_t ge_validation_logloss_workspace_bytes(int64_t B, int32_t negative_ratio);
 int ge_validation_tick_logloss(const float* table, int64_t N, int32_t d, const int32_t* valid, int64_t V, int64_t B,
                                const int32_t* id_to_type, const int64_t* type_offsets, int32_t n_types,
@@ -437,7 +440,9 @@ int ge_rank_1vK(const float* table, int64_t N, int32_t d, const int32_t* hr, int
  * stream-ordered allocation); a caller that ranks many batches against the same (table, cand, max_norm, model) --
  * holE.py:564-575 sweeps all entities for every test triple, tails and heads -- builds them once:
  *   ge_rank_planes_bytes   bytes of the buffer (0: this embedding_dim has no such sweep -- pass planes = NULL)
- *   ge_rank_planes         fills it (256-byte aligned); valid until the table, cand or max_norm change
+ *   ge_rank_planes         fills it (256-byte aligned); valid until the table, cand or max_norm change.  The buffer is
+ *                          opaque; the padding of its last tile and between its parts is UNDEFINED (never written,
+ *                          and never read into a result)
  *   ge_rank_1vK_planes     ge_rank_1vK with the buffer (NULL: as ge_rank_1vK).  cand_is_head does not enter the planes.
  * The contract says true_id[i] is in `cand`; where it is not, the split-precision sweep reports no rank (n_before =
  * n_known_before = 0, true_loss NaN) while the fp32 kernels rank the entity against the candidates all the same. */
@@ -539,7 +544,12 @@ int ge_known_cells(int pass, const int64_t* known_key, const int64_t* known_ent,
  * ev_pairs (nullable, HOST array of 2*n_steps events from ge_event_create): the events ride on the
  * dispatch of kernel `ev_kernel` of every step (1 = gather+score+hinge+grad, 2 = row update; 0 =
  * the per-step sampler of the fallback path) and report that kernel's own begin/end -- the hook
- * bench.py uses to time one kernel; NULL entries skip a step. */
+ * bench.py uses to time one kernel; NULL entries skip a step.
+ * ge_train_workspace_bytes (and ge_train_logloss_workspace_bytes) never shrink as B grows: a workspace sized for the
+ * largest batch serves every smaller one on the prepared path.  ge_train_logloss_workspace_bytes is NOT monotone in
+ * negative_ratio: the steps prepared per chunk and the gradient ring shrink as (1 + negative_ratio) * B grows, so a
+ * larger ratio can need fewer bytes (B = 1024, d = 8: ratio 31 needs more than ratio 32).  Size the workspace for the
+ * ratio the loop is called with; a call with another ratio than it was sized for may be GE_ENOMEM. */
 size_t ge_train_workspace_bytes(int64_t B, int32_t d);
 int ge_train_pipeline_create(void** pipeline);
 int ge_train_pipeline_reset(void* pipeline);
@@ -607,7 +617,8 @@ int ge_train_prepare_steps(const int32_t* triples, int64_t T, int64_t first_row,
  *     index in its owner's shard, grouped by owner; counts [S,G]: rows requested from each owner.
  *   peer_mapped = 1 (experiment, G <= 8): pos_src / neg_src name another owner's row by R * (1 + owner) + local row
  *     instead of R + u -- for ge_shard_grad with peer_shards (HOST array of the G shards' device addresses, mapped
- *     into this process; entry `rank` unused), which reads those rows in place and takes no staging buffer. */
+ *     into this process; entry `rank` unused), which reads those rows in place and takes no staging buffer.
+ *   workspace: ge_shard_plan_workspace_bytes(B, S) bytes (GE_ENOMEM when smaller), 256-byte aligned (else GE_EINVAL). */
 size_t ge_shard_plan_workspace_bytes(int64_t B, int64_t S);
 int ge_shard_plan(const int32_t* pos, const int32_t* neg, int64_t S, int64_t B, int64_t N, int32_t G, int32_t rank,
                   int32_t* records, int32_t* pos_src, int32_t* neg_src, int32_t* req_row, int32_t* counts,
@@ -627,7 +638,8 @@ int ge_shard_apply(float* shard, int64_t rows_local, int32_t d, const int32_t* r
 /* Owner side: req_all = the chunk's received request lists (rows of this shard) in (step, peer) order, step s =
  * [req_start[s], req_start[s+1]) (req_start: DEVICE int64 [S+1]); cap >= the longest per-step list.  records
  * [S, ge_shard_owner_record_words(cap)]: work items that add row j of the step's receive buffer to shard row
- * req[j] -- one read-modify-write per distinct row, fixed order. */
+ * req[j] -- one read-modify-write per distinct row, fixed order.  workspace: ge_shard_owner_workspace_bytes(cap, S)
+ * bytes (GE_ENOMEM when smaller), 256-byte aligned (else GE_EINVAL). */
 int64_t ge_shard_owner_record_words(int64_t cap);
 size_t ge_shard_owner_workspace_bytes(int64_t cap, int64_t S);
 int ge_shard_owner_plan(const int32_t* req_all, const int64_t* req_start, int64_t S, int64_t cap, int64_t rows_local,
