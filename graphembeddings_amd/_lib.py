@@ -119,6 +119,9 @@ SYMBOLS = {
     "ge_transr_topk_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32, _i64, _i32]),
     "ge_transr_topk": (C.c_int, [C.c_int, _p, _i64, _p, _p, _i64, _i32, _i32, _p, _i64, C.c_int, _p, _p, _i32, _p, _p,
                                  _p, _sz, _p]),
+    "ge_threshold_fit_workspace_bytes": (_sz, [_i64, _i32]),
+    "ge_threshold_fit": (C.c_int, [_p, _p, _p, _i64, _i32, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "ge_threshold_classify": (C.c_int, [_p, _p, _p, _i64, _i32, _p, _p, _p, _p]),
     "ge_event_create": (C.c_int, [C.POINTER(C.c_void_p)]),
     "ge_event_destroy": (C.c_int, [_p]),
     "ge_event_record": (C.c_int, [_p, _p]),

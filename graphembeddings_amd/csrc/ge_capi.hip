@@ -572,6 +572,30 @@ int ge_neighbor_topk(const float* table, int64_t N, int32_t d, const int32_t* qu
                               workspace, workspace_bytes, (hipStream_t)stream);
 }
 
+size_t ge_threshold_fit_workspace_bytes(int64_t M, int32_t n_seg) { return threshold_fit_ws_bytes(M, n_seg); }
+
+int ge_threshold_fit(const float* score, const int32_t* seg, const uint8_t* label, int64_t M, int32_t n_seg,
+                     float* thr_lo, float* thr_hi, int32_t* best_correct, int32_t* n_pos, int32_t* n_neg,
+                     void* workspace, size_t workspace_bytes, void* stream) {
+  if (M < 1 || M > INT32_MAX || n_seg < 1 || !score || !seg || !label) return GE_EINVAL;
+  if (!thr_lo || !thr_hi || !best_correct || !n_pos || !n_neg) return GE_EINVAL;
+  for (const void* p : {(const void*)score, (const void*)seg, (const void*)thr_lo, (const void*)thr_hi,
+                        (const void*)best_correct, (const void*)n_pos, (const void*)n_neg})
+    if (!aligned4(p)) return GE_EINVAL;
+  if (!workspace || ((uintptr_t)workspace & 255)) return GE_EINVAL;
+  if (workspace_bytes < threshold_fit_ws_bytes(M, n_seg)) return GE_ENOMEM;
+  return threshold_fit_launch(score, seg, label, M, n_seg, thr_lo, thr_hi, best_correct, n_pos, n_neg, workspace,
+                              (hipStream_t)stream);
+}
+
+int ge_threshold_classify(const float* score, const int32_t* seg, const uint8_t* label, int64_t M, int32_t n_seg,
+                          const float* thr, uint8_t* pred, int32_t* confusion, void* stream) {
+  if (M < 0 || M > INT32_MAX || n_seg < 1 || !thr || !aligned4(thr)) return GE_EINVAL;
+  if (confusion && (!label || !aligned4(confusion))) return GE_EINVAL;
+  if (M > 0 && (!score || !seg || !pred || !aligned4(score) || !aligned4(seg))) return GE_EINVAL;
+  return threshold_classify_launch(score, seg, label, M, n_seg, thr, pred, confusion, (hipStream_t)stream);
+}
+
 int ge_complex_score_1vK(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B,
                          const int32_t* cand, int64_t K, float max_norm, int apply_sigmoid, int cand_is_head,
                          float* out, void* stream) {

@@ -272,4 +272,12 @@ int transr_relrank_launch(int l1, const float* ent, int64_t E, const float* rel,
                           const uint16_t* known_rc, int32_t* n_before, int32_t* n_known_before, float* true_dist,
                           float* scores_out, void* workspace, size_t workspace_bytes, hipStream_t st);
 
+// ge_classify.hip: triple classification -- per-segment thresholds fitted from sorted labelled scores, the decision
+size_t threshold_fit_ws_bytes(int64_t M, int32_t n_seg);
+int threshold_fit_launch(const float* score, const int32_t* seg, const uint8_t* label, int64_t M, int32_t n_seg,
+                         float* thr_lo, float* thr_hi, int32_t* best_correct, int32_t* n_pos, int32_t* n_neg,
+                         void* workspace, hipStream_t st);
+int threshold_classify_launch(const float* score, const int32_t* seg, const uint8_t* label, int64_t M, int32_t n_seg,
+                              const float* thr, uint8_t* pred, int32_t* confusion, hipStream_t st);
+
 }  // namespace ge

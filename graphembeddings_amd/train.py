@@ -57,6 +57,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('--relation_ranks', action='store_true',
                    help='With --infer: also rank every test triple\'s relation among all relation rows, (h, ?, t), '
                         'filtered by train + valid; prints the line and returns it as the `relation` block.  One GPU.')
+    p.add_argument('--classify', action='store_true',
+                   help='With --infer: triple classification.  One threshold per relation is fitted on triples-valid.txt '
+                        'and the test triples are classified, negatives drawn one per positive by the type-safe sampler '
+                        '(draws that are known triples are dropped); prints a line, writes <output_dir>/<model>_classify.json '
+                        'and <model>_thresholds.tsv.  One GPU.')
+    p.add_argument('--classify_seed', type=int, default=0, help='With --classify: seed of the drawn negatives.')
     p.add_argument('--neighbors', type=int, default=0,
                    help='Write <output_dir>/neighbors.tsv from the checkpoint: the K nearest entities of every entity '
                         'row (no training).  Lines: query, query_name, position, neighbor, neighbor_name, distance.')
@@ -252,7 +258,40 @@ def infer_triples(FLAGS, log=print) -> dict:
         out['relation'] = rel = E.mrr_and_hits(raw, fil)
         log('relation: raw MRR {raw_mrr:.6f} (mean rank {mean_raw_pos:.1f}); filtered MRR {filtered_mrr:.6f} '
             '(mean rank {mean_filtered_pos:.1f}); hits@1/3/10 {hits1:.2f} / {hits3:.2f} / {hits10:.2f} %'.format(**rel))
+    if getattr(FLAGS, 'classify', False):
+        out['classify'] = classify_triples(FLAGS, data, emb, log=log)
     return out
+
+
+def classify_triples(FLAGS, data, emb, log=print) -> dict:
+    """--infer --classify: thresholds fitted on the validation split, the test split classified, negatives from the
+    type-safe sampler filtered by train + valid + test; <model>_classify.json and <model>_thresholds.tsv."""
+    from . import classify as C
+    if data.validation_triples is None or len(data.validation_triples) == 0:
+        raise SystemExit('--classify needs triples-valid.txt')
+    _, id_to_type, offsets, ids = data.type_arrays()
+    tt = H.TypeTables.from_host(id_to_type, offsets, ids, padded_size=FLAGS.padded_size)
+    known = np.concatenate([a for a in (data.triples, data.validation_triples, data.test_array) if a is not None], 0)
+    res = C.triple_classification(C.TableModel(emb, data.relation_count, tt, FLAGS.model), data.validation_triples,
+                                  data.test_array, known=known, seed=FLAGS.classify_seed)
+    log(C.summary_line(res))
+    json_path = os.path.join(FLAGS.output_dir, f'{FLAGS.model}_classify.json')
+    tsv = os.path.join(FLAGS.output_dir, f'{FLAGS.model}_thresholds.tsv')
+    C.write_results(res, json_path, tsv)
+    log(f'wrote {json_path} and {tsv}')
+    return C.report(res)
+
+
+def check_classify_flags(FLAGS, world: int = 1) -> None:
+    """--classify is part of --infer, on one GPU."""
+    if not FLAGS.classify:
+        return
+    if not FLAGS.infer:
+        raise SystemExit('--classify needs --infer')
+    if FLAGS.gpus > 1 or world > 1:
+        raise SystemExit('--classify runs on one GPU (drop --gpus)')
+    if FLAGS.classify_seed < 0:
+        raise SystemExit('--classify_seed must be >= 0')
 
 
 def check_neighbor_flags(FLAGS, world: int = 1) -> None:
@@ -317,6 +356,7 @@ def main(argv=None):
     if FLAGS.predict_k and (FLAGS.gpus > 1 or world > 1):
         raise SystemExit('--predict_k runs on one GPU: top-k prediction over a row-sharded table is not implemented '
                          '(drop --gpus or --predict_k)')
+    check_classify_flags(FLAGS, world)
     if FLAGS.relation_ranks and not FLAGS.infer:
         raise SystemExit('--relation_ranks needs --infer')
     if FLAGS.relation_ranks and (FLAGS.gpus > 1 or world > 1):

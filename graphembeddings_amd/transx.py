@@ -281,6 +281,13 @@ class _Model:
         from .evaluate import translation_ranks
         return translation_ranks(self, test, known, side=side, batch=batch)
 
+    def triple_classification(self, valid_pos, test_pos, valid_neg=None, test_neg=None, known=None, seed: int = 0,
+                              mode: str = "mid"):
+        """Per-relation thresholds fitted on the validation split, the test split classified:
+        classify.triple_classification."""
+        from .classify import triple_classification
+        return triple_classification(self, valid_pos, test_pos, valid_neg, test_neg, known=known, seed=seed, mode=mode)
+
     def trainer(self, triples, batch_size: int, *, margin: float = 1.0, learning_rate: float = 0.001,
                 seed: int = 0) -> Trainer:
         return self._trainer(self, triples, batch_size, margin=margin, learning_rate=learning_rate, seed=seed)

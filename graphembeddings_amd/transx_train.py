@@ -50,6 +50,15 @@ def add_common_flags(p: argparse.ArgumentParser, dims, out: str) -> None:
                    help=f"after the evaluation write {out}_predict_relations.tsv: the top K relations of every distinct "
                         "(h, t) of the --test_file.  Lines: head, tail, position, relation, distance, in_test.  Filter as "
                         "--predict_k: triple2id.txt + every --filter_file, not the test file")
+    p.add_argument("--classify", action="store_true",
+                   help=f"triple classification after the evaluation: fit one threshold per relation on the --valid_file, "
+                        f"classify the --test_file; prints a line, writes {out}_classify.json and {out}_thresholds.tsv.  "
+                        "Negatives not given are drawn one per positive by the filtered Bernoulli sampler over "
+                        "triple2id.txt + valid + test + every --filter_file")
+    p.add_argument("--valid_file", default=None, help="a *2id.txt file of validation triples (for --classify)")
+    p.add_argument("--valid_neg_file", default=None, help="false validation triples, same `h t r` id format")
+    p.add_argument("--test_neg_file", default=None, help="false test triples, same `h t r` id format")
+    p.add_argument("--classify_seed", type=int, default=0, help="seed of the drawn negatives")
     p.add_argument("--neighbors_k", type=int, default=None,
                    help=f"after saving write {out}_neighbors.tsv: the K nearest entities of every entity by the `ent` "
                         "table (lines: query, position, neighbor, distance)")
@@ -83,7 +92,16 @@ def check_eval_args(a) -> None:
     neighbors_k = getattr(a, "neighbors_k", None)       # (a Namespace built without the flag: none)
     if neighbors_k is not None and neighbors_k < 1:
         raise ValueError(f"--neighbors_k must be >= 1, got {neighbors_k}")
-    for path in ([a.test_file] if a.test_file else []) + list(a.filter_file) + ([a.load] if a.load else []):
+    classify_files = [getattr(a, k, None) for k in ("valid_file", "valid_neg_file", "test_neg_file")]
+    if getattr(a, "classify", False):
+        if not a.test_file or not a.valid_file:
+            raise ValueError("--classify needs --test_file and --valid_file")
+        if a.classify_seed < 0:
+            raise ValueError(f"--classify_seed must be non-negative, got {a.classify_seed}")
+    elif any(classify_files):
+        raise ValueError("--valid_file, --valid_neg_file and --test_neg_file need --classify")
+    for path in ([a.test_file] if a.test_file else []) + list(a.filter_file) + ([a.load] if a.load else []) \
+            + [f for f in classify_files if f]:
         if not os.path.isfile(path):
             raise ValueError(f"no such file: {path}")
 
@@ -92,7 +110,8 @@ def run(a, driver: str, make_model, name: str) -> int:
     """Everything after the flags are checked: read --data_dir, build make_model(E, R), --load, train, save
     <name>.pt (with --neighbors_k, <name>_neighbors.tsv) and, with --test_file, rank it (heads and tails, printed)
     into <name>_test.json (with --relation_ranks, relations too); with --predict_k, write <name>_predict.tsv; with
-    --predict_relations_k, <name>_predict_relations.tsv."""
+    --predict_relations_k, <name>_predict_relations.tsv; with --classify, <name>_classify.json and
+    <name>_thresholds.tsv."""
     import numpy as np
     from .transx import read_kg, read_triples
     E, R, tri = read_kg(a.data_dir)
@@ -141,6 +160,18 @@ def run(a, driver: str, make_model, name: str) -> int:
             n = write_translation_relation_predictions(m, test, np.concatenate([tri] + extra, 0),
                                                        a.predict_relations_k, tsv)
             print(f"wrote {tsv} ({n} lines)")
+    if getattr(a, "classify", False):  # negatives drawn against triple2id.txt + valid + test + --filter_file
+        from . import classify as C
+        test, valid = read_triples(a.test_file, E, R), read_triples(a.valid_file, E, R)
+        extra = [read_triples(f, E, R) for f in a.filter_file]
+        neg = {k: read_triples(getattr(a, k), E, R) if getattr(a, k) else None for k in ("valid_neg_file", "test_neg_file")}
+        res = m.triple_classification(valid, test, neg["valid_neg_file"], neg["test_neg_file"],
+                                      known=np.concatenate([tri, valid, test] + extra, 0), seed=a.classify_seed)
+        print(C.summary_line(res))
+        json_path = os.path.join(a.output_dir, f"{name}_classify.json")
+        tsv = os.path.join(a.output_dir, f"{name}_thresholds.tsv")
+        C.write_results(res, json_path, tsv)
+        print(f"wrote {json_path} and {tsv}")
     return 0
 
 

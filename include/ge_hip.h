@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define GE_VERSION 390 /* 0.3.9: + ge_transx_relation_rank / ge_transr_relation_rank (relation prediction (h, ?, t)) */
+#define GE_VERSION 400 /* 0.4.0: + ge_threshold_fit / ge_threshold_classify (triple classification) */
 
 /* argument errors (negative, -errno style) */
 #define GE_EINVAL (-22)  /* bad dimension / null pointer / misaligned buffer */
@@ -333,6 +333,39 @@ int ge_transr_relation_rank(int l1, const float* ent, int64_t n_ent, const float
                             const int32_t* known_off, const uint16_t* known_rc, int32_t* n_before,
                             int32_t* n_known_before, float* true_dist, float* scores_out, void* workspace,
                             size_t workspace_bytes, void* stream);
+
+/* --- triple classification: is (h, r, t) true?  All six models score "lower is more plausible" (the distance D of
+ * ge_transx_score / ge_transr_score, E = sigmoid(score) of ge_complex_score / ge_hole_score), so one rule serves them:
+ * a triple is predicted true iff  score <= thr[segment]  (a segment is a relation; a NaN score is never accepted).
+ *
+ * ge_threshold_fit fits thr from labelled scores.  score / seg / label [M] (label 0 or 1) are ORDERED by (seg ascending,
+ * score ascending, NaN last); an element whose seg is outside [0, n_seg) is ignored.  Per segment of m elements, m_v of
+ * them not NaN:  a cut p accepts the first p;  p is admissible iff p == 0, or 1 <= p <= m_v and (p == m_v or
+ * score[p-1] < score[p])  -- equal scores are never separated, NaNs are rejected at every cut;
+ * correct(p) = #positives in [0,p) + #negatives in [p,m);  the fit takes the admissible p with the largest correct(p),
+ * the smallest such p on a tie.  Outputs, each [n_seg]:
+ *     thr_lo = score[p-1] (-inf for p = 0)     thr_hi = score[p] (+inf for p = m_v)
+ *     best_correct = correct(p)                n_pos, n_neg = the segment's positives / negatives
+ * An empty segment gives -inf, +inf, 0, 0, 0.  Every output is an integer or a copy of an input float or an infinity.
+ * Any threshold in [thr_lo, thr_hi) reproduces the cut.  1 <= M <= 2^31 - 1, n_seg >= 1, segments of any length: the
+ * work is spread over workgroups of GE_THRESHOLD_FIT_TILE consecutive elements whatever the segment lengths are; the
+ * counting is in integers (integer atomics only), so the result does not depend on the grid and two identical calls
+ * agree bitwise.  Input that is not ordered gives other numbers but no access outside the buffers.
+ * workspace: ge_threshold_fit_workspace_bytes(M, n_seg) bytes (0 for sizes out of range; monotone in both arguments;
+ * GE_ENOMEM when smaller), 256-byte aligned (else GE_EINVAL).
+ *
+ * ge_threshold_classify decides, in any order of the input:  pred[i] = score[i] <= thr[seg[i]]  (uint8 0 / 1; 0 for a
+ * NaN score or threshold and for a seg outside [0, n_seg)).  thr [n_seg].  label and confusion are nullable; with both,
+ * confusion [n_seg, 4] = (tp, fp, tn, fn) per segment over the elements whose seg is in range, zeroed by the call and
+ * accumulated with integer atomics (confusion without label is GE_EINVAL).  M >= 0.
+ * Both: no host synchronisation inside; nothing allocated; no CPU path. */
+#define GE_THRESHOLD_FIT_TILE 2048
+size_t ge_threshold_fit_workspace_bytes(int64_t M, int32_t n_seg);
+int ge_threshold_fit(const float* score, const int32_t* seg, const uint8_t* label, int64_t M, int32_t n_seg,
+                     float* thr_lo, float* thr_hi, int32_t* best_correct, int32_t* n_pos, int32_t* n_neg,
+                     void* workspace, size_t workspace_bytes, void* stream);
+int ge_threshold_classify(const float* score, const int32_t* seg, const uint8_t* label, int64_t M, int32_t n_seg,
+                          const float* thr, uint8_t* pred, int32_t* confusion, void* stream);
 
 /* --- top-k tail / head prediction of the translation models over EVERY entity, selected inside the rank sweep (no
  * [B, n_ent] matrix).  Query row i = queries[2i], queries[2i+1] = (fixed f, relation r); every entity c is a candidate:
