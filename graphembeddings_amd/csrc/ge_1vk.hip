@@ -667,81 +667,63 @@ __global__ __launch_bounds__(kBlock) void score_1vK_f16_kernel(
   }
 }
 
+// ge_complex_score_1vK: a switch on route_score (ge_sweep_route.h).  Big sweeps take the rank sweeps' kernels writing
+// scores instead of counting; the rest the tile kernels of this file.
 int complex_score_1vK_launch(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B,
                              const int32_t* cand, int64_t K, float max_norm, int apply_sigmoid,
                              int cand_is_head, float* out, hipStream_t st) {
-  if (d <= 0 || (d & 1)) return GE_EINVAL;
-  if (B == 0 || K == 0) return 0;
-  // large sweeps with embedding_dim a multiple of 40 / 32 / 24: the software-pipelined kernel of ge_rank_pipe.hip
-  // (Q resident in LDS, operands and candidate rows issued between the MFMAs) writing scores instead of counting
-  if (((B + 127) / 128) * ((K + 127) / 128) >= 512 && reinterpret_cast<uintptr_t>(table) % 16 == 0) {
-    const int rc = score_pipe_launch(table, N, d, hr, B, cand, K, max_norm, apply_sigmoid, cand_is_head, out, st);
-    if (rc != GE_ENOTSUP) return rc;
-  }
+  const bool aligned = reinterpret_cast<uintptr_t>(table) % 16 == 0;
+  const SweepRoute r = route_score(N, d, B, K, max_norm, aligned ? 0 : 1);
   const int k = d / 2;
-  const bool v4 = (k % 4 == 0) && (reinterpret_cast<uintptr_t>(table) % 16 == 0);
-  const int64_t big_blocks = ((B + 127) / 128) * ((K + 127) / 128);
-  const bool big = big_blocks >= 512;
+  const bool v4 = (k % 4 == 0) && aligned, big = sweep_is_big(B, K);
   const int bm = big ? 128 : 64;
-  const int64_t gy = (B + bm - 1) / bm, gx = (K + bm - 1) / bm;
-  if (gy > 65535 || gx > 2147483647LL) return GE_ENOTSUP;
-  dim3 grid((unsigned)gx, (unsigned)gy);
-  if (!big && d % 8 == 0 && d >= 56 && d <= 224 && max_norm <= 8.f && reinterpret_cast<uintptr_t>(table) % 16 == 0) {
-    // up to a few hundred 64 x 64 tiles, split precision: all of the tile's loads in flight, f16 MFMAs
-    const int kkb = (d + 15) / 16, cgq = (k / 4 + 3) / 4;        // column groups per staging lane
-    const size_t lds16 = sizeof(_Float16) * (size_t)(4 * 64 * (16 * kkb + 8)) + sizeof(float) * 128;
-#define LH(NIT_)                                                                                                          \
-    {                                                                                                                     \
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(score_1vK_f16_kernel<NIT_>),                       \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                         \
-      if (e != hipSuccess) return (int)e;                                                                                 \
-      hipLaunchKernelGGL((score_1vK_f16_kernel<NIT_>), grid, dim3(kBlock), lds16, st, table, N, d, hr, B, cand, K,        \
-                         max_norm, apply_sigmoid, cand_is_head, out);                                                     \
-      return launch_status();                                                                                             \
-    }
-    switch (cgq) {                                               // (56 <= d <= 224: 2 ... 7 groups a lane, compiled exactly)
-      case 2: LH(2) case 3: LH(3) case 4: LH(4) case 5: LH(5) case 6: LH(6) default: LH(7)
-    }
-#undef LH
-  }
-  if (!big && d % 8 == 0 && d <= 256 && reinterpret_cast<uintptr_t>(table) % 16 == 0) {
-    // up to a few hundred 64 x 64 tiles: the whole tile's loads in flight in two batches, 16-byte LDS traffic
-    const size_t lds = sizeof(float) * std::max<size_t>((size_t)16 * (k / 4) * 64, 64 * 65) + sizeof(float) * 128;
-    const int cg = k / 4;
-#define LT(NA, NB)                                                                                                        \
-    {                                                                                                                     \
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(score_1vK_tile_kernel<NA, NB>),                    \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                         \
-      if (e != hipSuccess) return (int)e;                                                                                 \
-      hipLaunchKernelGGL((score_1vK_tile_kernel<NA, NB>), grid, dim3(kBlock), lds, st, table, N, d, hr, B, cand, K,       \
-                         max_norm, apply_sigmoid, cand_is_head, out);                                                     \
-      return launch_status();                                                                                             \
-    }
-    if (cg <= 8) LT(1, 1) else if (cg <= 16) LT(2, 2) else if (cg <= 28) LT(4, 3) else LT(4, 4)
-#undef LT
-  }
-  const int KP = (k + 3) & ~3;
-  const size_t fullk_lds = sizeof(float) * (size_t)(2 * 64 * (2 * KP + 1) + 128);
-  if (!big && fullk_lds <= 150 * 1024) {
-    // the opt-in is a per-device property: set it on every launch (idempotent, cheap) rather than cache a
-    // per-process flag that would be wrong on a second device
-    hipError_t e = v4 ? hipFuncSetAttribute(reinterpret_cast<const void*>(score_1vK_fullk_kernel<true>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)
-                      : hipFuncSetAttribute(reinterpret_cast<const void*>(score_1vK_fullk_kernel<false>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return (int)e;
-    if (v4)
-      hipLaunchKernelGGL(score_1vK_fullk_kernel<true>, grid, dim3(kBlock), fullk_lds, st, table, N, d, hr, B, cand, K, max_norm, apply_sigmoid, cand_is_head, out, KP);
-    else
-      hipLaunchKernelGGL(score_1vK_fullk_kernel<false>, grid, dim3(kBlock), fullk_lds, st, table, N, d, hr, B, cand, K, max_norm, apply_sigmoid, cand_is_head, out, KP);
+  const dim3 grid((unsigned)((K + bm - 1) / bm), (unsigned)((B + bm - 1) / bm));   // of the tile kernels
+  auto go = [&](auto kern, size_t lds, auto... extra) -> int {
+    if (lds != 0)                                      // (dynamic LDS: beyond the default 64 KiB)
+      if (int rc = lds_opt_in(kern)) return rc;
+    hipLaunchKernelGGL(kern, grid, dim3(kBlock), lds, st, table, N, d, hr, B, cand, K, max_norm, apply_sigmoid, cand_is_head,
+                       out, extra...);
     return launch_status();
+  };
+  switch (r.kernel) {
+    case SweepRoute::F16:
+    case SweepRoute::Pipe40:
+    case SweepRoute::Pipe32:
+    case SweepRoute::Pipe24: {
+      const SweepArgs a{table, N, d, hr, B, nullptr, cand, K, max_norm, cand_is_head, nullptr, nullptr, nullptr, nullptr,
+                        nullptr, out, /*spec=*/0, /*scores_only=*/1, /*sweep_flags=*/apply_sigmoid ? 1 : 0};
+      return r.kernel == SweepRoute::F16 ? f16_sweep_launch(a, nullptr, st) : pipe_sweep_launch(pipe_cw(r.kernel), a, st);
+    }
+    case SweepRoute::ScoreTileF16: {
+      // up to a few hundred 64 x 64 tiles, split precision: all of the tile's loads in flight, f16 MFMAs
+      const int kkb = (d + 15) / 16;
+      const size_t lds = sizeof(_Float16) * (size_t)(4 * 64 * (16 * kkb + 8)) + sizeof(float) * 128;
+      switch ((k / 4 + 3) / 4) {               // column groups per staging lane (56 <= d <= 224: 2 ... 7, compiled exactly)
+        case 2: return go(score_1vK_f16_kernel<2>, lds);
+        case 3: return go(score_1vK_f16_kernel<3>, lds);
+        case 4: return go(score_1vK_f16_kernel<4>, lds);
+        case 5: return go(score_1vK_f16_kernel<5>, lds);
+        case 6: return go(score_1vK_f16_kernel<6>, lds);
+        default: return go(score_1vK_f16_kernel<7>, lds);
+      }
+    }
+    case SweepRoute::ScoreTile: {
+      // up to a few hundred 64 x 64 tiles: the whole tile's loads in flight in two batches, 16-byte LDS traffic
+      const size_t lds = sizeof(float) * std::max<size_t>((size_t)16 * (k / 4) * 64, 64 * 65) + sizeof(float) * 128;
+      const int cg = k / 4;
+      if (cg <= 8) return go(score_1vK_tile_kernel<1, 1>, lds);
+      if (cg <= 16) return go(score_1vK_tile_kernel<2, 2>, lds);
+      if (cg <= 28) return go(score_1vK_tile_kernel<4, 3>, lds);
+      return go(score_1vK_tile_kernel<4, 4>, lds);
+    }
+    case SweepRoute::ScoreFullK:
+      return v4 ? go(score_1vK_fullk_kernel<true>, fullk_lds(d), fullk_kp(d))
+                : go(score_1vK_fullk_kernel<false>, fullk_lds(d), fullk_kp(d));
+    case SweepRoute::ScoreBasic:
+      if (big) return v4 ? go(score_1vK_kernel<2, 2, true>, 0) : go(score_1vK_kernel<2, 2, false>, 0);
+      return v4 ? go(score_1vK_kernel<1, 1, true>, 0) : go(score_1vK_kernel<1, 1, false>, 0);
+    default: return r.status;
   }
-#define L1VK(TM, TN, V) \
-  hipLaunchKernelGGL((score_1vK_kernel<TM, TN, V>), grid, dim3(kBlock), 0, st, table, N, d, hr, B, cand, K, max_norm, apply_sigmoid, cand_is_head, out)
-  if (big) { if (v4) L1VK(2, 2, true); else L1VK(2, 2, false); }
-  else { if (v4) L1VK(1, 1, true); else L1VK(1, 1, false); }
-#undef L1VK
-  return launch_status();
 }
 
 }  // namespace ge

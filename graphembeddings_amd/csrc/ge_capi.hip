@@ -605,14 +605,27 @@ int ge_complex_score_1vK(const float* table, int64_t N, int32_t d, const int32_t
                                   (hipStream_t)stream);
 }
 
-int ge_rank_max_dim(void) { return rank_max_dim(); }
+// the sweeps of ge_sweep_route.h serve ComplEx and HolE on a spectral table; 0, or the code for any other model
+static inline int sweep_model_ok(int model) {
+  if (model == GE_MODEL_COMPLEX || model == GE_MODEL_HOLE_SPECTRAL) return 0;
+  return model == GE_MODEL_HOLE || model == GE_MODEL_HOLE_DIRECT ? GE_ENOTSUP : GE_EINVAL;
+}
+
+// the rank sweeps add into their two counters
+static inline int zero_counts(int32_t* n_before, int32_t* n_known_before, int64_t B, hipStream_t st) {
+  hipError_t e = hipMemsetAsync(n_before, 0, sizeof(int32_t) * (size_t)B, st);
+  if (e == hipSuccess) e = hipMemsetAsync(n_known_before, 0, sizeof(int32_t) * (size_t)B, st);
+  return e == hipSuccess ? 0 : (int)e;
+}
+
+int ge_rank_max_dim(void) { return kRankMaxDim; }
 
 int64_t ge_rank_planes_bytes(int64_t N, int32_t d, int64_t K) { return rank_planes_bytes(N, d, K); }
 
 int ge_rank_planes(const float* table, int64_t N, int32_t d, const int32_t* cand, int64_t K, float max_norm, int model,
                    void* planes, void* stream) {
   if (K < 0 || !ok_table(table, N, d) || !max_norm_ok(max_norm) || !planes) return GE_EINVAL;
-  if (model != GE_MODEL_COMPLEX && model != GE_MODEL_HOLE_SPECTRAL) return model == GE_MODEL_HOLE || model == GE_MODEL_HOLE_DIRECT ? GE_ENOTSUP : GE_EINVAL;
+  if (int rc = sweep_model_ok(model)) return rc;
   if (K > 0 && !cand) return GE_EINVAL;
   return rank_planes_launch(table, N, d, cand, K, max_norm, model == GE_MODEL_HOLE_SPECTRAL, planes, (hipStream_t)stream);
 }
@@ -622,16 +635,14 @@ int ge_rank_1vK_planes(const float* table, int64_t N, int32_t d, const int32_t* 
                        const uint16_t* known_rc, int32_t* n_before, int32_t* n_known_before, float* true_loss,
                        float* scores_out, const void* planes, void* stream) {
   if (B < 0 || K < 0 || !ok_table(table, N, d) || !max_norm_ok(max_norm)) return GE_EINVAL;
-  if (model != GE_MODEL_COMPLEX && model != GE_MODEL_HOLE_SPECTRAL) return model == GE_MODEL_HOLE || model == GE_MODEL_HOLE_DIRECT ? GE_ENOTSUP : GE_EINVAL;
+  if (int rc = sweep_model_ok(model)) return rc;
   if (B > 0 && (!hr || !true_id || !n_before || !n_known_before)) return GE_EINVAL;
   if (B > 0 && K > 0 && !cand) return GE_EINVAL;
   if ((known_off == nullptr) != (known_rc == nullptr)) return GE_EINVAL;
   if (planes && (rank_planes_bytes(N, d, K) == 0 || reinterpret_cast<uintptr_t>(planes) % 256 != 0)) return GE_EINVAL;
   if (B == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  hipError_t e = hipMemsetAsync(n_before, 0, sizeof(int32_t) * (size_t)B, st);
-  if (e == hipSuccess) e = hipMemsetAsync(n_known_before, 0, sizeof(int32_t) * (size_t)B, st);
-  if (e != hipSuccess) return (int)e;
+  if (int rc = zero_counts(n_before, n_known_before, B, st)) return rc;
   return complex_rank_1vK_launch(table, N, d, hr, B, true_id, cand, K, max_norm, cand_is_head, known_off, known_rc,
                                  n_before, n_known_before, true_loss, scores_out, model == GE_MODEL_HOLE_SPECTRAL, planes, st);
 }
@@ -641,16 +652,14 @@ int ge_rank_1vK_vs_loss(const float* table, int64_t N, int32_t d, const int32_t*
                         const int32_t* known_off, const uint16_t* known_rc, int32_t* n_before, int32_t* n_known_before,
                         const void* planes, void* stream) {
   if (B < 0 || K < 0 || !ok_table(table, N, d) || !max_norm_ok(max_norm)) return GE_EINVAL;
-  if (model != GE_MODEL_COMPLEX && model != GE_MODEL_HOLE_SPECTRAL) return model == GE_MODEL_HOLE || model == GE_MODEL_HOLE_DIRECT ? GE_ENOTSUP : GE_EINVAL;
+  if (int rc = sweep_model_ok(model)) return rc;
   if (B > 0 && (!hr || !ref_id || !ref_loss || !n_before || !n_known_before)) return GE_EINVAL;
   if (B > 0 && K > 0 && !cand) return GE_EINVAL;
   if ((known_off == nullptr) != (known_rc == nullptr)) return GE_EINVAL;
   if (planes && (rank_planes_bytes(N, d, K) == 0 || reinterpret_cast<uintptr_t>(planes) % 256 != 0)) return GE_EINVAL;
   if (B == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  hipError_t e = hipMemsetAsync(n_before, 0, sizeof(int32_t) * (size_t)B, st);
-  if (e == hipSuccess) e = hipMemsetAsync(n_known_before, 0, sizeof(int32_t) * (size_t)B, st);
-  if (e != hipSuccess) return (int)e;
+  if (int rc = zero_counts(n_before, n_known_before, B, st)) return rc;
   if (K == 0) return 0;
   // (the launchers take the losses through their true_loss argument, which this mode only reads)
   return complex_rank_1vK_launch(table, N, d, hr, B, ref_id, cand, K, max_norm, cand_is_head, known_off, known_rc, n_before,
@@ -667,7 +676,7 @@ int ge_topk_1vK_planes(const float* table, int64_t N, int32_t d, const int32_t* 
                        const uint16_t* known_rc, int32_t k, int32_t* out_id, float* out_loss, const void* planes,
                        void* workspace, size_t workspace_bytes, void* stream) {
   if (B < 0 || K < 1 || k < 1 || !ok_table(table, N, d) || !max_norm_ok(max_norm)) return GE_EINVAL;
-  if (model != GE_MODEL_COMPLEX && model != GE_MODEL_HOLE_SPECTRAL) return model == GE_MODEL_HOLE || model == GE_MODEL_HOLE_DIRECT ? GE_ENOTSUP : GE_EINVAL;
+  if (int rc = sweep_model_ok(model)) return rc;
   if (B > 0 && (!hr || !cand || !out_id || !out_loss)) return GE_EINVAL;
   if ((known_off == nullptr) != (known_rc == nullptr)) return GE_EINVAL;
   if (planes && (rank_planes_bytes(N, d, K) == 0 || reinterpret_cast<uintptr_t>(planes) % 256 != 0)) return GE_EINVAL;

@@ -79,6 +79,23 @@ inline int launch_status() {
   return e == hipSuccess ? 0 : (int)e;
 }
 
+// compute units of the current device (256, the MI355X's, when the runtime does not say)
+inline int cu_count() {
+  int dev = 0, cus = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return 256;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) return 256;
+  return cus;
+}
+
+// the kernel may use the CU's whole LDS.  A per-device property: set before every launch that needs it (idempotent, cheap)
+// rather than cached in a per-process flag that would be wrong on a second device
+template <class Kern>
+int lds_opt_in(Kern kern) {
+  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           160 * 1024);
+  return e == hipSuccess ? 0 : (int)e;
+}
+
 // host-side workspace layout: v rounded up to a multiple of a
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 

@@ -10,7 +10,7 @@ namespace ge {
 namespace {
 
 constexpr int kBlk = 512;               // eight waves: wm = w >> 2 (64 rows), wn = w & 3 (32 candidates of the 128-wide tile)
-constexpr int kSL = 32;                 // candidates per slice of `planes` = one wave's columns
+// (kSL, kOpHalves, planes_slices -- the planes' sizes: ge_sweep_route.h)
 
 template <int I0, int N, typename F>
 __device__ __forceinline__ void static_for(F&& f) {
@@ -33,7 +33,6 @@ struct HCfg {
   static_assert(KKB >= 4 && KKB <= 18, "embedding_dim 56 ... 288 (LDS: the Q planes, 152 KB at 18 k blocks)");
 };
 constexpr float kQScale = 256.f;        // both operands: |q|, |t * clip| <= max_norm^2 resp. max_norm sqrt(d/2)
-constexpr int kOpHalves = kSL * 16;     // one operand fetch of one wave in `planes`: [32 candidates][16 columns], 1 KiB
 constexpr int kAhead = 3;               // k blocks between a candidate operand's request and its first MFMA
 
 struct HLds {
@@ -122,9 +121,6 @@ __device__ __forceinline__ void h_mfma_loop(const HLds& lds, const _Float16* __r
 #pragma unroll
   for (int j = 0; j < kAhead; ++j) B[j] = t[j];
 }
-
-// candidate slices of `planes` for K candidates: whole 128-candidate tiles
-inline int64_t planes_slices(int64_t K) { return 4 * ((K + kRB - 1) / kRB); }   // whole 128-candidate tiles
 
 }  // namespace
 }  // namespace ge

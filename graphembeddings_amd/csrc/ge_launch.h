@@ -1,10 +1,15 @@
 // ge_launch.h -- the host entry points one source of libge_hip.so defines and another calls: the one declaration of
 // each, included by the defining source too, so the compiler checks every definition against it.  Default arguments
-// live here and nowhere else.  Launchers return 0 or an error code (hipError_t, GE_E*).
+// live here and nowhere else.  Launchers return 0 or an error code (hipError_t, GE_E*);
+// the launchers behind a route (ge_sweep_route.h) assert the route's conditions instead -- on purpose in the shipped
+// library too (no NDEBUG): a launcher and the router out of step would otherwise launch on a shape the kernel cannot take.
 #pragma once
+#include <assert.h>
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+
+#include "ge_sweep_route.h"   // rank_planes_bytes, kRankMaxDim
 
 namespace ge {
 
@@ -68,32 +73,31 @@ int copy_if_launch(const float* src, float* dst, int64_t n, const int32_t* flag,
 int complex_score_1vK_launch(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* cand,
                              int64_t K, float max_norm, int apply_sigmoid, int cand_is_head, float* out, hipStream_t st);
 
-// ge_rank.hip: link-prediction ranks for any embedding_dim % 8 == 0
-int rank_max_dim();
+// ge_rank.hip: link-prediction ranks -- the switch on route_rank (ge_sweep_route.h) and the fp32 kernel
 int complex_rank_1vK_launch(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* true_id,
                             const int32_t* cand, int64_t K, float max_norm, int cand_is_head, const int32_t* known_off,
                             const uint16_t* known_rc, int32_t* raw_cnt, int32_t* skip_cnt, float* true_loss,
                             float* scores_out, int spec, const void* planes_ws, hipStream_t st, int vs_loss = 0);
 
-// ge_rank_pipe.hip: the pipelined sweep (embedding_dim % 40, % 32 or % 24 == 0); GE_ENOTSUP for any other dim.
-// spec: the table is a spectral HolE table.  score_pipe_launch: ge_complex_score_1vK on the same sweep.
-int rank_pipe_launch(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* true_id,
-                     const int32_t* cand, int64_t K, float max_norm, int cand_is_head, const int32_t* known_off,
-                     const uint16_t* known_rc, int32_t* raw_cnt, int32_t* skip_cnt, float* true_loss,
-                     float* scores_out, int spec, const void* planes_ws, hipStream_t st, int vs_loss = 0);
-int score_pipe_launch(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* cand,
-                      int64_t K, float max_norm, int apply_sigmoid, int cand_is_head, float* out, hipStream_t st);
+// What the sweep kernels behind route_rank / route_score take.  spec: the table is a spectral HolE table.
+// scores_only: no ranking, scores_out [B,K] = score (its sigmoid with sweep_flags & 1): ge_complex_score_1vK.
+// Ranks: scores_out may be null; sweep_flags & 2: true_loss is an INPUT, the loss every candidate of row i is ranked
+// against, and true_id the tie-break id (ge_rank_1vK_vs_loss).
+struct SweepArgs {
+  const float* table; int64_t N; int32_t d; const int32_t* hr; int64_t B; const int32_t* true_id; const int32_t* cand;
+  int64_t K; float max_norm; int cand_is_head; const int32_t* known_off; const uint16_t* known_rc; int32_t* raw_cnt;
+  int32_t* skip_cnt; float* true_loss; float* scores_out; int spec, scores_only, sweep_flags;
+};
 
-// ge_rank_f16.hip: the split-precision sweep (embedding_dim % 8 == 0 in 56 ... 288, max_norm <= 8), ranks or scores.
+// ge_rank_pipe.hip: Pipe<cw> of the route, cw in 40, 32, 24 dividing embedding_dim
+int pipe_sweep_launch(int cw, const SweepArgs& a, hipStream_t st);
+
+// ge_rank_f16.hip: the F16 of the route, ranks or scores.
 // planes_ws: the candidates' fp16 planes + entity -> position map (rank_planes_launch into rank_planes_bytes bytes,
 // 256-byte aligned) for the same (table, cand, max_norm, spec); NULL: built inside, in a stream-ordered allocation.
-int64_t rank_planes_bytes(int64_t N, int32_t d, int64_t K);
 int rank_planes_launch(const float* table, int64_t N, int32_t d, const int32_t* cand, int64_t K, float max_norm, int spec,
                        void* planes_ws, hipStream_t st);
-int sweep_f16_launch(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* true_id,
-                     const int32_t* cand, int64_t K, float max_norm, int cand_is_head, const int32_t* known_off,
-                     const uint16_t* known_rc, int32_t* raw_cnt, int32_t* skip_cnt, float* true_loss,
-                     float* scores_out, int spec, int scores_only, int sweep_flags, const void* planes_ws, hipStream_t st);
+int f16_sweep_launch(const SweepArgs& a, const void* planes_ws, hipStream_t st);
 // the top-k sweep on the same planes (ge_topk_1vK_planes): k <= topk_max_k(), workspace of topk_ws_bytes(B, K, k)
 int topk_max_k();
 size_t topk_ws_bytes(int64_t B, int64_t K, int32_t k);

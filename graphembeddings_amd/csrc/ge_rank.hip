@@ -1,4 +1,5 @@
-// ge_rank.hip -- link-prediction ranks straight out of the candidate sweep (holE.py:427-472, 564-575).
+// ge_rank.hip -- link-prediction ranks straight out of the candidate sweep (holE.py:427-472, 564-575): the entry of every
+// rank sweep, a switch on route_rank (ge_sweep_route.h), and the route's last resort, the fp32 kernel RankF32.
 //
 // The reference scores one (head, relation) against every candidate tail, pushes (loss, triple) on a
 // heap and pops it in ascending order: raw rank = pops until the true tail, filtered rank = the same
@@ -361,38 +362,37 @@ static size_t rank_lds_bytes(int d) {
   return sizeof(float) * ((size_t)kRB * lda + 2 * kRB * kLdb + 3 * kRB) + sizeof(unsigned) * kRB * 4 + sizeof(int) * 2 * kRB;
 }
 
-int rank_max_dim() { return 288; }   // the split-precision sweep's Q planes fill the LDS at 18 k blocks (max_norm <= 8);
-constexpr int kRankMaxDimF32 = 232;  // the fp32 kernels: Q (128 x (d+1) floats) + two candidate chunks must fit the CU's 160 KiB
+// RankF32 of the route: any embedding_dim % 8 == 0 up to kRankMaxDimF32
+static int rank_f32_launch(const SweepArgs& a, hipStream_t st) {
+  const int64_t n_rb = (a.B + kRB - 1) / kRB, n_ct = (a.K + kRB - 1) / kRB;
+  assert(a.d <= kRankMaxDimF32 && n_rb <= 65535);                // route_rank
+  // column splits: enough workgroups for ~4 waves of the 256 CUs, never more than column tiles
+  int64_t splits = (4 * 256 + n_rb - 1) / n_rb;
+  if (splits > n_ct) splits = n_ct;
+  if (splits < 1) splits = 1;
+  const size_t lds = rank_lds_bytes(a.d);
+  if (int rc = lds_opt_in(rank_1vK_kernel)) return rc;
+  hipLaunchKernelGGL(rank_1vK_kernel, dim3((unsigned)splits, (unsigned)n_rb), dim3(kBlock), lds, st, a.table, a.N, a.d, a.hr,
+                     a.B, a.true_id, a.cand, a.K, a.max_norm, a.cand_is_head, a.known_off, a.known_rc, a.raw_cnt, a.skip_cnt,
+                     a.true_loss, a.scores_out, a.d + 1, a.spec, (a.sweep_flags >> 1) & 1);
+  return launch_status();
+}
 
 int complex_rank_1vK_launch(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B,
                             const int32_t* true_id, const int32_t* cand, int64_t K, float max_norm, int cand_is_head,
                             const int32_t* known_off, const uint16_t* known_rc, int32_t* raw_cnt, int32_t* skip_cnt,
                             float* true_loss, float* scores_out, int spec, const void* planes_ws, hipStream_t st, int vs_loss) {
-  // vs_loss: true_loss is an INPUT -- the loss every candidate of row i is ranked against -- and true_id the tie-break id
-  if (d <= 0 || (d & 7)) return (d <= 0 || (d & 1)) ? GE_EINVAL : GE_ENOTSUP;   // 16-byte candidate loads, 8-float tail
-  if (d > rank_max_dim()) return GE_ENOTSUP;
-  if (reinterpret_cast<uintptr_t>(table) % 16 != 0) return GE_EINVAL;
-  if (B == 0 || K == 0) return 0;
-  {  // embedding_dim a multiple of 40, 32 or 24: the software-pipelined kernel (ge_rank_pipe.hip)
-    const int rc = rank_pipe_launch(table, N, d, hr, B, true_id, cand, K, max_norm, cand_is_head, known_off, known_rc,
-                                    raw_cnt, skip_cnt, true_loss, scores_out, spec, planes_ws, st, vs_loss);
-    if (rc != GE_ENOTSUP) return rc;
+  const SweepRoute r = route_rank(N, d, B, K, max_norm, (int)(reinterpret_cast<uintptr_t>(table) % 16));
+  const SweepArgs a{table, N, d, hr, B, true_id, cand, K, max_norm, cand_is_head, known_off, known_rc, raw_cnt, skip_cnt,
+                    true_loss, scores_out, spec, /*scores_only=*/0, /*sweep_flags=*/vs_loss ? 2 : 0};
+  switch (r.kernel) {
+    case SweepRoute::F16: return f16_sweep_launch(a, planes_ws, st);
+    case SweepRoute::Pipe40:
+    case SweepRoute::Pipe32:
+    case SweepRoute::Pipe24: return pipe_sweep_launch(pipe_cw(r.kernel), a, st);
+    case SweepRoute::RankF32: return rank_f32_launch(a, st);
+    default: return r.status;
   }
-  if (d > kRankMaxDimF32) return GE_ENOTSUP;                    // (233 ... 288 with max_norm > 8)
-  const int64_t n_rb = (B + kRB - 1) / kRB, n_ct = (K + kRB - 1) / kRB;
-  if (n_rb > 65535) return GE_ENOTSUP;
-  // column splits: enough workgroups for ~4 waves of the 256 CUs, never more than column tiles
-  int64_t splits = (4 * 256 + n_rb - 1) / n_rb;
-  if (splits > n_ct) splits = n_ct;
-  if (splits < 1) splits = 1;
-  const size_t lds = rank_lds_bytes(d);
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(rank_1vK_kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(rank_1vK_kernel, dim3((unsigned)splits, (unsigned)n_rb), dim3(kBlock), lds, st, table, N, d, hr, B,
-                     true_id, cand, K, max_norm, cand_is_head, known_off, known_rc, raw_cnt, skip_cnt, true_loss,
-                     scores_out, d + 1, spec, vs_loss);
-  return launch_status();
 }
 
 }  // namespace ge

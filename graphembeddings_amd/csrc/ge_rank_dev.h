@@ -1,13 +1,16 @@
-// ge_rank_dev.h -- what the two ranking kernels (ge_rank.hip: any embedding_dim % 8 == 0; ge_rank_pipe.hip:
-// the software-pipelined sweep for embedding_dim % 40, % 32 or % 24 == 0) share.
+// ge_rank_dev.h -- what the ranking kernels (ge_rank.hip: the fp32 kernel; ge_rank_pipe.hip: the fp32 pipeline;
+// ge_rank_f16.hip: the split-precision sweep) share.  Which of them runs: ge_sweep_route.h.
 #pragma once
 #include "ge_common.h"
+#include "ge_sweep_route.h"   // kRB
+
+#ifndef GE_PIPE_GRID_M
+#define GE_PIPE_GRID_M 2   // workgroups per CU (each CU holds one at a time): equal shares, two rounds
+#endif
 
 namespace ge {
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
-
-constexpr int kRB = 128;          // test rows per workgroup, candidates per tile
 
 // sigmoid for the ranking epilogue: 4 VALU instructions (v_exp_f32, v_rcp_f32; ~2 ulp), used for EVERY loss the
 // ranking kernels form -- candidates and true entities alike -- so comparisons are self-consistent; within 1e-6 of

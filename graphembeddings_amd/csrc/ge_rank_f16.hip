@@ -1,5 +1,6 @@
 // ge_rank_f16.hip -- the split-precision link-prediction sweep (holE.py:427-472, 564-575; semantics in ge_rank.hip):
-// f16 MFMAs on pre-split candidate planes, eight free-running waves per workgroup (two per SIMD).
+// f16 MFMAs on pre-split candidate planes, eight free-running waves per workgroup (two per SIMD).  F16 of
+// ge_sweep_route.h: the first choice of every rank sweep and big score sweep it can serve, the one kernel of the top-k.
 //
 // Why this shape (tools/probes/mfma_gap_probe.hip -> profiles/r03_mfma_gap_probe.txt; s_memtime stamps per phase and
 // ablated builds, recorded in DESIGN.md section 9):
@@ -34,10 +35,6 @@
 #include "ge_f16_dev.h"
 #include "ge_launch.h"
 #include "ge_topk_dev.h"
-
-#ifndef GE_PIPE_GRID_M
-#define GE_PIPE_GRID_M 2   // workgroups per CU (each CU holds one at a time): equal shares, two rounds
-#endif
 
 namespace ge {
 namespace {
@@ -672,40 +669,45 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const int32_t* __restri
   topk_emit<kTopkLane>(pool, n, k, lane, oid, ol, nullptr);
 }
 
-int f16_cu_count() {
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return 256;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) return 256;
-  return cus;
-}
-
-inline bool f16_dim_ok(int32_t d, float max_norm) { return d % 8 == 0 && d >= 56 && d <= 288 && max_norm <= 8.f; }
-inline int64_t pos_bytes(int64_t N) { return (N * (int64_t)sizeof(int32_t) + 255) / 256 * 256; }
-
 template <int KKB>
-int f16_launch_kkb(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* true_id,
-                   const int32_t* cand, int64_t K, float max_norm, int cand_is_head, const int32_t* known_off,
-                   const uint16_t* known_rc, int32_t* raw_cnt, int32_t* skip_cnt, float* true_loss, float* scores_out,
-                   int spec, int scores_only, int sweep_flags, const void* planes_ws, hipStream_t st) {
-  const int64_t n_rb = (B + kRB - 1) / kRB, n_ct = (K + kRB - 1) / kRB;
-  if (n_ct > INT32_MAX / 8 || n_rb > INT32_MAX / 8) return GE_ENOTSUP;
-  if (4 * n_ct * (int64_t)KKB * 2 * kOpHalves * 2 >= ((int64_t)1 << 32)) return GE_ENOTSUP;   // (32-bit byte offsets into the planes)
+int f16_launch_kkb(const SweepArgs& a, const void* planes_ws, hipStream_t st) {
+  const int64_t n_rb = (a.B + kRB - 1) / kRB, n_ct = (a.K + kRB - 1) / kRB;
+  assert(n_ct <= INT32_MAX / 8 && n_rb <= INT32_MAX / 8);        // route_main_road
   const int64_t n_tiles = n_rb * n_ct;
-  const int64_t grid = std::min<int64_t>(n_tiles, GE_PIPE_GRID_M * (int64_t)f16_cu_count());
+  const int64_t grid = std::min<int64_t>(n_tiles, GE_PIPE_GRID_M * (int64_t)cu_count());
   const int32_t* pos_of = reinterpret_cast<const int32_t*>(planes_ws);
-  const _Float16* planes = reinterpret_cast<const _Float16*>(reinterpret_cast<const char*>(planes_ws) + pos_bytes(N));
+  const _Float16* planes = reinterpret_cast<const _Float16*>(reinterpret_cast<const char*>(planes_ws) + pos_bytes(a.N));
   auto go = [&](auto kern) -> int {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       160 * 1024);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kBlk), h_lds_bytes<KKB>(), st, table, N, d, hr, B, true_id, cand, K,
-                       max_norm, cand_is_head, known_off, known_rc, raw_cnt, skip_cnt, true_loss, scores_out, (int)n_ct,
-                       n_tiles, spec, sweep_flags, pos_of, planes, TopkArgs{});
+    if (int rc = lds_opt_in(kern)) return rc;
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kBlk), h_lds_bytes<KKB>(), st, a.table, a.N, a.d, a.hr, a.B, a.true_id,
+                       a.cand, a.K, a.max_norm, a.cand_is_head, a.known_off, a.known_rc, a.raw_cnt, a.skip_cnt, a.true_loss,
+                       a.scores_out, (int)n_ct, n_tiles, a.spec, a.sweep_flags, pos_of, planes, TopkArgs{});
     return launch_status();
   };
-  if (scores_only) return go(rank_f16_kernel<KKB, 2>);
-  if (scores_out) return go(rank_f16_kernel<KKB, 1>);
+  if (a.scores_only) return go(rank_f16_kernel<KKB, 2>);
+  if (a.scores_out) return go(rank_f16_kernel<KKB, 1>);
   return go(rank_f16_kernel<KKB, 0>);
+}
+
+// run(planes_ws) on the caller's planes, or -- planes_ws NULL -- on planes built here in a stream-ordered allocation that
+// is freed on every path (one more pass over the K candidate rows)
+template <class Run>
+int with_planes(const float* table, int64_t N, int32_t d, const int32_t* cand, int64_t K, float max_norm, int spec,
+                const void* planes_ws, hipStream_t st, Run run) {
+  void* own = nullptr;
+  if (!planes_ws) {
+    hipError_t e = hipMallocAsync(&own, (size_t)rank_planes_bytes(N, d, K), st);
+    if (e != hipSuccess) return (int)e;
+    const int rc = rank_planes_launch(table, N, d, cand, K, max_norm, spec, own, st);
+    if (rc != 0) { (void)hipFreeAsync(own, st); return rc; }
+    planes_ws = own;
+  }
+  int rc = run(planes_ws);
+  if (own) {
+    const hipError_t e = hipFreeAsync(own, st);
+    if (rc == 0 && e != hipSuccess) rc = (int)e;
+  }
+  return rc;
 }
 
 }  // namespace
@@ -724,21 +726,10 @@ int64_t topk_ws_rows(int64_t n_rb, int64_t K, int32_t k) {      // bytes for n_r
   return n_rb * kRB * ns * (topk_kp(k) + 128 + k) * (int64_t)sizeof(u64);
 }
 
-// bytes of the candidate planes of a K-candidate sweep over an N-row table (0: embedding_dim has no split-precision sweep)
-int64_t rank_planes_bytes(int64_t N, int32_t d, int64_t K) {
-  if (d % 8 != 0 || d < 56 || d > 288 || N <= 0 || K <= 0) return 0;
-  const int64_t kkb = (d + 15) / 16;
-  const int64_t plane_bytes = planes_slices(K) * kkb * 2 * kOpHalves * (int64_t)sizeof(_Float16);
-  // the sweep addresses the planes with 32-bit byte offsets (about 5.1 M candidates at d = 200): beyond that there is no
-  // split-precision sweep -- said HERE, so that nobody allocates and fills 4 GiB of planes the sweep then refuses
-  if (plane_bytes >= ((int64_t)1 << 32)) return 0;
-  return pos_bytes(N) + plane_bytes;
-}
-
 // planes_ws (rank_planes_bytes, 256-byte aligned) <- the entity -> position map, then the candidates' fp16 planes
 int rank_planes_launch(const float* table, int64_t N, int32_t d, const int32_t* cand, int64_t K, float max_norm, int spec,
                        void* planes_ws, hipStream_t st) {
-  if (!f16_dim_ok(d, max_norm) || (K > 0 && N > 0 && rank_planes_bytes(N, d, K) == 0)) return GE_ENOTSUP;
+  if (!f16_sweep_ok(d, max_norm) || (K > 0 && N > 0 && rank_planes_bytes(N, d, K) == 0)) return GE_ENOTSUP;
   if (reinterpret_cast<uintptr_t>(planes_ws) % 256 != 0 || reinterpret_cast<uintptr_t>(table) % 16 != 0) return GE_EINVAL;
   if (K <= 0 || N <= 0) return 0;
   int32_t* pos_of = reinterpret_cast<int32_t*>(planes_ws);
@@ -746,8 +737,7 @@ int rank_planes_launch(const float* table, int64_t N, int32_t d, const int32_t* 
   hipError_t e = hipMemsetAsync(pos_of, 0xff, (size_t)N * sizeof(int32_t), st);
   if (e != hipSuccess) return (int)e;
   hipLaunchKernelGGL(rank_pos_kernel, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, st, cand, K, N, pos_of);
-  const int64_t n_blocks = planes_slices(K) / 2;                // 64 candidates a workgroup
-  if (n_blocks > INT32_MAX) return GE_ENOTSUP;
+  const int64_t n_blocks = planes_slices(K) / 2;                // 64 candidates a workgroup (< 2^20: the planes' 2^32 bytes)
 #define GE_CALL(KKB)                                                                                                   \
   hipLaunchKernelGGL(rank_planes_kernel<KKB>, dim3((unsigned)n_blocks), dim3(256), 0, st, table, N, d, cand, K, max_norm, \
                      spec, planes);                                                                                    \
@@ -756,37 +746,16 @@ int rank_planes_launch(const float* table, int64_t N, int32_t d, const int32_t* 
 #undef GE_CALL
 }
 
-// The split-precision sweep: embedding_dim % 8 == 0 in 56 ... 288 (k blocks 4 ... 18), max_norm <= 8
-// (|q sa (1/d)| <= 2 max_norm^2, |t clip| <= max_norm sqrt(d/2): x 2^8 inside fp16).  GE_ENOTSUP otherwise.
-// planes_ws: the candidates' planes from rank_planes_launch for the same (table, cand, max_norm, spec), or NULL -- then
-// they are built here in a stream-ordered allocation (one more pass over the K candidate rows).
-int sweep_f16_launch(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* true_id,
-                     const int32_t* cand, int64_t K, float max_norm, int cand_is_head, const int32_t* known_off,
-                     const uint16_t* known_rc, int32_t* raw_cnt, int32_t* skip_cnt, float* true_loss,
-                     float* scores_out, int spec, int scores_only, int sweep_flags, const void* planes_ws, hipStream_t st) {
-  if (!f16_dim_ok(d, max_norm) || rank_planes_bytes(N, d, K) == 0) return GE_ENOTSUP;   // (incl. planes beyond 32-bit offsets)
-  static_assert(h_lds_bytes<18>() <= 160 * 1024, "LDS of the largest instantiation");
-  void* own = nullptr;
-  if (!planes_ws) {
-    hipError_t e = hipMallocAsync(&own, (size_t)rank_planes_bytes(N, d, K), st);
-    if (e != hipSuccess) return (int)e;
-    const int rc = rank_planes_launch(table, N, d, cand, K, max_norm, spec, own, st);
-    if (rc != 0) { (void)hipFreeAsync(own, st); return rc; }
-    planes_ws = own;
-  }
-  auto run = [&]() -> int {
-#define GE_CALL(KKB)                                                                                                 \
-  return f16_launch_kkb<KKB>(table, N, d, hr, B, true_id, cand, K, max_norm, cand_is_head, known_off, known_rc,       \
-                             raw_cnt, skip_cnt, true_loss, scores_out, spec, scores_only, sweep_flags, planes_ws, st)
-    GE_KKB_SWITCH(d, GE_CALL)
+// The split-precision sweep.  planes_ws: the candidates' planes from rank_planes_launch for the same (table, cand,
+// max_norm, spec), or NULL.
+int f16_sweep_launch(const SweepArgs& a, const void* planes_ws, hipStream_t st) {
+  assert(f16_sweep_ok(a.d, a.max_norm) && rank_planes_bytes(a.N, a.d, a.K) != 0);   // route_main_road
+  static_assert(h_lds_bytes<18>() <= kLdsMax, "LDS of the largest instantiation");
+  return with_planes(a.table, a.N, a.d, a.cand, a.K, a.max_norm, a.spec, planes_ws, st, [&](const void* ws) -> int {
+#define GE_CALL(KKB) return f16_launch_kkb<KKB>(a, ws, st)
+    GE_KKB_SWITCH(a.d, GE_CALL)
 #undef GE_CALL
-  };
-  int rc = run();
-  if (own) {
-    const hipError_t e = hipFreeAsync(own, st);
-    if (rc == 0 && e != hipSuccess) rc = (int)e;
-  }
-  return rc;
+  });
 }
 
 int topk_max_k() { return kTopkMaxK; }
@@ -808,16 +777,14 @@ int topk_f16_launch(const float* table, int64_t N, int32_t d, const int32_t* hr,
                     float max_norm, int cand_is_head, const int32_t* known_off, const uint16_t* known_rc, int32_t k,
                     int32_t* out_id, float* out_loss, int spec, const void* planes_ws, void* workspace,
                     size_t workspace_bytes, hipStream_t st) {
-  if (!f16_dim_ok(d, max_norm) || rank_planes_bytes(N, d, K) == 0) return GE_ENOTSUP;
+  if (!f16_sweep_ok(d, max_norm) || rank_planes_bytes(N, d, K) == 0) return GE_ENOTSUP;   // (incl. planes beyond 32-bit offsets)
   if (k < 1) return GE_EINVAL;
   if (k > kTopkMaxK) return GE_ENOTSUP;
   if (B == 0) return 0;
   if (!workspace || reinterpret_cast<uintptr_t>(workspace) % 256 != 0) return GE_EINVAL;
   if (workspace_bytes < topk_ws_bytes(B, K, k)) return GE_ENOMEM;
-  static_assert(topk_lds_bytes<18>() <= 160 * 1024, "LDS of the largest top-k instantiation");
-  const int64_t n_rb = (B + kRB - 1) / kRB, n_ct = (K + kRB - 1) / kRB;
-  if (n_ct > INT32_MAX / 8) return GE_ENOTSUP;
-  if (4 * n_ct * (int64_t)((d + 15) / 16) * 2 * kOpHalves * 2 >= ((int64_t)1 << 32)) return GE_ENOTSUP;
+  static_assert(topk_lds_bytes<18>() <= kLdsMax, "LDS of the largest top-k instantiation");
+  const int64_t n_rb = (B + kRB - 1) / kRB, n_ct = (K + kRB - 1) / kRB;   // (n_ct < INT32_MAX / 8: the planes' 2^32 bytes)
   const int64_t ns = topk_splits(B, K);
   if (n_rb * ns > INT32_MAX) return GE_ENOTSUP;
   TopkArgs tk;
@@ -828,41 +795,27 @@ int topk_f16_launch(const float* table, int64_t N, int32_t d, const int32_t* hr,
   tk.part = tk.pool + B * ns * tk.cap;
   tk.out_id = out_id;
   tk.out_loss = out_loss;
-  void* own = nullptr;
-  if (!planes_ws) {
-    hipError_t e = hipMallocAsync(&own, (size_t)rank_planes_bytes(N, d, K), st);
-    if (e != hipSuccess) return (int)e;
-    const int rc = rank_planes_launch(table, N, d, cand, K, max_norm, spec, own, st);
-    if (rc != 0) { (void)hipFreeAsync(own, st); return rc; }
-    planes_ws = own;
-  }
-  const int32_t* pos_of = reinterpret_cast<const int32_t*>(planes_ws);
-  const _Float16* planes = reinterpret_cast<const _Float16*>(reinterpret_cast<const char*>(planes_ws) + pos_bytes(N));
-  auto run = [&]() -> int {
+  return with_planes(table, N, d, cand, K, max_norm, spec, planes_ws, st, [&](const void* ws) -> int {
+    const int32_t* pos_of = reinterpret_cast<const int32_t*>(ws);
+    const _Float16* planes = reinterpret_cast<const _Float16*>(reinterpret_cast<const char*>(ws) + pos_bytes(N));
+    auto sweep = [&]() -> int {
 #define GE_CALL(KKB)                                                                                                  \
   {                                                                                                                   \
     auto kern = rank_f16_kernel<KKB, 3>;                                                                              \
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                       160 * 1024);                                                                   \
-    if (e != hipSuccess) return (int)e;                                                                               \
+    if (int rc = lds_opt_in(kern)) return rc;                                                                         \
     hipLaunchKernelGGL(kern, dim3((unsigned)n_rb, (unsigned)ns), dim3(kBlk), topk_lds_bytes<KKB>(), st, table, N, d, hr, B,   \
                        nullptr, cand, K, max_norm, cand_is_head, known_off, known_rc, nullptr, nullptr, nullptr,      \
                        nullptr, (int)n_ct, n_rb * n_ct, spec, 0, pos_of, planes, tk);                                 \
     return launch_status();                                                                                           \
   }
-    GE_KKB_SWITCH(d, GE_CALL)
+      GE_KKB_SWITCH(d, GE_CALL)
 #undef GE_CALL
-  };
-  int rc = run();
-  if (rc == 0) {
+    };
+    const int rc = sweep();
+    if (rc != 0) return rc;
     hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, hr, B, N, tk);
-    rc = launch_status();
-  }
-  if (own) {
-    const hipError_t e = hipFreeAsync(own, st);
-    if (rc == 0 && e != hipSuccess) rc = (int)e;
-  }
-  return rc;
+    return launch_status();
+  });
 }
 
 }  // namespace ge

@@ -1,6 +1,6 @@
 // ge_rank_pipe.hip -- the link-prediction ranking sweep (holE.py:427-472, 564-575; semantics in ge_rank.hip) on the fp32
-// MFMA, software-pipelined for one wave per SIMD.  It serves what the split-precision sweep (ge_rank_f16.hip, tried
-// first by sweep_pipe_launch) does not: embedding_dim % 8 == 0 below 56, and max_norm > 8.
+// MFMA, software-pipelined for one wave per SIMD: Pipe40 / Pipe32 / Pipe24 of ge_sweep_route.h, which sends here what the
+// split-precision sweep does not take (embedding_dim below 56, max_norm > 8) when 40, 32 or 24 divides embedding_dim.
 //
 // What the microbenchmark (tools/probes/mfma_probe.hip) says about v_mfma_f32_32x32x2_f32 on gfx950 with one
 // wave per SIMD (the Q operand fills the LDS, so a CU holds one workgroup):
@@ -30,10 +30,6 @@
 #include "ge_rank_dev.h"
 #include "ge_launch.h"
 
-#ifndef GE_PIPE_GRID_M
-#define GE_PIPE_GRID_M 2   // workgroups per CU (each CU holds one at a time): equal shares, two rounds
-#endif
-
 namespace ge {
 namespace {
 
@@ -51,7 +47,7 @@ struct Cfg {
   static constexpr int kGS = 4;                 // k-pairs per operand group (16 MFMAs)
   static constexpr int kNG = CW / 2 / kGS;      // operand groups per chunk
   static constexpr int kNV = CW / 8;            // 16-byte requests per staging thread per chunk
-  static constexpr int kLdb = CW + 1;           // odd LDS row stride
+  static constexpr int kLdb = pipe_ldb(CW);     // odd LDS row stride
   static_assert(CW % 8 == 0 && kNG >= 2 && 4 * (kNG - 1) >= 2 * kNV, "chunk width");
 };
 
@@ -71,11 +67,7 @@ struct PipeLds {
   int* tI;         // [kRB] entity id of the true candidate (-1 beyond B)
 };
 
-template <int CW>
-size_t pipe_lds_bytes(int d) {
-  return sizeof(float) * ((size_t)kRB * (d + 1) + 2 * kRB * Cfg<CW>::kLdb + 3 * kRB) + sizeof(float2) * kRB +
-         sizeof(unsigned) * kRB * 4 + sizeof(int) * 2 * kRB;
-}
+// (pipe_lds_bytes<CW>(d), the bytes behind these pointers: ge_sweep_route.h)
 
 // chunk `c` (clamped to the row) of candidate row `cid`: thread t requests its CW/2 reals of row t>>1
 template <int CW>
@@ -518,73 +510,35 @@ __global__ __launch_bounds__(kBlock) void rank_pipe_kernel(
   }
 }
 
-int pipe_cu_count() {
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return 256;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) return 256;
-  return cus;
-}
-
 template <int CW>
-int pipe_launch_cw(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* true_id,
-                   const int32_t* cand, int64_t K, float max_norm, int cand_is_head, const int32_t* known_off,
-                   const uint16_t* known_rc, int32_t* raw_cnt, int32_t* skip_cnt, float* true_loss, float* scores_out,
-                   int spec, int scores_only, int sweep_flags, hipStream_t st) {
-  const size_t lds = pipe_lds_bytes<CW>(d);
-  if (lds > 160 * 1024) return GE_ENOTSUP;
-  const int64_t n_rb = (B + kRB - 1) / kRB, n_ct = (K + kRB - 1) / kRB;
-  if (n_ct > INT32_MAX / 2 || n_rb > INT32_MAX / 2) return GE_ENOTSUP;
+int pipe_launch_cw(const SweepArgs& a, hipStream_t st) {
+  const size_t lds = pipe_lds_bytes<CW>(a.d);
+  const int64_t n_rb = (a.B + kRB - 1) / kRB, n_ct = (a.K + kRB - 1) / kRB;
+  assert(a.d % CW == 0 && lds <= kLdsMax && n_ct <= INT32_MAX / 2 && n_rb <= INT32_MAX / 2);   // route_main_road
   const int64_t n_tiles = n_rb * n_ct;
-  const int64_t grid = std::min<int64_t>(n_tiles, GE_PIPE_GRID_M * (int64_t)pipe_cu_count());
+  const int64_t grid = std::min<int64_t>(n_tiles, GE_PIPE_GRID_M * (int64_t)cu_count());
   auto go = [&](auto kern) -> int {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       160 * 1024);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kBlock), lds, st, table, N, d, hr, B, true_id, cand, K, max_norm,
-                       cand_is_head, known_off, known_rc, raw_cnt, skip_cnt, true_loss, scores_out, (int)n_ct, n_tiles, spec, sweep_flags);
+    if (int rc = lds_opt_in(kern)) return rc;
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kBlock), lds, st, a.table, a.N, a.d, a.hr, a.B, a.true_id, a.cand, a.K,
+                       a.max_norm, a.cand_is_head, a.known_off, a.known_rc, a.raw_cnt, a.skip_cnt, a.true_loss, a.scores_out,
+                       (int)n_ct, n_tiles, a.spec, a.sweep_flags);
     return launch_status();
   };
-  if (scores_only) return (CW == 40 && d == 200) ? go(rank_pipe_kernel<CW, (CW == 40 ? 5 : 0), 2>) : go(rank_pipe_kernel<CW, 0, 2>);
-  if (scores_out) return go(rank_pipe_kernel<CW, 0, 1>);
-  if (CW == 40 && d == 200) return go(rank_pipe_kernel<CW, (CW == 40 ? 5 : 0), 0>);   // the FB15k configuration, unrolled
+  constexpr int kFb15k = CW == 40 ? 5 : 0;                          // the FB15k configuration (d = 200), unrolled
+  if (a.scores_only) return (CW == 40 && a.d == 200) ? go(rank_pipe_kernel<CW, kFb15k, 2>) : go(rank_pipe_kernel<CW, 0, 2>);
+  if (a.scores_out) return go(rank_pipe_kernel<CW, 0, 1>);
+  if (CW == 40 && a.d == 200) return go(rank_pipe_kernel<CW, kFb15k, 0>);
   return go(rank_pipe_kernel<CW, 0, 0>);
 }
 
 }  // namespace
 
-static int sweep_pipe_launch(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* true_id,
-                             const int32_t* cand, int64_t K, float max_norm, int cand_is_head, const int32_t* known_off,
-                             const uint16_t* known_rc, int32_t* raw_cnt, int32_t* skip_cnt, float* true_loss,
-                             float* scores_out, int spec, int scores_only, int sweep_flags, const void* planes_ws,
-                             hipStream_t st) {
-  {   // embedding_dim % 8 == 0 in 56 ... 288, max_norm <= 8: the split-precision sweep (ge_rank_f16.hip)
-    const int rc = sweep_f16_launch(table, N, d, hr, B, true_id, cand, K, max_norm, cand_is_head, known_off, known_rc, raw_cnt,
-                                    skip_cnt, true_loss, scores_out, spec, scores_only, sweep_flags, planes_ws, st);
-    if (rc != GE_ENOTSUP) return rc;
+int pipe_sweep_launch(int cw, const SweepArgs& a, hipStream_t st) {
+  switch (cw) {
+    case 40: return pipe_launch_cw<40>(a, st);
+    case 32: return pipe_launch_cw<32>(a, st);
+    default: return pipe_launch_cw<24>(a, st);
   }
-#define GE_PIPE(CW)                                                                                                  \
-  return pipe_launch_cw<CW>(table, N, d, hr, B, true_id, cand, K, max_norm, cand_is_head, known_off, known_rc, raw_cnt, \
-                            skip_cnt, true_loss, scores_out, spec, scores_only, sweep_flags, st)
-  if (d % 40 == 0) GE_PIPE(40);
-  if (d % 32 == 0) GE_PIPE(32);
-  if (d % 24 == 0) GE_PIPE(24);
-#undef GE_PIPE
-  return GE_ENOTSUP;
-}
-
-int rank_pipe_launch(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* true_id,
-                     const int32_t* cand, int64_t K, float max_norm, int cand_is_head, const int32_t* known_off,
-                     const uint16_t* known_rc, int32_t* raw_cnt, int32_t* skip_cnt, float* true_loss,
-                     float* scores_out, int spec, const void* planes_ws, hipStream_t st, int vs_loss) {
-  return sweep_pipe_launch(table, N, d, hr, B, true_id, cand, K, max_norm, cand_is_head, known_off, known_rc, raw_cnt,
-                           skip_cnt, true_loss, scores_out, spec, 0, vs_loss ? 2 : 0, planes_ws, st);
-}
-
-// ge_complex_score_1vK on the same pipeline: out [B,K] = score (sigmoid when apply_sigmoid)
-int score_pipe_launch(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* cand,
-                      int64_t K, float max_norm, int apply_sigmoid, int cand_is_head, float* out, hipStream_t st) {
-  return sweep_pipe_launch(table, N, d, hr, B, nullptr, cand, K, max_norm, cand_is_head, nullptr, nullptr, nullptr, nullptr,
-                           nullptr, out, 0, 1, apply_sigmoid ? 1 : 0, nullptr, st);
 }
 
 }  // namespace ge

@@ -106,7 +106,7 @@ def link_prediction_ranks(embeddings: torch.Tensor, test_triples: np.ndarray, ca
         raise ValueError(f"unknown model {model!r}")
     dev = embeddings.device
     d = embeddings.shape[1]
-    can_fuse = d % 8 == 0 and d <= H.rank_max_dim() and (d <= 232 or max_norm <= 8.0)   # (fp32 kernels: up to 232)
+    can_fuse = H.rank_fused_ok(d, max_norm)
     if fused is None:
         fused = can_fuse
     if model != "complex":
@@ -196,7 +196,7 @@ def evaluate_fb15k_style(embeddings: torch.Tensor, data, both_sides: bool = True
         embeddings, model = H.hole_to_spectral(embeddings.detach().clone()), "hole_spectral"
     d = embeddings.shape[1]
     planes = None                            # the candidates' fp16 planes: one build for tails and heads
-    if d % 8 == 0 and d <= H.rank_max_dim():
+    if H.rank_fused_ok(d, 1.0):              # (max_norm: the default of the calls below)
         planes = H.RankPlanes(embeddings, torch.as_tensor(cand).to(embeddings.device), model=model)
     # the known-triple indexes (a sort each) are kept on `data`: the train / valid splits do not change between the
     # evaluations of a training run
@@ -231,11 +231,6 @@ def evaluate_fb15k_style(embeddings: torch.Tensor, data, both_sides: bool = True
 
 
 # ------------------------------------------------------------------ top-k prediction
-def _split_f16_ok(d: int, max_norm: float) -> bool:
-    """embedding_dim has the split-precision sweep (the fused top-k's range)."""
-    return d % 8 == 0 and 56 <= d <= 288 and max_norm <= 8.0
-
-
 def _known_cells_rc(off: torch.Tensor, rc: torch.Tensor, n_cand: int):
     """(rows, columns) int64 of the per-tile known-cell lists of KnownIndex.cells."""
     dev = off.device
@@ -290,7 +285,7 @@ def predict_links(embeddings: torch.Tensor, queries, candidates, k: int, known_t
         raise ValueError("k must be >= 1")
     dev = embeddings.device
     N, d = embeddings.shape
-    can_fuse = _split_f16_ok(d, max_norm)
+    can_fuse = H.split_sweep_ok(d, max_norm)
     if fused is None:
         fused = can_fuse
     if fused and not can_fuse:
@@ -386,7 +381,7 @@ def predict_inference_results(embeddings: torch.Tensor, data, predict_k: int, in
     if model == "hole":
         embeddings, model = H.hole_to_spectral(embeddings.detach().clone()), "hole_spectral"
     dev = embeddings.device
-    fused = _split_f16_ok(embeddings.shape[1], 1.0)
+    fused = H.split_sweep_ok(embeddings.shape[1], 1.0)
     planes = H.RankPlanes(embeddings, torch.as_tensor(cand).to(dev), model=model) if fused else None
     kw = dict(model=model, fused=fused, planes=planes)
     K = int(predict_k)

@@ -324,6 +324,18 @@ def rank_max_dim() -> int:
     return int(_lib.load().ge_rank_max_dim())
 
 
+def split_sweep_ok(d: int, max_norm: float) -> bool:
+    """The split-precision sweep (the F16 of csrc/ge_sweep_route.h, f16_sweep_ok there) takes this embedding_dim and
+    max_norm: what the planes, the fused top-k and the main road of the rank sweep need."""
+    return d % 8 == 0 and 56 <= d <= 288 and max_norm <= 8.0
+
+
+def rank_fused_ok(d: int, max_norm: float) -> bool:
+    """Some kernel of route_rank (csrc/ge_sweep_route.h) ranks this embedding_dim and max_norm: a multiple of 8 that
+    the fp32 kernels hold (kRankMaxDimF32 = 232 there) or the split-precision sweep takes."""
+    return d % 8 == 0 and (0 < d <= 232 or split_sweep_ok(d, max_norm))
+
+
 class RankPlanes:
     """The candidates of a ranking sweep as the split-precision kernel reads them (ge_rank_planes: fp16 high halves and
     remainders of row * clip scale * 2^8 per 64-candidate tile, plus the entity -> position map), built ONCE for all the
@@ -337,7 +349,7 @@ class RankPlanes:
         _need_cuda(candidates, "candidates")
         self.cand = candidates.to(torch.int32).contiguous().view(-1)
         self.key = (emb.data_ptr(), emb.shape[0], emb.shape[1], self.cand.data_ptr(), self.cand.numel(), float(max_norm), model)
-        nbytes = int(_lib.load().ge_rank_planes_bytes(emb.shape[0], emb.shape[1], self.cand.numel())) if max_norm <= 8.0 else 0
+        nbytes = int(_lib.load().ge_rank_planes_bytes(emb.shape[0], emb.shape[1], self.cand.numel())) if split_sweep_ok(emb.shape[1], max_norm) else 0
         self.buffer = None
         if nbytes > 0:
             self.buffer = torch.empty(nbytes, dtype=torch.uint8, device=emb.device)     # (the allocator aligns to 256 bytes and more)

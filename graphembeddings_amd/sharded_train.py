@@ -283,7 +283,7 @@ def evaluate_sharded(shard: torch.Tensor, n_rows: int, relation_count: int, test
         world = dist.get_world_size(group) if dist.is_initialized() else 1
     dev, d = shard.device, int(shard.shape[1])
     N, R = int(n_rows), int(relation_count)
-    if d % 8 != 0 or d > H.rank_max_dim():
+    if not H.rank_fused_ok(d, 1.0):          # (the dim alone, as the message says; the sweep itself refuses max_norm > 8 above 232)
         raise ValueError("the sharded evaluation runs the fused sweep: embedding_dim a multiple of 8, <= %d" % H.rank_max_dim())
     test = np.asarray(test_triples, dtype=np.int64)
 

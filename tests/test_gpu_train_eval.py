@@ -336,7 +336,7 @@ def test_spectral_sweep_single_bin_rows_above_unit_max_norm(d, max_norm):
 def test_rank_sweep_edge_shapes_and_bad_ids(d):
     """One row / one candidate, sizes one past the 128-wide tiles, a max_norm below every row norm, ids outside the
     table: a bad (fixed, relation) row or true id ranks nothing before it, a bad candidate is never counted, nothing
-    faults (pipelined kernel at d = 40, generic at 56)."""
+    faults (ge_sweep_route.h: Pipe40 at d = 40, the split-precision sweep F16 at 56)."""
     from graphembeddings_amd import hole as H
     rng = np.random.default_rng(11)
     N = 300
@@ -382,6 +382,47 @@ def test_rank_sweep_edge_shapes_and_bad_ids(d):
         st = sc[i, tid[i] - 4]
         before_bad = (sc[i, 10] < st) or (sc[i, 10] == st and cand[10] < tid[i])
         assert got[i] == good[i] - int(before_bad)
+
+
+@pytest.mark.parametrize("d,max_norm,route", [(64, 9.0, "Pipe32"), (56, 9.0, "RankF32"), (200, 9.0, "Pipe40"),
+                                              (240, 9.0, None), (248, 9.0, None)])
+def test_rank_routes_behind_the_f16_sweep(d, max_norm, route):
+    """The kernels route_rank (ge_sweep_route.h) falls back on when max_norm > 8 keeps a dim off the split-precision
+    sweep: the fp32 pipeline at chunk width 32 and 40, the fp32 kernel; 130 rows x 300 candidates straddle the 128-wide
+    tiles.  Losses within 1e-5 of the fp64 oracle, counts equal to the heap's count over the kernel's own losses, with
+    and without return_scores.  Off the route the entry refuses: 248 has no chunk width; at 240 the first chunk width
+    that divides it, 40, needs 167 KiB of LDS, no narrower one is tried, and the fp32 kernel ends at 232."""
+    from graphembeddings_amd import _lib
+    from graphembeddings_amd import hole as H
+    rng = np.random.default_rng(13)
+    N, B = 304, 130
+    table = (rng.standard_normal((N, d)) * 0.3).astype(np.float32)
+    emb = torch.as_tensor(table).cuda()
+    cand = rng.permutation(np.arange(4, N)).astype(np.int32)          # K = 300
+    hr = np.stack([rng.integers(4, N, B), rng.integers(0, 4, B)], 1).astype(np.int32)
+    tid = cand[rng.integers(0, len(cand), B)].astype(np.int32)
+    args = (emb, torch.as_tensor(hr).cuda(), torch.as_tensor(tid).cuda(), torch.as_tensor(cand).cuda())
+    if route is None:
+        with pytest.raises(_lib.GeError) as err:
+            H.rank_candidates(*args, max_norm=max_norm)
+        assert err.value.code == _lib.GE_ENOTSUP
+        return
+    t64 = table.astype(np.float64)
+    pos = {int(c): j for j, c in enumerate(cand)}
+    for head in (False, True):
+        nb, nk, sc = H.rank_candidates(*args, cand_is_head=head, max_norm=max_norm, return_scores=True)
+        nb2, _ = H.rank_candidates(*args, cand_is_head=head, max_norm=max_norm)
+        sc = sc.cpu().numpy()
+        fixed, rel, cc = np.repeat(hr[:, 0], len(cand)), np.repeat(hr[:, 1], len(cand)), np.tile(cand, B)
+        triples = np.stack([cc, fixed, rel] if head else [fixed, cc, rel], 1).astype(np.int64)
+        err = np.abs(sc.reshape(-1) - O.evaluate_triples(triples, t64, max_norm)[:, 0]).max()
+        print(f"d={d} head={head}: max |loss - oracle| = {err:.3g}")
+        assert err < 1e-5
+        exp = []
+        for i in range(B):
+            st = sc[i, pos[int(tid[i])]]
+            exp.append(int(((sc[i] < st) | ((sc[i] == st) & (cand < tid[i]))).sum()))
+        assert nb.cpu().tolist() == exp and nb2.cpu().tolist() == exp and int(nk.abs().sum()) == 0
 
 
 def test_fused_and_unfused_rankers_agree_at_fb15k_scale():
@@ -557,7 +598,7 @@ def test_ranks_against_given_losses_add_over_candidate_shards(d, model):
         assert torch.equal(sb, nb) and torch.equal(sk, nk), side
 
 
-@pytest.mark.parametrize("d,fused", [(200, True), (64, True), (40, True), (16, True), (50, False)])     # f16 sweep, fp32 pipeline, generic kernel, stored scores
+@pytest.mark.parametrize("d,fused", [(200, True), (64, True), (40, True), (16, True), (50, False)])     # ge_sweep_route.h: F16, F16, Pipe40, RankF32; stored scores (ScoreFullK)
 def test_is_confident_gate_equals_the_reference_heap(d, fused):
     """--infer_threshold (holE.py:436-438, 464-466): only sweeps whose lowest loss is below the threshold record their
     positions.  link_prediction_ranks(infer_threshold=...) against the oracle's restatement fed with the sweep's own losses;
