@@ -226,15 +226,17 @@ int ge_bernoulli_corrupt_batch(const int32_t* pos, int64_t B, const int64_t* bh_
   if (B < 0 || !tail_threshold) return GE_EINVAL;
   if (n_known > 0 && (!bh_key || !bh_ent || !bt_key || !bt_ent)) return GE_EINVAL;
   if (B > 0 && (!pos || !neg)) return GE_EINVAL;
-  return bernoulli_corrupt_launch(pos, B, bh_key, bh_ent, bt_key, bt_ent, n_known, tail_threshold, n_rel,
-                                  ent_lo, n_ent, seed, step, neg, (hipStream_t)stream);
+  const SamplerArgs s{nullptr, 0, bh_key, bh_ent, bt_key, bt_ent, n_known, tail_threshold, n_rel, n_ent};
+  return bernoulli_corrupt_launch(pos, B, s, ent_lo, seed, step, neg, (hipStream_t)stream);
 }
 
-// ---------------------------------------------------------------- TransE / TransH / TransD
+// ---------------------------------------------------------------- translation models: the descriptor (ge_trans.h)
 static inline bool aligned4(const void* p) { return ((uintptr_t)p & 3) == 0; }
-// shapes and the model's tables: every table it has present and 4-byte aligned, ids fit the sort's 32-bit keys
-static inline int transx_tables_ok(int model, const void* ent, int64_t E, const void* rel, int64_t R,
-                                   const void* normal, const void* ent_transfer, const void* rel_transfer, int32_t d) {
+static inline bool sweep_batch_ok(int64_t B) { return B > 0 && B <= ((int64_t)1 << 28); }
+// TransE / TransH / TransD: shapes and the model's tables checked, m filled.  Every table the model has is present,
+// every table given 4-byte aligned, ids fit the sort's 32-bit keys.
+static int transx_model(TransModel& m, int model, int l1, const float* ent, int64_t E, const float* rel, int64_t R,
+                        const float* normal, const float* ent_transfer, const float* rel_transfer, int32_t d) {
   if (model < GE_TRANSX_TRANSE || model > GE_TRANSX_TRANSD) return GE_EINVAL;
   if (!ent || !rel || E <= 0 || R <= 0 || E + R >= ((int64_t)1 << 31)) return GE_EINVAL;
   if (d <= 0) return GE_EINVAL;
@@ -243,13 +245,43 @@ static inline int transx_tables_ok(int model, const void* ent, int64_t E, const 
   if (model == GE_TRANSX_TRANSD && (!ent_transfer || !rel_transfer)) return GE_EINVAL;
   for (const void* p : {ent, rel, normal, ent_transfer, rel_transfer})
     if (p && !aligned4(p)) return GE_EINVAL;
+  m = TransModel{model, l1, ent, rel, normal, ent_transfer, rel_transfer, nullptr, E, R, d, d};
   return 0;
 }
+// TransR: tables present and 4-byte aligned, dimensions in range, entity and relation ids fit the sorts' 32-bit keys
+static int transr_model(TransModel& m, int l1, const float* ent, int64_t E, const float* rel, const float* rel_matrix,
+                        int64_t R, int32_t dE, int32_t dR) {
+  if (!ent || !rel || !rel_matrix || E <= 0 || R <= 0 || E >= ((int64_t)1 << 31) || R >= ((int64_t)1 << 31))
+    return GE_EINVAL;
+  if (dE <= 0 || dR <= 0) return GE_EINVAL;
+  if (dE > transr_max_dim() || dR > transr_max_dim()) return GE_ENOTSUP;
+  for (const void* p : {ent, rel, rel_matrix})
+    if (!aligned4(p)) return GE_EINVAL;
+  m = TransModel{kTransR, l1, ent, rel, nullptr, nullptr, nullptr, rel_matrix, E, R, dE, dR};
+  return 0;
+}
+// The shape test of the six sweep size functions: m filled with the shape alone (model kTransR, which only the
+// ge_transr_* sizes pass: dE x dq, else an ABI model code and dE = dq = d).  id_limits: the tables' limit on the counts (TransX n_ent + n_rel < 2^31, TransR each < 2^31).  Only the
+// relation-rank sizes apply it; the rank and top-k sizes never did and answer for counts their entry points refuse.
+// Kept as it was: aligning them changes what callers see.
+static bool sweep_shape(TransModel& m, bool tr, int model, int64_t E, int64_t R, int32_t dE, int32_t dq, int64_t B,
+                        bool id_limits) {
+  const int dmax = tr ? transr_max_dim() : transx_max_dim();
+  if (!tr && (model < GE_TRANSX_TRANSE || model > GE_TRANSX_TRANSD)) return false;
+  if (E <= 0 || R <= 0 || dE <= 0 || dq <= 0 || dE > dmax || dq > dmax || !sweep_batch_ok(B)) return false;
+  if (id_limits && (tr ? E >= ((int64_t)1 << 31) || R >= ((int64_t)1 << 31) : E + R >= ((int64_t)1 << 31))) return false;
+  m = TransModel{model, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, E, R, dE, dq};
+  return true;
+}
+
+// ---------------------------------------------------------------- TransE / TransH / TransD
 static inline bool transx_batch_ok(int64_t B) { return B > 0 && B <= ((int64_t)1 << 31) / 5 - 1; }
-// the triples and Bernoulli tables a draw reads: T rows fit its 32-bit row pick, the four arrays are there when
-// n_known > 0
-static inline bool sampler_ok(const int32_t* triples, int64_t T, const uint32_t* tail_threshold, int64_t n_known,
-                              const int64_t* bh_key, const int32_t* bh_ent, const int64_t* bt_key, const int32_t* bt_ent) {
+// the triples and Bernoulli tables a draw reads, checked and s filled: T rows fit its 32-bit row pick, the four arrays
+// are there when n_known > 0
+static inline bool sampler_ok(SamplerArgs& s, const int32_t* triples, int64_t T, const uint32_t* tail_threshold,
+                              int64_t n_known, const int64_t* bh_key, const int32_t* bh_ent, const int64_t* bt_key,
+                              const int32_t* bt_ent, int32_t n_rel, int32_t n_ent) {
+  s = SamplerArgs{triples, T, bh_key, bh_ent, bt_key, bt_ent, n_known, tail_threshold, n_rel, n_ent};
   return triples && T > 0 && T <= ((int64_t)1 << 32) && tail_threshold && n_known >= 0 &&
          (n_known == 0 || (bh_key && bh_ent && bt_key && bt_ent));
 }
@@ -259,11 +291,11 @@ int ge_transx_max_dim(void) { return transx_max_dim(); }
 int ge_transx_score(int model, int l1, const float* ent, int64_t n_ent, const float* rel, int64_t n_rel,
                     const float* normal, const float* ent_transfer, const float* rel_transfer, int32_t d,
                     const int32_t* triples, int64_t B, float* out, void* stream) {
-  if (int rc = transx_tables_ok(model, ent, n_ent, rel, n_rel, normal, ent_transfer, rel_transfer, d)) return rc;
+  TransModel m;
+  if (int rc = transx_model(m, model, l1, ent, n_ent, rel, n_rel, normal, ent_transfer, rel_transfer, d)) return rc;
   if (B < 0) return GE_EINVAL;
   if (B > 0 && (!triples || !out || !aligned4(triples) || !aligned4(out))) return GE_EINVAL;
-  return transx_score_launch(model, l1, ent, n_ent, rel, n_rel, normal, ent_transfer, rel_transfer, d, triples, B, out,
-                             (hipStream_t)stream);
+  return transx_score_launch(m, triples, B, out, (hipStream_t)stream);
 }
 
 size_t ge_transx_step_workspace_bytes(int64_t n_ent, int64_t n_rel, int32_t d, int64_t B) {
@@ -275,7 +307,8 @@ int ge_transx_hinge_step(int model, int l1, float* ent, int64_t n_ent, float* re
                          float* ent_transfer, float* rel_transfer, int32_t d, const int32_t* pos, const int32_t* neg,
                          int64_t B, float margin, float lr, float* loss, void* workspace, size_t workspace_bytes,
                          void* stream) {
-  if (int rc = transx_tables_ok(model, ent, n_ent, rel, n_rel, normal, ent_transfer, rel_transfer, d)) return rc;
+  TransModel m;
+  if (int rc = transx_model(m, model, l1, ent, n_ent, rel, n_rel, normal, ent_transfer, rel_transfer, d)) return rc;
   if (!transx_batch_ok(B) || !pos || !neg || !loss || !workspace) return GE_EINVAL;
   if (!aligned4(pos) || !aligned4(neg) || !aligned4(loss) || ((uintptr_t)workspace & 255)) return GE_EINVAL;
   return transx_hinge_step_run(model, l1, ent, n_ent, rel, n_rel, normal, ent_transfer, rel_transfer, d, pos, neg, B,
@@ -286,10 +319,10 @@ int ge_transx_draw_batch(const int32_t* triples, int64_t T, int64_t B, const int
                          const int64_t* bt_key, const int32_t* bt_ent, int64_t n_known, const uint32_t* tail_threshold,
                          int32_t n_rel, int32_t n_ent, uint64_t seed, uint64_t step, int32_t* pos, int32_t* neg,
                          void* stream) {
-  if (!sampler_ok(triples, T, tail_threshold, n_known, bh_key, bh_ent, bt_key, bt_ent)) return GE_EINVAL;
+  SamplerArgs s;
+  if (!sampler_ok(s, triples, T, tail_threshold, n_known, bh_key, bh_ent, bt_key, bt_ent, n_rel, n_ent)) return GE_EINVAL;
   if (B < 0 || n_rel <= 0 || n_ent <= 0 || (B > 0 && (!pos || !neg))) return GE_EINVAL;
-  return transx_draw_launch(triples, T, B, bh_key, bh_ent, bt_key, bt_ent, n_known, tail_threshold, n_rel, n_ent, seed,
-                            step, pos, neg, (hipStream_t)stream);
+  return transx_draw_launch(s, B, seed, step, pos, neg, (hipStream_t)stream);
 }
 
 int ge_transx_train_steps(int model, int l1, float* ent, int64_t n_ent, float* rel, int64_t n_rel, float* normal,
@@ -298,28 +331,20 @@ int ge_transx_train_steps(int model, int l1, float* ent, int64_t n_ent, float* r
                           int64_t n_known, const uint32_t* tail_threshold, uint64_t seed, uint64_t first_step,
                           int64_t n_steps, int64_t B, float margin, float lr, float* losses, void* workspace,
                           size_t workspace_bytes, void* stream) {
-  if (int rc = transx_tables_ok(model, ent, n_ent, rel, n_rel, normal, ent_transfer, rel_transfer, d)) return rc;
+  TransModel m;
+  SamplerArgs s;
+  if (int rc = transx_model(m, model, l1, ent, n_ent, rel, n_rel, normal, ent_transfer, rel_transfer, d)) return rc;
   if (!transx_batch_ok(B) || n_steps < 0 || !losses || !workspace || ((uintptr_t)workspace & 255)) return GE_EINVAL;
-  if (!sampler_ok(triples, T, tail_threshold, n_known, bh_key, bh_ent, bt_key, bt_ent)) return GE_EINVAL;
-  return transx_train_steps_run(model, l1, ent, n_ent, rel, n_rel, normal, ent_transfer, rel_transfer, d, triples, T,
-                                bh_key, bh_ent, bt_key, bt_ent, n_known, tail_threshold, seed, first_step, n_steps, B,
-                                margin, lr, losses, workspace, workspace_bytes, (hipStream_t)stream);
+  if (!sampler_ok(s, triples, T, tail_threshold, n_known, bh_key, bh_ent, bt_key, bt_ent, (int32_t)n_rel, (int32_t)n_ent))
+    return GE_EINVAL;
+  return transx_train_steps_run(model, l1, ent, n_ent, rel, n_rel, normal, ent_transfer, rel_transfer, d, s, seed,
+                                first_step, n_steps, B, margin, lr, losses, workspace, workspace_bytes,
+                                (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------- TransR
-// tables present and 4-byte aligned, dimensions in range, entity and relation ids fit the sorts' 32-bit keys
-static inline int transr_tables_ok(const void* ent, int64_t E, const void* rel, const void* rel_matrix, int64_t R,
-                                   int32_t dE, int32_t dR) {
-  if (!ent || !rel || !rel_matrix || E <= 0 || R <= 0 || E >= ((int64_t)1 << 31) || R >= ((int64_t)1 << 31))
-    return GE_EINVAL;
-  if (dE <= 0 || dR <= 0) return GE_EINVAL;
-  if (dE > transr_max_dim() || dR > transr_max_dim()) return GE_ENOTSUP;
-  for (const void* p : {ent, rel, rel_matrix})
-    if (!aligned4(p)) return GE_EINVAL;
-  return 0;
-}
 // 4B entity slots and every sorted position fit an int32
-static inline bool transr_batch_ok(int64_t B) { return B > 0 && B <= ((int64_t)1 << 28); }
+static inline bool transr_batch_ok(int64_t B) { return sweep_batch_ok(B); }
 static inline bool adam_ok(float b1, float b2, float eps, int64_t t, const void* m, const void* v) {
   return b1 >= 0.f && b1 < 1.f && b2 >= 0.f && b2 < 1.f && eps >= 0.f && t >= 1 && m && v && aligned4(m) && aligned4(v);
 }
@@ -328,10 +353,11 @@ int ge_transr_max_dim(void) { return transr_max_dim(); }
 
 int ge_transr_score(int l1, const float* ent, int64_t n_ent, const float* rel, const float* rel_matrix, int64_t n_rel,
                     int32_t dim_e, int32_t dim_r, const int32_t* triples, int64_t B, float* out, void* stream) {
-  if (int rc = transr_tables_ok(ent, n_ent, rel, rel_matrix, n_rel, dim_e, dim_r)) return rc;
+  TransModel m;
+  if (int rc = transr_model(m, l1, ent, n_ent, rel, rel_matrix, n_rel, dim_e, dim_r)) return rc;
   if (B < 0) return GE_EINVAL;
   if (B > 0 && (!triples || !out || !aligned4(triples) || !aligned4(out))) return GE_EINVAL;
-  return transr_score_launch(l1, ent, n_ent, rel, rel_matrix, n_rel, dim_e, dim_r, triples, B, out, (hipStream_t)stream);
+  return transr_score_launch(m, triples, B, out, (hipStream_t)stream);
 }
 
 size_t ge_transr_step_workspace_bytes(int64_t n_ent, int64_t n_rel, int32_t dim_e, int32_t dim_r, int64_t B) {
@@ -344,7 +370,8 @@ int ge_transr_adam_step(int l1, float* ent, int64_t n_ent, float* rel, float* re
                         int32_t dim_r, float* m, float* v, const int32_t* pos, const int32_t* neg, int64_t B,
                         float margin, float lr, float b1, float b2, float eps, int64_t t, float* loss, void* workspace,
                         size_t workspace_bytes, void* stream) {
-  if (int rc = transr_tables_ok(ent, n_ent, rel, rel_matrix, n_rel, dim_e, dim_r)) return rc;
+  TransModel tm;
+  if (int rc = transr_model(tm, l1, ent, n_ent, rel, rel_matrix, n_rel, dim_e, dim_r)) return rc;
   if (!transr_batch_ok(B) || !pos || !neg || !loss || !workspace || !adam_ok(b1, b2, eps, t, m, v)) return GE_EINVAL;
   if (!aligned4(pos) || !aligned4(neg) || !aligned4(loss) || ((uintptr_t)workspace & 255)) return GE_EINVAL;
   return transr_adam_step_run(l1, ent, n_ent, rel, rel_matrix, n_rel, dim_e, dim_r, m, v, pos, neg, B, margin, lr, b1,
@@ -357,122 +384,37 @@ int ge_transr_train_steps(int l1, float* ent, int64_t n_ent, float* rel, float* 
                           int64_t n_known, const uint32_t* tail_threshold, uint64_t seed, uint64_t first_step,
                           int64_t n_steps, int64_t B, float margin, float lr, float b1, float b2, float eps,
                           int64_t first_t, float* losses, void* workspace, size_t workspace_bytes, void* stream) {
-  if (int rc = transr_tables_ok(ent, n_ent, rel, rel_matrix, n_rel, dim_e, dim_r)) return rc;
+  TransModel tm;
+  SamplerArgs s;
+  if (int rc = transr_model(tm, l1, ent, n_ent, rel, rel_matrix, n_rel, dim_e, dim_r)) return rc;
   if (!transr_batch_ok(B) || n_steps < 0 || !losses || !workspace || ((uintptr_t)workspace & 255)) return GE_EINVAL;
   if (!adam_ok(b1, b2, eps, first_t, m, v)) return GE_EINVAL;
-  if (!sampler_ok(triples, T, tail_threshold, n_known, bh_key, bh_ent, bt_key, bt_ent)) return GE_EINVAL;
-  return transr_train_steps_run(l1, ent, n_ent, rel, rel_matrix, n_rel, dim_e, dim_r, m, v, triples, T, bh_key, bh_ent,
-                                bt_key, bt_ent, n_known, tail_threshold, seed, first_step, n_steps, B, margin, lr, b1,
-                                b2, eps, first_t, losses, workspace, workspace_bytes, (hipStream_t)stream);
+  if (!sampler_ok(s, triples, T, tail_threshold, n_known, bh_key, bh_ent, bt_key, bt_ent, (int32_t)n_rel, (int32_t)n_ent))
+    return GE_EINVAL;
+  return transr_train_steps_run(l1, ent, n_ent, rel, rel_matrix, n_rel, dim_e, dim_r, m, v, s, seed, first_step, n_steps,
+                                B, margin, lr, b1, b2, eps, first_t, losses, workspace, workspace_bytes,
+                                (hipStream_t)stream);
 }
 
-// ---------------------------------------------------------------- translation-model ranks
+// ---------------------------------------------------------------- translation-model sweeps: entity ranks, relation
+// ranks, top-k.  Each has one body behind its TransX and its TransR entry point; the order inside is the tables (the
+// entry point's transx_model / transr_model), the outputs, B == 0 (returns 0), then the launcher's GE_ENOMEM.
 // B rows of int32 counters, q rows of the workspace and the sweep's row-chunk grid all fit; the outputs are 4-byte
 // aligned; the known lists come as a pair
-static inline int rank_outputs_ok(int64_t B, const int32_t* triples, const int32_t* known_off, const uint16_t* known_rc,
-                                  const int32_t* n_before, const int32_t* n_known_before, const float* true_dist,
-                                  const float* scores_out, const void* workspace) {
+static int rank_outputs_ok(int64_t B, const int32_t* triples, const RankOut& o, const void* workspace) {
   if (B < 0 || B > ((int64_t)1 << 28)) return GE_EINVAL;
-  if ((known_off == nullptr) != (known_rc == nullptr)) return GE_EINVAL;
+  if ((o.known_off == nullptr) != (o.known_rc == nullptr)) return GE_EINVAL;
   if (B == 0) return 0;
-  if (!triples || !n_before || !n_known_before || !true_dist || !workspace || ((uintptr_t)workspace & 255)) return GE_EINVAL;
-  for (const void* p : {(const void*)triples, (const void*)known_off, (const void*)n_before, (const void*)n_known_before,
-                        (const void*)true_dist, (const void*)scores_out})
+  if (!triples || !o.n_before || !o.n_known_before || !o.true_dist || !workspace || ((uintptr_t)workspace & 255))
+    return GE_EINVAL;
+  for (const void* p : {(const void*)triples, (const void*)o.known_off, (const void*)o.n_before,
+                        (const void*)o.n_known_before, (const void*)o.true_dist, (const void*)o.scores_out})
     if (p && !aligned4(p)) return GE_EINVAL;
   return 0;
 }
-
-size_t ge_transx_rank_workspace_bytes(int model, int64_t n_ent, int64_t n_rel, int32_t d, int64_t B) {
-  if (model < GE_TRANSX_TRANSE || model > GE_TRANSX_TRANSD || n_ent <= 0 || n_rel <= 0 || d <= 0 ||
-      d > transx_max_dim() || B <= 0 || B > ((int64_t)1 << 28))
-    return 0;
-  return transx_rank_ws_bytes(model, n_ent, n_rel, d, B);
-}
-
-int ge_transx_rank(int model, int l1, const float* ent, int64_t n_ent, const float* rel, int64_t n_rel,
-                   const float* normal, const float* ent_transfer, const float* rel_transfer, int32_t d,
-                   const int32_t* triples, int64_t B, int cand_is_head, const int32_t* known_off,
-                   const uint16_t* known_rc, int32_t* n_before, int32_t* n_known_before, float* true_dist,
-                   float* scores_out, void* workspace, size_t workspace_bytes, void* stream) {
-  if (int rc = transx_tables_ok(model, ent, n_ent, rel, n_rel, normal, ent_transfer, rel_transfer, d)) return rc;
-  if (int rc = rank_outputs_ok(B, triples, known_off, known_rc, n_before, n_known_before, true_dist, scores_out,
-                               workspace))
-    return rc;
-  if (B == 0) return 0;
-  return transx_rank_launch(model, l1, ent, n_ent, rel, n_rel, normal, ent_transfer, rel_transfer, d, triples, B,
-                            cand_is_head, known_off, known_rc, n_before, n_known_before, true_dist, scores_out, workspace,
-                            workspace_bytes, (hipStream_t)stream);
-}
-
-size_t ge_transr_rank_workspace_bytes(int64_t n_ent, int64_t n_rel, int32_t dim_e, int32_t dim_r, int64_t B) {
-  if (n_ent <= 0 || n_rel <= 0 || dim_e <= 0 || dim_r <= 0 || dim_e > transr_max_dim() || dim_r > transr_max_dim() ||
-      B <= 0 || B > ((int64_t)1 << 28))
-    return 0;
-  return transr_rank_ws_bytes(n_ent, n_rel, dim_r, B);
-}
-
-int ge_transr_rank(int l1, const float* ent, int64_t n_ent, const float* rel, const float* rel_matrix, int64_t n_rel,
-                   int32_t dim_e, int32_t dim_r, const int32_t* triples, int64_t B, int cand_is_head,
-                   const int32_t* known_off, const uint16_t* known_rc, int32_t* n_before, int32_t* n_known_before,
-                   float* true_dist, float* scores_out, void* workspace, size_t workspace_bytes, void* stream) {
-  if (int rc = transr_tables_ok(ent, n_ent, rel, rel_matrix, n_rel, dim_e, dim_r)) return rc;
-  if (int rc = rank_outputs_ok(B, triples, known_off, known_rc, n_before, n_known_before, true_dist, scores_out,
-                               workspace))
-    return rc;
-  if (B == 0) return 0;
-  return transr_rank_launch(l1, ent, n_ent, rel, rel_matrix, n_rel, dim_e, dim_r, triples, B, cand_is_head, known_off,
-                            known_rc, n_before, n_known_before, true_dist, scores_out, workspace, workspace_bytes,
-                            (hipStream_t)stream);
-}
-
-// ---------------------------------------------------------------- translation-model relation prediction
-size_t ge_transx_relation_rank_workspace_bytes(int model, int64_t n_ent, int64_t n_rel, int32_t d, int64_t B) {
-  if (model < GE_TRANSX_TRANSE || model > GE_TRANSX_TRANSD || n_ent <= 0 || n_rel <= 0 ||
-      n_ent + n_rel >= ((int64_t)1 << 31) || d <= 0 || d > transx_max_dim() || B <= 0 || B > ((int64_t)1 << 28))
-    return 0;
-  return transx_relrank_ws_bytes(model, n_rel, d, B);
-}
-
-int ge_transx_relation_rank(int model, int l1, const float* ent, int64_t n_ent, const float* rel, int64_t n_rel,
-                            const float* normal, const float* ent_transfer, const float* rel_transfer, int32_t d,
-                            const int32_t* triples, int64_t B, const int32_t* known_off, const uint16_t* known_rc,
-                            int32_t* n_before, int32_t* n_known_before, float* true_dist, float* scores_out,
-                            void* workspace, size_t workspace_bytes, void* stream) {
-  if (int rc = transx_tables_ok(model, ent, n_ent, rel, n_rel, normal, ent_transfer, rel_transfer, d)) return rc;
-  if (int rc = rank_outputs_ok(B, triples, known_off, known_rc, n_before, n_known_before, true_dist, scores_out,
-                               workspace))
-    return rc;
-  if (B == 0) return 0;
-  return transx_relrank_launch(model, l1, ent, n_ent, rel, n_rel, normal, ent_transfer, rel_transfer, d, triples, B,
-                               known_off, known_rc, n_before, n_known_before, true_dist, scores_out, workspace,
-                               workspace_bytes, (hipStream_t)stream);
-}
-
-size_t ge_transr_relation_rank_workspace_bytes(int64_t n_ent, int64_t n_rel, int32_t dim_e, int32_t dim_r, int64_t B) {
-  if (n_ent <= 0 || n_rel <= 0 || n_ent >= ((int64_t)1 << 31) || n_rel >= ((int64_t)1 << 31) || dim_e <= 0 ||
-      dim_r <= 0 || dim_e > transr_max_dim() || dim_r > transr_max_dim() || B <= 0 || B > ((int64_t)1 << 28))
-    return 0;
-  return transr_relrank_ws_bytes(n_rel, dim_e, B);
-}
-
-int ge_transr_relation_rank(int l1, const float* ent, int64_t n_ent, const float* rel, const float* rel_matrix,
-                            int64_t n_rel, int32_t dim_e, int32_t dim_r, const int32_t* triples, int64_t B,
-                            const int32_t* known_off, const uint16_t* known_rc, int32_t* n_before,
-                            int32_t* n_known_before, float* true_dist, float* scores_out, void* workspace,
-                            size_t workspace_bytes, void* stream) {
-  if (int rc = transr_tables_ok(ent, n_ent, rel, rel_matrix, n_rel, dim_e, dim_r)) return rc;
-  if (int rc = rank_outputs_ok(B, triples, known_off, known_rc, n_before, n_known_before, true_dist, scores_out,
-                               workspace))
-    return rc;
-  if (B == 0) return 0;
-  return transr_relrank_launch(l1, ent, n_ent, rel, rel_matrix, n_rel, dim_e, dim_r, triples, B, known_off, known_rc,
-                               n_before, n_known_before, true_dist, scores_out, workspace, workspace_bytes,
-                               (hipStream_t)stream);
-}
-
 // the top-k's outputs: B in range, k in [1, max_k], every buffer present and aligned; the known lists come as a pair
-static inline int topk_outputs_ok(int64_t B, const int32_t* queries, const int32_t* known_off, const uint16_t* known_rc,
-                                  int32_t k, const int32_t* out_id, const float* out_dist, const void* workspace) {
+static int topk_outputs_ok(int64_t B, const int32_t* queries, const int32_t* known_off, const uint16_t* known_rc,
+                           int32_t k, const int32_t* out_id, const float* out_dist, const void* workspace) {
   if (B < 0 || B > ((int64_t)1 << 28) || k < 1 || k > transx_topk_max_k()) return GE_EINVAL;
   if ((known_off == nullptr) != (known_rc == nullptr)) return GE_EINVAL;
   if (B == 0) return 0;
@@ -482,13 +424,95 @@ static inline int topk_outputs_ok(int64_t B, const int32_t* queries, const int32
   return 0;
 }
 
+static int trans_rank(const TransModel& m, const int32_t* triples, int64_t B, int cand_is_head, const RankOut& o,
+                      void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = rank_outputs_ok(B, triples, o, workspace)) return rc;
+  if (B == 0) return 0;
+  return trans_rank_launch(m, triples, B, cand_is_head, o, workspace, workspace_bytes, (hipStream_t)stream);
+}
+static int trans_relation_rank(const TransModel& m, const int32_t* triples, int64_t B, const RankOut& o, void* workspace,
+                               size_t workspace_bytes, void* stream) {
+  if (int rc = rank_outputs_ok(B, triples, o, workspace)) return rc;
+  if (B == 0) return 0;
+  return trans_relrank_launch(m, triples, B, o, workspace, workspace_bytes, (hipStream_t)stream);
+}
+static int trans_topk(const TransModel& m, const int32_t* queries, int64_t B, int cand_is_head, const int32_t* known_off,
+                      const uint16_t* known_rc, int32_t k, int32_t* out_id, float* out_dist, void* workspace,
+                      size_t workspace_bytes, void* stream) {
+  if (int rc = topk_outputs_ok(B, queries, known_off, known_rc, k, out_id, out_dist, workspace)) return rc;
+  if (B == 0) return 0;
+  return trans_topk_launch(m, queries, B, cand_is_head, known_off, known_rc, k, out_id, out_dist, workspace,
+                           workspace_bytes, (hipStream_t)stream);
+}
+
+size_t ge_transx_rank_workspace_bytes(int model, int64_t n_ent, int64_t n_rel, int32_t d, int64_t B) {
+  TransModel m;
+  return sweep_shape(m, false, model, n_ent, n_rel, d, d, B, false) ? trans_rank_ws_bytes(m, B) : 0;
+}
+
+int ge_transx_rank(int model, int l1, const float* ent, int64_t n_ent, const float* rel, int64_t n_rel,
+                   const float* normal, const float* ent_transfer, const float* rel_transfer, int32_t d,
+                   const int32_t* triples, int64_t B, int cand_is_head, const int32_t* known_off,
+                   const uint16_t* known_rc, int32_t* n_before, int32_t* n_known_before, float* true_dist,
+                   float* scores_out, void* workspace, size_t workspace_bytes, void* stream) {
+  TransModel m;
+  if (int rc = transx_model(m, model, l1, ent, n_ent, rel, n_rel, normal, ent_transfer, rel_transfer, d)) return rc;
+  return trans_rank(m, triples, B, cand_is_head, {known_off, known_rc, n_before, n_known_before, true_dist, scores_out},
+                    workspace, workspace_bytes, stream);
+}
+
+size_t ge_transr_rank_workspace_bytes(int64_t n_ent, int64_t n_rel, int32_t dim_e, int32_t dim_r, int64_t B) {
+  TransModel m;
+  return sweep_shape(m, true, kTransR, n_ent, n_rel, dim_e, dim_r, B, false) ? trans_rank_ws_bytes(m, B) : 0;
+}
+
+int ge_transr_rank(int l1, const float* ent, int64_t n_ent, const float* rel, const float* rel_matrix, int64_t n_rel,
+                   int32_t dim_e, int32_t dim_r, const int32_t* triples, int64_t B, int cand_is_head,
+                   const int32_t* known_off, const uint16_t* known_rc, int32_t* n_before, int32_t* n_known_before,
+                   float* true_dist, float* scores_out, void* workspace, size_t workspace_bytes, void* stream) {
+  TransModel m;
+  if (int rc = transr_model(m, l1, ent, n_ent, rel, rel_matrix, n_rel, dim_e, dim_r)) return rc;
+  return trans_rank(m, triples, B, cand_is_head, {known_off, known_rc, n_before, n_known_before, true_dist, scores_out},
+                    workspace, workspace_bytes, stream);
+}
+
+size_t ge_transx_relation_rank_workspace_bytes(int model, int64_t n_ent, int64_t n_rel, int32_t d, int64_t B) {
+  TransModel m;
+  return sweep_shape(m, false, model, n_ent, n_rel, d, d, B, true) ? trans_relrank_ws_bytes(m, B) : 0;
+}
+
+int ge_transx_relation_rank(int model, int l1, const float* ent, int64_t n_ent, const float* rel, int64_t n_rel,
+                            const float* normal, const float* ent_transfer, const float* rel_transfer, int32_t d,
+                            const int32_t* triples, int64_t B, const int32_t* known_off, const uint16_t* known_rc,
+                            int32_t* n_before, int32_t* n_known_before, float* true_dist, float* scores_out,
+                            void* workspace, size_t workspace_bytes, void* stream) {
+  TransModel m;
+  if (int rc = transx_model(m, model, l1, ent, n_ent, rel, n_rel, normal, ent_transfer, rel_transfer, d)) return rc;
+  return trans_relation_rank(m, triples, B, {known_off, known_rc, n_before, n_known_before, true_dist, scores_out},
+                             workspace, workspace_bytes, stream);
+}
+
+size_t ge_transr_relation_rank_workspace_bytes(int64_t n_ent, int64_t n_rel, int32_t dim_e, int32_t dim_r, int64_t B) {
+  TransModel m;
+  return sweep_shape(m, true, kTransR, n_ent, n_rel, dim_e, dim_r, B, true) ? trans_relrank_ws_bytes(m, B) : 0;
+}
+
+int ge_transr_relation_rank(int l1, const float* ent, int64_t n_ent, const float* rel, const float* rel_matrix,
+                            int64_t n_rel, int32_t dim_e, int32_t dim_r, const int32_t* triples, int64_t B,
+                            const int32_t* known_off, const uint16_t* known_rc, int32_t* n_before,
+                            int32_t* n_known_before, float* true_dist, float* scores_out, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+  TransModel m;
+  if (int rc = transr_model(m, l1, ent, n_ent, rel, rel_matrix, n_rel, dim_e, dim_r)) return rc;
+  return trans_relation_rank(m, triples, B, {known_off, known_rc, n_before, n_known_before, true_dist, scores_out},
+                             workspace, workspace_bytes, stream);
+}
+
 int ge_transx_topk_max_k(void) { return transx_topk_max_k(); }
 
 size_t ge_transx_topk_workspace_bytes(int model, int64_t n_ent, int64_t n_rel, int32_t d, int64_t B, int32_t k) {
-  if (model < GE_TRANSX_TRANSE || model > GE_TRANSX_TRANSD || n_ent <= 0 || n_rel <= 0 || d <= 0 ||
-      d > transx_max_dim() || B <= 0 || B > ((int64_t)1 << 28))
-    return 0;
-  return transx_topk_ws_bytes(model, n_ent, n_rel, d, B, k);
+  TransModel m;
+  return sweep_shape(m, false, model, n_ent, n_rel, d, d, B, false) ? trans_topk_ws_bytes(m, B, k) : 0;
 }
 
 int ge_transx_topk(int model, int l1, const float* ent, int64_t n_ent, const float* rel, int64_t n_rel,
@@ -496,30 +520,25 @@ int ge_transx_topk(int model, int l1, const float* ent, int64_t n_ent, const flo
                    const int32_t* queries, int64_t B, int cand_is_head, const int32_t* known_off,
                    const uint16_t* known_rc, int32_t k, int32_t* out_id, float* out_dist, void* workspace,
                    size_t workspace_bytes, void* stream) {
-  if (int rc = transx_tables_ok(model, ent, n_ent, rel, n_rel, normal, ent_transfer, rel_transfer, d)) return rc;
-  if (int rc = topk_outputs_ok(B, queries, known_off, known_rc, k, out_id, out_dist, workspace)) return rc;
-  if (B == 0) return 0;
-  return transx_topk_launch(model, l1, ent, n_ent, rel, n_rel, normal, ent_transfer, rel_transfer, d, queries, B,
-                            cand_is_head, known_off, known_rc, k, out_id, out_dist, workspace, workspace_bytes,
-                            (hipStream_t)stream);
+  TransModel m;
+  if (int rc = transx_model(m, model, l1, ent, n_ent, rel, n_rel, normal, ent_transfer, rel_transfer, d)) return rc;
+  return trans_topk(m, queries, B, cand_is_head, known_off, known_rc, k, out_id, out_dist, workspace, workspace_bytes,
+                    stream);
 }
 
 size_t ge_transr_topk_workspace_bytes(int64_t n_ent, int64_t n_rel, int32_t dim_e, int32_t dim_r, int64_t B, int32_t k) {
-  if (n_ent <= 0 || n_rel <= 0 || dim_e <= 0 || dim_r <= 0 || dim_e > transr_max_dim() || dim_r > transr_max_dim() ||
-      B <= 0 || B > ((int64_t)1 << 28))
-    return 0;
-  return transr_topk_ws_bytes(n_ent, n_rel, dim_r, B, k);
+  TransModel m;
+  return sweep_shape(m, true, kTransR, n_ent, n_rel, dim_e, dim_r, B, false) ? trans_topk_ws_bytes(m, B, k) : 0;
 }
 
 int ge_transr_topk(int l1, const float* ent, int64_t n_ent, const float* rel, const float* rel_matrix, int64_t n_rel,
                    int32_t dim_e, int32_t dim_r, const int32_t* queries, int64_t B, int cand_is_head,
                    const int32_t* known_off, const uint16_t* known_rc, int32_t k, int32_t* out_id, float* out_dist,
                    void* workspace, size_t workspace_bytes, void* stream) {
-  if (int rc = transr_tables_ok(ent, n_ent, rel, rel_matrix, n_rel, dim_e, dim_r)) return rc;
-  if (int rc = topk_outputs_ok(B, queries, known_off, known_rc, k, out_id, out_dist, workspace)) return rc;
-  if (B == 0) return 0;
-  return transr_topk_launch(l1, ent, n_ent, rel, rel_matrix, n_rel, dim_e, dim_r, queries, B, cand_is_head, known_off,
-                            known_rc, k, out_id, out_dist, workspace, workspace_bytes, (hipStream_t)stream);
+  TransModel m;
+  if (int rc = transr_model(m, l1, ent, n_ent, rel, rel_matrix, n_rel, dim_e, dim_r)) return rc;
+  return trans_topk(m, queries, B, cand_is_head, known_off, known_rc, k, out_id, out_dist, workspace, workspace_bytes,
+                    stream);
 }
 
 static inline int neighbor_args_ok(const float* table, int64_t N, int32_t d, const int32_t* queries, int64_t B,

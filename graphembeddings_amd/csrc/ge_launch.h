@@ -10,6 +10,7 @@
 #include <stdint.h>
 
 #include "ge_sweep_route.h"   // rank_planes_bytes, kRankMaxDim
+#include "ge_trans.h"         // TransModel
 
 namespace ge {
 
@@ -60,10 +61,14 @@ int gather_rows_launch(const float* table, int64_t N, int32_t d, const int32_t* 
 int corrupt_batch_launch(const int32_t* pos, int64_t B, const int32_t* id_to_type, int64_t N, const int64_t* type_offsets,
                          int32_t n_types, const int32_t* type_ids, uint64_t seed, uint64_t step, int32_t padded_size,
                          int32_t mode, int32_t* neg, hipStream_t st);
-int bernoulli_corrupt_launch(const int32_t* pos, int64_t B, const int64_t* bh_key, const int32_t* bh_ent,
-                             const int64_t* bt_key, const int32_t* bt_ent, int64_t n_known, const uint32_t* tail_threshold,
-                             int32_t n_rel, int32_t ent_lo, int32_t n_ent, uint64_t seed, uint64_t step, int32_t* neg,
-                             hipStream_t st);
+// What a Bernoulli draw reads: the triple list it picks positives from (transx_draw_launch alone) and the known
+// (entity, relation) keys with their entities, sorted, for the corruption.
+struct SamplerArgs {
+  const int32_t* triples; int64_t T; const int64_t* bh_key; const int32_t* bh_ent; const int64_t* bt_key;
+  const int32_t* bt_ent; int64_t n_known; const uint32_t* tail_threshold; int32_t n_rel, n_ent;
+};
+int bernoulli_corrupt_launch(const int32_t* pos, int64_t B, const SamplerArgs& s, int32_t ent_lo, uint64_t seed,
+                             uint64_t step, int32_t* neg, hipStream_t st);
 int select_rows_launch(const int32_t* valid, int64_t V, int64_t B, uint64_t seed, uint64_t counter, int32_t* out,
                        hipStream_t st);
 int mean_pocket_launch(const float* loss, int64_t B, float* mean_out, float* best, int32_t* flag, hipStream_t st);
@@ -189,92 +194,64 @@ int shard_owner_apply_launch(float* shard, int32_t d, const int32_t* record, int
 // ge_transx.hip: TransE / TransH / TransD scoring, hinge steps, sampler and native loop
 int transx_max_dim();
 size_t transx_ws_bytes(int64_t E, int64_t R, int32_t d, int64_t B);
-int transx_score_launch(int model, int l1, const float* ent, int64_t E, const float* rel, int64_t R, const float* normal,
-                        const float* ent_transfer, const float* rel_transfer, int32_t d, const int32_t* tri, int64_t B,
-                        float* out, hipStream_t st);
+int transx_score_launch(const TransModel& m, const int32_t* tri, int64_t B, float* out, hipStream_t st);
 int transx_hinge_step_run(int model, int l1, float* ent, int64_t E, float* rel, int64_t R, float* normal,
                           float* ent_transfer, float* rel_transfer, int32_t d, const int32_t* pos, const int32_t* neg,
                           int64_t B, float margin, float lr, float* loss, void* workspace, size_t workspace_bytes,
                           hipStream_t st);
-int transx_draw_launch(const int32_t* triples, int64_t T, int64_t B, const int64_t* bh_key, const int32_t* bh_ent,
-                       const int64_t* bt_key, const int32_t* bt_ent, int64_t n_known, const uint32_t* tail_threshold,
-                       int32_t n_rel, int32_t n_ent, uint64_t seed, uint64_t step, int32_t* pos, int32_t* neg,
+int transx_draw_launch(const SamplerArgs& s, int64_t B, uint64_t seed, uint64_t step, int32_t* pos, int32_t* neg,
                        hipStream_t st);
 // The native loop of transx_train_steps_run and transr_train_steps_run: for s in [0, n_steps), draw step
 // first_step + s's batch into pos / neg, then run step(s) on it; stops at the first nonzero code.
 template <class Step>
-int draw_then_step(const int32_t* triples, int64_t T, int64_t B, const int64_t* bh_key, const int32_t* bh_ent,
-                   const int64_t* bt_key, const int32_t* bt_ent, int64_t n_known, const uint32_t* tail_threshold,
-                   int32_t n_rel, int32_t n_ent, uint64_t seed, uint64_t first_step, int64_t n_steps, int32_t* pos,
+int draw_then_step(const SamplerArgs& sa, int64_t B, uint64_t seed, uint64_t first_step, int64_t n_steps, int32_t* pos,
                    int32_t* neg, hipStream_t st, Step step) {
   for (int64_t s = 0; s < n_steps; ++s) {
-    int rc = transx_draw_launch(triples, T, B, bh_key, bh_ent, bt_key, bt_ent, n_known, tail_threshold, n_rel, n_ent,
-                                seed, first_step + (uint64_t)s, pos, neg, st);
+    int rc = transx_draw_launch(sa, B, seed, first_step + (uint64_t)s, pos, neg, st);
     if (rc || (rc = step(s))) return rc;
   }
   return 0;
 }
 int transx_train_steps_run(int model, int l1, float* ent, int64_t E, float* rel, int64_t R, float* normal,
-                           float* ent_transfer, float* rel_transfer, int32_t d, const int32_t* triples, int64_t T,
-                           const int64_t* bh_key, const int32_t* bh_ent, const int64_t* bt_key, const int32_t* bt_ent,
-                           int64_t n_known, const uint32_t* tail_threshold, uint64_t seed, uint64_t first_step,
-                           int64_t n_steps, int64_t B, float margin, float lr, float* losses, void* workspace,
-                           size_t workspace_bytes, hipStream_t st);
+                           float* ent_transfer, float* rel_transfer, int32_t d, const SamplerArgs& sa, uint64_t seed,
+                           uint64_t first_step, int64_t n_steps, int64_t B, float margin, float lr, float* losses,
+                           void* workspace, size_t workspace_bytes, hipStream_t st);
 
 // ge_transr.hip: TransR scoring, Adam steps and native loop
 int transr_max_dim();
 size_t transr_ws_bytes(int64_t E, int64_t R, int32_t dE, int32_t dR, int64_t B);
-int transr_score_launch(int l1, const float* ent, int64_t E, const float* rel, const float* rel_matrix, int64_t R,
-                        int32_t dE, int32_t dR, const int32_t* tri, int64_t B, float* out, hipStream_t st);
+int transr_score_launch(const TransModel& m, const int32_t* tri, int64_t B, float* out, hipStream_t st);
 int transr_adam_step_run(int l1, float* ent, int64_t E, float* rel, float* rel_matrix, int64_t R, int32_t dE,
                          int32_t dR, float* m, float* v, const int32_t* pos, const int32_t* neg, int64_t B,
                          float margin, float lr, float b1, float b2, float eps, int64_t t, float* loss,
                          void* workspace, size_t workspace_bytes, hipStream_t st);
 int transr_train_steps_run(int l1, float* ent, int64_t E, float* rel, float* rel_matrix, int64_t R, int32_t dE,
-                           int32_t dR, float* m, float* v, const int32_t* triples, int64_t T, const int64_t* bh_key,
-                           const int32_t* bh_ent, const int64_t* bt_key, const int32_t* bt_ent, int64_t n_known,
-                           const uint32_t* tail_threshold, uint64_t seed, uint64_t first_step, int64_t n_steps,
-                           int64_t B, float margin, float lr, float b1, float b2, float eps, int64_t first_t,
-                           float* losses, void* workspace, size_t workspace_bytes, hipStream_t st);
+                           int32_t dR, float* m, float* v, const SamplerArgs& sa, uint64_t seed, uint64_t first_step,
+                           int64_t n_steps, int64_t B, float margin, float lr, float b1, float b2, float eps,
+                           int64_t first_t, float* losses, void* workspace, size_t workspace_bytes, hipStream_t st);
 
-// ge_transx_rank.hip: link-prediction ranks of TransE / TransH / TransD / TransR over every entity
-bool rank_vec4(const float* ent, int32_t d_ent, int32_t d_q);
-size_t transx_rank_ws_bytes(int model, int64_t E, int64_t R, int32_t d, int64_t B);
-size_t transr_rank_ws_bytes(int64_t E, int64_t R, int32_t dR, int64_t B);
-int transx_rank_launch(int model, int l1, const float* ent, int64_t E, const float* rel, int64_t R, const float* normal,
-                       const float* ent_transfer, const float* rel_transfer, int32_t d, const int32_t* tri, int64_t B,
-                       int cand_is_head, const int32_t* known_off, const uint16_t* known_rc, int32_t* n_before,
-                       int32_t* n_known_before, float* true_dist, float* scores_out, void* workspace,
-                       size_t workspace_bytes, hipStream_t st);
-int transr_rank_launch(int l1, const float* ent, int64_t E, const float* rel, const float* rel_matrix, int64_t R,
-                       int32_t dE, int32_t dR, const int32_t* tri, int64_t B, int cand_is_head, const int32_t* known_off,
-                       const uint16_t* known_rc, int32_t* n_before, int32_t* n_known_before, float* true_dist,
-                       float* scores_out, void* workspace, size_t workspace_bytes, hipStream_t st);
+// The outputs of a rank sweep (entities or relations); known_off / known_rc: ge_known_cells' lists, or both null.
+struct RankOut {
+  const int32_t* known_off; const uint16_t* known_rc; int32_t* n_before; int32_t* n_known_before; float* true_dist;
+  float* scores_out;
+};
+
+// ge_transx_rank.hip: link-prediction ranks of TransE / TransH / TransD / TransR over every entity.  The size
+// functions read m's shape alone.
+size_t trans_rank_ws_bytes(const TransModel& m, int64_t B);
+int trans_rank_launch(const TransModel& m, const int32_t* tri, int64_t B, int cand_is_head, const RankOut& o,
+                      void* workspace, size_t workspace_bytes, hipStream_t st);
 // top-k prediction of the same models on the rank sweep's distances: k <= transx_topk_max_k()
 int transx_topk_max_k();
-size_t transx_topk_ws_bytes(int model, int64_t E, int64_t R, int32_t d, int64_t B, int32_t k);
-size_t transr_topk_ws_bytes(int64_t E, int64_t R, int32_t dR, int64_t B, int32_t k);
-int transx_topk_launch(int model, int l1, const float* ent, int64_t E, const float* rel, int64_t R, const float* normal,
-                       const float* ent_transfer, const float* rel_transfer, int32_t d, const int32_t* queries,
-                       int64_t B, int cand_is_head, const int32_t* known_off, const uint16_t* known_rc, int32_t k,
-                       int32_t* out_id, float* out_dist, void* workspace, size_t workspace_bytes, hipStream_t st);
-int transr_topk_launch(int l1, const float* ent, int64_t E, const float* rel, const float* rel_matrix, int64_t R,
-                       int32_t dE, int32_t dR, const int32_t* queries, int64_t B, int cand_is_head,
-                       const int32_t* known_off, const uint16_t* known_rc, int32_t k, int32_t* out_id, float* out_dist,
-                       void* workspace, size_t workspace_bytes, hipStream_t st);
+size_t trans_topk_ws_bytes(const TransModel& m, int64_t B, int32_t k);
+int trans_topk_launch(const TransModel& m, const int32_t* queries, int64_t B, int cand_is_head,
+                      const int32_t* known_off, const uint16_t* known_rc, int32_t k, int32_t* out_id, float* out_dist,
+                      void* workspace, size_t workspace_bytes, hipStream_t st);
 
 // ge_transx_relrank.hip: relation prediction (h, ?, t) of TransE / TransH / TransD / TransR over every relation
-size_t transx_relrank_ws_bytes(int model, int64_t R, int32_t d, int64_t B);
-size_t transr_relrank_ws_bytes(int64_t R, int32_t dE, int64_t B);
-int transx_relrank_launch(int model, int l1, const float* ent, int64_t E, const float* rel, int64_t R,
-                          const float* normal, const float* ent_transfer, const float* rel_transfer, int32_t d,
-                          const int32_t* tri, int64_t B, const int32_t* known_off, const uint16_t* known_rc,
-                          int32_t* n_before, int32_t* n_known_before, float* true_dist, float* scores_out,
-                          void* workspace, size_t workspace_bytes, hipStream_t st);
-int transr_relrank_launch(int l1, const float* ent, int64_t E, const float* rel, const float* rel_matrix, int64_t R,
-                          int32_t dE, int32_t dR, const int32_t* tri, int64_t B, const int32_t* known_off,
-                          const uint16_t* known_rc, int32_t* n_before, int32_t* n_known_before, float* true_dist,
-                          float* scores_out, void* workspace, size_t workspace_bytes, hipStream_t st);
+size_t trans_relrank_ws_bytes(const TransModel& m, int64_t B);
+int trans_relrank_launch(const TransModel& m, const int32_t* tri, int64_t B, const RankOut& o, void* workspace,
+                         size_t workspace_bytes, hipStream_t st);
 
 // ge_classify.hip: triple classification -- per-segment thresholds fitted from sorted labelled scores, the decision
 size_t threshold_fit_ws_bytes(int64_t M, int32_t n_seg);

@@ -88,15 +88,13 @@ __global__ __launch_bounds__(kBlock) void bernoulli_corrupt_kernel(
   }
 }
 
-int bernoulli_corrupt_launch(const int32_t* pos, int64_t B, const int64_t* bh_key, const int32_t* bh_ent,
-                             const int64_t* bt_key, const int32_t* bt_ent, int64_t n_known,
-                             const uint32_t* tail_threshold, int32_t n_rel, int32_t ent_lo, int32_t n_ent,
-                             uint64_t seed, uint64_t step, int32_t* neg, hipStream_t st) {
-  if (n_known < 0 || n_rel <= 0 || n_ent <= 0) return GE_EINVAL;
+int bernoulli_corrupt_launch(const int32_t* pos, int64_t B, const SamplerArgs& s, int32_t ent_lo, uint64_t seed,
+                             uint64_t step, int32_t* neg, hipStream_t st) {
+  if (s.n_known < 0 || s.n_rel <= 0 || s.n_ent <= 0) return GE_EINVAL;
   if (B == 0) return 0;
   const int grid = grid_for(B, kBlock);
-  hipLaunchKernelGGL(bernoulli_corrupt_kernel, dim3(grid), dim3(kBlock), 0, st, pos, B, bh_key, bh_ent, bt_key,
-                     bt_ent, n_known, tail_threshold, n_rel, ent_lo, n_ent, seed, step, neg);
+  hipLaunchKernelGGL(bernoulli_corrupt_kernel, dim3(grid), dim3(kBlock), 0, st, pos, B, s.bh_key, s.bh_ent, s.bt_key,
+                     s.bt_ent, s.n_known, s.tail_threshold, s.n_rel, ent_lo, s.n_ent, seed, step, neg);
   return launch_status();
 }
 

@@ -415,12 +415,11 @@ size_t transr_ws_bytes(int64_t E, int64_t R, int32_t dE, int32_t dR, int64_t B) 
 
 int transr_max_dim() { return kTrMaxDim; }
 
-int transr_score_launch(int l1, const float* ent, int64_t E, const float* rel, const float* rel_matrix, int64_t R,
-                        int32_t dE, int32_t dR, const int32_t* tri, int64_t B, float* out, hipStream_t st) {
+int transr_score_launch(const TransModel& m, const int32_t* tri, int64_t B, float* out, hipStream_t st) {
   if (B == 0) return 0;
   const int grid = grid_for(B, kBlock / kWave);
-  if (l1) hipLaunchKernelGGL(transr_score_kernel<true>, dim3(grid), dim3(kBlock), 0, st, ent, rel, rel_matrix, E, R, (int)dE, (int)dR, tri, B, out);
-  else hipLaunchKernelGGL(transr_score_kernel<false>, dim3(grid), dim3(kBlock), 0, st, ent, rel, rel_matrix, E, R, (int)dE, (int)dR, tri, B, out);
+  if (m.l1) hipLaunchKernelGGL(transr_score_kernel<true>, dim3(grid), dim3(kBlock), 0, st, m.ent, m.rel, m.rel_matrix, m.E, m.R, m.dE, m.dq, tri, B, out);
+  else hipLaunchKernelGGL(transr_score_kernel<false>, dim3(grid), dim3(kBlock), 0, st, m.ent, m.rel, m.rel_matrix, m.E, m.R, m.dE, m.dq, tri, B, out);
   return launch_status();
 }
 
@@ -504,17 +503,14 @@ int transr_adam_step_run(int l1, float* ent, int64_t E, float* rel, float* rel_m
 }
 
 int transr_train_steps_run(int l1, float* ent, int64_t E, float* rel, float* rel_matrix, int64_t R, int32_t dE,
-                           int32_t dR, float* m, float* v, const int32_t* triples, int64_t T, const int64_t* bh_key,
-                           const int32_t* bh_ent, const int64_t* bt_key, const int32_t* bt_ent, int64_t n_known,
-                           const uint32_t* tail_threshold, uint64_t seed, uint64_t first_step, int64_t n_steps,
-                           int64_t B, float margin, float lr, float b1, float b2, float eps, int64_t first_t,
-                           float* losses, void* workspace, size_t workspace_bytes, hipStream_t st) {
+                           int32_t dR, float* m, float* v, const SamplerArgs& sa, uint64_t seed, uint64_t first_step,
+                           int64_t n_steps, int64_t B, float margin, float lr, float b1, float b2, float eps,
+                           int64_t first_t, float* losses, void* workspace, size_t workspace_bytes, hipStream_t st) {
   TrWs w;
   int rc = tr_ws_layout(E, R, dE, dR, B, workspace, w);
   if (rc) return rc;
   if (workspace_bytes < w.total) return GE_ENOMEM;
-  return draw_then_step(triples, T, B, bh_key, bh_ent, bt_key, bt_ent, n_known, tail_threshold, (int32_t)R, (int32_t)E,
-                        seed, first_step, n_steps, w.pos, w.neg, st, [&](int64_t s) {
+  return draw_then_step(sa, B, seed, first_step, n_steps, w.pos, w.neg, st, [&](int64_t s) {
     return tr_step_core(l1, ent, E, rel, rel_matrix, R, dE, dR, m, v, w.pos, w.neg, B, margin, lr, b1, b2, eps,
                         first_t + s, losses + s, w, st);
   });

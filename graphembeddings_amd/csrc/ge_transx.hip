@@ -31,7 +31,6 @@
 
 namespace ge {
 
-constexpr int kTransE = GE_TRANSX_TRANSE, kTransH = GE_TRANSX_TRANSH, kTransD = GE_TRANSX_TRANSD;
 constexpr int kTxMaxDim = 1024;
 constexpr int kWin = 32;                  // sorted slots per wave in the apply's first pass
 constexpr float kNormEps = 1e-12f;        // tf.nn.l2_normalize epsilon
@@ -502,17 +501,16 @@ static void extra_tables(int model, const float* normal, const float* ent_transf
   rel2 = model == kTransH ? normal : model == kTransD ? rel_transfer : nullptr;
 }
 
-int transx_score_launch(int model, int l1, const float* ent, int64_t E, const float* rel, int64_t R,
-                        const float* normal, const float* ent_transfer, const float* rel_transfer, int32_t d,
-                        const int32_t* tri, int64_t B, float* out, hipStream_t st) {
+int transx_score_launch(const TransModel& m, const int32_t* tri, int64_t B, float* out, hipStream_t st) {
   if (B == 0) return 0;
   const float *ent2, *rel2;
-  extra_tables(model, normal, ent_transfer, rel_transfer, ent2, rel2);
-  const bool v4 = d % 4 == 0 && aligned16({ent, rel, ent2, rel2});
+  extra_tables(m.model, m.normal, m.ent_transfer, m.rel_transfer, ent2, rel2);
+  const int d = m.dE;
+  const bool v4 = d % 4 == 0 && aligned16({m.ent, m.rel, ent2, rel2});
   const int nvec = v4 ? d / 4 : d, lpt = lpt_for(nvec);
   const int grid = grid_for((B + kWave / lpt - 1) / (kWave / lpt), kBlock / kWave);
-  if (v4) dispatch_mn<true, 4>(model, l1, lpt, grid, st, ent, rel, ent2, rel2, E, R, (int)d, tri, B, out);
-  else dispatch_mn<true, 1>(model, l1, lpt, grid, st, ent, rel, ent2, rel2, E, R, (int)d, tri, B, out);
+  if (v4) dispatch_mn<true, 4>(m.model, m.l1, lpt, grid, st, m.ent, m.rel, ent2, rel2, m.E, m.R, d, tri, B, out);
+  else dispatch_mn<true, 1>(m.model, m.l1, lpt, grid, st, m.ent, m.rel, ent2, rel2, m.E, m.R, d, tri, B, out);
   return launch_status();
 }
 
@@ -559,30 +557,25 @@ int transx_hinge_step_run(int model, int l1, float* ent, int64_t E, float* rel, 
   return step_core(model, l1, ent, E, rel, R, (float*)e2, (float*)r2, d, pos, neg, B, margin, lr, loss, w, st);
 }
 
-int transx_draw_launch(const int32_t* triples, int64_t T, int64_t B, const int64_t* bh_key, const int32_t* bh_ent,
-                       const int64_t* bt_key, const int32_t* bt_ent, int64_t n_known, const uint32_t* tail_threshold,
-                       int32_t n_rel, int32_t n_ent, uint64_t seed, uint64_t step, int32_t* pos, int32_t* neg,
+int transx_draw_launch(const SamplerArgs& s, int64_t B, uint64_t seed, uint64_t step, int32_t* pos, int32_t* neg,
                        hipStream_t st) {
   if (B == 0) return 0;
-  hipLaunchKernelGGL(transx_draw_kernel, dim3(grid_for(B, kBlock)), dim3(kBlock), 0, st, triples, T, B, bh_key, bh_ent,
-                     bt_key, bt_ent, n_known, tail_threshold, n_rel, n_ent, seed, step, pos, neg);
+  hipLaunchKernelGGL(transx_draw_kernel, dim3(grid_for(B, kBlock)), dim3(kBlock), 0, st, s.triples, s.T, B, s.bh_key,
+                     s.bh_ent, s.bt_key, s.bt_ent, s.n_known, s.tail_threshold, s.n_rel, s.n_ent, seed, step, pos, neg);
   return launch_status();
 }
 
 int transx_train_steps_run(int model, int l1, float* ent, int64_t E, float* rel, int64_t R, float* normal,
-                           float* ent_transfer, float* rel_transfer, int32_t d, const int32_t* triples, int64_t T,
-                           const int64_t* bh_key, const int32_t* bh_ent, const int64_t* bt_key, const int32_t* bt_ent,
-                           int64_t n_known, const uint32_t* tail_threshold, uint64_t seed, uint64_t first_step,
-                           int64_t n_steps, int64_t B, float margin, float lr, float* losses, void* workspace,
-                           size_t workspace_bytes, hipStream_t st) {
+                           float* ent_transfer, float* rel_transfer, int32_t d, const SamplerArgs& sa, uint64_t seed,
+                           uint64_t first_step, int64_t n_steps, int64_t B, float margin, float lr, float* losses,
+                           void* workspace, size_t workspace_bytes, hipStream_t st) {
   TxWs w;
   int rc = ws_layout(E, R, d, B, workspace, w);
   if (rc) return rc;
   if (workspace_bytes < w.total) return GE_ENOMEM;
   const float *e2, *r2;
   extra_tables(model, normal, ent_transfer, rel_transfer, e2, r2);
-  return draw_then_step(triples, T, B, bh_key, bh_ent, bt_key, bt_ent, n_known, tail_threshold, (int32_t)R, (int32_t)E,
-                        seed, first_step, n_steps, w.pos, w.neg, st, [&](int64_t s) {
+  return draw_then_step(sa, B, seed, first_step, n_steps, w.pos, w.neg, st, [&](int64_t s) {
     return step_core(model, l1, ent, E, rel, R, (float*)e2, (float*)r2, d, w.pos, w.neg, B, margin, lr, losses + s, w, st);
   });
 }

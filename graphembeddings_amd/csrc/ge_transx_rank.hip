@@ -27,40 +27,18 @@
 #include "ge_common.h"
 #include "ge_launch.h"
 #include "ge_topk_dev.h"
+#include "ge_trans_dev.h"
 
 #include <algorithm>
 
 namespace ge {
 namespace {
 
-constexpr int kTransE = GE_TRANSX_TRANSE, kTransH = GE_TRANSX_TRANSH, kTransD = GE_TRANSX_TRANSD;
-constexpr int kTransR = 3;               // this file's own code for TransR (not an ABI value)
 constexpr int kRows = 16;                // rows per sweep workgroup
-constexpr int kTile = 128;               // ge_known_cells' tile edge
-constexpr float kNormEps = 1e-12f;
-
-// the tables of one call
-struct RankTables {
-  const float* ent;     // [E, dE]
-  const float* rel;     // [R, dq]
-  const float* aux;     // TransH: n^ [R, d] (workspace);  TransD: rel_transfer [R, d];  TransR: rel_matrix [R, dq*dE]
-  const float* ent2;    // TransD: ent_transfer [E, d]
-  const float* A;       // TransD: A_c = e_c . e_p,c [E] (workspace)
-  int64_t E, R;
-  int dE, dq;           // entity width; width of q and of the distance (d for TransX, dim_r for TransR)
-};
-
-__device__ __forceinline__ float dist_acc(bool l1, float acc, float u) { return l1 ? acc + fabsf(u) : fmaf(u, u, acc); }
-
-__device__ __forceinline__ float dot_seq(const float* __restrict__ a, const float* __restrict__ b, int n) {
-  float s = 0.f;
-  for (int k = 0; k < n; ++k) s = fmaf(a[k], b[k], s);
-  return s;
-}
 
 // The projection scalar of entity e under relation r: TransH a = e . n^_r, TransD A_e, else 0.
 template <int MODEL>
-__device__ __forceinline__ float proj_scalar(const RankTables& T, int64_t e, int64_t r) {
+__device__ __forceinline__ float proj_scalar(const TransTables& T, int64_t e, int64_t r) {
   if constexpr (MODEL == kTransH) return dot_seq(T.ent + e * T.dE, T.aux + r * T.dq, T.dq);
   else if constexpr (MODEL == kTransD) return T.A[e];
   else return 0.f;
@@ -68,7 +46,7 @@ __device__ __forceinline__ float proj_scalar(const RankTables& T, int64_t e, int
 
 // Component k of entity e's projection under relation r (a: proj_scalar(e, r)).
 template <int MODEL>
-__device__ __forceinline__ float proj_elem(const RankTables& T, int64_t e, int64_t r, float a, int k) {
+__device__ __forceinline__ float proj_elem(const TransTables& T, int64_t e, int64_t r, float a, int k) {
   const float x = MODEL == kTransR ? 0.f : T.ent[e * T.dE + k];
   if constexpr (MODEL == kTransH) return fmaf(-a, T.aux[r * T.dq + k], x);
   else if constexpr (MODEL == kTransD) return fmaf(a, T.aux[r * T.dq + k], x);
@@ -83,34 +61,16 @@ __device__ __forceinline__ float proj_elem(const RankTables& T, int64_t e, int64
 
 // D of candidate c for the row whose query is q (relation r): the sweep's sequence, one lane.
 template <int MODEL, bool L1>
-__device__ __forceinline__ float dist_one(const RankTables& T, const float* __restrict__ q, int64_t c, int64_t r) {
+__device__ __forceinline__ float dist_one(const TransTables& T, const float* __restrict__ q, int64_t c, int64_t r) {
   const float a = proj_scalar<MODEL>(T, c, r);
   float acc = 0.f;
   for (int k = 0; k < T.dq; ++k) acc = dist_acc(L1, acc, q[k] - proj_elem<MODEL>(T, c, r, a, k));
   return acc;
 }
 
-// TransH: n^_r = n_r * rsqrt(max(n_r . n_r, 1e-12)), one thread per relation.
-__global__ __launch_bounds__(kBlock) void rank_nhat_kernel(const float* __restrict__ normal, int64_t R, int d,
-                                                           float* __restrict__ nhat) {
-  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= R) return;
-  const float* n = normal + r * d;
-  const float inv = rsqrtf(fmaxf(dot_seq(n, n, d), kNormEps));
-  for (int k = 0; k < d; ++k) nhat[r * d + k] = n[k] * inv;
-}
-
-// TransD: A_c = e_c . e_p,c, one thread per entity.
-__global__ __launch_bounds__(kBlock) void rank_transfer_dot_kernel(const float* __restrict__ ent,
-                                                                   const float* __restrict__ ent2, int64_t E, int d,
-                                                                   float* __restrict__ A) {
-  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e < E) A[e] = dot_seq(ent + e * d, ent2 + e * d, d);
-}
-
 // One thread per row: q, the sanitised relation and target, D_true, and the counters' initial values.
 template <int MODEL, bool L1>
-__global__ __launch_bounds__(kBlock) void rank_row_kernel(RankTables T, const int32_t* __restrict__ tri, int64_t B,
+__global__ __launch_bounds__(kBlock) void rank_row_kernel(TransTables T, const int32_t* __restrict__ tri, int64_t B,
                                                           int head, float* __restrict__ q, int32_t* __restrict__ rel_of,
                                                           int32_t* __restrict__ tid, float* __restrict__ true_dist,
                                                           int32_t* __restrict__ n_before, int32_t* __restrict__ n_known) {
@@ -191,7 +151,7 @@ __global__ __launch_bounds__(kBlock) void rank_row_kernel(RankTables T, const in
 
 // The rank sweep.  blockIdx.x: rows [x * kRows, +kRows); candidate blocks of 256 strided by gridDim.y.
 template <int MODEL, bool L1, int VEC>
-__global__ __launch_bounds__(kBlock) void rank_sweep_kernel(RankTables T, const float* __restrict__ q,
+__global__ __launch_bounds__(kBlock) void rank_sweep_kernel(TransTables T, const float* __restrict__ q,
                                                             const int32_t* __restrict__ rel_of,
                                                             const int32_t* __restrict__ tid,
                                                             const float* __restrict__ true_dist, int64_t B,
@@ -239,7 +199,7 @@ __global__ __launch_bounds__(kBlock) void rank_sweep_kernel(RankTables T, const 
 
 // One thread per known cell (grid-stride over known_off[n_tiles] entries; the cell's tile by binary search).
 template <int MODEL, bool L1>
-__global__ __launch_bounds__(kBlock) void rank_filter_kernel(RankTables T, const float* __restrict__ q,
+__global__ __launch_bounds__(kBlock) void rank_filter_kernel(TransTables T, const float* __restrict__ q,
                                                              const int32_t* __restrict__ rel_of,
                                                              const int32_t* __restrict__ tid,
                                                              const float* __restrict__ true_dist, int64_t B,
@@ -279,7 +239,7 @@ struct TopkWs {
 
 // One thread per query row: q (as rank_row_kernel forms it), the sanitised relation and the row's flag.
 template <int MODEL>
-__global__ __launch_bounds__(kBlock) void topk_row_kernel(RankTables T, const int32_t* __restrict__ qr, int64_t B,
+__global__ __launch_bounds__(kBlock) void topk_row_kernel(TransTables T, const int32_t* __restrict__ qr, int64_t B,
                                                           int head, float* __restrict__ q, int32_t* __restrict__ rel_of,
                                                           int32_t* __restrict__ bad) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -303,7 +263,7 @@ __global__ __launch_bounds__(kBlock) void topk_row_kernel(RankTables T, const in
 // pools past kp keys are cut back to k (one wave per row).  Known cells: a bitmap of the block's rows x candidates,
 // built from ge_known_cells' lists of the (at most two) 128 x 128 tiles the block covers.
 template <int MODEL, bool L1, int VEC>
-__global__ __launch_bounds__(kBlock) void topk_sweep_kernel(RankTables T, const float* __restrict__ q,
+__global__ __launch_bounds__(kBlock) void topk_sweep_kernel(TransTables T, const float* __restrict__ q,
                                                             const int32_t* __restrict__ rel_of, int64_t B,
                                                             const int32_t* __restrict__ known_off,
                                                             const uint16_t* __restrict__ known_rc, TopkWs W) {
@@ -439,52 +399,51 @@ __global__ __launch_bounds__(kBlock) void topk_merge_kernel(const u64* __restric
   else topk_emit<kTopkLanes>(pool, n, k, lane, nullptr, nullptr, out + wv * k);
 }
 
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+// float4 entity loads: both widths multiples of 4 and ent 16-byte aligned
+bool rank_vec4(const float* ent, int32_t d_ent, int32_t d_q) {
+  return d_ent % 4 == 0 && d_q % 4 == 0 && ((uintptr_t)ent & 15) == 0;
+}
 
-// workspace: q [B, dq] | rel_of [B] | tid [B] | n^ [R, d] (TransH) or A [E] (TransD)
-size_t ws_bytes(int model, int64_t E, int64_t R, int dq, int64_t B) {
-  size_t n = align256(sizeof(float) * (size_t)B * dq) + 2 * align256(sizeof(int32_t) * (size_t)B);
-  if (model == kTransH) n += align256(sizeof(float) * (size_t)R * dq);
-  if (model == kTransD) n += align256(sizeof(float) * (size_t)E);
-  return n;
+// What the rank and the top-k workspaces begin with: q [B, dq] | rel_of [B] | one int32 per row (rank: the target id;
+// top-k: the row's flag) | n^ [R, d] (TransH) or A [E] (TransD).  Offsets; end: the first byte after.
+struct SweepPrefix {
+  size_t q, rel_of, row, aux, end;
+};
+
+SweepPrefix sweep_prefix(const TransModel& m, int64_t B) {
+  SweepPrefix P;
+  P.q = 0;
+  P.rel_of = P.q + align_up(sizeof(float) * (size_t)B * m.dq, 256);
+  P.row = P.rel_of + align_up(sizeof(int32_t) * (size_t)B, 256);
+  P.aux = P.row + align_up(sizeof(int32_t) * (size_t)B, 256);
+  P.end = P.aux + trans_aux_bytes(m, true);
+  return P;
 }
 
 template <int MODEL, bool L1>
-int run(RankTables T, const float* normal, const int32_t* tri, int64_t B, int head, const int32_t* known_off,
-        const uint16_t* known_rc, int32_t* n_before, int32_t* n_known, float* true_dist, float* scores, void* ws,
-        hipStream_t st) {
+int run(const TransModel& m, const int32_t* tri, int64_t B, int head, const RankOut& o, void* ws, hipStream_t st) {
+  const SweepPrefix P = sweep_prefix(m, B);
   char* p = (char*)ws;
-  float* q = (float*)p;  p += align256(sizeof(float) * (size_t)B * T.dq);
-  int32_t* rel_of = (int32_t*)p;  p += align256(sizeof(int32_t) * (size_t)B);
-  int32_t* tid = (int32_t*)p;  p += align256(sizeof(int32_t) * (size_t)B);
-  if constexpr (MODEL == kTransH) {
-    float* nhat = (float*)p;
-    hipLaunchKernelGGL(rank_nhat_kernel, dim3((unsigned)((T.R + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, normal,
-                       T.R, T.dq, nhat);
-    T.aux = nhat;
-  }
-  if constexpr (MODEL == kTransD) {
-    float* A = (float*)p;
-    hipLaunchKernelGGL(rank_transfer_dot_kernel, dim3((unsigned)((T.E + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
-                       T.ent, T.ent2, T.E, T.dE, A);
-    T.A = A;
-  }
+  float* q = (float*)(p + P.q);
+  int32_t* rel_of = (int32_t*)(p + P.rel_of);
+  int32_t* tid = (int32_t*)(p + P.row);
+  const TransTables T = trans_prepare<true>(m, p + P.aux, st);
   hipLaunchKernelGGL((rank_row_kernel<MODEL, L1>), dim3((unsigned)((B + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, T,
-                     tri, B, head, q, rel_of, tid, true_dist, n_before, n_known);
+                     tri, B, head, q, rel_of, tid, o.true_dist, o.n_before, o.n_known_before);
   const int64_t n_chunks = (B + kRows - 1) / kRows, n_cb = (T.E + kBlock - 1) / kBlock;
   int64_t gy = (2 * kMaxBlocks + n_chunks - 1) / n_chunks;   // about two waves of resident workgroups
   gy = gy < 1 ? 1 : (gy > n_cb ? n_cb : gy);
   const dim3 grid((unsigned)n_chunks, (unsigned)gy);
   if (rank_vec4(T.ent, T.dE, T.dq))
-    hipLaunchKernelGGL((rank_sweep_kernel<MODEL, L1, 4>), grid, dim3(kBlock), 0, st, T, q, rel_of, tid, true_dist, B,
-                       n_before, scores);
+    hipLaunchKernelGGL((rank_sweep_kernel<MODEL, L1, 4>), grid, dim3(kBlock), 0, st, T, q, rel_of, tid, o.true_dist, B,
+                       o.n_before, o.scores_out);
   else
-    hipLaunchKernelGGL((rank_sweep_kernel<MODEL, L1, 1>), grid, dim3(kBlock), 0, st, T, q, rel_of, tid, true_dist, B,
-                       n_before, scores);
-  if (known_off && known_rc) {
+    hipLaunchKernelGGL((rank_sweep_kernel<MODEL, L1, 1>), grid, dim3(kBlock), 0, st, T, q, rel_of, tid, o.true_dist, B,
+                       o.n_before, o.scores_out);
+  if (o.known_off && o.known_rc) {
     const int64_t n_tiles = ((B + kTile - 1) / kTile) * ((T.E + kTile - 1) / kTile);
-    hipLaunchKernelGGL((rank_filter_kernel<MODEL, L1>), dim3(1024), dim3(kBlock), 0, st, T, q, rel_of, tid, true_dist,
-                       B, known_off, known_rc, n_tiles, n_known);
+    hipLaunchKernelGGL((rank_filter_kernel<MODEL, L1>), dim3(1024), dim3(kBlock), 0, st, T, q, rel_of, tid,
+                       o.true_dist, B, o.known_off, o.known_rc, n_tiles, o.n_known_before);
   }
   return launch_status();
 }
@@ -498,64 +457,50 @@ int64_t topk_ranges(int64_t B, int64_t E) {
   return ns < 1 ? 1 : (ns > n_cb ? n_cb : ns);
 }
 
-// workspace: q [B, dq] | rel_of [B] | bad [B] | n^ [R, d] (TransH) or A [E] (TransD) | pools [B][ns][cap] |
-// partial lists [B][ns][k] | the first merge round's lists [B][ceil(ns / kMergeFan)][k]
+// workspace: the sweeps' prefix (its row array: bad [B]) | pools [B][ns][cap] | partial lists [B][ns][k] | the first
+// merge round's lists [B][ceil(ns / kMergeFan)][k]
 struct TopkLayout {
-  size_t q, rel_of, bad, aux, pool, part, part2, total;
+  SweepPrefix P;
+  size_t pool, part, part2, total;
 };
 
-TopkLayout topk_layout(int model, int64_t E, int64_t R, int dq, int64_t B, int k) {
-  const int64_t ns = topk_ranges(B, E), cap = topk_kp(k) + kBlock;
+TopkLayout topk_layout(const TransModel& m, int64_t B, int k) {
+  const int64_t ns = topk_ranges(B, m.E), cap = topk_kp(k) + kBlock;
   TopkLayout L;
-  L.q = 0;
-  L.rel_of = L.q + align256(sizeof(float) * (size_t)B * dq);
-  L.bad = L.rel_of + align256(sizeof(int32_t) * (size_t)B);
-  L.aux = L.bad + align256(sizeof(int32_t) * (size_t)B);
-  L.pool = L.aux + (model == kTransH ? align256(sizeof(float) * (size_t)R * dq)
-                                     : model == kTransD ? align256(sizeof(float) * (size_t)E) : 0);
-  L.part = L.pool + align256(sizeof(u64) * (size_t)(B * ns * cap));
-  L.part2 = L.part + align256(sizeof(u64) * (size_t)(B * ns * k));
-  L.total = L.part2 + align256(sizeof(u64) * (size_t)(B * ((ns + kMergeFan - 1) / kMergeFan) * k));
+  L.P = sweep_prefix(m, B);
+  L.pool = L.P.end;
+  L.part = L.pool + align_up(sizeof(u64) * (size_t)(B * ns * cap), 256);
+  L.part2 = L.part + align_up(sizeof(u64) * (size_t)(B * ns * k), 256);
+  L.total = L.part2 + align_up(sizeof(u64) * (size_t)(B * ((ns + kMergeFan - 1) / kMergeFan) * k), 256);
   return L;
 }
 
 // the largest layout of any B' <= B (the ranges shrink as B grows), so that the size is monotone in B, E and k
-size_t topk_ws_bytes(int model, int64_t E, int64_t R, int dq, int64_t B, int32_t k) {
-  if (B <= 0 || E <= 0 || k < 1 || k > kTopkMaxK) return 0;
+size_t topk_ws_bytes(const TransModel& m, int64_t B, int32_t k) {
+  if (B <= 0 || m.E <= 0 || k < 1 || k > kTopkMaxK) return 0;
   const int64_t n_chunks = (B + kRows - 1) / kRows;
-  size_t need = topk_layout(model, E, R, dq, B, k).total;
+  size_t need = topk_layout(m, B, k).total;
   for (int64_t ch = 1; ch < n_chunks && ch <= kMaxBlocks; ++ch)
-    need = std::max(need, topk_layout(model, E, R, dq, ch * kRows, k).total);
+    need = std::max(need, topk_layout(m, ch * kRows, k).total);
   return need;
 }
 
 template <int MODEL, bool L1>
-int run_topk(RankTables T, const float* normal, const int32_t* qr, int64_t B, int head, const int32_t* known_off,
+int run_topk(const TransModel& m, const int32_t* qr, int64_t B, int head, const int32_t* known_off,
              const uint16_t* known_rc, int k, int32_t* out_id, float* out_dist, void* ws, hipStream_t st) {
-  const TopkLayout L = topk_layout(MODEL, T.E, T.R, T.dq, B, k);
+  const TopkLayout L = topk_layout(m, B, k);
   char* p = (char*)ws;
-  float* q = (float*)(p + L.q);
-  int32_t* rel_of = (int32_t*)(p + L.rel_of);
+  float* q = (float*)(p + L.P.q);
+  int32_t* rel_of = (int32_t*)(p + L.P.rel_of);
   TopkWs W;
   W.k = k;
   W.kp = topk_kp(k);
   W.cap = W.kp + kBlock;
-  W.bad = (int32_t*)(p + L.bad);
+  W.bad = (int32_t*)(p + L.P.row);
   W.pool = (u64*)(p + L.pool);
   W.part = (u64*)(p + L.part);
   u64* part2 = (u64*)(p + L.part2);
-  if constexpr (MODEL == kTransH) {
-    float* nhat = (float*)(p + L.aux);
-    hipLaunchKernelGGL(rank_nhat_kernel, dim3((unsigned)((T.R + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, normal,
-                       T.R, T.dq, nhat);
-    T.aux = nhat;
-  }
-  if constexpr (MODEL == kTransD) {
-    float* A = (float*)(p + L.aux);
-    hipLaunchKernelGGL(rank_transfer_dot_kernel, dim3((unsigned)((T.E + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
-                       T.ent, T.ent2, T.E, T.dE, A);
-    T.A = A;
-  }
+  const TransTables T = trans_prepare<true>(m, p + L.P.aux, st);
   hipLaunchKernelGGL((topk_row_kernel<MODEL>), dim3((unsigned)((B + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, T, qr,
                      B, head, q, rel_of, W.bad);
   const int64_t n_chunks = (B + kRows - 1) / kRows, ns = topk_ranges(B, T.E);
@@ -582,105 +527,30 @@ int run_topk(RankTables T, const float* normal, const int32_t* qr, int64_t B, in
   return launch_status();
 }
 
-template <int MODEL>
-int run_topk_l(int l1, RankTables T, const float* normal, const int32_t* qr, int64_t B, int head,
-               const int32_t* known_off, const uint16_t* known_rc, int k, int32_t* out_id, float* out_dist, void* ws,
-               hipStream_t st) {
-  return l1 ? run_topk<MODEL, true>(T, normal, qr, B, head, known_off, known_rc, k, out_id, out_dist, ws, st)
-            : run_topk<MODEL, false>(T, normal, qr, B, head, known_off, known_rc, k, out_id, out_dist, ws, st);
-}
-
-template <int MODEL>
-int run_l(int l1, RankTables T, const float* normal, const int32_t* tri, int64_t B, int head, const int32_t* known_off,
-          const uint16_t* known_rc, int32_t* n_before, int32_t* n_known, float* true_dist, float* scores, void* ws,
-          hipStream_t st) {
-  return l1 ? run<MODEL, true>(T, normal, tri, B, head, known_off, known_rc, n_before, n_known, true_dist, scores, ws, st)
-            : run<MODEL, false>(T, normal, tri, B, head, known_off, known_rc, n_before, n_known, true_dist, scores, ws, st);
-}
-
 }  // namespace
 
-bool rank_vec4(const float* ent, int32_t d_ent, int32_t d_q) {
-  return d_ent % 4 == 0 && d_q % 4 == 0 && ((uintptr_t)ent & 15) == 0;
-}
+size_t trans_rank_ws_bytes(const TransModel& m, int64_t B) { return sweep_prefix(m, B).end; }
 
-size_t transx_rank_ws_bytes(int model, int64_t E, int64_t R, int32_t d, int64_t B) { return ws_bytes(model, E, R, d, B); }
-
-size_t transr_rank_ws_bytes(int64_t E, int64_t R, int32_t dR, int64_t B) { return ws_bytes(kTransR, E, R, dR, B); }
-
-int transx_rank_launch(int model, int l1, const float* ent, int64_t E, const float* rel, int64_t R, const float* normal,
-                       const float* ent_transfer, const float* rel_transfer, int32_t d, const int32_t* tri, int64_t B,
-                       int cand_is_head, const int32_t* known_off, const uint16_t* known_rc, int32_t* n_before,
-                       int32_t* n_known_before, float* true_dist, float* scores_out, void* workspace,
-                       size_t workspace_bytes, hipStream_t st) {
-  if (workspace_bytes < ws_bytes(model, E, R, d, B)) return GE_ENOMEM;
-  RankTables T{ent, rel, nullptr, nullptr, nullptr, E, R, d, d};
-  const int head = cand_is_head ? 1 : 0;
-  switch (model) {
-    case kTransE:
-      return run_l<kTransE>(l1, T, nullptr, tri, B, head, known_off, known_rc, n_before, n_known_before, true_dist,
-                            scores_out, workspace, st);
-    case kTransH:
-      return run_l<kTransH>(l1, T, normal, tri, B, head, known_off, known_rc, n_before, n_known_before, true_dist,
-                            scores_out, workspace, st);
-    default:
-      T.aux = rel_transfer;
-      T.ent2 = ent_transfer;
-      return run_l<kTransD>(l1, T, nullptr, tri, B, head, known_off, known_rc, n_before, n_known_before, true_dist,
-                            scores_out, workspace, st);
-  }
-}
-
-int transr_rank_launch(int l1, const float* ent, int64_t E, const float* rel, const float* rel_matrix, int64_t R,
-                       int32_t dE, int32_t dR, const int32_t* tri, int64_t B, int cand_is_head, const int32_t* known_off,
-                       const uint16_t* known_rc, int32_t* n_before, int32_t* n_known_before, float* true_dist,
-                       float* scores_out, void* workspace, size_t workspace_bytes, hipStream_t st) {
-  if (workspace_bytes < ws_bytes(kTransR, E, R, dR, B)) return GE_ENOMEM;
-  RankTables T{ent, rel, rel_matrix, nullptr, nullptr, E, R, dE, dR};
-  return run_l<kTransR>(l1, T, nullptr, tri, B, cand_is_head ? 1 : 0, known_off, known_rc, n_before, n_known_before,
-                        true_dist, scores_out, workspace, st);
+int trans_rank_launch(const TransModel& m, const int32_t* tri, int64_t B, int cand_is_head, const RankOut& o,
+                      void* workspace, size_t workspace_bytes, hipStream_t st) {
+  if (workspace_bytes < trans_rank_ws_bytes(m, B)) return GE_ENOMEM;
+  return dispatch_trans(m, [&](auto model, auto l1) {
+    return run<decltype(model)::value, decltype(l1)::value>(m, tri, B, cand_is_head ? 1 : 0, o, workspace, st);
+  });
 }
 
 int transx_topk_max_k() { return kTopkMaxK; }
 
-size_t transx_topk_ws_bytes(int model, int64_t E, int64_t R, int32_t d, int64_t B, int32_t k) {
-  return topk_ws_bytes(model, E, R, d, B, k);
-}
+size_t trans_topk_ws_bytes(const TransModel& m, int64_t B, int32_t k) { return topk_ws_bytes(m, B, k); }
 
-size_t transr_topk_ws_bytes(int64_t E, int64_t R, int32_t dR, int64_t B, int32_t k) {
-  return topk_ws_bytes(kTransR, E, R, dR, B, k);
-}
-
-int transx_topk_launch(int model, int l1, const float* ent, int64_t E, const float* rel, int64_t R, const float* normal,
-                       const float* ent_transfer, const float* rel_transfer, int32_t d, const int32_t* queries,
-                       int64_t B, int cand_is_head, const int32_t* known_off, const uint16_t* known_rc, int32_t k,
-                       int32_t* out_id, float* out_dist, void* workspace, size_t workspace_bytes, hipStream_t st) {
-  if (workspace_bytes < topk_ws_bytes(model, E, R, d, B, k)) return GE_ENOMEM;
-  RankTables T{ent, rel, nullptr, nullptr, nullptr, E, R, d, d};
-  const int head = cand_is_head ? 1 : 0;
-  switch (model) {
-    case kTransE:
-      return run_topk_l<kTransE>(l1, T, nullptr, queries, B, head, known_off, known_rc, k, out_id, out_dist, workspace,
-                                 st);
-    case kTransH:
-      return run_topk_l<kTransH>(l1, T, normal, queries, B, head, known_off, known_rc, k, out_id, out_dist, workspace,
-                                 st);
-    default:
-      T.aux = rel_transfer;
-      T.ent2 = ent_transfer;
-      return run_topk_l<kTransD>(l1, T, nullptr, queries, B, head, known_off, known_rc, k, out_id, out_dist, workspace,
-                                 st);
-  }
-}
-
-int transr_topk_launch(int l1, const float* ent, int64_t E, const float* rel, const float* rel_matrix, int64_t R,
-                       int32_t dE, int32_t dR, const int32_t* queries, int64_t B, int cand_is_head,
-                       const int32_t* known_off, const uint16_t* known_rc, int32_t k, int32_t* out_id, float* out_dist,
-                       void* workspace, size_t workspace_bytes, hipStream_t st) {
-  if (workspace_bytes < topk_ws_bytes(kTransR, E, R, dR, B, k)) return GE_ENOMEM;
-  RankTables T{ent, rel, rel_matrix, nullptr, nullptr, E, R, dE, dR};
-  return run_topk_l<kTransR>(l1, T, nullptr, queries, B, cand_is_head ? 1 : 0, known_off, known_rc, k, out_id, out_dist,
-                             workspace, st);
+int trans_topk_launch(const TransModel& m, const int32_t* queries, int64_t B, int cand_is_head,
+                      const int32_t* known_off, const uint16_t* known_rc, int32_t k, int32_t* out_id, float* out_dist,
+                      void* workspace, size_t workspace_bytes, hipStream_t st) {
+  if (workspace_bytes < topk_ws_bytes(m, B, k)) return GE_ENOMEM;
+  return dispatch_trans(m, [&](auto model, auto l1) {
+    return run_topk<decltype(model)::value, decltype(l1)::value>(m, queries, B, cand_is_head ? 1 : 0, known_off,
+                                                                 known_rc, k, out_id, out_dist, workspace, st);
+  });
 }
 
 }  // namespace ge

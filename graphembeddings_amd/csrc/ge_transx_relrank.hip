@@ -25,35 +25,14 @@
 //   known   one thread per known cell of the chunk's row tiles: the same stored values, an integer atomic per hit
 #include "ge_common.h"
 #include "ge_launch.h"
+#include "ge_trans_dev.h"
 
 namespace ge {
 namespace {
 
-constexpr int kTransE = GE_TRANSX_TRANSE, kTransH = GE_TRANSX_TRANSH, kTransD = GE_TRANSX_TRANSD;
-constexpr int kTransR = 3;               // this file's own code for TransR (not an ABI value)
-constexpr int kTile = 128;               // ge_known_cells' tile edge
 constexpr int kPad = 4;                  // floats of padding per LDS panel row
-constexpr float kNormEps = 1e-12f;
 constexpr int64_t kChunkCells = (int64_t)1 << 22;   // stored distances per chunk, about
 constexpr int64_t kChunkMin = 1024, kChunkMax = 65536;
-
-__device__ __forceinline__ float dist_acc(bool l1, float acc, float u) { return l1 ? acc + fabsf(u) : fmaf(u, u, acc); }
-
-__device__ __forceinline__ float dot_seq(const float* __restrict__ a, const float* __restrict__ b, int n) {
-  float s = 0.f;
-  for (int k = 0; k < n; ++k) s = fmaf(a[k], b[k], s);
-  return s;
-}
-
-// TransH: n^_c = n_c * rsqrt(max(n_c . n_c, 1e-12)), one thread per relation.
-__global__ __launch_bounds__(kBlock) void relrank_nhat_kernel(const float* __restrict__ normal, int64_t R, int d,
-                                                              float* __restrict__ nhat) {
-  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= R) return;
-  const float* n = normal + r * d;
-  const float inv = rsqrtf(fmaxf(dot_seq(n, n, d), kNormEps));
-  for (int k = 0; k < d; ++k) nhat[r * d + k] = n[k] * inv;
-}
 
 // One thread per row of the chunk: w = e_h - e_t, TransD's s, the row's relation (-1: an id out of range; w = 0).
 template <int MODEL>
@@ -301,8 +280,6 @@ __global__ __launch_bounds__(kBlock) void relrank_known_kernel(const float* __re
   }
 }
 
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // rows per chunk: a power of two (a multiple of the known lists' tile edge), about kChunkCells stored distances
 int64_t chunk_rows(int64_t R) {
   int64_t c = kChunkMax;
@@ -310,37 +287,26 @@ int64_t chunk_rows(int64_t R) {
   return c;
 }
 
-// workspace: w [rows, dw] | s [rows] | rel_of [rows] | D [rows, R] | n^ [R, dw] (TransH); rows = min(B, chunk_rows(R))
+// workspace: w [rows, dE] | s [rows] | rel_of [rows] | D [rows, R] | n^ [R, d] (TransH); rows = min(B, chunk_rows(R))
 struct Layout {
   size_t w, s, rel_of, D, nhat, total;
   int64_t rows;
 };
 
-Layout layout(int model, int64_t R, int dw, int64_t B) {
+Layout layout(const TransModel& m, int64_t B) {
   Layout L;
-  L.rows = B < chunk_rows(R) ? B : chunk_rows(R);
+  L.rows = B < chunk_rows(m.R) ? B : chunk_rows(m.R);
   L.w = 0;
-  L.s = L.w + align256(sizeof(float) * (size_t)L.rows * dw);
-  L.rel_of = L.s + align256(sizeof(float) * (size_t)L.rows);
-  L.D = L.rel_of + align256(sizeof(int32_t) * (size_t)L.rows);
-  L.nhat = L.D + align256(sizeof(float) * (size_t)L.rows * (size_t)R);
-  L.total = L.nhat + (model == kTransH ? align256(sizeof(float) * (size_t)R * dw) : 0);
+  L.s = L.w + align_up(sizeof(float) * (size_t)L.rows * m.dE, 256);
+  L.rel_of = L.s + align_up(sizeof(float) * (size_t)L.rows, 256);
+  L.D = L.rel_of + align_up(sizeof(int32_t) * (size_t)L.rows, 256);
+  L.nhat = L.D + align_up(sizeof(float) * (size_t)L.rows * (size_t)m.R, 256);
+  L.total = L.nhat + trans_aux_bytes(m, false);
   return L;
 }
 
-// the tables of one call
-struct RelTables {
-  const float* ent;     // [E, dE]
-  const float* rel;     // [R, dq]
-  const float* aux;     // TransH: normal [R, d] (n^ in the workspace once run() has it);  TransD: rel_transfer [R, d];
-                        // TransR: rel_matrix [R, dq * dE]
-  const float* ent2;    // TransD: ent_transfer [E, d]
-  int64_t E, R;
-  int dE, dq;
-};
-
 template <int MODEL, bool L1, int VEC>
-void launch_dist(const RelTables& T, const float* w, const float* s, const int32_t* rel_of, int64_t n, float* D,
+void launch_dist(const TransTables& T, const float* w, const float* s, const int32_t* rel_of, int64_t n, float* D,
                  hipStream_t st) {
   if constexpr (MODEL == kTransR) {
     const dim3 grid((unsigned)T.R, (unsigned)((n + 63) / 64));
@@ -362,85 +328,45 @@ void launch_dist(const RelTables& T, const float* w, const float* s, const int32
 }
 
 template <int MODEL, bool L1>
-int run(RelTables T, const int32_t* tri, int64_t B, const int32_t* known_off, const uint16_t* known_rc,
-        int32_t* n_before, int32_t* n_known, float* true_dist, float* scores, void* ws, hipStream_t st) {
-  const Layout L = layout(MODEL, T.R, T.dE, B);
+int run(const TransModel& m, const int32_t* tri, int64_t B, const RankOut& o, void* ws, hipStream_t st) {
+  const Layout L = layout(m, B);
   char* p = (char*)ws;
   float* w = (float*)(p + L.w);
   float* s = (float*)(p + L.s);
   int32_t* rel_of = (int32_t*)(p + L.rel_of);
-  if constexpr (MODEL == kTransH) {
-    float* nhat = (float*)(p + L.nhat);
-    hipLaunchKernelGGL(relrank_nhat_kernel, dim3((unsigned)((T.R + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, T.aux,
-                       T.R, T.dq, nhat);
-    T.aux = nhat;
-  }
+  const TransTables T = trans_prepare<false>(m, p + L.nhat, st);
   // float4 staging: every staged table 16-byte aligned with a leading dimension % 4 == 0 (w and n^ lie in the workspace)
   const bool vec4 = T.dE % 4 == 0 && T.dq % 4 == 0 && aligned16({T.rel, T.aux});
   const int64_t n_ct = (T.R + kTile - 1) / kTile;
   for (int64_t r0 = 0; r0 < B; r0 += L.rows) {
     const int64_t n = B - r0 < L.rows ? B - r0 : L.rows;
-    float* D = scores ? scores + r0 * T.R : (float*)(p + L.D);
+    float* D = o.scores_out ? o.scores_out + r0 * T.R : (float*)(p + L.D);
     hipLaunchKernelGGL((relrank_row_kernel<MODEL>), dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
                        T.ent, T.ent2, T.E, T.R, T.dE, tri + 3 * r0, n, w, s, rel_of);
     if (vec4) launch_dist<MODEL, L1, 4>(T, w, s, rel_of, n, D, st);
     else launch_dist<MODEL, L1, 1>(T, w, s, rel_of, n, D, st);
     hipLaunchKernelGGL(relrank_count_kernel, dim3((unsigned)((n + 3) / 4)), dim3(kBlock), 0, st, D, rel_of, n, T.R,
-                       n_before + r0, n_known + r0, true_dist + r0);
-    if (known_off && known_rc) {
+                       o.n_before + r0, o.n_known_before + r0, o.true_dist + r0);
+    if (o.known_off && o.known_rc) {
       // (chunks are multiples of the tile edge: a chunk's row tiles are its own)
       const int64_t rt0 = r0 / kTile, rt1 = (r0 + n + kTile - 1) / kTile;
-      hipLaunchKernelGGL(relrank_known_kernel, dim3(512), dim3(kBlock), 0, st, D, rel_of, r0, n, T.R, known_off,
-                         known_rc, rt0 * n_ct, rt1 * n_ct, n_known + r0);
+      hipLaunchKernelGGL(relrank_known_kernel, dim3(512), dim3(kBlock), 0, st, D, rel_of, r0, n, T.R, o.known_off,
+                         o.known_rc, rt0 * n_ct, rt1 * n_ct, o.n_known_before + r0);
     }
   }
   return launch_status();
 }
 
-template <int MODEL>
-int run_l(int l1, const RelTables& T, const int32_t* tri, int64_t B, const int32_t* known_off, const uint16_t* known_rc,
-          int32_t* n_before, int32_t* n_known, float* true_dist, float* scores, void* ws, hipStream_t st) {
-  return l1 ? run<MODEL, true>(T, tri, B, known_off, known_rc, n_before, n_known, true_dist, scores, ws, st)
-            : run<MODEL, false>(T, tri, B, known_off, known_rc, n_before, n_known, true_dist, scores, ws, st);
-}
-
 }  // namespace
 
-size_t transx_relrank_ws_bytes(int model, int64_t R, int32_t d, int64_t B) { return layout(model, R, d, B).total; }
+size_t trans_relrank_ws_bytes(const TransModel& m, int64_t B) { return layout(m, B).total; }
 
-size_t transr_relrank_ws_bytes(int64_t R, int32_t dE, int64_t B) { return layout(kTransR, R, dE, B).total; }
-
-int transx_relrank_launch(int model, int l1, const float* ent, int64_t E, const float* rel, int64_t R,
-                          const float* normal, const float* ent_transfer, const float* rel_transfer, int32_t d,
-                          const int32_t* tri, int64_t B, const int32_t* known_off, const uint16_t* known_rc,
-                          int32_t* n_before, int32_t* n_known_before, float* true_dist, float* scores_out,
-                          void* workspace, size_t workspace_bytes, hipStream_t st) {
-  if (workspace_bytes < layout(model, R, d, B).total) return GE_ENOMEM;
-  RelTables T{ent, rel, nullptr, nullptr, E, R, d, d};
-  switch (model) {
-    case kTransE:
-      return run_l<kTransE>(l1, T, tri, B, known_off, known_rc, n_before, n_known_before, true_dist, scores_out,
-                            workspace, st);
-    case kTransH:
-      T.aux = normal;
-      return run_l<kTransH>(l1, T, tri, B, known_off, known_rc, n_before, n_known_before, true_dist, scores_out,
-                            workspace, st);
-    default:
-      T.aux = rel_transfer;
-      T.ent2 = ent_transfer;
-      return run_l<kTransD>(l1, T, tri, B, known_off, known_rc, n_before, n_known_before, true_dist, scores_out,
-                            workspace, st);
-  }
-}
-
-int transr_relrank_launch(int l1, const float* ent, int64_t E, const float* rel, const float* rel_matrix, int64_t R,
-                          int32_t dE, int32_t dR, const int32_t* tri, int64_t B, const int32_t* known_off,
-                          const uint16_t* known_rc, int32_t* n_before, int32_t* n_known_before, float* true_dist,
-                          float* scores_out, void* workspace, size_t workspace_bytes, hipStream_t st) {
-  if (workspace_bytes < layout(kTransR, R, dE, B).total) return GE_ENOMEM;
-  RelTables T{ent, rel, rel_matrix, nullptr, E, R, dE, dR};
-  return run_l<kTransR>(l1, T, tri, B, known_off, known_rc, n_before, n_known_before, true_dist, scores_out, workspace,
-                        st);
+int trans_relrank_launch(const TransModel& m, const int32_t* tri, int64_t B, const RankOut& o, void* workspace,
+                         size_t workspace_bytes, hipStream_t st) {
+  if (workspace_bytes < layout(m, B).total) return GE_ENOMEM;
+  return dispatch_trans(m, [&](auto model, auto l1) {
+    return run<decltype(model)::value, decltype(l1)::value>(m, tri, B, o, workspace, st);
+  });
 }
 
 }  // namespace ge
