@@ -13,10 +13,6 @@ extern "C" {
 
 int ge_version(void) { return GE_VERSION; }
 
-size_t ge_validation_workspace_bytes(int64_t B) {
-  return B <= 0 ? 0 : ((size_t)B * (3 + 3 + 1) * 4 + 16 + 255) / 256 * 256;
-}
-
 int ge_max_dim(void) { return complex_max_dim(); }
 
 int ge_complex_score(const float* table, int64_t N, int32_t d, const int32_t* triples, int64_t B,
@@ -81,70 +77,94 @@ int ge_hinge_loss(const float* table, int64_t N, int32_t d, const int32_t* pos, 
   return hole_hinge_loss_launch(table, N, d, pos, neg, B, margin, max_norm, loss, sig_out, (hipStream_t)stream);
 }
 
+// The type tables of a sampler, checked and ts filled.  check_ranges: mode, padded_size and n_types too.  The entry
+// points do NOT agree on that and are kept as they were (aligning them changes what callers see): the three loops
+// (ge_train_steps -- behind its workspace size, sampler_ranges_ok there --, ge_train_steps_logloss,
+// ge_train_prepare_steps) refuse a value out of range themselves; ge_corrupt_batch and the two validation ticks pass it
+// on to corrupt_batch_launch, which refuses it -- for a tick that is behind its workspace checks and its first launch.
+static int type_sampler(TypeSampler& ts, const int32_t* id_to_type, int64_t N, const int64_t* type_offsets, int32_t n_types,
+                        const int32_t* type_ids, uint64_t seed, int32_t padded_size, int32_t mode, bool check_ranges) {
+  ts = TypeSampler{id_to_type, N, type_offsets, n_types, type_ids, seed, padded_size, mode};
+  if (!id_to_type || !type_offsets || !type_ids) return GE_EINVAL;
+  return check_ranges && !sampler_ranges_ok(ts) ? GE_EINVAL : 0;
+}
+
+// validation tick workspace, K = 0 (hinge) or the negative ratio: (K > 0: sumsq 256 B) | pos [B,3] | neg [B,3] |
+// loss [(1+K)B] | flag
+struct TickWs { float* sumsq; int32_t* pos; int32_t* neg; float* loss; int32_t* flag; size_t bytes; };
+static TickWs tick_ws(void* base, int64_t B, int64_t K) {
+  const size_t lead = K > 0 ? 256 : 0, b = (size_t)B;
+  return TickWs{ws_at<float>(base, 0), ws_at<int32_t>(base, lead), ws_at<int32_t>(base, lead + 12 * b),
+                ws_at<float>(base, lead + 24 * b), ws_at<int32_t>(base, lead + 24 * b + 4 * (size_t)(1 + K) * b),
+                (b * (3 + 3 + 1 + (size_t)K) * 4 + 16 + 255) / 256 * 256 + lead};
+}
+size_t ge_validation_workspace_bytes(int64_t B) { return B <= 0 ? 0 : tick_ws(nullptr, B, 0).bytes; }
+size_t ge_validation_logloss_workspace_bytes(int64_t B, int32_t negative_ratio) {
+  return (B <= 0 || negative_ratio < 1) ? 0 : tick_ws(nullptr, B, negative_ratio).bytes;
+}
+// first half of both ticks, behind the entry point's own shape and table checks: the remaining pointers, the workspace
+// carved and its size tested, the batch drawn into w.pos
+static int tick_head(TickWs& w, const int32_t* valid, int64_t V, int64_t B, int64_t K, uint64_t seed, uint64_t counter,
+                     void* workspace, size_t workspace_bytes, const float* mean_out, const float* best, hipStream_t st) {
+  if (!valid || !workspace || !mean_out || !best) return GE_EINVAL;
+  if (reinterpret_cast<uintptr_t>(workspace) % 256 != 0) return GE_EINVAL;
+  w = tick_ws(workspace, B, K);
+  if (workspace_bytes < w.bytes) return GE_ENOMEM;
+  return select_rows_launch(valid, V, B, seed, counter, w.pos, st);
+}
+// second half: the mean of the M losses into the history, the pocket kept iff it is the best so far
+static int tick_tail(const TickWs& w, int64_t M, const float* table, int64_t N, int32_t d, float* mean_out, float* best,
+                     float* pocket, hipStream_t st) {
+  const int rc = mean_pocket_launch(w.loss, M, mean_out, best, w.flag, st);
+  if (rc || !pocket) return rc;
+  return copy_if_launch(table, pocket, N * (int64_t)d, w.flag, st);
+}
+
 int ge_validation_tick(const float* table, int64_t N, int32_t d, const int32_t* valid, int64_t V, int64_t B,
                        const int32_t* id_to_type, const int64_t* type_offsets, int32_t n_types, const int32_t* type_ids,
                        uint64_t seed, uint64_t counter, int32_t padded_size, int32_t mode, float margin, float max_norm,
                        int model, void* workspace, size_t workspace_bytes, float* mean_out, float* best, float* pocket,
                        void* stream) {
-  if (B <= 0 || V <= 0 || !ok_table(table, N, d) || !max_norm_ok(max_norm) || model < 0 || model > 2) return GE_EINVAL;
-  if (!valid || !id_to_type || !type_offsets || !type_ids || !workspace || !mean_out || !best) return GE_EINVAL;
-  if (reinterpret_cast<uintptr_t>(workspace) % 256 != 0) return GE_EINVAL;
-  if (workspace_bytes < ge_validation_workspace_bytes(B)) return GE_ENOMEM;
   hipStream_t st = (hipStream_t)stream;
-  int32_t* pos = (int32_t*)workspace;                 // [B,3] | neg [B,3] | loss [B] | flag
-  int32_t* neg = pos + 3 * B;
-  float* loss = (float*)(neg + 3 * B);
-  int32_t* flag = (int32_t*)(loss + B);
-  int rc = select_rows_launch(valid, V, B, seed, counter, pos, st);
+  TypeSampler ts;
+  TickWs w;
+  if (B <= 0 || V <= 0 || !ok_table(table, N, d) || !max_norm_ok(max_norm) || model < 0 || model > 2) return GE_EINVAL;
+  if (type_sampler(ts, id_to_type, N, type_offsets, n_types, type_ids, seed, padded_size, mode, false)) return GE_EINVAL;
+  int rc = tick_head(w, valid, V, B, 0, seed, counter, workspace, workspace_bytes, mean_out, best, st);
   if (rc) return rc;
-  rc = corrupt_batch_launch(pos, B, id_to_type, N, type_offsets, n_types, type_ids, seed, counter, padded_size, mode, neg, st);
+  rc = corrupt_batch_launch(w.pos, B, ts, counter, w.neg, st);
   if (rc) return rc;
-  rc = ge_hinge_loss(table, N, d, pos, neg, B, margin, max_norm, model, loss, nullptr, stream);
+  rc = ge_hinge_loss(table, N, d, w.pos, w.neg, B, margin, max_norm, model, w.loss, nullptr, stream);
   if (rc) return rc;
-  rc = mean_pocket_launch(loss, B, mean_out, best, flag, st);
-  if (rc || !pocket) return rc;
-  return copy_if_launch(table, pocket, N * (int64_t)d, flag, st);
+  return tick_tail(w, B, table, N, d, mean_out, best, pocket, st);
 }
 
 // the same tick for the --log_loss objective (holE.py:194-196, 206-220 on a validation batch): positives with
 // label +1, K corrupted batches with label -1, every loss plus l2 * l2_loss(table)
-size_t ge_validation_logloss_workspace_bytes(int64_t B, int32_t negative_ratio) {
-  if (B <= 0 || negative_ratio < 1) return 0;
-  return ((size_t)B * (3 + 3 + 1 + (size_t)negative_ratio) * 4 + 16 + 255) / 256 * 256 + 256;
-}
-
 int ge_validation_tick_logloss(const float* table, int64_t N, int32_t d, const int32_t* valid, int64_t V, int64_t B,
                                const int32_t* id_to_type, const int64_t* type_offsets, int32_t n_types,
                                const int32_t* type_ids, uint64_t seed, uint64_t counter, int32_t padded_size, int32_t mode,
                                int32_t negative_ratio, float l2, float max_norm, void* workspace, size_t workspace_bytes,
                                float* mean_out, float* best, float* pocket, void* stream) {
-  if (B <= 0 || V <= 0 || negative_ratio < 1 || !ok_table(table, N, d) || !max_norm_ok(max_norm)) return GE_EINVAL;
-  if (!valid || !id_to_type || !type_offsets || !type_ids || !workspace || !mean_out || !best) return GE_EINVAL;
-  if (reinterpret_cast<uintptr_t>(workspace) % 256 != 0) return GE_EINVAL;
-  if (workspace_bytes < ge_validation_logloss_workspace_bytes(B, negative_ratio)) return GE_ENOMEM;
   hipStream_t st = (hipStream_t)stream;
-  const int64_t K = negative_ratio, M = (1 + K) * B;
-  float* sumsq = (float*)workspace;                        // [256 B] | pos [B,3] | neg [B,3] | loss [(1+K)B] | flag
-  int32_t* pos = (int32_t*)((char*)workspace + 256);
-  int32_t* neg = pos + 3 * B;
-  float* loss = (float*)(neg + 3 * B);
-  int32_t* flag = (int32_t*)(loss + M);
-  int rc = select_rows_launch(valid, V, B, seed, counter, pos, st);
+  const int64_t K = negative_ratio;
+  TypeSampler ts;
+  TickWs w;
+  if (B <= 0 || V <= 0 || negative_ratio < 1 || !ok_table(table, N, d) || !max_norm_ok(max_norm)) return GE_EINVAL;
+  if (type_sampler(ts, id_to_type, N, type_offsets, n_types, type_ids, seed, padded_size, mode, false)) return GE_EINVAL;
+  int rc = tick_head(w, valid, V, B, K, seed, counter, workspace, workspace_bytes, mean_out, best, st);
   if (rc) return rc;
-  rc = table_sumsq_launch(table, N * (int64_t)d, sumsq, st);
+  rc = table_sumsq_launch(table, N * (int64_t)d, w.sumsq, st);
   if (rc) return rc;
-  rc = complex_score_launch(table, N, d, pos, B, max_norm, 2, loss, st, 0, 1.0f, l2, sumsq);
+  rc = complex_score_launch(table, N, d, w.pos, B, max_norm, 2, w.loss, st, 0, 1.0f, l2, w.sumsq);
   if (rc) return rc;
   for (int64_t k = 0; k < K; ++k) {
-    rc = corrupt_batch_launch(pos, B, id_to_type, N, type_offsets, n_types, type_ids, seed, counter * (uint64_t)K + (uint64_t)k,
-                              padded_size, mode, neg, st);
+    rc = corrupt_batch_launch(w.pos, B, ts, counter * (uint64_t)K + (uint64_t)k, w.neg, st);
     if (rc) return rc;
-    rc = complex_score_launch(table, N, d, neg, B, max_norm, 2, loss + (1 + k) * B, st, 0, -1.0f, l2, sumsq);
+    rc = complex_score_launch(table, N, d, w.neg, B, max_norm, 2, w.loss + (1 + k) * B, st, 0, -1.0f, l2, w.sumsq);
     if (rc) return rc;
   }
-  rc = mean_pocket_launch(loss, M, mean_out, best, flag, st);
-  if (rc || !pocket) return rc;
-  return copy_if_launch(table, pocket, N * (int64_t)d, flag, st);
+  return tick_tail(w, (1 + K) * B, table, N, d, mean_out, best, pocket, st);
 }
 
 int ge_hinge_grad(const float* rows, int64_t N, int32_t d, const int32_t* pos, const int32_t* neg,
@@ -172,10 +192,9 @@ int ge_gather_rows(const float* table, int64_t N, int32_t d, const int32_t* idx,
   return gather_rows_launch(table, N, d, idx, R, out, (hipStream_t)stream);
 }
 
-// workspace layout: [grad_idx: 6B int32, padded to 256 B][grad_val: 6B*d fp32]
 size_t ge_hinge_step_workspace_bytes(int64_t B, int32_t d) {
   if (B <= 0 || d <= 0) return 0;
-  return hinge_ws_bytes(B, d);
+  return hinge_ws(nullptr, B, d).bytes;
 }
 
 size_t ge_train_workspace_bytes(int64_t B, int32_t d) {
@@ -190,12 +209,11 @@ static int hinge_step(float* table, int64_t N, int32_t d, const int32_t* pos, co
   if (B == 0) return 0;
   if (!pos || !neg || !loss || !workspace) return GE_EINVAL;
   if (reinterpret_cast<uintptr_t>(workspace) % 256 != 0) return GE_EINVAL;
-  if (workspace_bytes < ge_hinge_step_workspace_bytes(B, d)) return GE_ENOMEM;
-  int32_t* gidx = reinterpret_cast<int32_t*>(workspace);
-  float* gval = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + align_up(sizeof(int32_t) * 6 * (size_t)B, 256));
-  int rc = ge_hinge_grad(table, N, d, pos, neg, B, margin, lr, max_norm, model, loss, gidx, gval, stream);
+  const HingeWs w = hinge_ws(workspace, B, d);
+  if (workspace_bytes < w.bytes) return GE_ENOMEM;
+  int rc = ge_hinge_grad(table, N, d, pos, neg, B, margin, lr, max_norm, model, loss, w.gidx, w.gval, stream);
   if (rc != 0) return rc;
-  return scatter_add_rows_launch(table, N, d, gidx, gval, 6 * B, (hipStream_t)stream);
+  return scatter_add_rows_launch(table, N, d, w.gidx, w.gval, 6 * B, (hipStream_t)stream);
 }
 
 int ge_complex_hinge_step(float* table, int64_t N, int32_t d, const int32_t* pos, const int32_t* neg,
@@ -213,10 +231,11 @@ int ge_hole_hinge_step(float* table, int64_t N, int32_t d, const int32_t* pos, c
 int ge_corrupt_batch(const int32_t* pos, int64_t B, const int32_t* id_to_type, int64_t N,
                      const int64_t* type_offsets, int32_t n_types, const int32_t* type_ids, uint64_t seed,
                      uint64_t step, int32_t padded_size, int32_t mode, int32_t* neg, void* stream) {
-  if (B < 0 || N <= 0 || !id_to_type || !type_offsets || !type_ids) return GE_EINVAL;
+  TypeSampler ts;
+  if (B < 0 || N <= 0 || type_sampler(ts, id_to_type, N, type_offsets, n_types, type_ids, seed, padded_size, mode, false))
+    return GE_EINVAL;
   if (B > 0 && (!pos || !neg)) return GE_EINVAL;
-  return corrupt_batch_launch(pos, B, id_to_type, N, type_offsets, n_types, type_ids, seed, step,
-                              padded_size, mode, neg, (hipStream_t)stream);
+  return corrupt_batch_launch(pos, B, ts, step, neg, (hipStream_t)stream);
 }
 
 int ge_bernoulli_corrupt_batch(const int32_t* pos, int64_t B, const int64_t* bh_key, const int32_t* bh_ent,
@@ -739,17 +758,18 @@ int ge_train_steps(float* table, int64_t N, int32_t d, const int32_t* triples, i
                    void* pipeline, void* stream) {
   if (B <= 0 || n_steps < 0 || T < B || first_row < 0 || !ok_table(table, N, d) || !max_norm_ok(max_norm))
     return GE_EINVAL;
-  if (!triples || !id_to_type || !type_offsets || !type_ids || !loss || !neg_ws || !workspace) return GE_EINVAL;
+  TypeSampler ts;
+  if (type_sampler(ts, id_to_type, N, type_offsets, n_types, type_ids, seed, padded_size, mode, false)) return GE_EINVAL;
+  if (!triples || !loss || !neg_ws || !workspace) return GE_EINVAL;
   if ((model & ~GE_STEP_DETERMINISTIC) < 0 || (model & ~GE_STEP_DETERMINISTIC) > 3) return GE_EINVAL;
   if ((model & ~GE_STEP_DETERMINISTIC) == GE_MODEL_HOLE_SPECTRAL && (d & 1)) return GE_EINVAL;
   if (reinterpret_cast<uintptr_t>(workspace) % 256 != 0) return GE_EINVAL;
   if (workspace_bytes < ge_hinge_step_workspace_bytes(B, d)) return GE_ENOMEM;
   if (ev_pairs && (ev_kernel < 0 || ev_kernel > 2)) return GE_EINVAL;
-  if (mode < 0 || mode > 3 || padded_size < 0 || n_types < 0) return GE_EINVAL;
-  return train_steps_run(table, N, d, triples, T, first_row, B, n_steps, id_to_type, type_offsets, n_types,
-                         type_ids, seed, global_step0, padded_size, mode, margin, lr0, decay_steps, decay_rate,
-                         max_norm, model, loss, keep_all_losses, neg_ws, workspace, workspace_bytes, ev_pairs,
-                         ev_kernel, pipeline, (hipStream_t)stream);
+  if (!sampler_ranges_ok(ts)) return GE_EINVAL;
+  return train_steps_run(table, d, StepSeq{triples, T, first_row, B, global_step0}, n_steps, ts, margin,
+                         StepHyper{lr0, decay_steps, decay_rate, max_norm}, model, loss, keep_all_losses, neg_ws, workspace,
+                         workspace_bytes, ev_pairs, ev_kernel, pipeline, (hipStream_t)stream);
 }
 
 size_t ge_train_logloss_workspace_bytes(int64_t B, int32_t negative_ratio, int32_t d) {
@@ -765,14 +785,14 @@ int ge_train_steps_logloss(float* table, int64_t N, int32_t d, const int32_t* tr
                            int32_t* neg_ws, void* workspace, size_t workspace_bytes, void* pipeline, void* stream) {
   if (B <= 0 || n_steps < 0 || T < B || first_row < 0 || !ok_table(table, N, d) || !max_norm_ok(max_norm)) return GE_EINVAL;
   if (negative_ratio <= 0 || negative_ratio > 1024 || (d & 1)) return GE_EINVAL;
-  if (!triples || !id_to_type || !type_offsets || !type_ids || !loss || !neg_ws || !workspace) return GE_EINVAL;
+  TypeSampler ts;
+  if (type_sampler(ts, id_to_type, N, type_offsets, n_types, type_ids, seed, padded_size, mode, true)) return GE_EINVAL;
+  if (!triples || !loss || !neg_ws || !workspace) return GE_EINVAL;
   if (reinterpret_cast<uintptr_t>(workspace) % 256 != 0) return GE_EINVAL;
-  if (mode < 0 || mode > 3 || padded_size < 0 || n_types < 0) return GE_EINVAL;
   if ((int64_t)(1 + negative_ratio) * B > ((int64_t)1 << 24)) return GE_ENOTSUP;
-  return train_logloss_run(table, N, d, triples, T, first_row, B, n_steps, id_to_type, type_offsets, n_types, type_ids,
-                           seed, global_step0, padded_size, mode, negative_ratio, l2, lr0, decay_steps, decay_rate,
-                           max_norm, loss, keep_all_losses, neg_ws, workspace, workspace_bytes, pipeline,
-                           (hipStream_t)stream);
+  return train_logloss_run(table, d, StepSeq{triples, T, first_row, B, global_step0}, n_steps, ts, negative_ratio, l2,
+                           StepHyper{lr0, decay_steps, decay_rate, max_norm}, loss, keep_all_losses, neg_ws, workspace,
+                           workspace_bytes, pipeline, (hipStream_t)stream);
 }
 
 int ge_train_pipeline_create(void** pipeline) { return pipeline ? pipeline_create(pipeline) : GE_EINVAL; }
@@ -792,11 +812,11 @@ int ge_train_prepare_steps(const int32_t* triples, int64_t T, int64_t first_row,
                            const int32_t* type_ids, uint64_t seed, uint64_t global_step0, int32_t padded_size,
                            int32_t mode, int direct, int32_t* out, size_t out_bytes, void* stream) {
   if (B <= 0 || n_steps < 0 || T < B || first_row < 0 || N <= 0) return GE_EINVAL;
-  if (!triples || !id_to_type || !type_offsets || !type_ids || !out) return GE_EINVAL;
-  if (mode < 0 || mode > 3 || padded_size < 0 || n_types < 0) return GE_EINVAL;
+  TypeSampler ts;
+  if (type_sampler(ts, id_to_type, N, type_offsets, n_types, type_ids, seed, padded_size, mode, true)) return GE_EINVAL;
+  if (!triples || !out) return GE_EINVAL;
   if (out_bytes < train_prepare_bytes(B, n_steps)) return GE_ENOMEM;
-  return train_prepare_run(triples, T, first_row, B, n_steps, id_to_type, N, type_offsets, n_types, type_ids, seed,
-                           global_step0, padded_size, mode, direct, out, (hipStream_t)stream);
+  return train_prepare_run(StepSeq{triples, T, first_row, B, global_step0}, n_steps, ts, direct, out, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------- the row-sharded step (csrc/ge_shard.hip)
@@ -862,10 +882,9 @@ int ge_shard_owner_apply(float* shard, int64_t rows_local, int32_t d, const int3
   return shard_owner_apply_launch(shard, d, record, cap, recv, (hipStream_t)stream);
 }
 
-// workspace: [sumsq: 256 B][grad_idx: 3M int32, 256-B padded][grad_val: 3M*d fp32]
 size_t ge_logloss_step_workspace_bytes(int64_t M, int32_t d) {
   if (M <= 0 || d <= 0) return 0;
-  return 256 + align_up(sizeof(int32_t) * 3 * (size_t)M, 256) + align_up(sizeof(float) * 3 * (size_t)M * (size_t)d, 256);
+  return logloss_ws(nullptr, M, d).bytes;
 }
 
 int ge_complex_logloss_step(float* table, int64_t N, int32_t d, const int32_t* triples, const float* labels,
@@ -875,21 +894,19 @@ int ge_complex_logloss_step(float* table, int64_t N, int32_t d, const int32_t* t
   if (M == 0) return 0;
   if (!triples || !labels || !loss || !workspace) return GE_EINVAL;
   if (reinterpret_cast<uintptr_t>(workspace) % 256 != 0) return GE_EINVAL;
-  if (workspace_bytes < ge_logloss_step_workspace_bytes(M, d)) return GE_ENOMEM;
+  const LoglossWs w = logloss_ws(workspace, M, d);
+  if (workspace_bytes < w.bytes) return GE_ENOMEM;
   hipStream_t st = (hipStream_t)stream;
-  float* sumsq = reinterpret_cast<float*>(workspace);
-  int32_t* gidx = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(workspace) + 256);
-  float* gval = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + 256 + align_up(sizeof(int32_t) * 3 * (size_t)M, 256));
-  int rc = table_sumsq_launch(table, N * (int64_t)d, sumsq, st);                 // l2_loss of the OLD table
+  int rc = table_sumsq_launch(table, N * (int64_t)d, w.sumsq, st);               // l2_loss of the OLD table
   if (rc) return rc;
-  rc = complex_logloss_grad_launch(table, N, d, triples, labels, M, lr, max_norm, l2, sumsq, loss, gidx, gval, st);
+  rc = complex_logloss_grad_launch(table, N, d, triples, labels, M, lr, max_norm, l2, w.sumsq, loss, w.gidx, w.gval, st);
   if (rc) return rc;
   // new = old - lr * (sparse + M * l2 * old) = old * (1 - lr*M*l2) + (-lr * sparse)
   if (l2 != 0.f) {
     rc = table_scale_launch(table, N * (int64_t)d, 1.0f - lr * (float)M * l2, st);
     if (rc) return rc;
   }
-  return scatter_add_rows_launch(table, N, d, gidx, gval, 3 * M, st);
+  return scatter_add_rows_launch(table, N, d, w.gidx, w.gval, 3 * M, st);
 }
 
 int ge_event_create(void** ev) {

@@ -9,6 +9,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "ge_step_id.h"       // TypeSampler, StepSeq
 #include "ge_sweep_route.h"   // rank_planes_bytes, kRankMaxDim
 #include "ge_trans.h"         // TransModel
 
@@ -58,9 +59,7 @@ int hole_spectral_launch(float* table, int64_t N, int32_t d, int inverse, hipStr
 int scatter_add_rows_launch(float* table, int64_t N, int32_t d, const int32_t* idx, const float* val, int64_t R,
                             hipStream_t st, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
 int gather_rows_launch(const float* table, int64_t N, int32_t d, const int32_t* idx, int64_t R, float* out, hipStream_t st);
-int corrupt_batch_launch(const int32_t* pos, int64_t B, const int32_t* id_to_type, int64_t N, const int64_t* type_offsets,
-                         int32_t n_types, const int32_t* type_ids, uint64_t seed, uint64_t step, int32_t padded_size,
-                         int32_t mode, int32_t* neg, hipStream_t st);
+int corrupt_batch_launch(const int32_t* pos, int64_t B, const TypeSampler& ts, uint64_t step, int32_t* neg, hipStream_t st);
 // What a Bernoulli draw reads: the triple list it picks positives from (transx_draw_launch alone) and the known
 // (entity, relation) keys with their entities, sorted, for the corruption.
 struct SamplerArgs {
@@ -140,35 +139,38 @@ int items_launch(const unsigned long long* sorted, int64_t n, const TileGeom& G,
 int relation_order_launch(const int32_t* triples, int64_t T, int64_t first_row, int64_t B, int64_t s0, int64_t n, int64_t N,
                           int32_t* out, int64_t stride, int64_t off_order, void* scratch, hipStream_t st);
 size_t prep_big_scratch_bytes(int64_t B, int64_t negs, int64_t n);
-int prepare_big_launch(const int32_t* triples, int64_t T, int64_t first_row, int64_t B, int64_t s0, int64_t n,
-                       const int32_t* id_to_type, int64_t N, const int64_t* type_offsets, int32_t n_types,
-                       const int32_t* type_ids, uint64_t seed, uint64_t global_step0, int32_t padded_size, int32_t mode,
-                       int direct, int32_t* out, void* scratch, hipStream_t st, int negs);
+int prepare_big_launch(const StepSeq& q, int64_t s0, int64_t n, const TypeSampler& ts, int direct, int32_t* out,
+                       void* scratch, hipStream_t st, int negs);
 
 // ge_train.hip: the native training loops, their prepare stage and pipeline handle, the row-sorted update
 int apply_items_launch(float* table, int d, const TileGeom& G, const int32_t* step_rec, const int32_t* gidx,
                        const float* gval, int split, float* out2, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop,
                        int det);
-size_t hinge_ws_bytes(int64_t B, int32_t d);
+// A workspace is carved in ONE place: a function that takes the base address and the shape and returns the pointers
+// and the total size.  The size function calls it on a null base, the user on its workspace.
+template <class T>
+inline T* ws_at(void* base, size_t off) { return reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(base) + off); }
+// the hinge step: gidx 6B int32, padded to 256 B | gval 6B x d fp32
+struct HingeWs { int32_t* gidx; float* gval; size_t bytes; };
+HingeWs hinge_ws(void* base, int64_t B, int32_t d);
+// the log-loss step of M triples: sumsq 256 B | gidx 3M int32, padded to 256 B | gval 3M x d fp32
+struct LoglossWs { float* sumsq; int32_t* gidx; float* gval; size_t bytes; };
+LoglossWs logloss_ws(void* base, int64_t M, int32_t d);
+// learning rate (tf.train.inverse_time_decay, no staircase; decay_steps <= 0: constant) and the clip of a loop
+struct StepHyper {
+  float lr0, decay_steps, decay_rate, max_norm;
+  float lr_at(uint64_t gs) const { return decay_steps > 0.f ? lr0 / (1.0f + decay_rate * ((float)gs / decay_steps)) : lr0; }
+};
 size_t train_ws_bytes(int64_t B, int32_t d);
-int train_steps_run(float* table, int64_t N, int32_t d, const int32_t* triples, int64_t T, int64_t first_row, int64_t B,
-                    int64_t n_steps, const int32_t* id_to_type, const int64_t* type_offsets, int32_t n_types,
-                    const int32_t* type_ids, uint64_t seed, uint64_t global_step0, int32_t padded_size, int32_t mode,
-                    float margin, float lr0, float decay_steps, float decay_rate, float max_norm, int model, float* loss,
-                    int keep_all_losses, int32_t* neg_ws, void* workspace, size_t workspace_bytes, void** ev_pairs,
-                    int ev_kernel, void* pipe_handle, hipStream_t st);
+int train_steps_run(float* table, int32_t d, const StepSeq& q, int64_t n_steps, const TypeSampler& ts, float margin,
+                    const StepHyper& hp, int model, float* loss, int keep_all_losses, int32_t* neg_ws, void* workspace,
+                    size_t workspace_bytes, void** ev_pairs, int ev_kernel, void* pipe_handle, hipStream_t st);
 size_t train_logloss_ws_bytes(int64_t B, int32_t negs, int32_t d);
-int train_logloss_run(float* table, int64_t N, int32_t d, const int32_t* triples, int64_t T, int64_t first_row, int64_t B,
-                      int64_t n_steps, const int32_t* id_to_type, const int64_t* type_offsets, int32_t n_types,
-                      const int32_t* type_ids, uint64_t seed, uint64_t global_step0, int32_t padded_size, int32_t mode,
-                      int32_t negs, float l2, float lr0, float decay_steps, float decay_rate, float max_norm, float* loss,
-                      int keep_all_losses, int32_t* neg_ws, void* workspace, size_t workspace_bytes, void* pipe_handle,
-                      hipStream_t st);
+int train_logloss_run(float* table, int32_t d, const StepSeq& q, int64_t n_steps, const TypeSampler& ts, int32_t negs,
+                      float l2, const StepHyper& hp, float* loss, int keep_all_losses, int32_t* neg_ws, void* workspace,
+                      size_t workspace_bytes, void* pipe_handle, hipStream_t st);
 size_t train_prepare_bytes(int64_t B, int64_t n_steps);
-int train_prepare_run(const int32_t* triples, int64_t T, int64_t first_row, int64_t B, int64_t n_steps,
-                      const int32_t* id_to_type, int64_t N, const int64_t* type_offsets, int32_t n_types,
-                      const int32_t* type_ids, uint64_t seed, uint64_t global_step0, int32_t padded_size, int32_t mode,
-                      int direct, int32_t* out, hipStream_t st);
+int train_prepare_run(const StepSeq& q, int64_t n_steps, const TypeSampler& ts, int direct, int32_t* out, hipStream_t st);
 void train_prepared_layout(int64_t B, int64_t* out);
 int pipeline_create(void** out);
 int pipeline_reset(void* h);

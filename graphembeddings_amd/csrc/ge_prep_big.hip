@@ -450,20 +450,19 @@ size_t prep_big_scratch_bytes(int64_t B, int64_t negs, int64_t n) {
   return L.n_sub <= 1 ? 0 : sort_scratch_bytes(n, L.n_sub, L.P);
 }
 
-int prepare_big_launch(const int32_t* triples, int64_t T, int64_t first_row, int64_t B, int64_t s0, int64_t n,
-                       const int32_t* id_to_type, int64_t N, const int64_t* type_offsets, int32_t n_types,
-                       const int32_t* type_ids, uint64_t seed, uint64_t global_step0, int32_t padded_size,
-                       int32_t mode, int direct, int32_t* out, void* scratch, hipStream_t st, int negs) {
-  const PrepLayout L = prep_layout(B, negs);
+int prepare_big_launch(const StepSeq& q, int64_t s0, int64_t n, const TypeSampler& ts, int direct, int32_t* out,
+                       void* scratch, hipStream_t st, int negs) {
+  const PrepLayout L = prep_layout(q.B, negs);
   const dim3 grid((unsigned)n, (unsigned)L.n_sub), block(kPrepThreads);
-  hipLaunchKernelGGL(prep_big_keys_kernel, grid, block, 0, st, triples, T, first_row, B, s0, id_to_type, N, type_offsets,
-                     n_types, type_ids, seed, global_step0, padded_size, mode, direct, negs, out, sort_scratch_keys(scratch));
+  hipLaunchKernelGGL(prep_big_keys_kernel, grid, block, 0, st, q.triples, q.T, q.first_row, q.B, s0, ts.id_to_type, ts.N,
+                     ts.type_offsets, ts.n_types, ts.type_ids, ts.seed, q.global_step0, ts.padded_size, ts.mode, direct, negs,
+                     out, sort_scratch_keys(scratch));
   const unsigned long long* sorted;
-  int rc = sort_tiles_launch(scratch, n, L.n_sub, L.P, N, st, nullptr, &sorted);
+  int rc = sort_tiles_launch(scratch, n, L.n_sub, L.P, ts.N, st, nullptr, &sorted);
   if (rc) return rc;
   rc = items_launch(sorted, n, geom_of(L), direct, out, nullptr, st);
   if (rc || L.off_order < 0) return rc;
-  return relation_order_launch(triples, T, first_row, B, s0, n, N, out, L.stride, L.off_order, scratch, st);
+  return relation_order_launch(q.triples, q.T, q.first_row, q.B, s0, n, ts.N, out, L.stride, L.off_order, scratch, st);
 }
 
 }  // namespace ge

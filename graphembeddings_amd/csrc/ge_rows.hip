@@ -122,15 +122,12 @@ int gather_rows_launch(const float* table, int64_t N, int32_t d, const int32_t* 
   return launch_status();
 }
 
-int corrupt_batch_launch(const int32_t* pos, int64_t B, const int32_t* id_to_type, int64_t N,
-                         const int64_t* type_offsets, int32_t n_types, const int32_t* type_ids,
-                         uint64_t seed, uint64_t step, int32_t padded_size, int32_t mode, int32_t* neg,
-                         hipStream_t st) {
-  if (mode < 0 || mode > 3 || padded_size < 0 || n_types < 0) return GE_EINVAL;
+int corrupt_batch_launch(const int32_t* pos, int64_t B, const TypeSampler& ts, uint64_t step, int32_t* neg, hipStream_t st) {
+  if (!sampler_ranges_ok(ts)) return GE_EINVAL;
   if (B == 0) return 0;
   const int grid = grid_for(B, kBlock);
-  hipLaunchKernelGGL(corrupt_batch_kernel, dim3(grid), dim3(kBlock), 0, st, pos, B, id_to_type, N,
-                     type_offsets, n_types, type_ids, seed, step, padded_size, mode, neg);
+  hipLaunchKernelGGL(corrupt_batch_kernel, dim3(grid), dim3(kBlock), 0, st, pos, B, ts.id_to_type, ts.N,
+                     ts.type_offsets, ts.n_types, ts.type_ids, ts.seed, step, ts.padded_size, ts.mode, neg);
   return launch_status();
 }
 

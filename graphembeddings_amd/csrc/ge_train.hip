@@ -717,8 +717,12 @@ static int apply_sorted_launch(float* table, int d, const PrepLayout& L, const i
   return apply_items_launch(table, d, geom_of(L), step_rec, gidx, gval, 0x7FFFFFFF, nullptr, st, ev_start, ev_stop, det);
 }
 
-size_t hinge_ws_bytes(int64_t B, int32_t d) {
-  return align_up(sizeof(int32_t) * 6 * (size_t)B, 256) + align_up(sizeof(float) * 6 * (size_t)B * (size_t)d, 256);
+static size_t grad_region_bytes(int64_t B, int32_t d) {
+  return align_up(sizeof(float) * 6 * (size_t)B * (size_t)d, 256);
+}
+HingeWs hinge_ws(void* base, int64_t B, int32_t d) {
+  const size_t idx = align_up(sizeof(int32_t) * 6 * (size_t)B, 256);
+  return HingeWs{ws_at<int32_t>(base, 0), ws_at<float>(base, idx), idx + grad_region_bytes(B, d)};
 }
 
 static bool train_fast_ok(int64_t B, int32_t d) { return B >= 1 && B <= (int64_t)1 << 24 && d <= 1024; }
@@ -734,15 +738,13 @@ static int64_t prep_chunk_steps(int64_t B, int64_t negs = 0) {
   return c < floor_steps ? floor_steps : c;
 }
 
-// training workspace: [gidx 6B][gval RING x (6B x d)][prep chunk buffer 0][prep chunk buffer 1].
+// training workspace: the hinge step's [gidx 6B][gval 6B x d], the latter RING times, then
+// [prep chunk buffer 0][prep chunk buffer 1][(B > 4096) the key arrays of the multi-tile sort of ONE prepare sequence].
 // The gradient rows go to a RING of regions, one per step in turn: a region is written by the grad kernel
 // on one XCD and read by the apply kernel on another, and rewriting lines that still sit in another XCD's
 // L2 costs ~3.7 us per 13 MB (tools/probes/xcd_locality_probe.hip: 9.1 vs 5.4 us); by the time a region comes
 // round again (normally 4 steps later, > the 32 MB of L2 in between) its lines have been evicted and the
 // stores take the fast path.
-static size_t grad_region_bytes(int64_t B, int32_t d) {
-  return align_up(sizeof(float) * 6 * (size_t)B * (size_t)d, 256);
-}
 static int grad_ring(int64_t B, int32_t d) {
   const size_t reg = grad_region_bytes(B, d);
   // measured at B=4096, d=200 (20 MB regions): 1 -> 22.4, 2 -> 21.3, 4 -> 21.0, 8 -> 21.0, 16 -> 21.8, 32 -> 22.8 us/step:
@@ -753,11 +755,20 @@ static int grad_ring(int64_t B, int32_t d) {
   if (r < 4 && 4 * reg <= ((size_t)160 << 20)) r = 4;
   return (int)r;
 }
-static size_t train_grad_bytes(int64_t B, int32_t d) {
-  return align_up(sizeof(int32_t) * 6 * (size_t)B, 256) + (size_t)grad_ring(B, d) * grad_region_bytes(B, d);
-}
 static size_t prep_chunk_bytes(int64_t B, int64_t negs = 0) {
   return align_up(sizeof(int32_t) * (size_t)prep_chunk_steps(B, negs) * (size_t)prep_layout(B, negs).stride, 256);
+}
+// what lies behind the gradient rows of either loop, `off` bytes into the workspace
+static size_t prep_region_bytes(int64_t B, int64_t negs) {
+  return 2 * prep_chunk_bytes(B, negs) + prep_big_scratch_bytes(B, negs, prep_chunk_steps(B, negs));
+}
+struct TrainWs { HingeWs g; int ring; size_t region_floats; int32_t* prep; size_t bytes; };
+static TrainWs train_ws(void* base, int64_t B, int32_t d) {
+  const HingeWs g = hinge_ws(base, B, d);
+  const size_t region = grad_region_bytes(B, d);
+  const int ring = grad_ring(B, d);
+  const size_t grad = g.bytes + (size_t)(ring - 1) * region;
+  return TrainWs{g, ring, region / sizeof(float), ws_at<int32_t>(base, grad), grad + prep_region_bytes(B, 0)};
 }
 // The layout of a batch size b is cut from two step functions that only fall as b grows (steps prepared per chunk, regions
 // in the gradient ring), so the bytes it needs drop where one of them steps down.  A workspace size must not: a caller
@@ -778,14 +789,10 @@ static size_t largest_need_up_to(int64_t B, Need need, Step step) {
   return best;
 }
 
-static size_t train_layout_bytes(int64_t B, int32_t d) {
-  // two chunk buffers + (B > 4096) the key arrays of the multi-tile sort of ONE prepare sequence
-  return train_grad_bytes(B, d) + 2 * prep_chunk_bytes(B) + prep_big_scratch_bytes(B, 0, prep_chunk_steps(B));
-}
 size_t train_ws_bytes(int64_t B, int32_t d) {
-  if (!train_fast_ok(B, d)) return hinge_ws_bytes(B, d);
+  if (!train_fast_ok(B, d)) return hinge_ws(nullptr, B, d).bytes;
   // what this batch size's layout takes, and no less than any smaller batch's (ge_train_workspace_bytes is monotone in B)
-  return largest_need_up_to(B, [&](int64_t b) { return train_layout_bytes(b, d); },
+  return largest_need_up_to(B, [&](int64_t b) { return train_ws(nullptr, b, d).bytes; },
                             [&](int64_t b) { return std::make_pair(prep_chunk_steps(b), (int64_t)grad_ring(b, d)); });
 }
 
@@ -793,43 +800,37 @@ static size_t prep_lds_bytes(const PrepLayout& L) {
   return sizeof(unsigned long long) * (size_t)L.P + sizeof(unsigned) * kPrepWaves * kMaxRadix + sizeof(int) * 32;
 }
 
-static int prepare_launch(const int32_t* triples, int64_t T, int64_t first_row, int64_t B, int64_t s0, int64_t n,
-                          const int32_t* id_to_type, int64_t N, const int64_t* type_offsets, int32_t n_types,
-                          const int32_t* type_ids, uint64_t seed, uint64_t global_step0, int32_t padded_size,
-                          int32_t mode, int direct, int32_t* out, void* scratch, hipStream_t st, int negs = 0) {
-  const PrepLayout L = prep_layout(B, negs);
+static int prepare_launch(const StepSeq& q, int64_t s0, int64_t n, const TypeSampler& ts, int direct, int32_t* out,
+                          void* scratch, hipStream_t st, int negs = 0) {
+  const PrepLayout L = prep_layout(q.B, negs);
   if (L.n_sub > 1)   // more keys than one workgroup's LDS holds: the sort runs across workgroups
-    return prepare_big_launch(triples, T, first_row, B, s0, n, id_to_type, N, type_offsets, n_types, type_ids, seed,
-                              global_step0, padded_size, mode, direct, out, scratch, st, negs);
-  const SortBits sb = sort_bits_for(N);
+    return prepare_big_launch(q, s0, n, ts, direct, out, scratch, st, negs);
+  const SortBits sb = sort_bits_for(ts.N);
   const int n_pass = sb.n_pass, bits = sb.bits;
   const size_t lds = prep_lds_bytes(L);
   // per device, idempotent and cheap: no cached flag, so no state and nothing to get stale on a second device
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(train_prepare_kernel),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(train_prepare_kernel, dim3((unsigned)n, (unsigned)L.n_sub), dim3(kPrepThreads), lds, st, triples,
-                     T, first_row, B, s0, id_to_type, N, type_offsets, n_types, type_ids, seed, global_step0,
-                     padded_size, mode, direct, n_pass, bits, negs, out);
+  hipLaunchKernelGGL(train_prepare_kernel, dim3((unsigned)n, (unsigned)L.n_sub), dim3(kPrepThreads), lds, st, q.triples,
+                     q.T, q.first_row, q.B, s0, ts.id_to_type, ts.N, ts.type_offsets, ts.n_types, ts.type_ids, ts.seed,
+                     q.global_step0, ts.padded_size, ts.mode, direct, n_pass, bits, negs, out);
   return launch_status();
 }
 
 #define GE_HIP_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return (int)e_; } while (0)
 
 // ------------------------------------------------------------------ the pipeline handle (host object)
-// Identity of the sequence of prepared steps + which chunk each of the two workspace buffers holds.
+// Identity of the sequence of prepared steps (id.seq.first_row / global_step0: where the sequence STARTED, the row
+// normalised) + how far it has come + which chunk each of the two workspace buffers holds.
 struct Pipeline {
   int device = -1;
   hipStream_t side = nullptr;
   hipEvent_t prep_done[2] = {nullptr, nullptr};
   hipEvent_t buf_free[2] = {nullptr, nullptr};
   bool live = false;
-  const int32_t* triples = nullptr; const int32_t* id_to_type = nullptr; const int64_t* type_offsets = nullptr;
-  const int32_t* type_ids = nullptr; void* workspace = nullptr;
-  int64_t T = 0, B = 0, N = 0, origin_row = 0, next_abs = 0, resident[2] = {-1, -1};
-  uint64_t seed = 0, origin_gs = 0;
-  int32_t n_types = 0, padded_size = 0, mode = 0, d = 0;
-  int direct = 0, negs = 0;
+  StepIdentity id = {};
+  int64_t next_abs = 0, resident[2] = {-1, -1};
 };
 
 int pipeline_create(void** out) {
@@ -869,23 +870,25 @@ static inline int64_t norm_row(int64_t first_row, int64_t T, int64_t B) {
   if (f + B > T) f = 0;
   return f;
 }
+// b goes on where a sequence that started at a (row normalised) and has run `done` steps stopped
+static inline bool continues(const StepSeq& a, int64_t done, const StepSeq& b) {
+  return b.global_step0 == a.global_step0 + (uint64_t)done &&
+         norm_row(b.first_row, b.T, b.B) == step_row(a.first_row, b.T, b.B, done);
+}
 
 // ------------------------------------------------------------------ walking the prepared records
 // Shared by the hinge and the log-loss loops: which chunk of steps each of the two workspace buffers holds,
 // when a prepare launch is due (on the handle's side stream, one chunk ahead, or on the caller's stream
 // without a handle) and where step s finds its record.
-struct StepIdentity {
-  const int32_t* triples; int64_t T, first_row, B; const int32_t* id_to_type; int64_t N;
-  const int64_t* type_offsets; int32_t n_types; const int32_t* type_ids; uint64_t seed, global_step0;
-  int32_t padded_size, mode, d; int direct, negs; void* workspace;
-};
-
 class PrepCursor {
  public:
+  // the sequence is taken from its first row as the loops see it (norm_row): that is what a prepare launch starts from
   PrepCursor(const StepIdentity& id, Pipeline* handle, int32_t* prep_base, hipStream_t st)
-      : id_(id), L_(prep_layout(id.B, id.negs)), K_(prep_chunk_steps(id.B, id.negs)),
-        buf_ints_((int64_t)(prep_chunk_bytes(id.B, id.negs) / sizeof(int32_t))), base_(prep_base), st_(st),
-        pipe_(handle ? handle : &local_), own_side_(handle != nullptr) {}
+      : id_(id), L_(prep_layout(id.seq.B, id.negs)), K_(prep_chunk_steps(id.seq.B, id.negs)),
+        buf_ints_((int64_t)(prep_chunk_bytes(id.seq.B, id.negs) / sizeof(int32_t))), base_(prep_base), st_(st),
+        pipe_(handle ? handle : &local_), own_side_(handle != nullptr) {
+    id_.seq.first_row = norm_row(id.seq.first_row, id.seq.T, id.seq.B);
+  }
 
   int begin() {
     if (own_side_) {
@@ -893,26 +896,16 @@ class PrepCursor {
       GE_HIP_TRY(hipGetDevice(&dev));
       if (dev != pipe_->device) return GE_EINVAL;
       Pipeline* p = pipe_;
-      const bool cont = p->live && p->triples == id_.triples && p->id_to_type == id_.id_to_type &&
-                        p->type_offsets == id_.type_offsets && p->type_ids == id_.type_ids &&
-                        p->workspace == id_.workspace && p->T == id_.T && p->B == id_.B && p->N == id_.N &&
-                        p->seed == id_.seed && p->n_types == id_.n_types && p->padded_size == id_.padded_size &&
-                        p->mode == id_.mode && p->d == id_.d && p->direct == id_.direct && p->negs == id_.negs &&
-                        id_.global_step0 == p->origin_gs + (uint64_t)p->next_abs &&
-                        norm_row(id_.first_row, id_.T, id_.B) == step_row(p->origin_row, id_.T, id_.B, p->next_abs);
+      const bool cont = p->live && same_source(p->id, id_) && continues(p->id.seq, p->next_abs, id_.seq);
       if (!cont) {
         p->live = true;
-        p->triples = id_.triples; p->id_to_type = id_.id_to_type; p->type_offsets = id_.type_offsets;
-        p->type_ids = id_.type_ids; p->workspace = id_.workspace; p->T = id_.T; p->B = id_.B; p->N = id_.N;
-        p->seed = id_.seed; p->n_types = id_.n_types; p->padded_size = id_.padded_size; p->mode = id_.mode;
-        p->d = id_.d; p->direct = id_.direct; p->negs = id_.negs;
-        p->origin_row = norm_row(id_.first_row, id_.T, id_.B); p->origin_gs = id_.global_step0; p->next_abs = 0;
+        p->id = id_;
+        p->next_abs = 0;
         p->resident[0] = p->resident[1] = -1;
       }
       base_abs_ = p->next_abs;
     } else {
-      pipe_->origin_row = norm_row(id_.first_row, id_.T, id_.B);
-      pipe_->origin_gs = id_.global_step0;
+      pipe_->id = id_;
       pipe_->side = st_;
     }
     return 0;
@@ -962,9 +955,8 @@ class PrepCursor {
       GE_HIP_TRY(hipEventRecord(pipe_->buf_free[b], st_));
       GE_HIP_TRY(hipStreamWaitEvent(pipe_->side, pipe_->buf_free[b], 0));
     }
-    int rc = prepare_launch(id_.triples, id_.T, pipe_->origin_row, id_.B, c * K_, K_, id_.id_to_type, id_.N,
-                            id_.type_offsets, id_.n_types, id_.type_ids, id_.seed, pipe_->origin_gs, id_.padded_size,
-                            id_.mode, id_.direct, base_ + b * buf_ints_, base_ + 2 * buf_ints_, pipe_->side, id_.negs);
+    int rc = prepare_launch(pipe_->id.seq, c * K_, K_, id_.ts, id_.direct, base_ + b * buf_ints_, base_ + 2 * buf_ints_,
+                            pipe_->side, id_.negs);
     if (rc) return rc;
     if (own_side_) GE_HIP_TRY(hipEventRecord(pipe_->prep_done[b], pipe_->side));
     pipe_->resident[b] = c;
@@ -982,13 +974,11 @@ class PrepCursor {
   int64_t base_abs_ = 0;
 };
 
-int train_steps_run(float* table, int64_t N, int32_t d, const int32_t* triples, int64_t T, int64_t first_row,
-                    int64_t B, int64_t n_steps, const int32_t* id_to_type, const int64_t* type_offsets,
-                    int32_t n_types, const int32_t* type_ids, uint64_t seed, uint64_t global_step0,
-                    int32_t padded_size, int32_t mode, float margin, float lr0, float decay_steps,
-                    float decay_rate, float max_norm, int model, float* loss, int keep_all_losses,
-                    int32_t* neg_ws, void* workspace, size_t workspace_bytes, void** ev_pairs, int ev_kernel,
-                    void* pipe_handle, hipStream_t st) {
+int train_steps_run(float* table, int32_t d, const StepSeq& q, int64_t n_steps, const TypeSampler& ts, float margin,
+                    const StepHyper& hp, int model, float* loss, int keep_all_losses, int32_t* neg_ws, void* workspace,
+                    size_t workspace_bytes, void** ev_pairs, int ev_kernel, void* pipe_handle, hipStream_t st) {
+  const int64_t N = ts.N, B = q.B;
+  const float max_norm = hp.max_norm;
   if (n_steps <= 0) return 0;
   const int deterministic = (model & GE_STEP_DETERMINISTIC) ? 1 : 0;   // rows with > 16 slots reduced in a fixed order (prepared path)
   model &= ~GE_STEP_DETERMINISTIC;
@@ -1001,25 +991,21 @@ int train_steps_run(float* table, int64_t N, int32_t d, const int32_t* triples, 
   const bool spectral = transform || model == GE_MODEL_HOLE_SPECTRAL;
   const bool hole_direct = (model == GE_MODEL_HOLE && (d & 1)) || model == GE_MODEL_HOLE_DIRECT;
   if (transform) { int rc = hole_spectral_launch(table, N, d, /*inverse=*/0, st); if (rc) return rc; }
-  int32_t* gidx = reinterpret_cast<int32_t*>(workspace);
-  float* gval0 = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + align_up(sizeof(int32_t) * 6 * (size_t)B, 256));
   const bool fast = train_fast_ok(B, d) && workspace_bytes >= train_ws_bytes(B, d);
-  const int ring = fast ? grad_ring(B, d) : 1;
-  const size_t region_floats = grad_region_bytes(B, d) / sizeof(float);
+  // without the prepared path: the hinge step's workspace alone -- one region, no records
+  const TrainWs w = fast ? train_ws(workspace, B, d) : TrainWs{hinge_ws(workspace, B, d), 1, 0, nullptr, 0};
+  int32_t* const gidx = w.g.gidx;
+  float* const gval0 = w.g.gval;
+  const int ring = w.ring;
+  const size_t region_floats = w.region_floats;
   const int direct = hole_direct ? 0 : 1;   // sole-slot rows updated by the producing pair
-  const StepIdentity ident{triples, T, first_row, B, id_to_type, N, type_offsets, n_types, type_ids, seed, global_step0,
-                           padded_size, mode, d, direct, 0, workspace};
-  PrepCursor cur(ident, fast ? static_cast<Pipeline*>(pipe_handle) : nullptr,
-                 reinterpret_cast<int32_t*>(reinterpret_cast<char*>(workspace) + train_grad_bytes(B, d)), st);
+  PrepCursor cur(StepIdentity{q, ts, d, direct, 0, workspace}, fast ? static_cast<Pipeline*>(pipe_handle) : nullptr, w.prep, st);
   const PrepLayout& L = cur.layout();
   if (fast) { int rc = cur.begin(); if (rc) return rc; }
-  auto lr_at = [&](uint64_t gs) {
-    return decay_steps > 0.f ? lr0 / (1.0f + decay_rate * ((float)gs / decay_steps)) : lr0;
-  };
   for (int64_t s = 0; s < n_steps; ++s) {
-    const uint64_t gs = global_step0 + (uint64_t)s;
-    const float lr = lr_at(gs);
-    const int32_t* pos = triples + 3 * step_row(first_row, T, B, s);
+    const uint64_t gs = q.global_step0 + (uint64_t)s;
+    const float lr = hp.lr_at(gs);
+    const int32_t* pos = q.triples + 3 * step_row(q.first_row, q.T, B, s);
     float* loss_s = keep_all_losses ? loss + s * B : loss;
     hipEvent_t e0 = ev_pairs ? (hipEvent_t)ev_pairs[2 * s] : nullptr;
     hipEvent_t e1 = ev_pairs ? (hipEvent_t)ev_pairs[2 * s + 1] : nullptr;
@@ -1032,8 +1018,7 @@ int train_steps_run(float* table, int64_t N, int32_t d, const int32_t* triples, 
       if (rc) return rc;
       neg = step_rec;
     } else {
-      rc = corrupt_batch_launch(pos, B, id_to_type, N, type_offsets, n_types, type_ids, seed, gs, padded_size,
-                                mode, neg_ws, st);
+      rc = corrupt_batch_launch(pos, B, ts, gs, neg_ws, st);
       if (rc) return rc;
       neg = neg_ws;
     }
@@ -1075,47 +1060,48 @@ int train_steps_run(float* table, int64_t N, int32_t d, const int32_t* triples, 
 // pass) at the end of the call, or earlier if |g| leaves [2^-40, 2^40] or a factor is exactly 0.
 // l2_loss(table) enters only the reported loss values: it is summed (one read pass) for the steps whose loss
 // vector the caller keeps (all of them with keep_all_losses, else the last).
+static size_t logloss_region_bytes(int64_t M, int32_t d) { return align_up(sizeof(float) * 3 * (size_t)M * (size_t)d, 256); }
+LoglossWs logloss_ws(void* base, int64_t M, int32_t d) {
+  const size_t idx = align_up(sizeof(int32_t) * 3 * (size_t)M, 256);
+  return LoglossWs{ws_at<float>(base, 0), ws_at<int32_t>(base, 256), ws_at<float>(base, 256 + idx),
+                   256 + idx + logloss_region_bytes(M, d)};
+}
 static size_t logloss_ring(int64_t B, int32_t negs, int32_t d) {
-  const size_t M = (size_t)(1 + negs) * (size_t)B;
-  const size_t region = align_up(sizeof(float) * 3 * M * (size_t)d, 256);
-  size_t ring = ((size_t)64 << 20) / region + 1;
+  size_t ring = ((size_t)64 << 20) / logloss_region_bytes((int64_t)(1 + negs) * B, d) + 1;
   if (ring < 2) ring = 2;
   if (ring > 8) ring = 8;
   return ring;
 }
-static size_t train_logloss_layout_bytes(int64_t B, int32_t negs, int32_t d) {
-  const size_t M = (size_t)(1 + negs) * (size_t)B;
-  const size_t region = align_up(sizeof(float) * 3 * M * (size_t)d, 256);
-  return 256 + align_up(sizeof(int32_t) * 3 * M, 256) + logloss_ring(B, negs, d) * region + 2 * prep_chunk_bytes(B, negs) +
-         prep_big_scratch_bytes(B, negs, prep_chunk_steps(B, negs));
+// the loop's workspace: the log-loss step's of M = (1+K)B triples, its gval RING times (see grad_ring), then the
+// prepared records as in the hinge loop's
+struct LoglossLoopWs { LoglossWs g; size_t ring, region; int32_t* prep; size_t bytes; };
+static LoglossLoopWs train_logloss_ws(void* base, int64_t B, int32_t negs, int32_t d) {
+  const int64_t M = (int64_t)(1 + negs) * B;
+  const LoglossWs g = logloss_ws(base, M, d);
+  const size_t region = logloss_region_bytes(M, d), ring = logloss_ring(B, negs, d);
+  const size_t grad = g.bytes + (ring - 1) * region;
+  return LoglossLoopWs{g, ring, region, ws_at<int32_t>(base, grad), grad + prep_region_bytes(B, negs)};
 }
 size_t train_logloss_ws_bytes(int64_t B, int32_t negs, int32_t d) {
   // monotone in B, as train_ws_bytes is
-  return largest_need_up_to(B, [&](int64_t b) { return train_logloss_layout_bytes(b, negs, d); },
+  return largest_need_up_to(B, [&](int64_t b) { return train_logloss_ws(nullptr, b, negs, d).bytes; },
                             [&](int64_t b) { return std::make_pair(prep_chunk_steps(b, negs), (int64_t)logloss_ring(b, negs, d)); });
 }
 
-int train_logloss_run(float* table, int64_t N, int32_t d, const int32_t* triples, int64_t T, int64_t first_row,
-                      int64_t B, int64_t n_steps, const int32_t* id_to_type, const int64_t* type_offsets,
-                      int32_t n_types, const int32_t* type_ids, uint64_t seed, uint64_t global_step0,
-                      int32_t padded_size, int32_t mode, int32_t negs, float l2, float lr0, float decay_steps,
-                      float decay_rate, float max_norm, float* loss, int keep_all_losses, int32_t* neg_ws,
-                      void* workspace, size_t workspace_bytes, void* pipe_handle, hipStream_t st) {
+int train_logloss_run(float* table, int32_t d, const StepSeq& q, int64_t n_steps, const TypeSampler& ts, int32_t negs,
+                      float l2, const StepHyper& hp, float* loss, int keep_all_losses, int32_t* neg_ws, void* workspace,
+                      size_t workspace_bytes, void* pipe_handle, hipStream_t st) {
+  const int64_t N = ts.N, B = q.B;
+  const float max_norm = hp.max_norm;
   if (n_steps <= 0) return 0;
   if (workspace_bytes < train_logloss_ws_bytes(B, negs, d)) return GE_ENOMEM;
   const size_t M = (size_t)(1 + negs) * (size_t)B;
-  const size_t region = align_up(sizeof(float) * 3 * M * (size_t)d, 256);
-  size_t ring = ((size_t)64 << 20) / region + 1;
-  if (ring < 2) ring = 2;
-  if (ring > 8) ring = 8;
-  char* w = reinterpret_cast<char*>(workspace);
-  float* sumsq = reinterpret_cast<float*>(w);
-  int32_t* gidx = reinterpret_cast<int32_t*>(w + 256);
-  char* gval0 = w + 256 + align_up(sizeof(int32_t) * 3 * M, 256);
-  int32_t* prep_base = reinterpret_cast<int32_t*>(gval0 + ring * region);
-  const StepIdentity ident{triples, T, first_row, B, id_to_type, N, type_offsets, n_types, type_ids, seed, global_step0,
-                           padded_size, mode, d, 0, negs, workspace};
-  PrepCursor cur(ident, static_cast<Pipeline*>(pipe_handle), prep_base, st);
+  const LoglossLoopWs w = train_logloss_ws(workspace, B, negs, d);
+  float* const sumsq = w.g.sumsq;
+  int32_t* const gidx = w.g.gidx;
+  char* const gval0 = reinterpret_cast<char*>(w.g.gval);
+  const size_t ring = w.ring, region = w.region;
+  PrepCursor cur(StepIdentity{q, ts, d, 0, negs, workspace}, static_cast<Pipeline*>(pipe_handle), w.prep, st);
   const PrepLayout& L = cur.layout();
   int rc = cur.begin();
   if (rc) return rc;
@@ -1127,9 +1113,9 @@ int train_logloss_run(float* table, int64_t N, int32_t d, const int32_t* triples
     return r2;
   };
   for (int64_t s = 0; s < n_steps; ++s) {
-    const uint64_t gs = global_step0 + (uint64_t)s;
-    const float lr = decay_steps > 0.f ? lr0 / (1.0f + decay_rate * ((float)gs / decay_steps)) : lr0;
-    const int32_t* pos = triples + 3 * step_row(first_row, T, B, s);
+    const uint64_t gs = q.global_step0 + (uint64_t)s;
+    const float lr = hp.lr_at(gs);
+    const int32_t* pos = q.triples + 3 * step_row(q.first_row, q.T, B, s);
     const int32_t* step_rec = nullptr;
     rc = cur.step(s, &step_rec);
     if (rc) return rc;
@@ -1171,17 +1157,17 @@ int train_logloss_run(float* table, int64_t N, int32_t d, const int32_t* triples
 
 // prepared records of `n_steps` consecutive steps into a caller buffer (tests, tools): the same launch
 // ge_train_steps uses.  For B > 4096 the buffer also holds the multi-tile sort's scratch, behind the records.
-size_t train_prepare_bytes(int64_t B, int64_t n_steps) {
-  return align_up(sizeof(int32_t) * (size_t)n_steps * (size_t)prep_layout(B).stride, 256) + prep_big_scratch_bytes(B, 0, n_steps);
+static size_t prepared_records_bytes(int64_t B, int64_t n_steps) {
+  return align_up(sizeof(int32_t) * (size_t)n_steps * (size_t)prep_layout(B).stride, 256);
 }
-int train_prepare_run(const int32_t* triples, int64_t T, int64_t first_row, int64_t B, int64_t n_steps,
-                      const int32_t* id_to_type, int64_t N, const int64_t* type_offsets, int32_t n_types,
-                      const int32_t* type_ids, uint64_t seed, uint64_t global_step0, int32_t padded_size,
-                      int32_t mode, int direct, int32_t* out, hipStream_t st) {
+size_t train_prepare_bytes(int64_t B, int64_t n_steps) {
+  return prepared_records_bytes(B, n_steps) + prep_big_scratch_bytes(B, 0, n_steps);
+}
+int train_prepare_run(const StepSeq& q, int64_t n_steps, const TypeSampler& ts, int direct, int32_t* out, hipStream_t st) {
   if (n_steps == 0) return 0;
-  void* scratch = reinterpret_cast<char*>(out) + align_up(sizeof(int32_t) * (size_t)n_steps * (size_t)prep_layout(B).stride, 256);
-  return prepare_launch(triples, T, norm_row(first_row, T, B), B, 0, n_steps, id_to_type, N, type_offsets, n_types,
-                        type_ids, seed, global_step0, padded_size, mode, direct ? 1 : 0, out, scratch, st);
+  StepSeq from = q;
+  from.first_row = norm_row(q.first_row, q.T, q.B);
+  return prepare_launch(from, 0, n_steps, ts, direct ? 1 : 0, out, ws_at<void>(out, prepared_records_bytes(q.B, n_steps)), st);
 }
 
 void train_prepared_layout(int64_t B, int64_t* out) {

@@ -130,6 +130,10 @@ class TypeTables:
     def n_types(self) -> int:
         return int(self.type_offsets.numel()) - 1
 
+    def abi(self):
+        """The tables as the C ABI takes them: (id_to_type, type_offsets, n_types, type_ids), pointers as integers."""
+        return self.id_to_type.data_ptr(), self.type_offsets.data_ptr(), self.n_types, self.type_ids.data_ptr()
+
 
 def corrupt_batch(type_tables: TypeTables, relation_count: int, triples: torch.Tensor, *, seed: int = 0,
                   step: int = 0, mode: int = CORRUPT_BATCH_COIN) -> torch.Tensor:
@@ -139,10 +143,9 @@ def corrupt_batch(type_tables: TypeTables, relation_count: int, triples: torch.T
     tb = _triples(triples, "triples")
     _need_cuda(type_tables.id_to_type, "type tables")
     neg = torch.empty_like(tb)
-    _lib.call("ge_corrupt_batch", tb.data_ptr(), tb.shape[0], type_tables.id_to_type.data_ptr(),
-              type_tables.id_to_type.numel(), type_tables.type_offsets.data_ptr(), type_tables.n_types,
-              type_tables.type_ids.data_ptr(), int(seed) & (2**64 - 1), int(step) & (2**64 - 1),
-              type_tables.padded_size, int(mode), neg.data_ptr(), _stream())
+    id_to_type, *rest = type_tables.abi()
+    _lib.call("ge_corrupt_batch", tb.data_ptr(), tb.shape[0], id_to_type, type_tables.id_to_type.numel(), *rest,
+              int(seed) & (2**64 - 1), int(step) & (2**64 - 1), type_tables.padded_size, int(mode), neg.data_ptr(), _stream())
     return neg
 
 
@@ -336,6 +339,42 @@ def rank_fused_ok(d: int, max_norm: float) -> bool:
     return d % 8 == 0 and (0 < d <= 232 or split_sweep_ok(d, max_norm))
 
 
+def _sweep_model(model, who: str, hint: str = "") -> int:
+    """The model code of a sweep of csrc/ge_sweep_route.h: ComplEx, or HolE on a spectral table."""
+    if model not in ("complex", "hole_spectral"):
+        raise ValueError(f"{who}: model must be 'complex' or 'hole_spectral'{hint}")
+    return _MODELS[model]
+
+
+_TRANSFORM_FIRST = " (transform a real HolE table first)"
+
+
+def _known_ok(known_off, known_rc, B=None, K=None):
+    """The known-true lists of a sweep come together; with (B, K) their shape is checked too.  Returns their pointers."""
+    if (known_off is None) != (known_rc is None):
+        raise ValueError("known_off and known_rc come together")
+    if known_off is None:
+        return None, None
+    if B is not None:
+        n_tiles = ((B + 127) // 128) * ((K + 127) // 128)
+        if known_off.dtype != torch.int32 or known_off.numel() != n_tiles + 1 or known_rc.dtype != torch.int16:
+            raise ValueError("known_off must be int32 [tiles+1], known_rc int16 (row%128 << 7 | col%128)")
+    return known_off.data_ptr(), known_rc.data_ptr()
+
+
+def _planes_ptr(planes, emb, cand, K, max_norm, model, who):
+    """(candidates, planes pointer) of a sweep given `planes`: the RankPlanes' own candidate tensor and buffer once they
+    are known to be built for this (table, candidate list, max_norm, model); (cand, None) without planes."""
+    if planes is None or planes.buffer is None:
+        return cand, None
+    same = planes.key == (emb.data_ptr(), emb.shape[0], emb.shape[1], planes.cand.data_ptr(), K, float(max_norm), model)
+    if same and cand.data_ptr() != planes.cand.data_ptr():      # another tensor: compare the ids (one synchronisation)
+        same = bool(torch.equal(planes.cand, cand))
+    if not same:
+        raise ValueError(f"{who}: `planes` were built for another table / candidate list / max_norm / model")
+    return planes.cand, planes.buffer.data_ptr()
+
+
 class RankPlanes:
     """The candidates of a ranking sweep as the split-precision kernel reads them (ge_rank_planes: fp16 high halves and
     remainders of row * clip scale * 2^8 per 64-candidate tile, plus the entity -> position map), built ONCE for all the
@@ -343,8 +382,7 @@ class RankPlanes:
     embedding_dim has no split-precision sweep (rank_candidates then ignores it).  Rebuild after the table changes."""
 
     def __init__(self, embeddings: torch.Tensor, candidates: torch.Tensor, *, max_norm: float = 1.0, model: str = "complex"):
-        if model not in ("complex", "hole_spectral"):
-            raise ValueError("RankPlanes: model must be 'complex' or 'hole_spectral'")
+        code = _sweep_model(model, "RankPlanes")
         emb = _table(embeddings)
         _need_cuda(candidates, "candidates")
         self.cand = candidates.to(torch.int32).contiguous().view(-1)
@@ -354,7 +392,7 @@ class RankPlanes:
         if nbytes > 0:
             self.buffer = torch.empty(nbytes, dtype=torch.uint8, device=emb.device)     # (the allocator aligns to 256 bytes and more)
             _lib.call("ge_rank_planes", emb.data_ptr(), emb.shape[0], emb.shape[1], self.cand.data_ptr(), self.cand.numel(),
-                      max_norm, _MODELS[model], self.buffer.data_ptr(), _stream())
+                      max_norm, code, self.buffer.data_ptr(), _stream())
 
 
 def rank_candidates(embeddings: torch.Tensor, fixed_and_relation: torch.Tensor, true_ids: torch.Tensor,
@@ -369,8 +407,7 @@ def rank_candidates(embeddings: torch.Tensor, fixed_and_relation: torch.Tensor, 
     known_off / known_rc: the per-(128 rows x 128 candidates)-tile lists of known-true cells (evaluate.py).
     model: "complex", or "hole_spectral" for a table held in the frequency domain (hole_to_spectral).
     planes: RankPlanes(embeddings, candidates, ...) built once for many calls (otherwise the kernel rebuilds them)."""
-    if model not in ("complex", "hole_spectral"):
-        raise ValueError("rank_candidates: model must be 'complex' or 'hole_spectral' (transform a real HolE table first)")
+    code = _sweep_model(model, "rank_candidates", _TRANSFORM_FIRST)
     emb = _table(embeddings)
     for name, t in (("fixed_and_relation", fixed_and_relation), ("true_ids", true_ids), ("candidates", candidates)):
         _need_cuda(t, name)
@@ -384,24 +421,10 @@ def rank_candidates(embeddings: torch.Tensor, fixed_and_relation: torch.Tensor, 
     n_known = torch.empty(B, dtype=torch.int32, device=emb.device)
     tl = torch.empty(B, dtype=torch.float32, device=emb.device) if return_true_loss else None
     sc = torch.empty(B, K, dtype=torch.float32, device=emb.device) if return_scores else None
-    if (known_off is None) != (known_rc is None):
-        raise ValueError("known_off and known_rc come together")
-    if known_off is not None:
-        n_tiles = ((B + 127) // 128) * ((K + 127) // 128)
-        if known_off.dtype != torch.int32 or known_off.numel() != n_tiles + 1 or known_rc.dtype != torch.int16:
-            raise ValueError("known_off must be int32 [tiles+1], known_rc int16 (row%128 << 7 | col%128)")
-    pl = None
-    if planes is not None and planes.buffer is not None:
-        same = planes.key == (emb.data_ptr(), emb.shape[0], emb.shape[1], planes.cand.data_ptr(), K, float(max_norm), model)
-        if same and cand.data_ptr() != planes.cand.data_ptr():      # another tensor: compare the ids (one synchronisation)
-            same = bool(torch.equal(planes.cand, cand))
-        if not same:
-            raise ValueError("rank_candidates: `planes` were built for another table / candidate list / max_norm / model")
-        cand, pl = planes.cand, planes.buffer.data_ptr()
+    known = _known_ok(known_off, known_rc, B, K)
+    cand, pl = _planes_ptr(planes, emb, cand, K, max_norm, model, "rank_candidates")
     _lib.call("ge_rank_1vK_planes", emb.data_ptr(), emb.shape[0], emb.shape[1], hr.data_ptr(), B, tid.data_ptr(),
-              cand.data_ptr(), K, max_norm, _MODELS[model], int(cand_is_head),
-              known_off.data_ptr() if known_off is not None else None,
-              known_rc.data_ptr() if known_rc is not None else None, n_before.data_ptr(), n_known.data_ptr(),
+              cand.data_ptr(), K, max_norm, code, int(cand_is_head), *known, n_before.data_ptr(), n_known.data_ptr(),
               tl.data_ptr() if tl is not None else None, sc.data_ptr() if sc is not None else None, pl, _stream())
     out = (n_before, n_known)
     if return_true_loss:
@@ -420,8 +443,7 @@ def rank_candidates_vs_loss(embeddings: torch.Tensor, fixed_and_relation: torch.
     ref_ids[i] -- which need not be among them -- and how many of those are known-true.  What a rank of a row-sharded
     evaluation computes over its own candidates (the counts add across ranks), and what the reference's is_confident
     gate (holE.py:436-438) reduces to: min_loss < threshold  <=>  n_before(threshold, id = INT32_MIN) > 0."""
-    if model not in ("complex", "hole_spectral"):
-        raise ValueError("rank_candidates_vs_loss: model must be 'complex' or 'hole_spectral'")
+    code = _sweep_model(model, "rank_candidates_vs_loss")
     emb = _table(embeddings)
     for name, t in (("fixed_and_relation", fixed_and_relation), ("ref_ids", ref_ids), ("ref_losses", ref_losses),
                     ("candidates", candidates)):
@@ -433,22 +455,13 @@ def rank_candidates_vs_loss(embeddings: torch.Tensor, fixed_and_relation: torch.
     B, K = hr.shape[0], cand.numel()
     if hr.dim() != 2 or hr.shape[1] != 2 or rid.numel() != B or rl.numel() != B:
         raise ValueError("fixed_and_relation must be [B,2] (entity, relation), ref_ids and ref_losses [B]")
-    if (known_off is None) != (known_rc is None):
-        raise ValueError("known_off and known_rc come together")
-    pl = None
-    if planes is not None and planes.buffer is not None:
-        same = planes.key == (emb.data_ptr(), emb.shape[0], emb.shape[1], planes.cand.data_ptr(), K, float(max_norm), model)
-        if same and cand.data_ptr() != planes.cand.data_ptr():
-            same = bool(torch.equal(planes.cand, cand))
-        if not same:
-            raise ValueError("rank_candidates_vs_loss: `planes` were built for another table / candidate list / max_norm / model")
-        cand, pl = planes.cand, planes.buffer.data_ptr()
+    known = _known_ok(known_off, known_rc)
+    cand, pl = _planes_ptr(planes, emb, cand, K, max_norm, model, "rank_candidates_vs_loss")
     n_before = torch.empty(B, dtype=torch.int32, device=emb.device)
     n_known = torch.empty(B, dtype=torch.int32, device=emb.device)
     _lib.call("ge_rank_1vK_vs_loss", emb.data_ptr(), emb.shape[0], emb.shape[1], hr.data_ptr(), B, rid.data_ptr(),
-              rl.data_ptr(), cand.data_ptr(), K, max_norm, _MODELS[model], int(cand_is_head),
-              known_off.data_ptr() if known_off is not None else None,
-              known_rc.data_ptr() if known_rc is not None else None, n_before.data_ptr(), n_known.data_ptr(), pl, _stream())
+              rl.data_ptr(), cand.data_ptr(), K, max_norm, code, int(cand_is_head), *known, n_before.data_ptr(),
+              n_known.data_ptr(), pl, _stream())
     return n_before, n_known
 
 
@@ -467,8 +480,7 @@ def topk_candidates(embeddings: torch.Tensor, fixed_and_relation: torch.Tensor, 
     (ids int32 [B,k], losses float32 [B,k]); a row with fewer eligible candidates is padded with -1 / +inf, a row whose
     ids are out of range is -1 / NaN.  The losses are bit-equal to rank_candidates(..., return_scores=True)'s.
     embedding_dim % 8 == 0 in 56 ... 288, max_norm <= 8, 1 <= k <= topk_max_k(); otherwise GeError (GE_ENOTSUP)."""
-    if model not in ("complex", "hole_spectral"):
-        raise ValueError("topk_candidates: model must be 'complex' or 'hole_spectral' (transform a real HolE table first)")
+    code = _sweep_model(model, "topk_candidates", _TRANSFORM_FIRST)
     emb = _table(embeddings)
     for name, t in (("fixed_and_relation", fixed_and_relation), ("candidates", candidates)):
         _need_cuda(t, name)
@@ -488,20 +500,8 @@ def topk_candidates(embeddings: torch.Tensor, fixed_and_relation: torch.Tensor, 
         raise ValueError("candidates must be distinct")
     if B and bool(((hr < 0) | (hr >= N)).any()):
         raise ValueError("a fixed entity or relation id is outside the table")
-    if (known_off is None) != (known_rc is None):
-        raise ValueError("known_off and known_rc come together")
-    if known_off is not None:
-        n_tiles = ((B + 127) // 128) * ((K + 127) // 128)
-        if known_off.dtype != torch.int32 or known_off.numel() != n_tiles + 1 or known_rc.dtype != torch.int16:
-            raise ValueError("known_off must be int32 [tiles+1], known_rc int16 (row%128 << 7 | col%128)")
-    pl = None
-    if planes is not None and planes.buffer is not None:
-        same = planes.key == (emb.data_ptr(), emb.shape[0], emb.shape[1], planes.cand.data_ptr(), K, float(max_norm), model)
-        if same and cand.data_ptr() != planes.cand.data_ptr():
-            same = bool(torch.equal(planes.cand, cand))
-        if not same:
-            raise ValueError("topk_candidates: `planes` were built for another table / candidate list / max_norm / model")
-        cand, pl = planes.cand, planes.buffer.data_ptr()
+    known = _known_ok(known_off, known_rc, B, K)
+    cand, pl = _planes_ptr(planes, emb, cand, K, max_norm, model, "topk_candidates")
     ids = torch.empty(B, k, dtype=torch.int32, device=emb.device)
     losses = torch.empty(B, k, dtype=torch.float32, device=emb.device)
     if B == 0:
@@ -509,9 +509,7 @@ def topk_candidates(embeddings: torch.Tensor, fixed_and_relation: torch.Tensor, 
     nbytes = int(_lib.load().ge_topk_workspace_bytes(B, K, k))
     ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=emb.device)
     _lib.call("ge_topk_1vK_planes", emb.data_ptr(), N, emb.shape[1], hr.data_ptr(), B, cand.data_ptr(), K, max_norm,
-              _MODELS[model], int(cand_is_head), known_off.data_ptr() if known_off is not None else None,
-              known_rc.data_ptr() if known_rc is not None else None, k, ids.data_ptr(), losses.data_ptr(), pl,
-              ws.data_ptr(), ws.numel(), _stream())
+              code, int(cand_is_head), *known, k, ids.data_ptr(), losses.data_ptr(), pl, ws.data_ptr(), ws.numel(), _stream())
     return ids, losses
 
 
@@ -562,20 +560,15 @@ class ValidationPocket:
         if len(self._steps) >= self.hist.numel():
             raise RuntimeError("ValidationPocket: read() the pending ticks first (capacity %d)" % self.hist.numel())
         tt, i = self.tt, len(self._steps)
+        head = (self.emb.data_ptr(), self.emb.shape[0], self.emb.shape[1], self.valid.data_ptr(), self.valid.shape[0], self.B,
+                *tt.abi(), self.seed & (2**64 - 1), int(counter) & (2**64 - 1), tt.padded_size, self.mode)
+        tail = (self.max_norm,) + (() if self.log_loss is not None else (self.model,)) + (
+            self._ws.data_ptr(), self._ws.numel(), self.hist.data_ptr() + 4 * i, self.best.data_ptr(),
+            self.pocket.data_ptr() if self.pocket is not None else None, _stream())
         if self.log_loss is not None:
-            _lib.call("ge_validation_tick_logloss", self.emb.data_ptr(), self.emb.shape[0], self.emb.shape[1],
-                      self.valid.data_ptr(), self.valid.shape[0], self.B, tt.id_to_type.data_ptr(), tt.type_offsets.data_ptr(),
-                      tt.n_types, tt.type_ids.data_ptr(), self.seed & (2**64 - 1), int(counter) & (2**64 - 1), tt.padded_size,
-                      self.mode, self.log_loss[0], self.log_loss[1], self.max_norm, self._ws.data_ptr(), self._ws.numel(),
-                      self.hist.data_ptr() + 4 * i, self.best.data_ptr(),
-                      self.pocket.data_ptr() if self.pocket is not None else None, _stream())
-            self._steps.append(int(global_step))
-            return
-        _lib.call("ge_validation_tick", self.emb.data_ptr(), self.emb.shape[0], self.emb.shape[1], self.valid.data_ptr(),
-                  self.valid.shape[0], self.B, tt.id_to_type.data_ptr(), tt.type_offsets.data_ptr(), tt.n_types,
-                  tt.type_ids.data_ptr(), self.seed & (2**64 - 1), int(counter) & (2**64 - 1), tt.padded_size, self.mode, self.margin, self.max_norm,
-                  self.model, self._ws.data_ptr(), self._ws.numel(), self.hist.data_ptr() + 4 * i, self.best.data_ptr(),
-                  self.pocket.data_ptr() if self.pocket is not None else None, _stream())
+            _lib.call("ge_validation_tick_logloss", *head, *self.log_loss, *tail)
+        else:
+            _lib.call("ge_validation_tick", *head, self.margin, *tail)
         self._steps.append(int(global_step))
 
     def read(self):
@@ -802,53 +795,44 @@ class Trainer:
         self.invalidate()
         return self
 
-    def _run_logloss(self, n_steps: int, keep_losses: bool):
-        emb, T = self.embeddings, self.triples.shape[0]
-        M = (1 + self.K) * self.B
-        loss = torch.empty(n_steps * M, dtype=torch.float32, device=emb.device) if keep_losses else self.last_loss
-        _lib.call("ge_train_steps_logloss", emb.data_ptr(), emb.shape[0], emb.shape[1], self.triples.data_ptr(), T,
-                  self.row, self.B, n_steps, self.tt.id_to_type.data_ptr(), self.tt.type_offsets.data_ptr(),
-                  self.tt.n_types, self.tt.type_ids.data_ptr(), self.seed & (2**64 - 1), self.global_step,
-                  self.tt.padded_size, self.mode, self.K, self.l2, self.lr0, self.decay_steps, self.decay_rate,
-                  self.max_norm, loss.data_ptr(), int(keep_losses), self._neg.data_ptr(), self._ws.data_ptr(),
-                  self._ws.numel(), self._pipe, _stream())
-        row = self.row % T
+    def _source(self, n_steps: int):
+        """The step sequence and its sampler as both loops take them, up to `mode`."""
+        return (self.triples.data_ptr(), self.triples.shape[0], self.row, self.B, n_steps, *self.tt.abi(),
+                self.seed & (2**64 - 1), self.global_step, self.tt.padded_size, self.mode)
+
+    def _advance(self, n_steps: int):
+        """Mirror the C loops' row bookkeeping (step_row of csrc/ge_prep.h) and step count."""
+        T, row = self.triples.shape[0], self.row % self.triples.shape[0]
         for _ in range(n_steps):
             if row + self.B > T:
                 row = 0
             row += self.B
         self.row = row
         self.global_step += n_steps
-        return loss.view(n_steps, M) if keep_losses else loss
 
     def run(self, n_steps: int, *, keep_losses: bool = False, events=None, ev_kernel: int = 2):
         """Enqueue n_steps training steps on the current stream; returns the loss tensor
-        ([n_steps,B] if keep_losses else the last step's [B])."""
+        ([n_steps,B] if keep_losses else the last step's [B]; with enable_log_loss (1+K)*B per step)."""
         import ctypes as C
-        if getattr(self, "K", 0):
-            return self._run_logloss(n_steps, keep_losses)
-        emb, T = self.embeddings, self.triples.shape[0]
-        loss = (torch.empty(n_steps * self.B, dtype=torch.float32, device=emb.device)
-                if keep_losses else self.last_loss)
-        evp = None
-        if events is not None:
-            assert len(events) == 2 * n_steps
-            evp = (C.c_void_p * len(events))(*events)
-        _lib.call("ge_train_steps", emb.data_ptr(), emb.shape[0], emb.shape[1], self.triples.data_ptr(), T,
-                  self.row, self.B, n_steps, self.tt.id_to_type.data_ptr(), self.tt.type_offsets.data_ptr(),
-                  self.tt.n_types, self.tt.type_ids.data_ptr(), self.seed & (2**64 - 1), self.global_step,
-                  self.tt.padded_size, self.mode, self.margin, self.lr0, self.decay_steps, self.decay_rate,
-                  self.max_norm, self.model | (STEP_DETERMINISTIC if self.deterministic else 0), loss.data_ptr(), int(keep_losses),
-                  self._neg.data_ptr(), self._ws.data_ptr(), self._ws.numel(), evp, int(ev_kernel), self._pipe, _stream())
-        # mirror the C loop's row bookkeeping
-        row = self.row % T
-        for _ in range(n_steps):
-            if row + self.B > T:
-                row = 0
-            row += self.B
-        self.row = row
-        self.global_step += n_steps
-        return loss.view(n_steps, self.B) if keep_losses else loss
+        emb = self.embeddings
+        K = getattr(self, "K", 0)
+        M = (1 + K) * self.B
+        loss = torch.empty(n_steps * M, dtype=torch.float32, device=emb.device) if keep_losses else self.last_loss
+        table = (emb.data_ptr(), emb.shape[0], emb.shape[1])
+        rates = (self.lr0, self.decay_steps, self.decay_rate, self.max_norm)
+        out = (loss.data_ptr(), int(keep_losses), self._neg.data_ptr(), self._ws.data_ptr(), self._ws.numel())
+        if K:
+            _lib.call("ge_train_steps_logloss", *table, *self._source(n_steps), K, self.l2, *rates, *out, self._pipe, _stream())
+        else:
+            evp = None
+            if events is not None:
+                assert len(events) == 2 * n_steps
+                evp = (C.c_void_p * len(events))(*events)
+            _lib.call("ge_train_steps", *table, *self._source(n_steps), self.margin, *rates,
+                      self.model | (STEP_DETERMINISTIC if self.deterministic else 0), *out, evp, int(ev_kernel), self._pipe,
+                      _stream())
+        self._advance(n_steps)
+        return loss.view(n_steps, M) if keep_losses else loss
 
 
 def prepared_layout(batch_size: int):
@@ -870,11 +854,10 @@ def prepare_steps(triples: torch.Tensor, type_tables: TypeTables, batch_size: in
     nbytes = int(_lib.load().ge_train_prepare_bytes(int(batch_size), int(n_steps)))   # records + (B > 4096) sort scratch
     buf = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=tb.device)
     out = buf[:n_steps * lay[0]].view(n_steps, lay[0])
-    tt = type_tables
+    id_to_type, *rest = type_tables.abi()
     _lib.call("ge_train_prepare_steps", tb.data_ptr(), tb.shape[0], int(first_row), int(batch_size), int(n_steps),
-              tt.id_to_type.data_ptr(), tt.id_to_type.numel(), tt.type_offsets.data_ptr(), tt.n_types,
-              tt.type_ids.data_ptr(), int(seed) & (2**64 - 1), int(global_step), tt.padded_size, int(mode),
-              int(bool(direct)), buf.data_ptr(), buf.numel() * 4, _stream())
+              id_to_type, type_tables.id_to_type.numel(), *rest, int(seed) & (2**64 - 1), int(global_step),
+              type_tables.padded_size, int(mode), int(bool(direct)), buf.data_ptr(), buf.numel() * 4, _stream())
     return out
 
 

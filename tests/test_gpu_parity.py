@@ -1019,6 +1019,72 @@ def test_train_steps_lookahead_survives_between_calls(H):
         assert torch.equal(outs[0], o) and torch.equal(losses[0], l)
 
 
+def _lookahead_problem(H):
+    """96 rows, d = 8, B = 8, T = 40 (5 batches a pass), two entity types; the 24 ids of every batch are distinct, so no
+    row collects more than 16 gradient slots in a step and every run is bitwise reproducible."""
+    rng = np.random.default_rng(11)
+    N, d, B, T = 96, 8, 8, 40
+
+    def triples():
+        return np.concatenate([rng.permutation(N)[:3 * B].reshape(B, 3) for _ in range(T // B)]).astype(np.int32)
+
+    def tables(types):
+        order = np.argsort(types, kind="stable").astype(np.int32)
+        return H.TypeTables.from_host(types.astype(np.int32), np.array([0, int((types == 0).sum()), N], np.int64), order,
+                                      padded_size=0)
+
+    ids = np.arange(N)
+    return dict(N=N, d=d, B=B, tri=triples(), tri2=triples(), types=ids % 2, types2=(ids // 7) % 2, tables=tables,
+                table=(rng.standard_normal((N, d)) * 0.3).astype(np.float32))
+
+
+@pytest.mark.parametrize("objective", ["hinge", "log_loss"])
+@pytest.mark.parametrize("change", ["seed", "mode", "padded_size", "tables", "triples", "global_step", "row"])
+def test_lookahead_is_dropped_when_the_source_changes(H, change, objective):
+    """A pipeline handle keeps records prepared ahead (prep_chunk_steps(8) = 32: all six steps lie in chunk 0).  When
+    anything they were drawn from changes between two run() calls -- without invalidate() -- the second call must not
+    consume them: table and losses equal, bit for bit, a trainer without a handle driven the same way (which prepares
+    afresh on every call).  The change is one that matters: without it the same six steps end elsewhere."""
+    P = _lookahead_problem(H)
+    keep_alive = []
+
+    def drive(lookahead, changed):
+        emb = dev(P["table"])
+        tt = P["tables"](P["types"])
+        tr = H.Trainer(emb, dev(P["tri"]), tt, P["B"], seed=8, model="complex", learning_rate=0.5, decay_steps=4.0,
+                       corrupt_mode=H.CORRUPT_HEADS, lookahead=lookahead)
+        if objective == "log_loss":
+            tr.enable_log_loss(1, 0.1)
+        keep_alive.extend([tr.triples, tt])                       # the allocator must not hand their addresses out again
+        losses = [tr.run(3, keep_losses=True)]
+        if changed:
+            if change == "seed":
+                tr.seed = 9
+            elif change == "mode":
+                tr.mode = H.CORRUPT_TAILS
+            elif change == "padded_size":
+                tr.tt.padded_size = 3
+            elif change == "tables":
+                tr.tt = P["tables"](P["types2"])
+            elif change == "triples":
+                tr.triples = dev(P["tri2"])
+            elif change == "global_step":
+                tr.global_step += 5
+            elif change == "row":
+                tr.row += P["B"]
+        losses.append(tr.run(3, keep_losses=True))
+        torch.cuda.synchronize()
+        tr.close()
+        return emb, torch.cat(losses)
+
+    got, got_loss = drive(True, True)
+    ref, ref_loss = drive(False, True)
+    same, _ = drive(True, False)
+    assert not torch.equal(ref, same), "the change does not reach the table: the case checks nothing"
+    assert torch.equal(got_loss, ref_loss)
+    assert torch.equal(got, ref)
+
+
 def test_score_candidates_large_tiles_path(H):
     # >= 512 tiles of 128x128: the chunked 2x2-tiles-per-wave kernel (FB15k evaluation shape family)
     N, d, B, K = 16296, 200, 2048, 8192
