@@ -722,6 +722,61 @@ int ge_topk_1vK_planes(const float* table, int64_t N, int32_t d, const int32_t* 
                          model == GE_MODEL_HOLE_SPECTRAL, planes, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
+int64_t ge_candidate_mask_words(int64_t K) { return candidate_mask_words(K); }
+
+int ge_candidate_mask_from_classes(const int32_t* cand_class, int64_t K, const uint32_t* allow, int32_t n_sets,
+                                   int32_t n_class, uint32_t* mask, void* stream) {
+  if (K < 1 || K > INT32_MAX || n_sets < 1 || n_class < 1 || !cand_class || !allow || !mask) return GE_EINVAL;
+  if (!aligned4(cand_class) || !aligned4(allow) || !aligned4(mask)) return GE_EINVAL;
+  return mask_from_classes_launch(cand_class, K, allow, n_sets, n_class, mask, (hipStream_t)stream);
+}
+
+int ge_candidate_mask_from_cells(const int32_t* cells, int64_t M, int32_t n_sets, int64_t K, uint32_t* mask, void* stream) {
+  if (K < 1 || K > INT32_MAX || n_sets < 1 || M < 0 || !mask || (M > 0 && !cells)) return GE_EINVAL;
+  if (!aligned4(cells) || !aligned4(mask)) return GE_EINVAL;
+  return mask_from_cells_launch(cells, M, n_sets, K, mask, (hipStream_t)stream);
+}
+
+int ge_rank_1vK_masked(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* true_id,
+                       const int32_t* cand, int64_t K, float max_norm, int model, int cand_is_head, const int32_t* known_off,
+                       const uint16_t* known_rc, int32_t* n_before, int32_t* n_known_before, float* true_loss,
+                       float* scores_out, const void* planes, const int32_t* row_set, const uint32_t* mask, int32_t n_sets,
+                       void* stream) {
+  if (B < 0 || K < 0 || !ok_table(table, N, d) || !max_norm_ok(max_norm)) return GE_EINVAL;
+  if (!row_set || !mask || n_sets < 1 || !aligned4(row_set) || !aligned4(mask)) return GE_EINVAL;
+  if (int rc = sweep_model_ok(model)) return rc;
+  if (B > 0 && (!hr || !true_id || !n_before || !n_known_before)) return GE_EINVAL;
+  if (B > 0 && K > 0 && !cand) return GE_EINVAL;
+  if ((known_off == nullptr) != (known_rc == nullptr)) return GE_EINVAL;
+  if (!f16_sweep_ok(d, max_norm)) return GE_ENOTSUP;
+  if (planes && (rank_planes_bytes(N, d, K) == 0 || reinterpret_cast<uintptr_t>(planes) % 256 != 0)) return GE_EINVAL;
+  if (B == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = zero_counts(n_before, n_known_before, B, st)) return rc;
+  if (K == 0) return 0;
+  const SweepArgs a{table, N, d, hr, B, true_id, cand, K, max_norm, cand_is_head, known_off, known_rc, n_before,
+                    n_known_before, true_loss, scores_out, model == GE_MODEL_HOLE_SPECTRAL, /*scores_only=*/0,
+                    /*sweep_flags=*/0};
+  return masked_rank_launch(a, row_set, mask, n_sets, planes, st);
+}
+
+int ge_topk_1vK_masked(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* cand,
+                       int64_t K, float max_norm, int model, int cand_is_head, const int32_t* known_off,
+                       const uint16_t* known_rc, int32_t k, int32_t* out_id, float* out_loss, const void* planes,
+                       void* workspace, size_t workspace_bytes, const int32_t* row_set, const uint32_t* mask,
+                       int32_t n_sets, void* stream) {
+  if (B < 0 || K < 1 || k < 1 || !ok_table(table, N, d) || !max_norm_ok(max_norm)) return GE_EINVAL;
+  if (!row_set || !mask || n_sets < 1 || !aligned4(row_set) || !aligned4(mask)) return GE_EINVAL;
+  if (int rc = sweep_model_ok(model)) return rc;
+  if (B > 0 && (!hr || !cand || !out_id || !out_loss)) return GE_EINVAL;
+  if ((known_off == nullptr) != (known_rc == nullptr)) return GE_EINVAL;
+  if (!f16_sweep_ok(d, max_norm)) return GE_ENOTSUP;
+  if (planes && (rank_planes_bytes(N, d, K) == 0 || reinterpret_cast<uintptr_t>(planes) % 256 != 0)) return GE_EINVAL;
+  return masked_topk_launch(table, N, d, hr, B, cand, K, max_norm, cand_is_head, known_off, known_rc, k, out_id, out_loss,
+                            model == GE_MODEL_HOLE_SPECTRAL, row_set, mask, n_sets, planes, workspace, workspace_bytes,
+                            (hipStream_t)stream);
+}
+
 int ge_rank_1vK(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* true_id,
                 const int32_t* cand, int64_t K, float max_norm, int model, int cand_is_head, const int32_t* known_off,
                 const uint16_t* known_rc, int32_t* n_before, int32_t* n_known_before, float* true_loss,

@@ -111,6 +111,19 @@ int topk_f16_launch(const float* table, int64_t N, int32_t d, const int32_t* hr,
                     size_t workspace_bytes, hipStream_t st);
 int64_t topk_splits(int64_t B, int64_t K);
 
+// ge_rank_f16_masked.hip: the same two sweeps with per-row candidate sets (mask [n_sets][candidate_mask_words(K)], row_set
+// [B]; include/ge_hip.h), split-precision shapes only (GE_ENOTSUP otherwise), and the mask builders
+int64_t candidate_mask_words(int64_t K);
+int mask_from_classes_launch(const int32_t* cand_class, int64_t K, const uint32_t* allow, int32_t n_sets, int32_t n_class,
+                             uint32_t* mask, hipStream_t st);
+int mask_from_cells_launch(const int32_t* cells, int64_t M, int32_t n_sets, int64_t K, uint32_t* mask, hipStream_t st);
+int masked_rank_launch(const SweepArgs& a, const int32_t* row_set, const uint32_t* mask, int32_t n_sets,
+                       const void* planes_ws, hipStream_t st);
+int masked_topk_launch(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* cand, int64_t K,
+                       float max_norm, int cand_is_head, const int32_t* known_off, const uint16_t* known_rc, int32_t k,
+                       int32_t* out_id, float* out_loss, int spec, const int32_t* row_set, const uint32_t* mask,
+                       int32_t n_sets, const void* planes_ws, void* workspace, size_t workspace_bytes, hipStream_t st);
+
 // ge_neighbors.hip: nearest-neighbour search (cosine / Euclidean) on the split-precision sweep; embedding_dim 1 ... 288
 int neighbor_max_k();
 int neighbor_max_dim();

@@ -80,11 +80,185 @@ class KnownIndex:
         return off, rc
 
 
+class CandidateSets:
+    """Per-relation candidate sets of a sweep over `candidates` (the type-constrained, domain / range protocol; the
+    reference's InferenceCandidates, holE.py:493-499, 535-541, gives each group of relations its own tail candidates and
+    leaves "get candidate tail type from training triples" as a TODO, holE.py:533): set s admits a subset of the
+    candidate list, and a query row is ranked against / predicts from the set named by its row set (default: its
+    relation id).
+      mask     int32 [n_sets, 4 * ceil(K / 128)] on the device: bit c & 31 of word c >> 5 = the candidate at position c
+      n_sets, counts (int64 [n_sets] numpy: admissible candidates per set), cand (the int32 device candidate ids)
+    The host part of each builder -- cell lists, allow bitmaps -- is plain numpy (the static methods); the mask itself is
+    built on the device (ge_candidate_mask_from_cells / ge_candidate_mask_from_classes)."""
+
+    def __init__(self, cand: torch.Tensor, mask: torch.Tensor, counts: np.ndarray):
+        self.cand, self.mask = cand, mask
+        self.n_sets = int(mask.shape[0])
+        self.counts = np.asarray(counts, dtype=np.int64)
+
+    # ---- host parts
+    @staticmethod
+    def _candidates(candidates) -> np.ndarray:
+        c = np.asarray(candidates.cpu() if isinstance(candidates, torch.Tensor) else candidates, dtype=np.int64).reshape(-1)
+        if c.size == 0 or c.min() < 0 or np.unique(c).size != c.size:
+            raise ValueError("candidates must be distinct non-negative ids")
+        return c
+
+    @staticmethod
+    def positions_of(candidates: np.ndarray, ids: np.ndarray) -> np.ndarray:
+        """Position of every id in the candidate list (-1: not a candidate)."""
+        ids = np.asarray(ids, dtype=np.int64)
+        order = np.argsort(candidates, kind="stable")
+        j = np.searchsorted(candidates[order], ids)
+        j = np.minimum(j, candidates.size - 1)
+        pos = order[j]
+        return np.where(candidates[pos] == ids, pos, -1)
+
+    @staticmethod
+    def cells_from_lists(candidates, lists: dict, n_sets: int = None):
+        """(cells int32 [M,2] = distinct (set, candidate position) pairs, n_sets) of explicit lists {set: entity ids}.
+        An id that is no candidate, or a set index outside [0, n_sets), is a ValueError."""
+        cand = CandidateSets._candidates(candidates)
+        keys = [int(k) for k in lists.keys()]
+        if n_sets is None:
+            n_sets = max(keys) + 1 if keys else 1
+        if n_sets < 1 or any(k < 0 or k >= n_sets for k in keys):
+            raise ValueError("a set index is outside [0, n_sets)")
+        parts = []
+        for k, ids in lists.items():
+            pos = CandidateSets.positions_of(cand, np.asarray(list(ids), dtype=np.int64).reshape(-1))
+            if (pos < 0).any():
+                raise ValueError(f"set {k} lists an id that is not a candidate")
+            parts.append(np.stack([np.full(pos.size, int(k), dtype=np.int64), pos], 1))
+        cells = np.unique(np.concatenate(parts, 0), axis=0) if parts else np.zeros((0, 2), dtype=np.int64)
+        return cells.astype(np.int32).reshape(-1, 2), int(n_sets)
+
+    @staticmethod
+    def _side_columns(triples, relation_count: int, side: str):
+        if side not in ("tail", "head"):
+            raise ValueError("side must be 'tail' or 'head'")
+        t = np.asarray(triples, dtype=np.int64).reshape(-1, 3)
+        if relation_count < 1 or (t.size and (t[:, 2].min() < 0 or t[:, 2].max() >= relation_count)):
+            raise ValueError("a triple's relation is outside [0, relation_count)")
+        return t[:, 2], t[:, 1 if side == "tail" else 0]
+
+    @staticmethod
+    def cells_from_observed(candidates, triples, relation_count: int, side: str) -> np.ndarray:
+        """cells int32 [M,2]: set r = the candidates seen on `side` of relation r in `triples` ([n,3] head, tail, relation);
+        entities that are no candidates are dropped."""
+        cand = CandidateSets._candidates(candidates)
+        rel, ent = CandidateSets._side_columns(triples, relation_count, side)
+        pos = CandidateSets.positions_of(cand, ent)
+        keep = pos >= 0
+        cells = np.unique(np.stack([rel[keep], pos[keep]], 1), axis=0) if keep.any() else np.zeros((0, 2), dtype=np.int64)
+        return cells.astype(np.int32).reshape(-1, 2)
+
+    @staticmethod
+    def type_codes(id_to_type, n_rows: int = None) -> np.ndarray:
+        """int32 type code per table row (-1: no type) from an integer array, or from a dict id -> type name."""
+        if isinstance(id_to_type, dict):
+            n = (max(id_to_type) + 1 if id_to_type else 0) if n_rows is None else int(n_rows)
+            names = {ty: i for i, ty in enumerate(sorted(set(id_to_type.values()), key=str))}
+            codes = np.full(n, -1, dtype=np.int32)
+            for idx, ty in id_to_type.items():
+                if 0 <= idx < n:
+                    codes[idx] = names[ty]
+            return codes
+        codes = np.asarray(id_to_type)
+        if codes.ndim != 1 or codes.dtype.kind not in "iu":
+            raise ValueError("id_to_type must be a 1-d integer array of type codes (or a dict id -> type)")
+        return codes.astype(np.int32)
+
+    @staticmethod
+    def allow_from_types(id_to_type, triples, relation_count: int, side: str):
+        """(codes int32 [n_rows], allow uint32 [relation_count, ceil(n_class / 32)], n_class): bit t of allow[r] = some
+        triple of relation r has an entity of type t on `side` (untyped entities, code < 0, allow nothing)."""
+        codes = CandidateSets.type_codes(id_to_type)
+        rel, ent = CandidateSets._side_columns(triples, relation_count, side)
+        if ent.size and (ent.min() < 0 or ent.max() >= codes.size):
+            raise ValueError("a triple's entity has no entry in id_to_type")
+        n_class = max(1, int(codes.max()) + 1 if codes.size else 1)
+        allow = np.zeros((relation_count, (n_class + 31) // 32), dtype=np.uint32)
+        ty = codes[ent].astype(np.int64)
+        keep = ty >= 0
+        pairs = np.unique(np.stack([rel[keep], ty[keep]], 1), axis=0) if keep.any() else np.zeros((0, 2), dtype=np.int64)
+        np.bitwise_or.at(allow, (pairs[:, 0], pairs[:, 1] >> 5), (np.uint32(1) << (pairs[:, 1] & 31).astype(np.uint32)))
+        return codes, allow, n_class
+
+    # ---- builders
+    @classmethod
+    def _from_cells(cls, candidates, cells: np.ndarray, n_sets: int, device) -> "CandidateSets":
+        cand = torch.as_tensor(cls._candidates(candidates).astype(np.int32)).to(device)
+        K = cand.numel()
+        mask = torch.empty(n_sets, H.candidate_mask_words(K), dtype=torch.int32, device=device)
+        c = torch.as_tensor(np.ascontiguousarray(cells, dtype=np.int32)).to(device)
+        H._lib.call("ge_candidate_mask_from_cells", c.data_ptr(), c.shape[0], n_sets, K, mask.data_ptr(), H._stream())
+        counts = np.bincount(cells[:, 0], minlength=n_sets) if len(cells) else np.zeros(n_sets, dtype=np.int64)
+        return cls(cand, mask, counts)
+
+    @classmethod
+    def from_lists(cls, candidates, lists: dict, n_sets: int = None, device="cuda") -> "CandidateSets":
+        """Explicit lists {set: entity ids} (the reference's per-group candidate lists, holE.py:495)."""
+        cells, n_sets = cls.cells_from_lists(candidates, lists, n_sets)
+        return cls._from_cells(candidates, cells, n_sets, device)
+
+    @classmethod
+    def from_observed(cls, candidates, triples, relation_count: int, side: str, device="cuda") -> "CandidateSets":
+        """Set r = the candidates seen on `side` ("tail" / "head") of relation r in `triples`."""
+        return cls._from_cells(candidates, cls.cells_from_observed(candidates, triples, relation_count, side),
+                               int(relation_count), device)
+
+    @classmethod
+    def from_types(cls, candidates, id_to_type, triples, relation_count: int, side: str, device="cuda") -> "CandidateSets":
+        """Set r = every candidate whose type was seen on `side` of relation r in `triples` (the reference's TODO,
+        holE.py:533).  id_to_type: int type code per table row (HolEData.type_arrays()[1]; -1: none), or a dict."""
+        cand_np = cls._candidates(candidates)
+        codes, allow, n_class = cls.allow_from_types(id_to_type, triples, relation_count, side)
+        if cand_np.max() >= codes.size:
+            raise ValueError("a candidate has no entry in id_to_type")
+        cand_class = codes[cand_np]
+        cand = torch.as_tensor(cand_np.astype(np.int32)).to(device)
+        K = cand.numel()
+        mask = torch.empty(int(relation_count), H.candidate_mask_words(K), dtype=torch.int32, device=device)
+        cc = torch.as_tensor(np.ascontiguousarray(cand_class, dtype=np.int32)).to(device)
+        al = torch.as_tensor(allow.view(np.int32)).to(device)
+        H._lib.call("ge_candidate_mask_from_classes", cc.data_ptr(), K, al.data_ptr(), int(relation_count), n_class,
+                    mask.data_ptr(), H._stream())
+        hist = np.bincount(cand_class[cand_class >= 0], minlength=n_class).astype(np.int64)
+        bits = (allow[:, np.arange(n_class) >> 5] >> (np.arange(n_class) & 31).astype(np.uint32)) & 1
+        return cls(cand, mask, bits.astype(np.int64) @ hist)
+
+    # ---- what the host-side paths read
+    def _check(self, cand: torch.Tensor, who: str):
+        if self.cand.numel() != cand.numel() or not bool(torch.equal(self.cand.to(cand.device), cand.to(torch.int32))):
+            raise ValueError(f"{who}: candidate_sets were built for another candidate list")
+
+    def row_sets(self, row_sets, default: torch.Tensor, who: str) -> torch.Tensor:
+        """int64 device row sets of a chunk (default: the rows' relation ids), range-checked."""
+        rs = default if row_sets is None else torch.as_tensor(np.asarray(row_sets, dtype=np.int64)).to(default.device)
+        if rs.dim() != 1 or rs.numel() != default.numel():
+            raise ValueError(f"{who}: row_sets must have one entry per row")
+        if rs.numel() and bool(((rs < -1) | (rs >= self.n_sets)).any()):
+            raise ValueError(f"{who}: a row's set index is outside [-1, {self.n_sets})")
+        return rs.to(torch.int64)
+
+    def admissible(self, rs: torch.Tensor, pos: torch.Tensor = None) -> torch.Tensor:
+        """bool [b, K] (pos None), or bool [b] for candidate position pos[i] of row i: admissible in row set rs[i]."""
+        rows = self.mask[rs.clamp(min=0)]
+        if pos is None:
+            p = torch.arange(self.cand.numel(), device=rows.device)
+            bits = (rows[:, p >> 5] >> (p & 31).to(torch.int32)) & 1
+            return (bits != 0) | (rs < 0).view(-1, 1)
+        bits = (rows.gather(1, (pos >> 5).view(-1, 1)).view(-1) >> (pos & 31).to(torch.int32)) & 1
+        return (bits != 0) | (rs < 0)
+
+
 @torch.no_grad()
 def link_prediction_ranks(embeddings: torch.Tensor, test_triples: np.ndarray, candidates: np.ndarray,
                           known_triples: np.ndarray = None, side: str = "tail", batch: int = None,
                           max_norm: float = 1.0, fused: bool = None, model: str = "complex", planes=None,
-                          infer_threshold: float = None, return_confident: bool = False):
+                          infer_threshold: float = None, return_confident: bool = False, candidate_sets=None,
+                          row_sets=None, return_admissible: bool = False):
     """Raw and filtered rank of every test triple's true entity among `candidates`, with the
     semantics of holE.py:446-469.  side="tail": candidates replace the tail; "head": the head.
     known_triples: an [n,3] array, or a KnownIndex built for this side (evaluate_fb15k_style keeps the two it builds).
@@ -100,8 +274,17 @@ def link_prediction_ranks(embeddings: torch.Tensor, test_triples: np.ndarray, ca
     infer_threshold: the reference's gate (holE.py:436-438, flag holE.py:616): a sweep is `is_confident` when the lowest
     loss among its candidates is below the threshold, and ONLY confident sweeps record their positions (holE.py:464-466)
     -- the returned arrays then hold the confident rows' ranks only (return_confident=True adds the bool mask over all
-    test rows).  None: every row is recorded (the reference with a threshold above every loss)."""
+    test rows).  None: every row is recorded (the reference with a threshold above every loss).
+    candidate_sets (CandidateSets built for `candidates` and this side) / row_sets ([n], default each row's relation id;
+    -1: unrestricted): every rank counts only the candidates admissible in the row's set; the true entity need not be one
+    of them (return_admissible=True adds the bool array "true entity admissible in its set").  On the split-precision
+    sweep this is the masked kernel; elsewhere (fused=False, other embedding_dims) the same ranks come from stored losses
+    in chunks of 1024 rows.  Not combined with infer_threshold."""
     assert side in ("tail", "head")
+    if candidate_sets is None and (row_sets is not None or return_admissible):
+        raise ValueError("row_sets / return_admissible need candidate_sets")
+    if candidate_sets is not None and infer_threshold is not None:
+        raise ValueError("candidate_sets with infer_threshold is not implemented")
     if model not in ("complex", "hole", "hole_spectral"):
         raise ValueError(f"unknown model {model!r}")
     dev = embeddings.device
@@ -126,7 +309,15 @@ def link_prediction_ranks(embeddings: torch.Tensor, test_triples: np.ndarray, ca
         # test rows per call: the stored-scores path holds a [batch, K] fp32 matrix; the fused sweep holds nothing
         # per row, and longer calls amortise its per-row-block set-up (the whole FB15k test set is one call)
         batch = 1 << 17 if fused else 16384
-    raw_all, fil_all, conf_all = [], [], []
+    # candidate sets: the masked sweep where the split-precision kernel runs, stored losses elsewhere
+    in_kernel = fused and (candidate_sets is None or H.split_sweep_ok(d, max_norm))
+    if candidate_sets is not None:
+        candidate_sets._check(cand, "link_prediction_ranks")
+        if row_sets is not None and len(row_sets) != len(test):
+            raise ValueError("row_sets must have one entry per test triple")
+        if not in_kernel:
+            batch = min(batch, 1024)
+    raw_all, fil_all, conf_all, adm_all = [], [], [], []
     fixed_col, true_col = (0, 1) if side == "tail" else (1, 0)
     if fused and planes is None:
         planes = H.RankPlanes(embeddings, cand, max_norm=max_norm, model=model)
@@ -144,16 +335,27 @@ def link_prediction_ranks(embeddings: torch.Tensor, test_triples: np.ndarray, ca
         if (tpos < 0).any():
             raise ValueError("a test triple's true entity is not in the candidate list")
         off, rc = index.cells(fixed, rel, pos_of, cand.numel())
-        if fused:
+        rs = None
+        if candidate_sets is not None:
+            rs = candidate_sets.row_sets(None if row_sets is None else row_sets[s:s + batch], rel, "link_prediction_ranks")
+            adm_all.append(candidate_sets.admissible(rs, tpos).cpu().numpy())
+        if in_kernel:
             n_before, n_known = H.rank_candidates(embeddings, hr, true_id, cand, known_off=off, known_rc=rc,
-                                                  cand_is_head=(side == "head"), max_norm=max_norm, model=model, planes=planes)
+                                                  cand_is_head=(side == "head"), max_norm=max_norm, model=model, planes=planes,
+                                                  candidate_sets=candidate_sets, row_sets=rs)
             raw = n_before.to(torch.int64) + 1
             fil = raw - n_known.to(torch.int64)
         else:
-            scores = H.score_candidates(embeddings, hr, cand, cand_is_head=(side == "head"), max_norm=max_norm)
+            if fused:                                # (candidate sets off the split-precision range: the sweep's own losses)
+                scores = H.rank_candidates(embeddings, hr, true_id, cand, cand_is_head=(side == "head"), max_norm=max_norm,
+                                           return_scores=True, model=model, planes=planes)[-1]
+            else:
+                scores = H.score_candidates(embeddings, hr, cand, cand_is_head=(side == "head"), max_norm=max_norm)
             s_true = scores.gather(1, tpos.view(-1, 1))
             # ascending by (loss, triple tuple): among equal losses the smaller entity id pops first
             before = (scores < s_true) | ((scores == s_true) & (cand64.view(1, -1) < true_id.view(-1, 1)))
+            if rs is not None:
+                before &= candidate_sets.admissible(rs)
             raw = before.sum(1) + 1
             # filtered: known-true candidates popped before the target do not advance the rank
             n_ct = (cand.numel() + 127) // 128
@@ -179,7 +381,46 @@ def link_prediction_ranks(embeddings: torch.Tensor, test_triples: np.ndarray, ca
     out = (np.concatenate(raw_all), np.concatenate(fil_all))
     if return_confident:
         out += (np.concatenate(conf_all) if conf_all else np.ones(len(test), dtype=bool),)
+    if return_admissible:
+        out += (np.concatenate(adm_all) if adm_all else np.zeros(0, dtype=bool),)
     return out
+
+
+def evaluate_constrained(embeddings: torch.Tensor, data, kind: str, model: str = "complex", verbose: bool = True):
+    """Type-constrained link prediction over data.test_array, both sides: each row is ranked against its relation's
+    candidate set -- kind "types": every entity whose type was seen on that side of the relation; "observed": the
+    entities seen there -- built from train + valid, which are also the filter.  Returns (block, {side: CandidateSets}):
+    block = {"mrr_and_hits": ..., "admissible_true": share of rows whose true entity is in its set, "mean_set_size":
+    the mean over the ranked rows of their set's size}."""
+    if kind not in ("types", "observed"):
+        raise ValueError("kind must be 'types' or 'observed'")
+    R, N = data.relation_count, data.entity_count
+    cand = np.arange(R, N, dtype=np.int32)
+    parts = [a for a in (data.triples, data.validation_triples) if a is not None]
+    if not parts:
+        raise ValueError("candidate sets are built from the train / valid triples: none found")
+    known = np.concatenate(parts, 0)
+    if model == "hole":
+        embeddings, model = H.hole_to_spectral(embeddings.detach().clone()), "hole_spectral"
+    dev = embeddings.device
+    planes = H.RankPlanes(embeddings, torch.as_tensor(cand).to(dev), model=model) if H.rank_fused_ok(embeddings.shape[1], 1.0) else None
+    id_to_type = data.type_arrays()[1] if kind == "types" else None
+    sets, raw, fil, adm, size = {}, [], [], [], []
+    test = np.asarray(data.test_array, dtype=np.int64)
+    for side in ("tail", "head"):
+        sets[side] = cs = (CandidateSets.from_types(cand, id_to_type, known, R, side, device=dev) if kind == "types"
+                           else CandidateSets.from_observed(cand, known, R, side, device=dev))
+        r, f, a = link_prediction_ranks(embeddings, test, cand, known, side, model=model, planes=planes, candidate_sets=cs,
+                                        return_admissible=True)
+        raw.append(r); fil.append(f); adm.append(a); size.append(cs.counts[test[:, 2]])
+    raw, fil, adm, size = (np.concatenate(x) for x in (raw, fil, adm, size))
+    block = {"mrr_and_hits": mrr_and_hits(raw, fil), "admissible_true": float(adm.mean()) if adm.size else float("nan"),
+             "mean_set_size": float(size.mean()) if size.size else float("nan")}
+    if verbose:
+        print("constrained: ({kind} sets) raw MRR {raw_mrr:.6f}; filtered MRR {filtered_mrr:.6f} (mean rank "
+              "{mean_filtered_pos:.1f}); hits@1/3/10 {hits1:.2f} / {hits3:.2f} / {hits10:.2f} %; ".format(kind=kind, **block["mrr_and_hits"])
+              + "true entity admissible {:.2f} %; mean set size {:.1f}".format(100.0 * block["admissible_true"], block["mean_set_size"]))
+    return block, sets
 
 
 def evaluate_fb15k_style(embeddings: torch.Tensor, data, both_sides: bool = True, batch: int = None,
@@ -262,7 +503,8 @@ def _topk_of_losses(losses: torch.Tensor, cand64: torch.Tensor, k: int, known=No
 
 @torch.no_grad()
 def predict_links(embeddings: torch.Tensor, queries, candidates, k: int, known_triples=None, side: str = "tail",
-                  model: str = "complex", batch: int = None, fused: bool = None, planes=None, max_norm: float = 1.0):
+                  model: str = "complex", batch: int = None, fused: bool = None, planes=None, max_norm: float = 1.0,
+                  candidate_sets=None, row_sets=None):
     """Top-k link prediction: for every query (fixed entity, relation) the first k pops of the reference's heap
     (holE.py:427-469) over `candidates` -- ascending loss E = sigmoid(score), ties by entity id.  side="tail" predicts
     (fixed, ?, relation), "head" (?, fixed, relation).  known_triples (an [n,3] array or a KnownIndex for this side):
@@ -276,8 +518,13 @@ def predict_links(embeddings: torch.Tensor, queries, candidates, k: int, known_t
     model: "complex", "hole" (a real-valued HolE table: a copy is transformed once) or "hole_spectral"; HolE needs the
     fused sweep.  planes: hole.RankPlanes of (embeddings, candidates) shared between calls.  The copy model="hole" makes
     is new on every call, so planes cannot be built for it: with HolE and planes, transform the table once
-    (hole.hole_to_spectral), build the planes with model="hole_spectral" and pass that table and model here."""
+    (hole.hole_to_spectral), build the planes with model="hole_spectral" and pass that table and model here.
+    candidate_sets (CandidateSets for `candidates` and this side) / row_sets ([n], default each query's relation id; -1:
+    unrestricted): only candidates admissible in the row's set are returned -- inside the masked sweep, or by masking the
+    stored losses on the two fallback paths."""
     assert side in ("tail", "head")
+    if candidate_sets is None and row_sets is not None:
+        raise ValueError("row_sets need candidate_sets")
     if model not in ("complex", "hole", "hole_spectral"):
         raise ValueError(f"unknown model {model!r}")
     k = int(k)
@@ -322,6 +569,10 @@ def predict_links(embeddings: torch.Tensor, queries, candidates, k: int, known_t
             raise ValueError("`planes` were built for another candidate list")
         cand = planes.cand
     in_kernel = fused and k <= H.topk_max_k()
+    if candidate_sets is not None:
+        candidate_sets._check(cand, "predict_links")
+        if row_sets is not None and len(row_sets) != len(q):
+            raise ValueError("row_sets must have one entry per query")
     if batch is None:
         batch = 1 << 17 if in_kernel else 1024
     if not in_kernel:
@@ -334,9 +585,13 @@ def predict_links(embeddings: torch.Tensor, queries, candidates, k: int, known_t
         off = rc = None
         if index is not None:
             off, rc = index.cells(fixed, rel, pos_of, K)
+        rs = None
+        if candidate_sets is not None:
+            rs = candidate_sets.row_sets(None if row_sets is None else row_sets[s0:s0 + batch], rel, "predict_links")
         if in_kernel:
             ids, losses = H.topk_candidates(embeddings, hr, cand, k, known_off=off, known_rc=rc, cand_is_head=(side == "head"),
-                                            max_norm=max_norm, model=model, planes=planes)
+                                            max_norm=max_norm, model=model, planes=planes, candidate_sets=candidate_sets,
+                                            row_sets=rs)
             ids = ids.to(torch.int64)
         else:
             if fused:                            # the fused sweep's own losses (MODE 1 of the rank kernel)
@@ -345,6 +600,8 @@ def predict_links(embeddings: torch.Tensor, queries, candidates, k: int, known_t
                                            return_scores=True, model=model, planes=planes)[-1]
             else:
                 losses = H.score_candidates(embeddings, hr, cand, cand_is_head=(side == "head"), max_norm=max_norm)
+            if rs is not None:                   # (every query id is in range: no NaN row to keep apart)
+                losses = torch.where(candidate_sets.admissible(rs), losses, torch.full_like(losses, float("inf")))
             ids, losses = _topk_of_losses(losses, cand64, k, _known_cells_rc(off, rc, K) if off is not None else None)
         ids_all.append(ids.cpu().numpy())
         loss_all.append(losses.cpu().numpy())
@@ -362,14 +619,17 @@ def inference_lines(head: int, relation: int, pop_ids, pop_losses, in_sample_set
 
 @torch.no_grad()
 def predict_inference_results(embeddings: torch.Tensor, data, predict_k: int, infer_threshold: float, path: str,
-                              model: str = "complex", log=print) -> dict:
+                              model: str = "complex", log=print, candidate_sets=None) -> dict:
     """The prediction output of the reference's --infer (holE.py:427-469) for the distinct (head, relation) pairs of the
     test triples, in order of first appearance, over every entity row: for each query whose lowest loss is below
     infer_threshold (is_confident, holE.py:436-438), every pop up to and including the predict_k-th filtered pop --
     known-true (train / valid) pops interleaved with in_sample = True -- as the reference's lines, written to `path`
     (truncated first; the reference appends to ./inference_results.tsv).
     Exact: the filtered top-k gives the k-th filtered pop; its raw position m (rank_candidates_vs_loss, or the stored
-    scores off the fused range) gives the raw top-m that holds every line."""
+    scores off the fused range) gives the raw top-m that holds every line.
+    candidate_sets (CandidateSets over the entity rows, tail side; set = the query's relation): every pop, the gate's
+    lowest loss included, is taken among the tails admissible for the relation; a relation with an empty set writes
+    nothing."""
     R, N = data.relation_count, data.entity_count
     cand = np.arange(R, N, dtype=np.int64)
     test = np.asarray(data.test_array, dtype=np.int64)
@@ -383,17 +643,23 @@ def predict_inference_results(embeddings: torch.Tensor, data, predict_k: int, in
     dev = embeddings.device
     fused = H.split_sweep_ok(embeddings.shape[1], 1.0)
     planes = H.RankPlanes(embeddings, torch.as_tensor(cand).to(dev), model=model) if fused else None
-    kw = dict(model=model, fused=fused, planes=planes)
+    kw = dict(model=model, fused=fused, planes=planes, candidate_sets=candidate_sets)
+    cs = candidate_sets
     K = int(predict_k)
     fid, floss = predict_links(embeddings, queries, cand, K, known_triples=KnownIndex(known, N, "tail", dev), **kw)
     # m = raw position of the K-th filtered pop (every pop when fewer than K candidates are eligible)
-    m = np.full(len(queries), len(cand), dtype=np.int64)
+    m = np.full(len(queries), len(cand), dtype=np.int64) if cs is None else cs.counts[queries[:, 1]].astype(np.int64)
     rows = np.nonzero(fid[:, K - 1] >= 0)[0]
     if rows.size:
         hr = torch.as_tensor(queries[rows]).to(dev).to(torch.int32)
         ref_id = torch.as_tensor(fid[rows, K - 1]).to(dev)
         ref_loss = torch.as_tensor(floss[rows, K - 1]).to(dev)
-        if fused:
+        if fused and cs is not None:
+            # (the K-th filtered pop is a candidate: ranking it as the true entity of the masked sweep counts the admissible
+            # pops before it, its own loss recomputed by the same sweep)
+            nb, _ = H.rank_candidates(embeddings, hr, ref_id, planes.cand, model=model, planes=planes, candidate_sets=cs)
+            m[rows] = nb.cpu().numpy().astype(np.int64) + 1
+        elif fused:
             nb, _ = H.rank_candidates_vs_loss(embeddings, hr, ref_id, ref_loss, planes.cand, model=model, planes=planes)
             m[rows] = nb.cpu().numpy().astype(np.int64) + 1
         else:
@@ -401,12 +667,18 @@ def predict_inference_results(embeddings: torch.Tensor, data, predict_k: int, in
             for s0 in range(0, rows.size, 1024):
                 sc = H.score_candidates(embeddings, hr[s0:s0 + 1024], c64)
                 rl, ri = ref_loss[s0:s0 + 1024, None], ref_id[s0:s0 + 1024, None]
-                m[rows[s0:s0 + 1024]] = (((sc < rl) | ((sc == rl) & (c64[None, :] < ri))).sum(1) + 1).cpu().numpy()
+                before = (sc < rl) | ((sc == rl) & (c64[None, :] < ri))
+                if cs is not None:
+                    before &= cs.admissible(hr[s0:s0 + 1024, 1].to(torch.int64))
+                m[rows[s0:s0 + 1024]] = (before.sum(1) + 1).cpu().numpy()
     # the raw pops: rows sorted by m and cut into chunks, each predicted with its own longest m -- up to 16384 rows
     # while that fits the fused kernel, 1024 rows (the fallback's [rows, K] losses) beyond it
     raw_id = [None] * len(queries)
     raw_loss = [None] * len(queries)
     order = np.argsort(m, kind="stable")
+    for i in order[m[order] == 0]:                           # (an empty set: no pop at all)
+        raw_id[i], raw_loss[i] = np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.float32)
+    order = order[m[order] > 0]
     kmax = H.topk_max_k()
     s0 = 0
     while s0 < order.size:
@@ -421,7 +693,7 @@ def predict_inference_results(embeddings: torch.Tensor, data, predict_k: int, in
     n_conf = n_lines = 0
     with open(path, "w") as out:
         for i, (h, r) in enumerate(queries):
-            if not raw_loss[i][0] < infer_threshold:       # is_confident: the lowest loss of the sweep (holE.py:438)
+            if len(raw_loss[i]) == 0 or not raw_loss[i][0] < infer_threshold:       # is_confident: the lowest loss of the sweep (holE.py:438)
                 continue
             n_conf += 1
             lines = inference_lines(h, r, raw_id[i], raw_loss[i], data.true_triples[int(h)][int(r)])

@@ -375,6 +375,37 @@ def _planes_ptr(planes, emb, cand, K, max_norm, model, who):
     return planes.cand, planes.buffer.data_ptr()
 
 
+def candidate_mask_words(K: int) -> int:
+    """Words per set of a candidate mask over K candidates (ge_candidate_mask_words): 4 per 128-candidate tile."""
+    return 0 if K <= 0 else 4 * ((int(K) + 127) // 128)
+
+
+def _sets_args(candidate_sets, row_sets, hr, cand, who):
+    """() without candidate sets, else (row_set pointer, mask pointer, n_sets) of a masked sweep -- after the host checks:
+    the mask's shape, that it was built for this candidate list, the row sets' length and range (one synchronisation).
+    candidate_sets: anything with .mask (int32 [n_sets, candidate_mask_words(K)], CUDA), .n_sets and .cand (the int32
+    candidate ids it was built for): evaluate.CandidateSets.  row_sets default: each row's relation id."""
+    if candidate_sets is None:
+        if row_sets is not None:
+            raise ValueError(f"{who}: row_sets without candidate_sets")
+        return (), None
+    cs, B, K = candidate_sets, hr.shape[0], cand.numel()
+    mask = cs.mask
+    if (not isinstance(mask, torch.Tensor) or not mask.is_cuda or mask.dtype != torch.int32 or not mask.is_contiguous()
+            or tuple(mask.shape) != (int(cs.n_sets), candidate_mask_words(K)) or cs.n_sets < 1):
+        raise ValueError(f"{who}: candidate_sets.mask must be a contiguous CUDA int32 [n_sets, {candidate_mask_words(K)}] "
+                         f"tensor for these {K} candidates")
+    if cs.cand.numel() != K or (cs.cand.data_ptr() != cand.data_ptr() and not bool(torch.equal(cs.cand.to(cand.device), cand))):
+        raise ValueError(f"{who}: candidate_sets were built for another candidate list")
+    rs = hr[:, 1] if row_sets is None else torch.as_tensor(row_sets).to(hr.device)
+    if rs.dim() != 1 or rs.numel() != B or rs.dtype.is_floating_point:
+        raise ValueError(f"{who}: row_sets must be [B] integers")
+    if B and bool(((rs < -1) | (rs >= cs.n_sets)).any()):
+        raise ValueError(f"{who}: a row's set index is outside [-1, {cs.n_sets})")
+    rs = rs.to(torch.int32).contiguous()
+    return (rs.data_ptr(), mask.data_ptr(), int(cs.n_sets)), rs     # (rs: kept alive by the caller until the launch)
+
+
 class RankPlanes:
     """The candidates of a ranking sweep as the split-precision kernel reads them (ge_rank_planes: fp16 high halves and
     remainders of row * clip scale * 2^8 per 64-candidate tile, plus the entity -> position map), built ONCE for all the
@@ -399,14 +430,17 @@ def rank_candidates(embeddings: torch.Tensor, fixed_and_relation: torch.Tensor, 
                     candidates: torch.Tensor, *, known_off: Optional[torch.Tensor] = None,
                     known_rc: Optional[torch.Tensor] = None, cand_is_head: bool = False, max_norm: float = 1.0,
                     return_true_loss: bool = False, return_scores: bool = False, model: str = "complex",
-                    planes: Optional[RankPlanes] = None):
+                    planes: Optional[RankPlanes] = None, candidate_sets=None, row_sets=None):
     """The candidate sweep of holE.py:564-569 with the ranking of holE.py:427-472 as its epilogue
     (ge_complex_rank_1vK): per test row the number of candidates that pop from the reference's heap before the
     true one (n_before; raw rank = 1 + n_before) and how many of those are known-true (n_known_before; filtered
     rank = raw - n_known_before).  No [B,K] score matrix exists unless return_scores asks for it (tests).
     known_off / known_rc: the per-(128 rows x 128 candidates)-tile lists of known-true cells (evaluate.py).
     model: "complex", or "hole_spectral" for a table held in the frequency domain (hole_to_spectral).
-    planes: RankPlanes(embeddings, candidates, ...) built once for many calls (otherwise the kernel rebuilds them)."""
+    planes: RankPlanes(embeddings, candidates, ...) built once for many calls (otherwise the kernel rebuilds them).
+    candidate_sets (evaluate.CandidateSets) / row_sets ([B], default the row's relation id; -1: unrestricted): only the
+    candidates admissible in the row's set are counted (ge_rank_1vK_masked); losses and true_loss are unchanged.  The
+    split-precision range only (split_sweep_ok), otherwise GeError (GE_ENOTSUP); bad sets raise ValueError."""
     code = _sweep_model(model, "rank_candidates", _TRANSFORM_FIRST)
     emb = _table(embeddings)
     for name, t in (("fixed_and_relation", fixed_and_relation), ("true_ids", true_ids), ("candidates", candidates)):
@@ -423,9 +457,11 @@ def rank_candidates(embeddings: torch.Tensor, fixed_and_relation: torch.Tensor, 
     sc = torch.empty(B, K, dtype=torch.float32, device=emb.device) if return_scores else None
     known = _known_ok(known_off, known_rc, B, K)
     cand, pl = _planes_ptr(planes, emb, cand, K, max_norm, model, "rank_candidates")
-    _lib.call("ge_rank_1vK_planes", emb.data_ptr(), emb.shape[0], emb.shape[1], hr.data_ptr(), B, tid.data_ptr(),
+    sets, _rs = _sets_args(candidate_sets, row_sets, hr, cand, "rank_candidates")
+    _lib.call("ge_rank_1vK_masked" if sets else "ge_rank_1vK_planes", emb.data_ptr(), emb.shape[0], emb.shape[1],
+              hr.data_ptr(), B, tid.data_ptr(),
               cand.data_ptr(), K, max_norm, code, int(cand_is_head), *known, n_before.data_ptr(), n_known.data_ptr(),
-              tl.data_ptr() if tl is not None else None, sc.data_ptr() if sc is not None else None, pl, _stream())
+              tl.data_ptr() if tl is not None else None, sc.data_ptr() if sc is not None else None, pl, *sets, _stream())
     out = (n_before, n_known)
     if return_true_loss:
         out += (tl,)
@@ -473,13 +509,15 @@ def topk_max_k() -> int:
 def topk_candidates(embeddings: torch.Tensor, fixed_and_relation: torch.Tensor, candidates: torch.Tensor, k: int, *,
                     known_off: Optional[torch.Tensor] = None, known_rc: Optional[torch.Tensor] = None,
                     cand_is_head: bool = False, max_norm: float = 1.0, model: str = "complex",
-                    planes: Optional[RankPlanes] = None):
+                    planes: Optional[RankPlanes] = None, candidate_sets=None, row_sets=None):
     """The first k pops of the reference's heap (holE.py:427-469: ascending loss, ties by entity id) per query row
     (fixed entity, relation) among `candidates`, on the split-precision sweep (ge_topk_1vK_planes) -- no [B,K] matrix.
     With known_off / known_rc (as rank_candidates takes them) known-true candidates are skipped.  Returns
     (ids int32 [B,k], losses float32 [B,k]); a row with fewer eligible candidates is padded with -1 / +inf, a row whose
     ids are out of range is -1 / NaN.  The losses are bit-equal to rank_candidates(..., return_scores=True)'s.
-    embedding_dim % 8 == 0 in 56 ... 288, max_norm <= 8, 1 <= k <= topk_max_k(); otherwise GeError (GE_ENOTSUP)."""
+    embedding_dim % 8 == 0 in 56 ... 288, max_norm <= 8, 1 <= k <= topk_max_k(); otherwise GeError (GE_ENOTSUP).
+    candidate_sets / row_sets (as rank_candidates takes them): the first k pops that are admissible in the row's set and
+    not known (ge_topk_1vK_masked); an empty set gives a row of -1 / +inf."""
     code = _sweep_model(model, "topk_candidates", _TRANSFORM_FIRST)
     emb = _table(embeddings)
     for name, t in (("fixed_and_relation", fixed_and_relation), ("candidates", candidates)):
@@ -502,14 +540,16 @@ def topk_candidates(embeddings: torch.Tensor, fixed_and_relation: torch.Tensor, 
         raise ValueError("a fixed entity or relation id is outside the table")
     known = _known_ok(known_off, known_rc, B, K)
     cand, pl = _planes_ptr(planes, emb, cand, K, max_norm, model, "topk_candidates")
+    sets, _rs = _sets_args(candidate_sets, row_sets, hr, cand, "topk_candidates")
     ids = torch.empty(B, k, dtype=torch.int32, device=emb.device)
     losses = torch.empty(B, k, dtype=torch.float32, device=emb.device)
     if B == 0:
         return ids, losses
     nbytes = int(_lib.load().ge_topk_workspace_bytes(B, K, k))
     ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=emb.device)
-    _lib.call("ge_topk_1vK_planes", emb.data_ptr(), N, emb.shape[1], hr.data_ptr(), B, cand.data_ptr(), K, max_norm,
-              code, int(cand_is_head), *known, k, ids.data_ptr(), losses.data_ptr(), pl, ws.data_ptr(), ws.numel(), _stream())
+    _lib.call("ge_topk_1vK_masked" if sets else "ge_topk_1vK_planes", emb.data_ptr(), N, emb.shape[1], hr.data_ptr(), B,
+              cand.data_ptr(), K, max_norm, code, int(cand_is_head), *known, k, ids.data_ptr(), losses.data_ptr(), pl,
+              ws.data_ptr(), ws.numel(), *sets, _stream())
     return ids, losses
 
 

@@ -54,6 +54,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('--predict_k', type=int, default=0,
                    help='With --infer: also write <output_dir>/inference_results.tsv, every pop up to the K-th filtered '
                         'prediction of each confident (head, relation) test query (0: no predictions).')
+    p.add_argument('--candidate_sets', choices=['types', 'observed'], default=None,
+                   help='With --infer: also rank every test triple against its relation\'s own candidate set (types: every '
+                        'entity whose type was seen on that side of the relation in train + valid; observed: the entities seen '
+                        'there) and print a "constrained:" line; --predict_k then predicts from the tail sets only.')
     p.add_argument('--relation_ranks', action='store_true',
                    help='With --infer: also rank every test triple\'s relation among all relation rows, (h, ?, t), '
                         'filtered by train + valid; prints the line and returns it as the `relation` block.  One GPU.')
@@ -246,10 +250,16 @@ def infer_triples(FLAGS, log=print) -> dict:
     # --model hole: the checkpoint holds the real-valued table; ranks use the HolE score (README.md:42), not ComplEx
     # positions are recorded for confident sweeps only: lowest loss < --infer_threshold (holE.py:436-438, 464-466, 616)
     out = E.evaluate_fb15k_style(emb, data, both_sides=True, model=FLAGS.model, infer_threshold=FLAGS.infer_threshold)
+    tail_sets = None
+    if getattr(FLAGS, 'candidate_sets', None):
+        # the type-constrained protocol: the sets come from train + valid, every test row is recorded (no gate)
+        out['constrained'], sets = E.evaluate_constrained(emb, data, FLAGS.candidate_sets, model=FLAGS.model)
+        tail_sets = sets['tail']
     if FLAGS.predict_k > 0:
         # the reference's prediction lines (holE.py:445-456), into the output directory (truncated), not appended to ./
         E.predict_inference_results(emb, data, FLAGS.predict_k, FLAGS.infer_threshold,
-                                    os.path.join(FLAGS.output_dir, 'inference_results.tsv'), model=FLAGS.model, log=log)
+                                    os.path.join(FLAGS.output_dir, 'inference_results.tsv'), model=FLAGS.model, log=log,
+                                    candidate_sets=tail_sets)
     if getattr(FLAGS, 'relation_ranks', False):
         # (h, ?, t): the head-side sweep over the relation rows on the triples with head and relation exchanged
         parts = [a for a in (data.triples, data.validation_triples) if a is not None]
@@ -292,6 +302,16 @@ def check_classify_flags(FLAGS, world: int = 1) -> None:
         raise SystemExit('--classify runs on one GPU (drop --gpus)')
     if FLAGS.classify_seed < 0:
         raise SystemExit('--classify_seed must be >= 0')
+
+
+def check_candidate_set_flags(FLAGS, world: int = 1) -> None:
+    """--candidate_sets is part of --infer, on one GPU."""
+    if not getattr(FLAGS, 'candidate_sets', None):
+        return
+    if not FLAGS.infer:
+        raise SystemExit('--candidate_sets needs --infer')
+    if FLAGS.gpus > 1 or world > 1:
+        raise SystemExit('--candidate_sets runs on one GPU (drop --gpus)')
 
 
 def check_neighbor_flags(FLAGS, world: int = 1) -> None:
@@ -357,6 +377,7 @@ def main(argv=None):
         raise SystemExit('--predict_k runs on one GPU: top-k prediction over a row-sharded table is not implemented '
                          '(drop --gpus or --predict_k)')
     check_classify_flags(FLAGS, world)
+    check_candidate_set_flags(FLAGS, world)
     if FLAGS.relation_ranks and not FLAGS.infer:
         raise SystemExit('--relation_ranks needs --infer')
     if FLAGS.relation_ranks and (FLAGS.gpus > 1 or world > 1):

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define GE_VERSION 400 /* 0.4.0: + ge_threshold_fit / ge_threshold_classify (triple classification) */
+#define GE_VERSION 410 /* 0.4.1: + ge_rank_1vK_masked / ge_topk_1vK_masked and the mask builders (per-relation candidate sets) */
 
 /* argument errors (negative, -errno style) */
 #define GE_EINVAL (-22)  /* bad dimension / null pointer / misaligned buffer */
@@ -525,6 +525,44 @@ int ge_topk_1vK_planes(const float* table, int64_t N, int32_t d, const int32_t* 
                        int64_t K, float max_norm, int model, int cand_is_head, const int32_t* known_off,
                        const uint16_t* known_rc, int32_t k, int32_t* out_id, float* out_loss, const void* planes,
                        void* workspace, size_t workspace_bytes, void* stream);
+
+/* --- per-relation candidate sets on the two sweeps above (the type-constrained protocol; holE.py:493-499, 535-541 give
+ * each group of relations its own tail candidates).  A sweep over cand[K] takes
+ *     mask     uint32 [n_sets][W], W = ge_candidate_mask_words(K) = 4 * ceil(K / 128) (0 for K <= 0): bit c & 31 of word
+ *              c >> 5 of row s is set iff the candidate at POSITION c of `cand` is admissible in set s; bits at positions
+ *              >= K are ignored
+ *     row_set  int32 [B]: row i uses set row_set[i]; -1: unrestricted.  Any other value outside [0, n_sets) makes the row
+ *              a bad row, with exactly what a fixed id out of range gives (ranks: counts 0, true_loss and stored losses
+ *              NaN; top-k: id -1, loss NaN in every slot).
+ * ge_rank_1vK_masked: n_before[i] counts the ADMISSIBLE candidates whose (E, id) is below the true candidate's,
+ * n_known_before[i] those of them that are known cells; true_loss and scores_out are unchanged.  The true candidate
+ * need not be admissible: its rank is the position it would take among the admissible ones (as ge_rank_1vK_vs_loss).
+ * ge_topk_1vK_masked: the first k pops that are admissible and not known; fewer than k of them, or an empty set: id -1,
+ * loss +inf padding.  workspace: ge_topk_workspace_bytes(B, K, k).
+ * The losses are the unmasked sweep's, bit for bit: every masked result is a function of what ge_rank_1vK_planes stores
+ * in scores_out, and with every bit set, or row_set = -1, the outputs equal the unmasked entry points' bitwise.
+ * Scope: the split-precision range only (embedding_dim % 8 == 0 in 56 ... 288, max_norm <= 8, GE_MODEL_COMPLEX or
+ * GE_MODEL_HOLE_SPECTRAL), else GE_ENOTSUP -- the fp32 kernels take no mask.  A null mask or row_set, or n_sets < 1:
+ * GE_EINVAL.  No host synchronisation, no allocation beyond the planes' stream-ordered one when planes is NULL.
+ * Mask builders (all device pointers):
+ *   ge_candidate_mask_from_classes  mask[s] <- the candidates c with allow[s] bit cand_class[c] set; cand_class int32 [K]
+ *                                   (a class outside [0, n_class): never admissible), allow uint32 [n_sets][ceil(n_class/32)]
+ *   ge_candidate_mask_from_cells    mask <- 0, then the bit of every (set, position) pair of cells int32 [M][2]; pairs
+ *                                   outside [0, n_sets) x [0, K) are ignored */
+int64_t ge_candidate_mask_words(int64_t K);
+int ge_candidate_mask_from_classes(const int32_t* cand_class, int64_t K, const uint32_t* allow, int32_t n_sets,
+                                   int32_t n_class, uint32_t* mask, void* stream);
+int ge_candidate_mask_from_cells(const int32_t* cells, int64_t M, int32_t n_sets, int64_t K, uint32_t* mask, void* stream);
+int ge_rank_1vK_masked(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* true_id,
+                       const int32_t* cand, int64_t K, float max_norm, int model, int cand_is_head, const int32_t* known_off,
+                       const uint16_t* known_rc, int32_t* n_before, int32_t* n_known_before, float* true_loss,
+                       float* scores_out, const void* planes, const int32_t* row_set, const uint32_t* mask, int32_t n_sets,
+                       void* stream);
+int ge_topk_1vK_masked(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* cand,
+                       int64_t K, float max_norm, int model, int cand_is_head, const int32_t* known_off,
+                       const uint16_t* known_rc, int32_t k, int32_t* out_id, float* out_loss, const void* planes,
+                       void* workspace, size_t workspace_bytes, const int32_t* row_set, const uint32_t* mask,
+                       int32_t n_sets, void* stream);
 
 /* --- the known_off / known_rc lists of ge_rank_1vK from a sorted index of the known-true triples (the filter of
  * holE.py:454-463, built by the reference as a dict of sets, holE.py:413-422).  known_key [M] ascending = fixed entity *
