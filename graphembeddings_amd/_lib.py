@@ -126,6 +126,15 @@ SYMBOLS = {
     "ge_transr_topk_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32, _i64, _i32]),
     "ge_transr_topk": (C.c_int, [C.c_int, _p, _i64, _p, _p, _i64, _i32, _i32, _p, _i64, C.c_int, _p, _p, _i32, _p, _p,
                                  _p, _sz, _p]),
+    # (row_set, mask, n_sets) after the known-cell pointers; the rank forms have no scores_out
+    "ge_transx_rank_masked": (C.c_int, [C.c_int, C.c_int, _p, _i64, _p, _i64, _p, _p, _p, _i32, _p, _i64, C.c_int, _p, _p,
+                                        _p, _p, _i32, _p, _p, _p, _p, _sz, _p]),
+    "ge_transr_rank_masked": (C.c_int, [C.c_int, _p, _i64, _p, _p, _i64, _i32, _i32, _p, _i64, C.c_int, _p, _p,
+                                        _p, _p, _i32, _p, _p, _p, _p, _sz, _p]),
+    "ge_transx_topk_masked": (C.c_int, [C.c_int, C.c_int, _p, _i64, _p, _i64, _p, _p, _p, _i32, _p, _i64, C.c_int, _p, _p,
+                                        _p, _p, _i32, _i32, _p, _p, _p, _sz, _p]),
+    "ge_transr_topk_masked": (C.c_int, [C.c_int, _p, _i64, _p, _p, _i64, _i32, _i32, _p, _i64, C.c_int, _p, _p,
+                                        _p, _p, _i32, _i32, _p, _p, _p, _sz, _p]),
     "ge_threshold_fit_workspace_bytes": (_sz, [_i64, _i32]),
     "ge_threshold_fit": (C.c_int, [_p, _p, _p, _i64, _i32, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "ge_threshold_classify": (C.c_int, [_p, _p, _p, _i64, _i32, _p, _p, _p, _p]),

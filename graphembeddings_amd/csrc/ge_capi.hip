@@ -560,6 +560,76 @@ int ge_transr_topk(int l1, const float* ent, int64_t n_ent, const float* rel, co
                     stream);
 }
 
+// The same sweeps with per-relation candidate sets (ge_transx_rank_masked.hip): the sets, then the unmasked order.
+static int sets_ok(const int32_t* row_set, const uint32_t* mask, int32_t n_sets) {
+  return row_set && mask && n_sets >= 1 && aligned4(row_set) && aligned4(mask) ? 0 : GE_EINVAL;
+}
+static int trans_rank_masked(const TransModel& m, const int32_t* triples, int64_t B, int cand_is_head, const RankOut& o,
+                             const int32_t* row_set, const uint32_t* mask, int32_t n_sets, void* workspace,
+                             size_t workspace_bytes, void* stream) {
+  if (int rc = sets_ok(row_set, mask, n_sets)) return rc;
+  if (int rc = rank_outputs_ok(B, triples, o, workspace)) return rc;
+  if (B == 0) return 0;
+  return trans_rank_masked_launch(m, triples, B, cand_is_head, o, row_set, mask, n_sets, workspace, workspace_bytes,
+                                  (hipStream_t)stream);
+}
+static int trans_topk_masked(const TransModel& m, const int32_t* queries, int64_t B, int cand_is_head,
+                             const int32_t* known_off, const uint16_t* known_rc, const int32_t* row_set,
+                             const uint32_t* mask, int32_t n_sets, int32_t k, int32_t* out_id, float* out_dist,
+                             void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = sets_ok(row_set, mask, n_sets)) return rc;
+  if (int rc = topk_outputs_ok(B, queries, known_off, known_rc, k, out_id, out_dist, workspace)) return rc;
+  if (B == 0) return 0;
+  return trans_topk_masked_launch(m, queries, B, cand_is_head, known_off, known_rc, k, out_id, out_dist, row_set, mask,
+                                  n_sets, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int ge_transx_rank_masked(int model, int l1, const float* ent, int64_t n_ent, const float* rel, int64_t n_rel,
+                          const float* normal, const float* ent_transfer, const float* rel_transfer, int32_t d,
+                          const int32_t* triples, int64_t B, int cand_is_head, const int32_t* known_off,
+                          const uint16_t* known_rc, const int32_t* row_set, const uint32_t* mask, int32_t n_sets,
+                          int32_t* n_before, int32_t* n_known_before, float* true_dist, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+  TransModel m;
+  if (int rc = transx_model(m, model, l1, ent, n_ent, rel, n_rel, normal, ent_transfer, rel_transfer, d)) return rc;
+  return trans_rank_masked(m, triples, B, cand_is_head, {known_off, known_rc, n_before, n_known_before, true_dist, nullptr},
+                           row_set, mask, n_sets, workspace, workspace_bytes, stream);
+}
+
+int ge_transr_rank_masked(int l1, const float* ent, int64_t n_ent, const float* rel, const float* rel_matrix,
+                          int64_t n_rel, int32_t dim_e, int32_t dim_r, const int32_t* triples, int64_t B,
+                          int cand_is_head, const int32_t* known_off, const uint16_t* known_rc, const int32_t* row_set,
+                          const uint32_t* mask, int32_t n_sets, int32_t* n_before, int32_t* n_known_before,
+                          float* true_dist, void* workspace, size_t workspace_bytes, void* stream) {
+  TransModel m;
+  if (int rc = transr_model(m, l1, ent, n_ent, rel, rel_matrix, n_rel, dim_e, dim_r)) return rc;
+  return trans_rank_masked(m, triples, B, cand_is_head, {known_off, known_rc, n_before, n_known_before, true_dist, nullptr},
+                           row_set, mask, n_sets, workspace, workspace_bytes, stream);
+}
+
+int ge_transx_topk_masked(int model, int l1, const float* ent, int64_t n_ent, const float* rel, int64_t n_rel,
+                          const float* normal, const float* ent_transfer, const float* rel_transfer, int32_t d,
+                          const int32_t* queries, int64_t B, int cand_is_head, const int32_t* known_off,
+                          const uint16_t* known_rc, const int32_t* row_set, const uint32_t* mask, int32_t n_sets,
+                          int32_t k, int32_t* out_id, float* out_dist, void* workspace, size_t workspace_bytes,
+                          void* stream) {
+  TransModel m;
+  if (int rc = transx_model(m, model, l1, ent, n_ent, rel, n_rel, normal, ent_transfer, rel_transfer, d)) return rc;
+  return trans_topk_masked(m, queries, B, cand_is_head, known_off, known_rc, row_set, mask, n_sets, k, out_id, out_dist,
+                           workspace, workspace_bytes, stream);
+}
+
+int ge_transr_topk_masked(int l1, const float* ent, int64_t n_ent, const float* rel, const float* rel_matrix,
+                          int64_t n_rel, int32_t dim_e, int32_t dim_r, const int32_t* queries, int64_t B,
+                          int cand_is_head, const int32_t* known_off, const uint16_t* known_rc, const int32_t* row_set,
+                          const uint32_t* mask, int32_t n_sets, int32_t k, int32_t* out_id, float* out_dist,
+                          void* workspace, size_t workspace_bytes, void* stream) {
+  TransModel m;
+  if (int rc = transr_model(m, l1, ent, n_ent, rel, rel_matrix, n_rel, dim_e, dim_r)) return rc;
+  return trans_topk_masked(m, queries, B, cand_is_head, known_off, known_rc, row_set, mask, n_sets, k, out_id, out_dist,
+                           workspace, workspace_bytes, stream);
+}
+
 static inline int neighbor_args_ok(const float* table, int64_t N, int32_t d, const int32_t* queries, int64_t B,
                                    const int32_t* cand, int64_t K, int metric, const void* planes) {
   if (!ok_table(table, N, d) || B < 0 || B > ((int64_t)1 << 28) || K <= 0 || K > INT32_MAX) return GE_EINVAL;

@@ -737,64 +737,138 @@ def _translation_sweep_setup(model, rel, known, side: str):
     return order, index, pos_of
 
 
+def _translation_sets(model, candidate_sets, row_sets, n_rows: int, who: str):
+    """The host checks of a translation-model sweep's candidate sets, before any device work: built for arange(n_ent),
+    one row set per row, every index in [-1, n_sets).  Returns row_sets as an int64 numpy array, or None (the default:
+    each row's relation id)."""
+    if not isinstance(candidate_sets, CandidateSets):
+        raise ValueError(f"{who}: candidate_sets must be a CandidateSets")
+    if candidate_sets.cand.numel() != model.n_ent:
+        raise ValueError(f"{who}: candidate_sets were built for another candidate list (need arange(n_ent))")
+    if row_sets is None:
+        if candidate_sets.n_sets < model.n_rel:
+            raise ValueError(f"{who}: the default row set is the relation id, but candidate_sets holds "
+                             f"{candidate_sets.n_sets} sets for {model.n_rel} relations")
+        return None
+    rs = np.asarray(row_sets.cpu().numpy() if isinstance(row_sets, torch.Tensor) else row_sets)
+    if rs.ndim != 1 or rs.shape[0] != n_rows:
+        raise ValueError(f"{who}: row_sets must have one entry per row")
+    if rs.size and not np.issubdtype(rs.dtype, np.integer):
+        raise ValueError(f"{who}: row_sets must be integer set indices")
+    rs = rs.astype(np.int64)
+    if rs.size and (rs.min() < -1 or rs.max() >= candidate_sets.n_sets):
+        raise ValueError(f"{who}: a row's set index is outside [-1, {candidate_sets.n_sets})")
+    return rs
+
+
 @torch.no_grad()
-def translation_ranks(model, test, known=None, side: str = "tail", batch: int = None):
+def translation_ranks(model, test, known=None, side: str = "tail", batch: int = None, candidate_sets=None,
+                      row_sets=None, return_admissible: bool = False):
     """Raw and filtered rank of every test triple's true entity among ALL entities for a TransX or TransR model
     (int64 arrays, in test order).  side="tail": every entity replaces the tail; "head": the head.  Order: ascending
     by (D, entity id), as link_prediction_ranks.  known: an [n,3] array of triples to filter, or a KnownIndex built
     for this side with n_rows = max(n_ent, n_rel) (None: filtered == raw).  The rows are grouped by relation for the
     sweep (a stable sort on the host) and the ranks returned in the caller's order; a row's ranks do not depend on
-    the grouping.  batch: rows per native call (default 131072)."""
+    the grouping.  batch: rows per native call (default 131072).
+    candidate_sets (CandidateSets built for arange(n_ent) and this side) / row_sets ([n], default each row's relation
+    id; -1: unrestricted): every rank counts only the entities admissible in the row's set, inside the masked sweep
+    (rank_counts with row_set / mask), which computes a distance for those entities alone.  The true entity need not be
+    admissible; return_admissible=True adds the bool array "true entity admissible in its set"."""
+    if side not in ("tail", "head"):
+        raise ValueError(f"side must be 'tail' or 'head', got {side!r}")
+    if candidate_sets is None and (row_sets is not None or return_admissible):
+        raise ValueError("row_sets / return_admissible need candidate_sets")
     test = _translation_test(model, test)
+    rs_all = None
+    if candidate_sets is not None:
+        rs_all = _translation_sets(model, candidate_sets, row_sets, len(test), "translation_ranks")
+        if rs_all is None:
+            rs_all = test[:, 2]
     order, index, pos_of = _translation_sweep_setup(model, test[:, 2], known, side)
     E, dev = model.n_ent, model.tables["ent"].device
+    if candidate_sets is not None:
+        candidate_sets._check(torch.arange(E, dtype=torch.int32, device=dev), "translation_ranks")
     if batch is None:
         batch = 1 << 17
     if batch <= 0:
         raise ValueError("batch must be positive")
     raw = np.empty(len(test), dtype=np.int64)
     fil = np.empty(len(test), dtype=np.int64)
+    adm = np.empty(len(test), dtype=bool)
     if len(test) == 0:
-        return raw, fil
-    fixed_col = 0 if side == "tail" else 1
+        return (raw, fil, adm) if return_admissible else (raw, fil)
+    fixed_col, true_col = (0, 1) if side == "tail" else (1, 0)
     for s in range(0, len(test), batch):
         idx = order[s:s + batch]
         chunk = torch.as_tensor(test[idx]).to(dev)
         off, rc = index.cells(chunk[:, fixed_col], chunk[:, 2], pos_of, E)
-        nb, nk, _ = model.rank_counts(chunk, cand_is_head=(side == "head"), known_off=off, known_rc=rc)
+        sets = {}
+        if candidate_sets is not None:
+            rs = torch.as_tensor(rs_all[idx]).to(dev)
+            sets = {"row_set": rs.to(torch.int32).contiguous(), "mask": candidate_sets.mask}
+            adm[idx] = candidate_sets.admissible(rs, chunk[:, true_col]).cpu().numpy()
+        nb, nk, _ = model.rank_counts(chunk, cand_is_head=(side == "head"), known_off=off, known_rc=rc, **sets)
         nb, nk = nb.cpu().numpy().astype(np.int64), nk.cpu().numpy().astype(np.int64)
         if (nb < 0).any() or (nk < 0).any():
             raise ValueError("a test triple holds an id outside the model's tables")
         raw[idx] = nb + 1
         fil[idx] = nb + 1 - nk
-    return raw, fil
+    return (raw, fil, adm) if return_admissible else (raw, fil)
 
 
 def evaluate_translation(model, test, known=None, both_sides: bool = True, batch: int = None, verbose: bool = False,
-                         relations: bool = False) -> dict:
+                         relations: bool = False, candidate_sets=None) -> dict:
     """Filtered link prediction of a TransX / TransR model over all entities: mrr_and_hits of the tail ranks (and the
     head ranks with both_sides) plus `sweeps`, and per side `tail` / `head` dicts of the same numbers.  known: the
     triples to filter (the Bordes et al. setting filters train + valid + test).  relations: add a `relation` dict, the
-    same numbers for the relation ranks (translation_relation_ranks); the other entries do not change."""
+    same numbers for the relation ranks (translation_relation_ranks); the other entries do not change.
+    candidate_sets: {"tail": CandidateSets, "head": CandidateSets} built for arange(n_ent) (row set = relation id) adds a
+    `constrained` dict -- mrr_and_hits of the type-constrained ranks over the evaluated sides, `admissible_true` (the
+    share of rows whose true entity is in its set) and `mean_set_size` (over the rows); the other entries do not
+    change."""
     n_rows = max(model.n_ent, model.n_rel)
     dev = model.tables["ent"].device
+    sides = ("tail", "head") if both_sides else ("tail",)
+    if candidate_sets is not None and (not isinstance(candidate_sets, dict) or any(s not in candidate_sets for s in sides)):
+        raise ValueError("candidate_sets must be a dict with a CandidateSets per evaluated side ('tail', 'head')")
     per, raw_all, fil_all = {}, [], []
-    for side in ("tail", "head") if both_sides else ("tail",):
+    c_raw, c_fil, c_adm, c_size = [], [], [], []
+    for side in sides:
         idx = KnownIndex(None if known is None else np.asarray(known, dtype=np.int64), n_rows, side, dev)
         raw, fil = translation_ranks(model, test, idx, side=side, batch=batch)
         per[side] = mrr_and_hits(raw, fil)
         raw_all.append(raw); fil_all.append(fil)
+        if candidate_sets is not None:
+            r, f, a = translation_ranks(model, test, idx, side=side, batch=batch, candidate_sets=candidate_sets[side],
+                                        return_admissible=True)
+            c_raw.append(r); c_fil.append(f); c_adm.append(a)
+            c_size.append(candidate_sets[side].counts[_translation_test(model, test)[:, 2]])
     out = mrr_and_hits(np.concatenate(raw_all), np.concatenate(fil_all))
     out["sweeps"] = int(sum(r.size for r in raw_all))
     if relations:
         per["relation"] = mrr_and_hits(*translation_relation_ranks(model, test, known, batch=batch))
     out.update(per)
+    if candidate_sets is not None:
+        con = mrr_and_hits(np.concatenate(c_raw), np.concatenate(c_fil))
+        adm, size = np.concatenate(c_adm), np.concatenate(c_size)
+        con["admissible_true"] = float(adm.mean()) if adm.size else 0.0
+        con["mean_set_size"] = float(size.mean()) if size.size else 0.0
+        out["constrained"] = con
     if verbose:
         for name, m in list(per.items()) + [("both", out)]:
             print(f"{name}: raw MRR {m['raw_mrr']:.6f} (mean rank {m['mean_raw_pos']:.1f}); filtered MRR "
                   f"{m['filtered_mrr']:.6f} (mean rank {m['mean_filtered_pos']:.1f}); hits@1/3/10 "
                   f"{m['hits1']:.2f} / {m['hits3']:.2f} / {m['hits10']:.2f} %")
+        if candidate_sets is not None:
+            print(constrained_line(out["constrained"]))
     return out
+
+
+def constrained_line(m: dict) -> str:
+    """The `constrained:` line of evaluate_translation's constrained block."""
+    return (f"constrained: raw MRR {m['raw_mrr']:.6f}; filtered MRR {m['filtered_mrr']:.6f} (mean rank "
+            f"{m['mean_filtered_pos']:.1f}); hits@1/3/10 {m['hits1']:.2f} / {m['hits3']:.2f} / {m['hits10']:.2f} %; true "
+            f"entity admissible {100.0 * m['admissible_true']:.2f} %; mean set size {m['mean_set_size']:.1f}")
 
 
 def _translation_queries(model, queries) -> np.ndarray:
@@ -813,7 +887,8 @@ def _translation_queries(model, queries) -> np.ndarray:
 
 
 @torch.no_grad()
-def predict_translation(model, queries, k: int, known=None, side: str = "tail", batch: int = None, fused: bool = None):
+def predict_translation(model, queries, k: int, known=None, side: str = "tail", batch: int = None, fused: bool = None,
+                        candidate_sets=None, row_sets=None):
     """Top-k link prediction of a TransX / TransR model over ALL entities: for every query (fixed f, relation r) the
     first k entities c in ascending (D, c), D = D(f, c, r) (side="tail") or D(c, f, r) ("head") -- the rank sweep's own
     distance, so the filtered rank (translation_ranks, same `known`) of the j-th candidate is j + 1.  known: an [m,3]
@@ -823,14 +898,29 @@ def predict_translation(model, queries, k: int, known=None, side: str = "tail", 
     The rows are grouped by relation for the sweep.  fused (default: k <= transx.topk_max_k()): the list is selected
     inside the sweep (topk_candidates), no [n, n_ent] matrix exists.  k > max_k or fused=False: the rank sweep's stored
     distances (rank_counts(return_scores=True)) in chunks of <= 1024 rows, sorted stably on the device -- the same
-    arrays where both routes apply.  batch: rows per native call."""
+    arrays where both routes apply.  batch: rows per native call.
+    candidate_sets (CandidateSets built for arange(n_ent) and this side) / row_sets ([n], default each query's relation
+    id; -1: unrestricted): only entities admissible in the row's set are returned -- inside the masked sweep
+    (topk_candidates with row_set / mask), or on the stored-distance route by treating the inadmissible entities as
+    known cells."""
     from .transx import topk_max_k
     k = int(k)
     if k < 1:
         raise ValueError("k must be >= 1")
+    if side not in ("tail", "head"):
+        raise ValueError(f"side must be 'tail' or 'head', got {side!r}")
+    if candidate_sets is None and row_sets is not None:
+        raise ValueError("row_sets need candidate_sets")
     q = _translation_queries(model, queries)
+    rs_all = None
+    if candidate_sets is not None:
+        rs_all = _translation_sets(model, candidate_sets, row_sets, len(q), "predict_translation")
+        if rs_all is None:
+            rs_all = q[:, 1]
     order, index, pos_of = _translation_sweep_setup(model, q[:, 1], known, side)
     E, dev = model.n_ent, model.tables["ent"].device
+    if candidate_sets is not None:
+        candidate_sets._check(torch.arange(E, dtype=torch.int32, device=dev), "predict_translation")
     in_kernel = fused is not False and k <= topk_max_k()
     if batch is None:
         batch = 1 << 15 if in_kernel else 1024
@@ -848,14 +938,19 @@ def predict_translation(model, queries, k: int, known=None, side: str = "tail", 
         off = rc = None
         if filtered:
             off, rc = index.cells(chunk[:, 0], chunk[:, 1], pos_of, E)
+        rs = None if candidate_sets is None else torch.as_tensor(rs_all[idx]).to(dev)
         if in_kernel:
-            ids, dist = model.topk_candidates(chunk, k, cand_is_head=head, known_off=off, known_rc=rc)
+            sets = {} if rs is None else {"row_set": rs.to(torch.int32).contiguous(), "mask": candidate_sets.mask}
+            ids, dist = model.topk_candidates(chunk, k, cand_is_head=head, known_off=off, known_rc=rc, **sets)
         else:
             # rows (f, any valid target, r): the target's counts are discarded, the distances are the row's
             zero = torch.zeros_like(chunk[:, 0])
             tri = torch.stack([zero, chunk[:, 0], chunk[:, 1]] if head else [chunk[:, 0], zero, chunk[:, 1]], 1)
             dist_all = model.rank_counts(tri, cand_is_head=head, return_scores=True)[-1]
             cells = _known_cells_rc(off, rc, E) if off is not None else None
+            if rs is not None:                   # the inadmissible entities join the known cells
+                out_r, out_c = torch.nonzero(~candidate_sets.admissible(rs), as_tuple=True)
+                cells = (out_r, out_c) if cells is None else (torch.cat([cells[0], out_r]), torch.cat([cells[1], out_c]))
             ids, dist = _topk_of_losses(dist_all, torch.arange(E, device=dev), k, cells)
         ids_out[idx] = ids.to(torch.int64).cpu().numpy()
         dist_out[idx] = dist.cpu().numpy()
@@ -1035,15 +1130,17 @@ def translation_predict_lines(side: str, queries, ids, dist, test_triples) -> li
     return lines
 
 
-def write_translation_predictions(model, test, known, k: int, path: str) -> int:
+def write_translation_predictions(model, test, known, k: int, path: str, candidate_sets: dict = None) -> int:
     """The driver's top-k prediction file: tails for the distinct (h, r) pairs of the test triples, then heads for the
-    distinct (t, r) pairs, each in order of first appearance, filtered by `known`; returns the number of lines."""
+    distinct (t, r) pairs, each in order of first appearance, filtered by `known`; returns the number of lines.
+    candidate_sets ({"tail": CandidateSets, "head": CandidateSets}): each side predicts from its relation's set only."""
     test = np.asarray(test, dtype=np.int64).reshape(-1, 3)
     n = 0
     with open(path, "w") as out:
         for side, cols in (("tail", [0, 2]), ("head", [1, 2])):
             queries = distinct_pairs(test[:, cols])
-            ids, dist = predict_translation(model, queries, k, known, side=side)
+            ids, dist = predict_translation(model, queries, k, known, side=side,
+                                            candidate_sets=None if candidate_sets is None else candidate_sets[side])
             lines = translation_predict_lines(side, queries, ids, dist, test)
             out.writelines(lines)
             n += len(lines)

@@ -182,14 +182,37 @@ class _Model:
             raise ValueError("pos and neg must be non-empty and of the same shape")
         return pb, nb, self.workspace(pb.shape[0])
 
+    def _sets_args(self, B: int, row_set, mask):
+        """(row_set pointer, mask pointer, n_sets) of a masked sweep over every entity, the tensors checked; () without
+        sets.  mask: int32 / uint32-as-int32 [n_sets, ge_candidate_mask_words(n_ent)], row_set: int32 [B] (-1:
+        unrestricted), both on the device and kept alive by the caller's frame."""
+        if row_set is None and mask is None:
+            return ()
+        if row_set is None or mask is None:
+            raise ValueError("row_set and mask come together")
+        _need_cuda(row_set, "row_set")
+        _need_cuda(mask, "mask")
+        words = int(_lib.load().ge_candidate_mask_words(self.n_ent))
+        if mask.dtype != torch.int32 or mask.dim() != 2 or mask.shape[0] < 1 or mask.shape[1] != words or not mask.is_contiguous():
+            raise ValueError(f"mask must be a contiguous int32 [n_sets, {words}] tensor (sets built for arange(n_ent))")
+        if row_set.dtype != torch.int32 or row_set.dim() != 1 or row_set.numel() != B or not row_set.is_contiguous():
+            raise ValueError(f"row_set must be a contiguous int32 [{B}] tensor")
+        return (row_set.data_ptr(), mask.data_ptr(), int(mask.shape[0]))
+
     def rank_counts(self, triples: torch.Tensor, cand_is_head: bool = False, known_off: torch.Tensor = None,
-                    known_rc: torch.Tensor = None, return_scores: bool = False):
+                    known_rc: torch.Tensor = None, return_scores: bool = False, row_set: torch.Tensor = None,
+                    mask: torch.Tensor = None):
         """ge_transx_rank / ge_transr_rank on the [B,3] rows as given: (n_before, n_known_before, true_dist) device
         tensors, plus the [B, n_ent] distances with return_scores (tests).  known_off / known_rc: ge_known_cells'
         lists for these rows with pos_of = the identity (None: unfiltered).  Rows with an id out of range get -1
-        counts."""
+        counts.  row_set / mask (int32 [B]; int32 [n_sets, words], CandidateSets.mask for arange(n_ent)): only the
+        entities admissible in the row's set are counted (ge_transx_rank_masked / ge_transr_rank_masked, which store no
+        distances: not with return_scores); a set index outside [-1, n_sets) gives the row -1 counts."""
         tb = _pairs(triples, "triples")
         B, dev = tb.shape[0], tb.device
+        sets = self._sets_args(B, row_set, mask)
+        if sets and return_scores:
+            raise ValueError("the masked rank sweep stores no distances: return_scores needs row_set = mask = None")
         ws_bytes = self._ws_bytes("rank", max(B, 1))
         if (known_off is None) != (known_rc is None):
             raise ValueError("known_off and known_rc come together")
@@ -201,17 +224,24 @@ class _Model:
         sc = torch.empty((B, self.n_ent) if return_scores else (0,), dtype=torch.float32, device=dev)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         p = lambda t: None if t is None else t.data_ptr()
+        if sets:
+            _lib.call(self.PREFIX + "_rank_masked", *self._ptrs(), tb.data_ptr(), B, int(bool(cand_is_head)),
+                      p(known_off), p(known_rc), *sets, nb.data_ptr(), nk.data_ptr(), td.data_ptr(), ws.data_ptr(),
+                      ws.numel(), _stream())
+            return nb, nk, td
         _lib.call(self.PREFIX + "_rank", *self._ptrs(), tb.data_ptr(), B, int(bool(cand_is_head)), p(known_off),
                   p(known_rc), nb.data_ptr(), nk.data_ptr(), td.data_ptr(), sc.data_ptr() if return_scores else None,
                   ws.data_ptr(), ws.numel(), _stream())
         return (nb, nk, td, sc) if return_scores else (nb, nk, td)
 
     def topk_candidates(self, queries: torch.Tensor, k: int, cand_is_head: bool = False, known_off: torch.Tensor = None,
-                        known_rc: torch.Tensor = None):
+                        known_rc: torch.Tensor = None, row_set: torch.Tensor = None, mask: torch.Tensor = None):
         """ge_transx_topk / ge_transr_topk on the [B,2] (fixed, relation) rows as given: (ids int32 [B,k], dist fp32
         [B,k]) device tensors, the first k entities in ascending (D, id), D the rank sweep's own distance.  known_off /
         known_rc: ge_known_cells' lists for these rows with pos_of = the identity (None: unfiltered); known cells are
-        skipped.  Padding -1 / +inf; a row with an id out of range or a NaN distance is -1 / NaN."""
+        skipped.  Padding -1 / +inf; a row with an id out of range or a NaN distance is -1 / NaN.  row_set / mask (as
+        rank_counts): only entities admissible in the row's set are returned (ge_transx_topk_masked /
+        ge_transr_topk_masked); an empty set gives a row of -1 / +inf, a set index outside [-1, n_sets) -1 / NaN."""
         _need_cuda(queries, "queries")
         qb = queries.to(torch.int32).contiguous()
         if qb.dim() != 2 or qb.shape[1] != 2:
@@ -222,6 +252,7 @@ class _Model:
         if (known_off is None) != (known_rc is None):
             raise ValueError("known_off and known_rc come together")
         B, dev = qb.shape[0], qb.device
+        sets = self._sets_args(B, row_set, mask)
         ids = torch.empty(B, k, dtype=torch.int32, device=dev)
         dist = torch.empty(B, k, dtype=torch.float32, device=dev)
         if B == 0:
@@ -231,8 +262,9 @@ class _Model:
             raise RuntimeError(f"{self.PREFIX}_topk_workspace_bytes failed")
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         p = lambda t: None if t is None else t.data_ptr()
-        _lib.call(self.PREFIX + "_topk", *self._ptrs(), qb.data_ptr(), B, int(bool(cand_is_head)), p(known_off),
-                  p(known_rc), k, ids.data_ptr(), dist.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+        _lib.call(self.PREFIX + ("_topk_masked" if sets else "_topk"), *self._ptrs(), qb.data_ptr(), B,
+                  int(bool(cand_is_head)), p(known_off), p(known_rc), *sets, k, ids.data_ptr(), dist.data_ptr(),
+                  ws.data_ptr(), ws.numel(), _stream())
         return ids, dist
 
     def relation_rank_counts(self, triples: torch.Tensor, known_off: torch.Tensor = None, known_rc: torch.Tensor = None,
@@ -271,15 +303,21 @@ class _Model:
         from .evaluate import predict_translation_relations
         return predict_translation_relations(self, pairs, k, known, batch=batch)
 
-    def predict(self, queries, k: int, known=None, side: str = "tail", batch: int = None, fused: bool = None):
-        """Top-k tail (or head) prediction over every entity: evaluate.predict_translation."""
+    def predict(self, queries, k: int, known=None, side: str = "tail", batch: int = None, fused: bool = None,
+                candidate_sets=None, row_sets=None):
+        """Top-k tail (or head) prediction over every entity, or with candidate_sets over each row's set:
+        evaluate.predict_translation."""
         from .evaluate import predict_translation
-        return predict_translation(self, queries, k, known, side=side, batch=batch, fused=fused)
+        return predict_translation(self, queries, k, known, side=side, batch=batch, fused=fused,
+                                   candidate_sets=candidate_sets, row_sets=row_sets)
 
-    def ranks(self, test, known=None, side: str = "tail", batch: int = None):
-        """(raw, filtered) int64 rank arrays of the test triples over every entity: evaluate.translation_ranks."""
+    def ranks(self, test, known=None, side: str = "tail", batch: int = None, candidate_sets=None, row_sets=None,
+              return_admissible: bool = False):
+        """(raw, filtered) int64 rank arrays of the test triples over every entity, or with candidate_sets over each
+        row's set: evaluate.translation_ranks."""
         from .evaluate import translation_ranks
-        return translation_ranks(self, test, known, side=side, batch=batch)
+        return translation_ranks(self, test, known, side=side, batch=batch, candidate_sets=candidate_sets,
+                                 row_sets=row_sets, return_admissible=return_admissible)
 
     def triple_classification(self, valid_pos, test_pos, valid_neg=None, test_neg=None, known=None, seed: int = 0,
                               mode: str = "mid"):

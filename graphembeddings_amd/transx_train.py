@@ -43,6 +43,11 @@ def add_common_flags(p: argparse.ArgumentParser, dims, out: str) -> None:
                         "--test_file, then the top K heads of every distinct (t, r), over all entities.  Lines: side, "
                         "fixed, relation, position, entity, distance, in_test.  Its filter is triple2id.txt + every "
                         "--filter_file but NOT the test file (unlike the ranking filter), so held-out answers can appear")
+    p.add_argument("--candidate_sets", choices=("observed",), default=None,
+                   help="with --test_file: also the type-constrained protocol -- each row ranked against the entities seen "
+                        "on that side of its relation in triple2id.txt + every --filter_file (not the test file).  Prints "
+                        f"a `constrained:` line and adds a `constrained` block to {out}_test.json; with --predict_k the "
+                        "tails and heads are predicted from the relation's set only")
     p.add_argument("--relation_ranks", action="store_true",
                    help=f"with --test_file: also rank every test triple's relation among all relations (h, ?, t), same "
                         f"filter; adds a `relation` block to {out}_test.json and prints its line")
@@ -81,6 +86,11 @@ def check_eval_args(a) -> None:
             raise ValueError("--predict_k needs --test_file")
         if a.predict_k < 1:
             raise ValueError(f"--predict_k must be >= 1, got {a.predict_k}")
+    if getattr(a, "candidate_sets", None) is not None:
+        if a.candidate_sets != "observed":
+            raise ValueError(f"--candidate_sets must be 'observed', got {a.candidate_sets!r}")
+        if not a.test_file:
+            raise ValueError("--candidate_sets needs --test_file")
     if getattr(a, "relation_ranks", False) and not a.test_file:
         raise ValueError("--relation_ranks needs --test_file")
     rel_k = getattr(a, "predict_relations_k", None)     # (a Namespace built without the flag: none)
@@ -109,7 +119,8 @@ def check_eval_args(a) -> None:
 def run(a, driver: str, make_model, name: str) -> int:
     """Everything after the flags are checked: read --data_dir, build make_model(E, R), --load, train, save
     <name>.pt (with --neighbors_k, <name>_neighbors.tsv) and, with --test_file, rank it (heads and tails, printed)
-    into <name>_test.json (with --relation_ranks, relations too); with --predict_k, write <name>_predict.tsv; with
+    into <name>_test.json (with --relation_ranks, relations too; with --candidate_sets, the `constrained` block and
+    line); with --predict_k, write <name>_predict.tsv (from the relation's set with --candidate_sets); with
     --predict_relations_k, <name>_predict_relations.tsv; with --classify, <name>_classify.json and
     <name>_thresholds.tsv."""
     import numpy as np
@@ -145,15 +156,22 @@ def run(a, driver: str, make_model, name: str) -> int:
         test = read_triples(a.test_file, E, R)
         extra = [read_triples(f, E, R) for f in a.filter_file]
         known = np.concatenate([tri, test] + extra, 0)
+        sets = None
+        if getattr(a, "candidate_sets", None) == "observed":   # from triple2id.txt + --filter_file, not the test file
+            from .evaluate import CandidateSets
+            seen = np.concatenate([tri] + extra, 0)
+            sets = {side: CandidateSets.from_observed(np.arange(E), seen, R, side, device=m.tables["ent"].device)
+                    for side in ("tail", "head")}
         res = evaluate_translation(m, test, known, both_sides=True, verbose=True,
-                                   relations=bool(getattr(a, "relation_ranks", False)))
+                                   relations=bool(getattr(a, "relation_ranks", False)), candidate_sets=sets)
         json_path = os.path.join(a.output_dir, f"{name}_test.json")
         with open(json_path, "w") as f:
             json.dump(res, f, indent=1, sort_keys=True)
         print(f"wrote {json_path}")
         if a.predict_k is not None:  # filter: triple2id.txt + --filter_file, not the test file
             tsv = os.path.join(a.output_dir, f"{name}_predict.tsv")
-            n = write_translation_predictions(m, test, np.concatenate([tri] + extra, 0), a.predict_k, tsv)
+            n = write_translation_predictions(m, test, np.concatenate([tri] + extra, 0), a.predict_k, tsv,
+                                              candidate_sets=sets)
             print(f"wrote {tsv} ({n} lines)")
         if getattr(a, "predict_relations_k", None) is not None:
             tsv = os.path.join(a.output_dir, f"{name}_predict_relations.tsv")

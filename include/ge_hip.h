@@ -564,6 +564,51 @@ int ge_topk_1vK_masked(const float* table, int64_t N, int32_t d, const int32_t* 
                        void* workspace, size_t workspace_bytes, const int32_t* row_set, const uint32_t* mask,
                        int32_t n_sets, void* stream);
 
+/* --- per-relation candidate sets on the translation models' sweeps over every entity (ge_transx_rank / ge_transr_rank,
+ * ge_transx_topk / ge_transr_topk): the same type-constrained protocol (holE.py:493-499, 533-541), with candidate
+ * position = entity id.  Each entry point has its unmasked counterpart's arguments with (row_set, mask, n_sets) after the
+ * known-cell pointers; the rank forms have no scores_out.
+ *     mask     uint32 [n_sets][W], W = ge_candidate_mask_words(n_ent): bit c & 31 of word c >> 5 of row s is set iff
+ *              entity c is admissible in set s; bits at positions >= n_ent are ignored (what the mask builders above
+ *              produce for cand = 0 .. n_ent - 1)
+ *     row_set  int32 [B]: row i uses set row_set[i]; -1: unrestricted.  Any other value outside [0, n_sets) makes the row
+ *              a bad row, with exactly what an id out of range gives (ranks: n_before = n_known_before = -1, true_dist
+ *              NaN; top-k: id -1, distance NaN in every slot).
+ * ge_transx_rank_masked / ge_transr_rank_masked: n_before[i] counts the ADMISSIBLE entities c with (D_c, c) below
+ * (D_true, true), n_known_before[i] those of them that are known cells; true_dist is unchanged.  The true entity need
+ * not be admissible: its rank is the place it would take among the admissible ones.
+ * ge_transx_topk_masked / ge_transr_topk_masked: the first k entities in ascending (D, c) that are admissible and not
+ * known; fewer than k of them, or an empty set: id -1, distance +inf padding.  A NaN distance flags the row (-1 / NaN)
+ * only at an entity that is admissible and not known.
+ * Every distance is the unmasked sweep's own, bit for bit: every masked result is a function of what ge_transx_rank /
+ * ge_transr_rank store in scores_out, and with every bit set, or row_set = -1 everywhere, the outputs equal the unmasked
+ * entry points' bitwise.  The sweep computes a distance only for entities that some row of a 16-row chunk admits.
+ * workspace: ge_transx_rank_workspace_bytes / ge_transx_topk_workspace_bytes (ge_transr_* for TransR) of the same shape;
+ * a shortfall is GE_ENOMEM, a workspace not 256-byte aligned GE_EINVAL.  A null mask or row_set, or n_sets < 1:
+ * GE_EINVAL.  No host synchronisation, no allocation, no CPU path. */
+int ge_transx_rank_masked(int model, int l1, const float* ent, int64_t n_ent, const float* rel, int64_t n_rel,
+                          const float* normal, const float* ent_transfer, const float* rel_transfer, int32_t d,
+                          const int32_t* triples, int64_t B, int cand_is_head, const int32_t* known_off,
+                          const uint16_t* known_rc, const int32_t* row_set, const uint32_t* mask, int32_t n_sets,
+                          int32_t* n_before, int32_t* n_known_before, float* true_dist, void* workspace,
+                          size_t workspace_bytes, void* stream);
+int ge_transr_rank_masked(int l1, const float* ent, int64_t n_ent, const float* rel, const float* rel_matrix,
+                          int64_t n_rel, int32_t dim_e, int32_t dim_r, const int32_t* triples, int64_t B,
+                          int cand_is_head, const int32_t* known_off, const uint16_t* known_rc, const int32_t* row_set,
+                          const uint32_t* mask, int32_t n_sets, int32_t* n_before, int32_t* n_known_before,
+                          float* true_dist, void* workspace, size_t workspace_bytes, void* stream);
+int ge_transx_topk_masked(int model, int l1, const float* ent, int64_t n_ent, const float* rel, int64_t n_rel,
+                          const float* normal, const float* ent_transfer, const float* rel_transfer, int32_t d,
+                          const int32_t* queries, int64_t B, int cand_is_head, const int32_t* known_off,
+                          const uint16_t* known_rc, const int32_t* row_set, const uint32_t* mask, int32_t n_sets,
+                          int32_t k, int32_t* out_id, float* out_dist, void* workspace, size_t workspace_bytes,
+                          void* stream);
+int ge_transr_topk_masked(int l1, const float* ent, int64_t n_ent, const float* rel, const float* rel_matrix,
+                          int64_t n_rel, int32_t dim_e, int32_t dim_r, const int32_t* queries, int64_t B,
+                          int cand_is_head, const int32_t* known_off, const uint16_t* known_rc, const int32_t* row_set,
+                          const uint32_t* mask, int32_t n_sets, int32_t k, int32_t* out_id, float* out_dist,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
 /* --- the known_off / known_rc lists of ge_rank_1vK from a sorted index of the known-true triples (the filter of
  * holE.py:454-463, built by the reference as a dict of sets, holE.py:413-422).  known_key [M] ascending = fixed entity *
  * n_rows + relation of every distinct known (fixed, other, relation); known_ent [M] = the other entity; fixed / rel [B] =
