@@ -417,7 +417,8 @@ int ge_transr_train_steps(int l1, float* ent, int64_t n_ent, float* rel, float* 
 
 // ---------------------------------------------------------------- translation-model sweeps: entity ranks, relation
 // ranks, top-k.  Each has one body behind its TransX and its TransR entry point; the order inside is the tables (the
-// entry point's transx_model / transr_model), the outputs, B == 0 (returns 0), then the launcher's GE_ENOMEM.
+// entry point's transx_model / transr_model), the candidate sets where the entry point has them, the outputs, B == 0
+// (returns 0), then the launcher's GE_ENOMEM.
 // B rows of int32 counters, q rows of the workspace and the sweep's row-chunk grid all fit; the outputs are 4-byte
 // aligned; the known lists come as a pair
 static int rank_outputs_ok(int64_t B, const int32_t* triples, const RankOut& o, const void* workspace) {
@@ -443,10 +444,20 @@ static int topk_outputs_ok(int64_t B, const int32_t* queries, const int32_t* kno
   return 0;
 }
 
+// the candidate sets of a masked entry point
+static int sets_ok(const SetArgs& s) {
+  return s.row_set && s.mask && s.n_sets >= 1 && aligned4(s.row_set) && aligned4(s.mask) ? 0 : GE_EINVAL;
+}
+
 static int trans_rank(const TransModel& m, const int32_t* triples, int64_t B, int cand_is_head, const RankOut& o,
-                      void* workspace, size_t workspace_bytes, void* stream) {
+                      void* workspace, size_t workspace_bytes, void* stream, const SetArgs* sets = nullptr) {
+  if (sets)
+    if (int rc = sets_ok(*sets)) return rc;
   if (int rc = rank_outputs_ok(B, triples, o, workspace)) return rc;
   if (B == 0) return 0;
+  if (sets)
+    return trans_rank_masked_launch(m, triples, B, cand_is_head, o, *sets, workspace, workspace_bytes,
+                                    (hipStream_t)stream);
   return trans_rank_launch(m, triples, B, cand_is_head, o, workspace, workspace_bytes, (hipStream_t)stream);
 }
 static int trans_relation_rank(const TransModel& m, const int32_t* triples, int64_t B, const RankOut& o, void* workspace,
@@ -457,9 +468,14 @@ static int trans_relation_rank(const TransModel& m, const int32_t* triples, int6
 }
 static int trans_topk(const TransModel& m, const int32_t* queries, int64_t B, int cand_is_head, const int32_t* known_off,
                       const uint16_t* known_rc, int32_t k, int32_t* out_id, float* out_dist, void* workspace,
-                      size_t workspace_bytes, void* stream) {
+                      size_t workspace_bytes, void* stream, const SetArgs* sets = nullptr) {
+  if (sets)
+    if (int rc = sets_ok(*sets)) return rc;
   if (int rc = topk_outputs_ok(B, queries, known_off, known_rc, k, out_id, out_dist, workspace)) return rc;
   if (B == 0) return 0;
+  if (sets)
+    return trans_topk_masked_launch(m, queries, B, cand_is_head, known_off, known_rc, k, out_id, out_dist, *sets,
+                                    workspace, workspace_bytes, (hipStream_t)stream);
   return trans_topk_launch(m, queries, B, cand_is_head, known_off, known_rc, k, out_id, out_dist, workspace,
                            workspace_bytes, (hipStream_t)stream);
 }
@@ -560,30 +576,7 @@ int ge_transr_topk(int l1, const float* ent, int64_t n_ent, const float* rel, co
                     stream);
 }
 
-// The same sweeps with per-relation candidate sets (ge_transx_rank_masked.hip): the sets, then the unmasked order.
-static int sets_ok(const int32_t* row_set, const uint32_t* mask, int32_t n_sets) {
-  return row_set && mask && n_sets >= 1 && aligned4(row_set) && aligned4(mask) ? 0 : GE_EINVAL;
-}
-static int trans_rank_masked(const TransModel& m, const int32_t* triples, int64_t B, int cand_is_head, const RankOut& o,
-                             const int32_t* row_set, const uint32_t* mask, int32_t n_sets, void* workspace,
-                             size_t workspace_bytes, void* stream) {
-  if (int rc = sets_ok(row_set, mask, n_sets)) return rc;
-  if (int rc = rank_outputs_ok(B, triples, o, workspace)) return rc;
-  if (B == 0) return 0;
-  return trans_rank_masked_launch(m, triples, B, cand_is_head, o, row_set, mask, n_sets, workspace, workspace_bytes,
-                                  (hipStream_t)stream);
-}
-static int trans_topk_masked(const TransModel& m, const int32_t* queries, int64_t B, int cand_is_head,
-                             const int32_t* known_off, const uint16_t* known_rc, const int32_t* row_set,
-                             const uint32_t* mask, int32_t n_sets, int32_t k, int32_t* out_id, float* out_dist,
-                             void* workspace, size_t workspace_bytes, void* stream) {
-  if (int rc = sets_ok(row_set, mask, n_sets)) return rc;
-  if (int rc = topk_outputs_ok(B, queries, known_off, known_rc, k, out_id, out_dist, workspace)) return rc;
-  if (B == 0) return 0;
-  return trans_topk_masked_launch(m, queries, B, cand_is_head, known_off, known_rc, k, out_id, out_dist, row_set, mask,
-                                  n_sets, workspace, workspace_bytes, (hipStream_t)stream);
-}
-
+// The same sweeps with per-relation candidate sets (ge_transx_rank_masked.hip): trans_rank / trans_topk with the sets.
 int ge_transx_rank_masked(int model, int l1, const float* ent, int64_t n_ent, const float* rel, int64_t n_rel,
                           const float* normal, const float* ent_transfer, const float* rel_transfer, int32_t d,
                           const int32_t* triples, int64_t B, int cand_is_head, const int32_t* known_off,
@@ -592,8 +585,9 @@ int ge_transx_rank_masked(int model, int l1, const float* ent, int64_t n_ent, co
                           size_t workspace_bytes, void* stream) {
   TransModel m;
   if (int rc = transx_model(m, model, l1, ent, n_ent, rel, n_rel, normal, ent_transfer, rel_transfer, d)) return rc;
-  return trans_rank_masked(m, triples, B, cand_is_head, {known_off, known_rc, n_before, n_known_before, true_dist, nullptr},
-                           row_set, mask, n_sets, workspace, workspace_bytes, stream);
+  const SetArgs sets{row_set, mask, n_sets, 0};
+  return trans_rank(m, triples, B, cand_is_head, {known_off, known_rc, n_before, n_known_before, true_dist, nullptr},
+                    workspace, workspace_bytes, stream, &sets);
 }
 
 int ge_transr_rank_masked(int l1, const float* ent, int64_t n_ent, const float* rel, const float* rel_matrix,
@@ -603,8 +597,9 @@ int ge_transr_rank_masked(int l1, const float* ent, int64_t n_ent, const float* 
                           float* true_dist, void* workspace, size_t workspace_bytes, void* stream) {
   TransModel m;
   if (int rc = transr_model(m, l1, ent, n_ent, rel, rel_matrix, n_rel, dim_e, dim_r)) return rc;
-  return trans_rank_masked(m, triples, B, cand_is_head, {known_off, known_rc, n_before, n_known_before, true_dist, nullptr},
-                           row_set, mask, n_sets, workspace, workspace_bytes, stream);
+  const SetArgs sets{row_set, mask, n_sets, 0};
+  return trans_rank(m, triples, B, cand_is_head, {known_off, known_rc, n_before, n_known_before, true_dist, nullptr},
+                    workspace, workspace_bytes, stream, &sets);
 }
 
 int ge_transx_topk_masked(int model, int l1, const float* ent, int64_t n_ent, const float* rel, int64_t n_rel,
@@ -615,8 +610,9 @@ int ge_transx_topk_masked(int model, int l1, const float* ent, int64_t n_ent, co
                           void* stream) {
   TransModel m;
   if (int rc = transx_model(m, model, l1, ent, n_ent, rel, n_rel, normal, ent_transfer, rel_transfer, d)) return rc;
-  return trans_topk_masked(m, queries, B, cand_is_head, known_off, known_rc, row_set, mask, n_sets, k, out_id, out_dist,
-                           workspace, workspace_bytes, stream);
+  const SetArgs sets{row_set, mask, n_sets, 0};
+  return trans_topk(m, queries, B, cand_is_head, known_off, known_rc, k, out_id, out_dist, workspace, workspace_bytes,
+                    stream, &sets);
 }
 
 int ge_transr_topk_masked(int l1, const float* ent, int64_t n_ent, const float* rel, const float* rel_matrix,
@@ -626,8 +622,9 @@ int ge_transr_topk_masked(int l1, const float* ent, int64_t n_ent, const float* 
                           void* workspace, size_t workspace_bytes, void* stream) {
   TransModel m;
   if (int rc = transr_model(m, l1, ent, n_ent, rel, rel_matrix, n_rel, dim_e, dim_r)) return rc;
-  return trans_topk_masked(m, queries, B, cand_is_head, known_off, known_rc, row_set, mask, n_sets, k, out_id, out_dist,
-                           workspace, workspace_bytes, stream);
+  const SetArgs sets{row_set, mask, n_sets, 0};
+  return trans_topk(m, queries, B, cand_is_head, known_off, known_rc, k, out_id, out_dist, workspace, workspace_bytes,
+                    stream, &sets);
 }
 
 static inline int neighbor_args_ok(const float* table, int64_t N, int32_t d, const int32_t* queries, int64_t B,

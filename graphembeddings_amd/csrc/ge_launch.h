@@ -262,15 +262,20 @@ size_t trans_topk_ws_bytes(const TransModel& m, int64_t B, int32_t k);
 int trans_topk_launch(const TransModel& m, const int32_t* queries, int64_t B, int cand_is_head,
                       const int32_t* known_off, const uint16_t* known_rc, int32_t k, int32_t* out_id, float* out_dist,
                       void* workspace, size_t workspace_bytes, hipStream_t st);
-// ge_transx_rank_masked.hip: the same two sweeps with per-row candidate sets over the entities (mask
-// [n_sets][candidate_mask_words(E)], row_set [B]; include/ge_hip.h); the workspaces of the unmasked forms; o.scores_out unused
+// The candidate sets of a call (include/ge_hip.h): mask [n_sets][candidate_mask_words(E)], row_set [B].  The C ABI fills
+// the first three; mw, the words per mask row, is the launcher's.
+struct SetArgs {
+  const int32_t* row_set; const uint32_t* mask; int32_t n_sets;
+  int64_t mw;
+};
+// ge_transx_rank_masked.hip: the same two sweeps with per-row candidate sets over the entities; the workspaces of the
+// unmasked forms; o.scores_out unused
 int trans_rank_masked_launch(const TransModel& m, const int32_t* tri, int64_t B, int cand_is_head, const RankOut& o,
-                             const int32_t* row_set, const uint32_t* mask, int32_t n_sets, void* workspace,
-                             size_t workspace_bytes, hipStream_t st);
+                             const SetArgs& sets, void* workspace, size_t workspace_bytes, hipStream_t st);
 int trans_topk_masked_launch(const TransModel& m, const int32_t* queries, int64_t B, int cand_is_head,
                              const int32_t* known_off, const uint16_t* known_rc, int32_t k, int32_t* out_id,
-                             float* out_dist, const int32_t* row_set, const uint32_t* mask, int32_t n_sets,
-                             void* workspace, size_t workspace_bytes, hipStream_t st);
+                             float* out_dist, const SetArgs& sets, void* workspace, size_t workspace_bytes,
+                             hipStream_t st);
 
 // ge_transx_relrank.hip: relation prediction (h, ?, t) of TransE / TransH / TransD / TransR over every relation
 size_t trans_relrank_ws_bytes(const TransModel& m, int64_t B);

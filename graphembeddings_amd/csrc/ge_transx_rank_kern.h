@@ -1,6 +1,9 @@
 // ge_transx_rank_kern.h -- what the translation models' entity sweeps share between ge_transx_rank.hip (ranks and
-// top-k over every entity) and ge_transx_rank_masked.hip (the same with per-relation candidate sets): the projection
-// and distance device code, the one distance loop GE_SWEEP_DISTS, the top-k merge kernel and the workspace layouts.
+// top-k over every entity) and ge_transx_rank_masked.hip (the same with per-relation candidate sets): everything but
+// the loops of the four sweep kernels.  Device: the projection and distance code, the set test, the row and filter
+// kernels (instantiated with a SetArgs they check the row's set), the sweeps' shared texts as macros (GE_SWEEP_DISTS,
+// GE_RANK_COMMIT, GE_TOPK_*) and the top-k merge kernel.  Host: the workspace layouts and their carving, the grid
+// rules, the launches of the row and filter kernels and the merge rounds.
 // The masked sweeps live in a translation unit of their own so that the unmasked kernels stay the code they were.
 #pragma once
 #include "ge_common.h"
@@ -47,6 +50,97 @@ __device__ __forceinline__ float dist_one(const TransTables& T, const float* __r
   return acc;
 }
 
+// ---- candidate sets (SetArgs, ge_launch.h): a row's set index is -1 (unrestricted), in [0, n_sets), or bad
+constexpr int kSetFree = -1;             // a sanitised set index: unrestricted
+constexpr int kSetBad = -2;              //                        index out of range: the row admits nothing
+
+__device__ __forceinline__ bool set_ok(int32_t s, int32_t n_sets) { return s >= -1 && s < n_sets; }
+
+// The word of set s (in [0, n_sets)) that holds entity c's bit (c < E), and that bit of it.
+__device__ __forceinline__ uint32_t mask_word(const SetArgs& S, int32_t s, int64_t c) {
+  return S.mask[(int64_t)s * S.mw + (c >> 5)];
+}
+__device__ __forceinline__ unsigned mask_bit(uint32_t word, int64_t c) { return (word >> (c & 31)) & 1u; }
+
+// The row and filter kernels end in a pack SETS: empty, or one SetArgs, whose sets they then check.
+
+// One thread per row: q, the sanitised relation and target, D_true, and the counters' initial values: 0, or -1 for a
+// bad row (an id out of range; with sets: or a bad set index), whose NaN D_true keeps sweep and filter from counting.
+template <int MODEL, bool L1, class... SETS>
+__global__ __launch_bounds__(kBlock) void rank_row_kernel(TransTables T, const int32_t* __restrict__ tri, int64_t B,
+                                                          int head, float* __restrict__ q, int32_t* __restrict__ rel_of,
+                                                          int32_t* __restrict__ tid, float* __restrict__ true_dist,
+                                                          int32_t* __restrict__ n_before, int32_t* __restrict__ n_known,
+                                                          SETS... sets) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B) return;
+  int32_t h = tri[3 * i], t = tri[3 * i + 1], r = tri[3 * i + 2];
+  bool ok = h >= 0 && h < T.E && t >= 0 && t < T.E && r >= 0 && r < T.R;
+  if (!ok) h = t = r = 0;
+  if constexpr (sizeof...(SETS) != 0) ok = ok && set_ok((sets, ...).row_set[i], (sets, ...).n_sets);
+  const int32_t fixed = head ? t : h, target = head ? h : t;
+  float* qi = q + i * T.dq;
+  const float a = proj_scalar<MODEL>(T, fixed, r);
+  for (int k = 0; k < T.dq; ++k) {
+    const float p = proj_elem<MODEL>(T, fixed, r, a, k), rk = T.rel[(int64_t)r * T.dq + k];
+    qi[k] = head ? p - rk : p + rk;
+  }
+  rel_of[i] = r;
+  tid[i] = target;
+  true_dist[i] = ok ? dist_one<MODEL, L1>(T, qi, target, r) : __builtin_nanf("");
+  n_before[i] = ok ? 0 : -1;
+  n_known[i] = ok ? 0 : -1;
+}
+
+// One thread per known cell (grid-stride over known_off[n_tiles] entries; the cell's tile by binary search): recompute
+// D with the row's operands, integer atomic when it ranks before.  With sets: a cell whose column the row's set does
+// not admit is skipped.
+template <int MODEL, bool L1, class... SETS>
+__global__ __launch_bounds__(kBlock) void rank_filter_kernel(TransTables T, const float* __restrict__ q,
+                                                             const int32_t* __restrict__ rel_of,
+                                                             const int32_t* __restrict__ tid,
+                                                             const float* __restrict__ true_dist, int64_t B,
+                                                             const int32_t* __restrict__ off,
+                                                             const uint16_t* __restrict__ rc, int64_t n_tiles,
+                                                             int32_t* __restrict__ n_known, SETS... sets) {
+  const int64_t total = off[n_tiles];
+  const int64_t n_ct = (T.E + kTile - 1) / kTile;
+  for (int64_t x = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; x < total; x += (int64_t)gridDim.x * blockDim.x) {
+    int64_t lo = 0, hi = n_tiles;                       // the last tile with off[tile] <= x
+    while (hi - lo > 1) {
+      const int64_t mid = (lo + hi) >> 1;
+      if (off[mid] <= x) lo = mid; else hi = mid;
+    }
+    const int cell = rc[x];
+    const int64_t row = (lo / n_ct) * kTile + (cell >> 7), col = (lo % n_ct) * kTile + (cell & 127);
+    if (row >= B || col >= T.E) continue;
+    if constexpr (sizeof...(SETS) != 0) {
+      const SetArgs& S = (sets, ...);
+      const int32_t s = S.row_set[row];
+      if (!set_ok(s, S.n_sets)) continue;               // a bad row: its counters stay -1
+      if (s >= 0 && !mask_bit(mask_word(S, s, col), col)) continue;
+    }
+    const float dt = true_dist[row];
+    const float D = dist_one<MODEL, L1>(T, q + row * T.dq, col, rel_of[row]);
+    if (D < dt || (D == dt && col < tid[row])) atomicAdd(&n_known[row], 1);
+  }
+}
+
+// The end of a rank sweep: the four waves' counts cnt[kRows] summed in LDS (wave_cnt[kBlock / kWave][kRows]), one
+// integer atomic per row and workgroup.  A macro for GE_SWEEP_DISTS' reason.  Reads the kernel's wave_cnt, cnt,
+// n_before, row0, nrows, lane, w.
+#define GE_RANK_COMMIT \
+  if (lane == 0) {                                                                                 \
+    _Pragma("unroll")                                                                              \
+    for (int j = 0; j < kRows; ++j) wave_cnt[w][j] = cnt[j];                                       \
+  }                                                                                                \
+  __syncthreads();                                                                                 \
+  if (threadIdx.x < nrows) {                                                                       \
+    int32_t tot = 0;                                                                               \
+    _Pragma("unroll")                                                                              \
+    for (int x = 0; x < kBlock / kWave; ++x) tot += wave_cnt[x][threadIdx.x];                      \
+    if (tot) atomicAdd(&n_before[row0 + threadIdx.x], tot);                                        \
+  }
 
 // The distances of one lane's candidate cc (a real row: a padding lane passes E - 1) to the rows [row0, row0 + nrows)
 // of a sweep workgroup: declares and fills float acc[kRows], acc[j] for row j.  The rank sweep and the top-k sweep
@@ -117,6 +211,100 @@ struct TopkWs {
   u64* part;            // [B][n_split][k]: each (row chunk, candidate range)'s k best, sorted, kNoKey-padded
   int32_t* bad;         // [B]: an id out of range, or a NaN distance of a candidate that is not known
 };
+
+// One thread per query row: q (as rank_row_kernel forms it), the sanitised relation and the row's flag (an id out of
+// range; with sets: or a bad set index).
+template <int MODEL, class... SETS>
+__global__ __launch_bounds__(kBlock) void topk_row_kernel(TransTables T, const int32_t* __restrict__ qr, int64_t B,
+                                                          int head, float* __restrict__ q, int32_t* __restrict__ rel_of,
+                                                          int32_t* __restrict__ bad, SETS... sets) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B) return;
+  int32_t f = qr[2 * i], r = qr[2 * i + 1];
+  bool ok = f >= 0 && f < T.E && r >= 0 && r < T.R;
+  if (!ok) f = r = 0;
+  if constexpr (sizeof...(SETS) != 0) ok = ok && set_ok((sets, ...).row_set[i], (sets, ...).n_sets);
+  float* qi = q + i * T.dq;
+  const float a = proj_scalar<MODEL>(T, f, r);
+  for (int k = 0; k < T.dq; ++k) {
+    const float p = proj_elem<MODEL>(T, f, r, a, k), rk = T.rel[(int64_t)r * T.dq + k];
+    qi[k] = head ? p - rk : p + rk;
+  }
+  rel_of[i] = r;
+  bad[i] = ok ? 0 : 1;
+}
+
+// The texts of a top-k sweep around its distance loop, macros for GE_SWEEP_DISTS' reason.  A workgroup keeps, per row,
+// a pool of keys in the workspace (row j's at pool0 + j * pstride), and in LDS the pool's fill[kRows], the row's k-th
+// best key kth[kRows] (kNoKey until a cut-back) and the known bitmap bm[kRows][kBlock / 32].  They read those and the
+// kernel's known_off, known_rc, cb, n_ct, rtile, rsub, acc, c, W, row0, nrows, ns, nan_rows, lane, w.
+
+// bm = the known cells of the workgroup's rows x the 256 candidates of source block cb, from ge_known_cells' lists of
+// the (at most two) 128 x 128 tiles the block covers.  The whole workgroup runs it (two barriers).
+#define GE_TOPK_KNOWN_BITMAP \
+  if (threadIdx.x < kRows * kBlock / 32) (&bm[0][0])[threadIdx.x] = 0u;                            \
+  __syncthreads();                                                                                 \
+  for (int h = 0; h < 2 && 2 * cb + h < n_ct; ++h) {                                               \
+    const int64_t tile = rtile * n_ct + 2 * cb + h;                                                \
+    const int32_t x1 = known_off[tile + 1];                                                        \
+    for (int32_t x = known_off[tile] + threadIdx.x; x < x1; x += kBlock) {                         \
+      const int cell = known_rc[x], rl = (cell >> 7) - rsub, cl = (cell & 127) + kTile * h;        \
+      if (rl >= 0 && rl < kRows) atomicOr(&bm[rl][cl >> 5], 1u << (cl & 31));                      \
+    }                                                                                              \
+  }                                                                                                \
+  __syncthreads();
+
+// bm's bit of row j and this lane's candidate of the source block
+__device__ __forceinline__ bool known_bit(const uint32_t (&bm)[kRows][kBlock / 32], int j) {
+  return (bm[j][threadIdx.x >> 5] >> (threadIdx.x & 31)) & 1u;
+}
+
+// The lane offers its candidate c to row j (ON: c is a real candidate that row j admits and does not know).  A NaN
+// flags the row; a key below the row's k-th best goes to the pool: ballot + prefix count, one LDS atomic per wave and
+// row.  (The index stays below cap: <= kp keys before a block or batch, <= 256 in it.)
+#define GE_TOPK_OFFER(ON) \
+  const float D = acc[j];                                                                          \
+  if (__ballot((ON) && D != D)) nan_rows |= 1u << j;                                               \
+  const u64 key = topk_key(D, (int32_t)c);                                                         \
+  const bool take = (ON) && D < __builtin_inff() && key < kth[j];                                  \
+  const u64 m = __ballot(take);                                                                    \
+  if (m) {                                                                                         \
+    int base = 0;                                                                                  \
+    if (lane == 0) base = atomicAdd(&fill[j], __popcll(m));                                        \
+    base = __shfl(base, 0);                                                                        \
+    const int below = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u)); \
+    if (take) pool0[j * pstride + base + below] = key;                                             \
+  }
+
+// After a block's or a batch's offers are in (a barrier): the pools past kp keys are cut back to k; wave w cuts rows
+// 4 w ... 4 w + 3.
+#define GE_TOPK_CUT \
+  for (int jj = 0; jj < kRows / 4; ++jj) {                                                         \
+    const int rl = w * (kRows / 4) + jj;                                                           \
+    const int n = __builtin_amdgcn_readfirstlane(fill[rl]);                                        \
+    if (n > W.kp) {                                                                                \
+      const u64 t = topk_shrink<kTopkLanes>(pool0 + rl * pstride, n, W.k, lane);                   \
+      if (lane == 0) {                                                                             \
+        fill[rl] = W.k;                                                                            \
+        kth[rl] = t;                                                                               \
+      }                                                                                            \
+    }                                                                                              \
+  }
+
+// The end of a top-k sweep (after a barrier): the NaN rows flagged, and each row's list of this candidate range
+// (blockIdx.y of ns), sorted and padded, to W.part.
+#define GE_TOPK_FINISH \
+  if (lane == 0 && nan_rows) {                                                                     \
+    for (int j = 0; j < nrows; ++j)                                                                \
+      if ((nan_rows >> j) & 1u) W.bad[row0 + j] = 1;                                               \
+  }                                                                                                \
+  for (int jj = 0; jj < kRows / 4; ++jj) {                                                         \
+    const int rl = w * (kRows / 4) + jj;                                                           \
+    if (rl >= nrows) break;                                                                        \
+    const int n = __builtin_amdgcn_readfirstlane(fill[rl]);                                        \
+    topk_emit<kTopkLanes>(pool0 + rl * pstride, n, W.k, lane, nullptr, nullptr,                    \
+                          W.part + ((row0 + rl) * ns + blockIdx.y) * W.k);                         \
+  }
 
 // One wave per (row, group of up to kMergeFan partial lists): the group's lists -- each sorted, kNoKey-padded -- into
 // one (out), or, in the last round (out_id set, one group per row), into the row's ids and distances: -1 / NaN for a
@@ -191,6 +379,43 @@ SweepPrefix sweep_prefix(const TransModel& m, int64_t B) {
   return P;
 }
 
+// The prefix's arrays in a workspace.
+struct SweepWs {
+  float* q; int32_t* rel_of; int32_t* row; void* aux;
+};
+
+SweepWs sweep_carve(const SweepPrefix& P, void* ws) {
+  char* p = (char*)ws;
+  return {(float*)(p + P.q), (int32_t*)(p + P.rel_of), (int32_t*)(p + P.row), p + P.aux};
+}
+
+// The rank sweep's grid: 16-row chunks x about two waves of resident workgroups (kMaxBlocks) over the grid, at most
+// one per candidate block:  gridDim.y = ceil(2 * kMaxBlocks / n_chunks) clamped to [1, ceil(E / 256)].
+dim3 rank_grid(int64_t B, int64_t E) {
+  const int64_t n_chunks = (B + kRows - 1) / kRows, n_cb = (E + kBlock - 1) / kBlock;
+  int64_t gy = (2 * kMaxBlocks + n_chunks - 1) / n_chunks;
+  gy = gy < 1 ? 1 : (gy > n_cb ? n_cb : gy);
+  return dim3((unsigned)n_chunks, (unsigned)gy);
+}
+
+// The row kernel's launch (w: the carved workspace) and, when known lists are given, the filter pass's; S: none, or
+// the call's SetArgs.
+template <int MODEL, bool L1, class... SETS>
+void rank_row_launch(const TransTables& T, const int32_t* tri, int64_t B, int head, const SweepWs& w, const RankOut& o,
+                     hipStream_t st, const SETS&... S) {
+  hipLaunchKernelGGL((rank_row_kernel<MODEL, L1, SETS...>), dim3((unsigned)((B + kBlock - 1) / kBlock)), dim3(kBlock),
+                     0, st, T, tri, B, head, w.q, w.rel_of, w.row, o.true_dist, o.n_before, o.n_known_before, S...);
+}
+
+template <int MODEL, bool L1, class... SETS>
+void rank_filter_launch(const TransTables& T, int64_t B, const SweepWs& w, const RankOut& o, hipStream_t st,
+                        const SETS&... S) {
+  if (!o.known_off || !o.known_rc) return;
+  const int64_t n_tiles = ((B + kTile - 1) / kTile) * ((T.E + kTile - 1) / kTile);
+  hipLaunchKernelGGL((rank_filter_kernel<MODEL, L1, SETS...>), dim3(1024), dim3(kBlock), 0, st, T, w.q, w.rel_of, w.row,
+                     o.true_dist, B, o.known_off, o.known_rc, n_tiles, o.n_known_before, S...);
+}
+
 // ---- the top-k's host side
 // candidate ranges per 16-row chunk: about one round of resident workgroups (kMaxBlocks) over the grid, at most one
 // range per candidate block.  A function of (B, E) alone, so that the workspace is.
@@ -226,6 +451,51 @@ size_t topk_ws_bytes(const TransModel& m, int64_t B, int32_t k) {
   for (int64_t ch = 1; ch < n_chunks && ch <= kMaxBlocks; ++ch)
     need = std::max(need, topk_layout(m, ch * kRows, k).total);
   return need;
+}
+
+// A top-k call's workspace carved: the prefix, the kernels' TopkWs (bad = the prefix's row array), the second list
+// buffer, and ns = topk_ranges(B, E), the sweep's gridDim.y.
+struct TopkCall {
+  SweepWs s; TopkWs W; u64* part2; int64_t ns;
+};
+
+TopkCall topk_carve(const TransModel& m, int64_t B, int k, void* ws) {
+  const TopkLayout L = topk_layout(m, B, k);
+  char* p = (char*)ws;
+  TopkCall c;
+  c.s = sweep_carve(L.P, ws);
+  c.W = {k, topk_kp(k), topk_kp(k) + kBlock, (u64*)(p + L.pool), (u64*)(p + L.part), c.s.row};
+  c.part2 = (u64*)(p + L.part2);
+  c.ns = topk_ranges(B, m.E);
+  return c;
+}
+
+// The top-k row kernel's launch; S: none, or the call's SetArgs.
+template <int MODEL, class... SETS>
+void topk_row_launch(const TransTables& T, const int32_t* qr, int64_t B, int head, const TopkCall& c, hipStream_t st,
+                     const SETS&... S) {
+  hipLaunchKernelGGL((topk_row_kernel<MODEL, SETS...>), dim3((unsigned)((B + kBlock - 1) / kBlock)), dim3(kBlock), 0,
+                     st, T, qr, B, head, c.s.q, c.s.rel_of, c.W.bad, S...);
+}
+
+// The top-k sweep's grid: 16-row chunks x candidate ranges.
+dim3 topk_grid(int64_t B, const TopkCall& c) { return dim3((unsigned)((B + kRows - 1) / kRows), (unsigned)c.ns); }
+
+// Merge rounds over the c.ns sorted lists per row that the sweep left in W.part: groups of kMergeFan lists, until one
+// group per row is left; that round writes ids / distances.  A round reads one of W.part / part2 and writes the other.
+void topk_merge_rounds(const TopkCall& c, int64_t B, int32_t* out_id, float* out_dist, hipStream_t st) {
+  u64* lists[2] = {c.W.part, c.part2};
+  int cur = 0;
+  for (int64_t n = c.ns;;) {
+    const int64_t n_out = (n + kMergeFan - 1) / kMergeFan, waves = B * n_out;
+    const dim3 mg((unsigned)((waves + kBlock / kWave - 1) / (kBlock / kWave)));
+    const bool last = n_out == 1;
+    hipLaunchKernelGGL(topk_merge_kernel, mg, dim3(kBlock), 0, st, lists[cur], (int)n, last ? nullptr : lists[cur ^ 1],
+                       B, c.W, last ? out_id : nullptr, last ? out_dist : nullptr);
+    if (last) break;
+    cur ^= 1;
+    n = n_out;
+  }
 }
 
 }  // namespace

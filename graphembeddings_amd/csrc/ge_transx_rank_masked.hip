@@ -19,76 +19,16 @@
 // Which entries share a batch depends on the order the waves append in; no result does: the counts are sums over the
 // admissible candidates, and the top-k pools only ever drop keys that k smaller keys of the same row exclude.
 //
-// Grid rule (unchanged from the unmasked sweeps; the workspace layouts depend on the top-k's):
-//   ranks  gridDim.y = ceil(2 * kMaxBlocks / n_chunks) clamped to [1, ceil(E / 256)], n_chunks = ceil(B / kRows)
-//   top-k  gridDim.y = topk_ranges(B, E) = ceil(kMaxBlocks / n_chunks) clamped the same way: a function of (B, E) alone
+// This file holds the queue, the two masked sweep kernels and their launchers.  The row and filter kernels (here with
+// the sets), the set test, the sweeps' shared texts (GE_SWEEP_DISTS, GE_RANK_COMMIT, GE_TOPK_*), the merge rounds, the
+// workspace carving and the grid rules (rank_grid, topk_ranges: those of the unmasked sweeps; the workspace layouts
+// depend on the top-k's) are in ge_transx_rank_kern.h.
 #include "ge_transx_rank_kern.h"
 
 namespace ge {
 namespace {
 
 constexpr int kQueue = 2 * kBlock;       // queue entries: < 256 carried over + <= 256 of one source block
-constexpr int kSetFree = -1;             // a row's set in LDS: unrestricted
-constexpr int kSetBad = -2;              //                     index out of range: the row admits nothing
-
-struct SetArgs {
-  const int32_t* row_set;                // [B]
-  const uint32_t* mask;                  // [n_sets][mw]
-  int32_t n_sets;
-  int64_t mw;                            // words per mask row
-};
-
-__device__ __forceinline__ bool set_ok(int32_t s, int32_t n_sets) { return s >= -1 && s < n_sets; }
-
-// rank_row_kernel of ge_transx_rank.hip with the set index checked: a bad index is a bad row (NaN, counters -1).
-template <int MODEL, bool L1>
-__global__ __launch_bounds__(kBlock) void rank_row_masked_kernel(TransTables T, const int32_t* __restrict__ tri,
-                                                                 int64_t B, int head, const int32_t* __restrict__ row_set,
-                                                                 int32_t n_sets, float* __restrict__ q,
-                                                                 int32_t* __restrict__ rel_of, int32_t* __restrict__ tid,
-                                                                 float* __restrict__ true_dist,
-                                                                 int32_t* __restrict__ n_before,
-                                                                 int32_t* __restrict__ n_known) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= B) return;
-  int32_t h = tri[3 * i], t = tri[3 * i + 1], r = tri[3 * i + 2];
-  const bool ids_ok = h >= 0 && h < T.E && t >= 0 && t < T.E && r >= 0 && r < T.R;
-  if (!ids_ok) h = t = r = 0;
-  const bool ok = ids_ok && set_ok(row_set[i], n_sets);
-  const int32_t fixed = head ? t : h, target = head ? h : t;
-  float* qi = q + i * T.dq;
-  const float a = proj_scalar<MODEL>(T, fixed, r);
-  for (int k = 0; k < T.dq; ++k) {
-    const float p = proj_elem<MODEL>(T, fixed, r, a, k), rk = T.rel[(int64_t)r * T.dq + k];
-    qi[k] = head ? p - rk : p + rk;
-  }
-  rel_of[i] = r;
-  tid[i] = target;
-  true_dist[i] = ok ? dist_one<MODEL, L1>(T, qi, target, r) : __builtin_nanf("");   // NaN: the sweep never counts
-  n_before[i] = ok ? 0 : -1;
-  n_known[i] = ok ? 0 : -1;
-}
-
-// topk_row_kernel of ge_transx_rank.hip with the set index checked: a bad index flags the row.
-template <int MODEL>
-__global__ __launch_bounds__(kBlock) void topk_row_masked_kernel(TransTables T, const int32_t* __restrict__ qr, int64_t B,
-                                                                 int head, const int32_t* __restrict__ row_set,
-                                                                 int32_t n_sets, float* __restrict__ q,
-                                                                 int32_t* __restrict__ rel_of, int32_t* __restrict__ bad) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= B) return;
-  int32_t f = qr[2 * i], r = qr[2 * i + 1];
-  const bool ok = f >= 0 && f < T.E && r >= 0 && r < T.R;
-  if (!ok) f = r = 0;
-  float* qi = q + i * T.dq;
-  const float a = proj_scalar<MODEL>(T, f, r);
-  for (int k = 0; k < T.dq; ++k) {
-    const float p = proj_elem<MODEL>(T, f, r, a, k), rk = T.rel[(int64_t)r * T.dq + k];
-    qi[k] = head ? p - rk : p + rk;
-  }
-  rel_of[i] = r;
-  bad[i] = ok && set_ok(row_set[i], n_sets) ? 0 : 1;
-}
 
 // The queue and the chunk's sets in LDS.
 struct SweepQueue {
@@ -124,9 +64,9 @@ __device__ __forceinline__ unsigned admit_bits(const SweepQueue& Q, const SetArg
       if (s == kSetFree) {
         bits |= 1u << j;
       } else if (s >= 0) {
-        if (s != prev) word = S.mask[(int64_t)s * S.mw + (c >> 5)];
+        if (s != prev) word = mask_word(S, s, c);
         prev = s;
-        bits |= ((word >> (c & 31)) & 1u) << j;
+        bits |= mask_bit(word, c) << j;
       }
     }
   }
@@ -201,46 +141,7 @@ __global__ __launch_bounds__(kBlock) void rank_sweep_masked_kernel(TransTables T
     if (!more) break;
     __syncthreads();                                     // Q.n as the batch left it, before the next block appends
   }
-  if (lane == 0) {
-#pragma unroll
-    for (int j = 0; j < kRows; ++j) wave_cnt[w][j] = cnt[j];
-  }
-  __syncthreads();
-  if ((int)threadIdx.x < nrows) {
-    int32_t tot = 0;
-#pragma unroll
-    for (int x = 0; x < kBlock / kWave; ++x) tot += wave_cnt[x][threadIdx.x];
-    if (tot) atomicAdd(&n_before[row0 + threadIdx.x], tot);
-  }
-}
-
-// rank_filter_kernel of ge_transx_rank.hip; a cell whose column the row's set does not admit is skipped.
-template <int MODEL, bool L1>
-__global__ __launch_bounds__(kBlock) void rank_filter_masked_kernel(TransTables T, const float* __restrict__ q,
-                                                                    const int32_t* __restrict__ rel_of,
-                                                                    const int32_t* __restrict__ tid,
-                                                                    const float* __restrict__ true_dist, int64_t B,
-                                                                    const int32_t* __restrict__ off,
-                                                                    const uint16_t* __restrict__ rc, int64_t n_tiles,
-                                                                    int32_t* __restrict__ n_known, SetArgs S) {
-  const int64_t total = off[n_tiles];
-  const int64_t n_ct = (T.E + kTile - 1) / kTile;
-  for (int64_t x = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; x < total; x += (int64_t)gridDim.x * blockDim.x) {
-    int64_t lo = 0, hi = n_tiles;                       // the last tile with off[tile] <= x
-    while (hi - lo > 1) {
-      const int64_t mid = (lo + hi) >> 1;
-      if (off[mid] <= x) lo = mid; else hi = mid;
-    }
-    const int cell = rc[x];
-    const int64_t row = (lo / n_ct) * kTile + (cell >> 7), col = (lo % n_ct) * kTile + (cell & 127);
-    if (row >= B || col >= T.E) continue;
-    const int32_t s = S.row_set[row];
-    if (!set_ok(s, S.n_sets)) continue;                 // a bad row: its counters stay -1
-    if (s >= 0 && !((S.mask[(int64_t)s * S.mw + (col >> 5)] >> (col & 31)) & 1u)) continue;
-    const float dt = true_dist[row];
-    const float D = dist_one<MODEL, L1>(T, q + row * T.dq, col, rel_of[row]);
-    if (D < dt || (D == dt && col < tid[row])) atomicAdd(&n_known[row], 1);
-  }
+  GE_RANK_COMMIT
 }
 
 // The masked top-k sweep: topk_sweep_kernel's grid, pools and cut-back, over the queue's batches.  A lane's row bit says
@@ -277,22 +178,12 @@ __global__ __launch_bounds__(kBlock) void topk_sweep_masked_kernel(TransTables T
     if (more) {
       const int64_t c = cb * kBlock + threadIdx.x;
       if (known_off) {
-        if (threadIdx.x < kRows * kBlock / 32) (&bm[0][0])[threadIdx.x] = 0u;
-        __syncthreads();
-        for (int h = 0; h < 2 && 2 * cb + h < n_ct; ++h) {
-          const int64_t tile = rtile * n_ct + 2 * cb + h;
-          const int32_t x1 = known_off[tile + 1];
-          for (int32_t x = known_off[tile] + threadIdx.x; x < x1; x += kBlock) {
-            const int cell = known_rc[x], rl = (cell >> 7) - rsub, cl = (cell & 127) + kTile * h;
-            if (rl >= 0 && rl < kRows) atomicOr(&bm[rl][cl >> 5], 1u << (cl & 31));
-          }
-        }
-        __syncthreads();
+        GE_TOPK_KNOWN_BITMAP
       }
       unsigned bits = c < T.E ? admit_bits(Q, S, c, nrows) : 0u;
       if (known_off) {
 #pragma unroll
-        for (int j = 0; j < kRows; ++j) bits &= ~(((bm[j][threadIdx.x >> 5] >> (threadIdx.x & 31)) & 1u) << j);
+        for (int j = 0; j < kRows; ++j) bits &= ~((unsigned)known_bit(bm, j) << j);
       }
       queue_append(Q, c, bits, lane);
     }
@@ -310,77 +201,32 @@ __global__ __launch_bounds__(kBlock) void topk_sweep_masked_kernel(TransTables T
 #pragma unroll
       for (int j = 0; j < kRows; ++j) {
         if (j < nrows) {
-          const bool on = (bits >> j) & 1u;              // admissible in row j's set and not known
-          const float D = acc[j];
-          if (__ballot(on && D != D)) nan_rows |= 1u << j;
-          const u64 key = topk_key(D, (int32_t)c);
-          const bool take = on && D < __builtin_inff() && key < kth[j];
-          const u64 m = __ballot(take);
-          if (m) {
-            int base = 0;
-            if (lane == 0) base = atomicAdd(&fill[j], __popcll(m));
-            base = __shfl(base, 0);
-            const int below = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-            if (take) pool0[j * pstride + base + below] = key;        // < cap: <= kp before the batch, <= 256 in it
-          }
+          GE_TOPK_OFFER((bits >> j) & 1u)                // bit j: admissible in row j's set and not known
         }
       }
       __syncthreads();                                   // the batch's appends are in
-      for (int jj = 0; jj < kRows / 4; ++jj) {           // wave w cuts rows 4 w ... 4 w + 3
-        const int rl = w * (kRows / 4) + jj;
-        const int nf = __builtin_amdgcn_readfirstlane(fill[rl]);
-        if (nf > W.kp) {
-          const u64 t = topk_shrink<kTopkLanes>(pool0 + rl * pstride, nf, W.k, lane);
-          if (lane == 0) {
-            fill[rl] = W.k;
-            kth[rl] = t;
-          }
-        }
-      }
+      GE_TOPK_CUT
     }
     if (!more) break;
     __syncthreads();                                     // Q.n, fill and kth as the batch left them
   }
   __syncthreads();
-  if (lane == 0 && nan_rows) {
-    for (int j = 0; j < nrows; ++j)
-      if ((nan_rows >> j) & 1u) W.bad[row0 + j] = 1;
-  }
-  for (int jj = 0; jj < kRows / 4; ++jj) {               // each row's list of this candidate range, sorted and padded
-    const int rl = w * (kRows / 4) + jj;
-    if (rl >= nrows) break;
-    const int nf = __builtin_amdgcn_readfirstlane(fill[rl]);
-    topk_emit<kTopkLanes>(pool0 + rl * pstride, nf, W.k, lane, nullptr, nullptr,
-                          W.part + ((row0 + rl) * ns + blockIdx.y) * W.k);
-  }
+  GE_TOPK_FINISH
 }
 
 template <int MODEL, bool L1>
 int run_masked(const TransModel& m, const int32_t* tri, int64_t B, int head, const RankOut& o, const SetArgs& S, void* ws,
                hipStream_t st) {
-  const SweepPrefix P = sweep_prefix(m, B);
-  char* p = (char*)ws;
-  float* q = (float*)(p + P.q);
-  int32_t* rel_of = (int32_t*)(p + P.rel_of);
-  int32_t* tid = (int32_t*)(p + P.row);
-  const TransTables T = trans_prepare<true>(m, p + P.aux, st);
-  hipLaunchKernelGGL((rank_row_masked_kernel<MODEL, L1>), dim3((unsigned)((B + kBlock - 1) / kBlock)), dim3(kBlock), 0,
-                     st, T, tri, B, head, S.row_set, S.n_sets, q, rel_of, tid, o.true_dist, o.n_before, o.n_known_before);
-  const int64_t n_chunks = (B + kRows - 1) / kRows, n_cb = (T.E + kBlock - 1) / kBlock;
-  int64_t gy = (2 * kMaxBlocks + n_chunks - 1) / n_chunks;   // the unmasked sweep's rule: about two waves of workgroups
-  gy = gy < 1 ? 1 : (gy > n_cb ? n_cb : gy);
-  const dim3 grid((unsigned)n_chunks, (unsigned)gy);
+  const SweepWs w = sweep_carve(sweep_prefix(m, B), ws);
+  const TransTables T = trans_prepare<true>(m, w.aux, st);
+  rank_row_launch<MODEL, L1>(T, tri, B, head, w, o, st, S);
   if (rank_vec4(T.ent, T.dE, T.dq))
-    hipLaunchKernelGGL((rank_sweep_masked_kernel<MODEL, L1, 4>), grid, dim3(kBlock), 0, st, T, q, rel_of, tid,
-                       o.true_dist, B, o.n_before, S);
+    hipLaunchKernelGGL((rank_sweep_masked_kernel<MODEL, L1, 4>), rank_grid(B, T.E), dim3(kBlock), 0, st, T, w.q,
+                       w.rel_of, w.row, o.true_dist, B, o.n_before, S);
   else
-    hipLaunchKernelGGL((rank_sweep_masked_kernel<MODEL, L1, 1>), grid, dim3(kBlock), 0, st, T, q, rel_of, tid,
-                       o.true_dist, B, o.n_before, S);
-  if (o.known_off && o.known_rc) {
-    const int64_t n_tiles = ((B + kTile - 1) / kTile) * ((T.E + kTile - 1) / kTile);
-    hipLaunchKernelGGL((rank_filter_masked_kernel<MODEL, L1>), dim3(1024), dim3(kBlock), 0, st, T, q, rel_of, tid,
-                       o.true_dist, B, o.known_off, o.known_rc, n_tiles, o.n_known_before, S);
-  }
+    hipLaunchKernelGGL((rank_sweep_masked_kernel<MODEL, L1, 1>), rank_grid(B, T.E), dim3(kBlock), 0, st, T, w.q,
+                       w.rel_of, w.row, o.true_dist, B, o.n_before, S);
+  rank_filter_launch<MODEL, L1>(T, B, w, o, st, S);
   return launch_status();
 }
 
@@ -388,52 +234,25 @@ template <int MODEL, bool L1>
 int run_topk_masked(const TransModel& m, const int32_t* qr, int64_t B, int head, const int32_t* known_off,
                     const uint16_t* known_rc, int k, int32_t* out_id, float* out_dist, const SetArgs& S, void* ws,
                     hipStream_t st) {
-  const TopkLayout L = topk_layout(m, B, k);
-  char* p = (char*)ws;
-  float* q = (float*)(p + L.P.q);
-  int32_t* rel_of = (int32_t*)(p + L.P.rel_of);
-  TopkWs W;
-  W.k = k;
-  W.kp = topk_kp(k);
-  W.cap = W.kp + kBlock;
-  W.bad = (int32_t*)(p + L.P.row);
-  W.pool = (u64*)(p + L.pool);
-  W.part = (u64*)(p + L.part);
-  u64* part2 = (u64*)(p + L.part2);
-  const TransTables T = trans_prepare<true>(m, p + L.P.aux, st);
-  hipLaunchKernelGGL((topk_row_masked_kernel<MODEL>), dim3((unsigned)((B + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, T,
-                     qr, B, head, S.row_set, S.n_sets, q, rel_of, W.bad);
-  const int64_t n_chunks = (B + kRows - 1) / kRows, ns = topk_ranges(B, T.E);
-  const dim3 grid((unsigned)n_chunks, (unsigned)ns);
+  const TopkCall c = topk_carve(m, B, k, ws);
+  const TransTables T = trans_prepare<true>(m, c.s.aux, st);
+  topk_row_launch<MODEL>(T, qr, B, head, c, st, S);
   if (rank_vec4(T.ent, T.dE, T.dq))
-    hipLaunchKernelGGL((topk_sweep_masked_kernel<MODEL, L1, 4>), grid, dim3(kBlock), 0, st, T, q, rel_of, B, known_off,
-                       known_rc, W, S);
+    hipLaunchKernelGGL((topk_sweep_masked_kernel<MODEL, L1, 4>), topk_grid(B, c), dim3(kBlock), 0, st, T, c.s.q,
+                       c.s.rel_of, B, known_off, known_rc, c.W, S);
   else
-    hipLaunchKernelGGL((topk_sweep_masked_kernel<MODEL, L1, 1>), grid, dim3(kBlock), 0, st, T, q, rel_of, B, known_off,
-                       known_rc, W, S);
-  // merge rounds, as the unmasked top-k runs them
-  u64* lists[2] = {W.part, part2};
-  int cur = 0;
-  for (int64_t n = ns;;) {
-    const int64_t n_out = (n + kMergeFan - 1) / kMergeFan, waves = B * n_out;
-    const dim3 mg((unsigned)((waves + kBlock / kWave - 1) / (kBlock / kWave)));
-    const bool last = n_out == 1;
-    hipLaunchKernelGGL(topk_merge_kernel, mg, dim3(kBlock), 0, st, lists[cur], (int)n, last ? nullptr : lists[cur ^ 1],
-                       B, W, last ? out_id : nullptr, last ? out_dist : nullptr);
-    if (last) break;
-    cur ^= 1;
-    n = n_out;
-  }
+    hipLaunchKernelGGL((topk_sweep_masked_kernel<MODEL, L1, 1>), topk_grid(B, c), dim3(kBlock), 0, st, T, c.s.q,
+                       c.s.rel_of, B, known_off, known_rc, c.W, S);
+  topk_merge_rounds(c, B, out_id, out_dist, st);
   return launch_status();
 }
 
 }  // namespace
 
 int trans_rank_masked_launch(const TransModel& m, const int32_t* tri, int64_t B, int cand_is_head, const RankOut& o,
-                             const int32_t* row_set, const uint32_t* mask, int32_t n_sets, void* workspace,
-                             size_t workspace_bytes, hipStream_t st) {
+                             const SetArgs& sets, void* workspace, size_t workspace_bytes, hipStream_t st) {
   if (workspace_bytes < sweep_prefix(m, B).end) return GE_ENOMEM;
-  const SetArgs S{row_set, mask, n_sets, candidate_mask_words(m.E)};
+  const SetArgs S{sets.row_set, sets.mask, sets.n_sets, candidate_mask_words(m.E)};
   return dispatch_trans(m, [&](auto model, auto l1) {
     return run_masked<decltype(model)::value, decltype(l1)::value>(m, tri, B, cand_is_head ? 1 : 0, o, S, workspace, st);
   });
@@ -441,10 +260,10 @@ int trans_rank_masked_launch(const TransModel& m, const int32_t* tri, int64_t B,
 
 int trans_topk_masked_launch(const TransModel& m, const int32_t* queries, int64_t B, int cand_is_head,
                              const int32_t* known_off, const uint16_t* known_rc, int32_t k, int32_t* out_id,
-                             float* out_dist, const int32_t* row_set, const uint32_t* mask, int32_t n_sets,
-                             void* workspace, size_t workspace_bytes, hipStream_t st) {
+                             float* out_dist, const SetArgs& sets, void* workspace, size_t workspace_bytes,
+                             hipStream_t st) {
   if (workspace_bytes < topk_ws_bytes(m, B, k)) return GE_ENOMEM;
-  const SetArgs S{row_set, mask, n_sets, candidate_mask_words(m.E)};
+  const SetArgs S{sets.row_set, sets.mask, sets.n_sets, candidate_mask_words(m.E)};
   return dispatch_trans(m, [&](auto model, auto l1) {
     return run_topk_masked<decltype(model)::value, decltype(l1)::value>(m, queries, B, cand_is_head ? 1 : 0, known_off,
                                                                         known_rc, k, out_id, out_dist, S, workspace, st);

@@ -225,6 +225,34 @@ def test_nan_entity_flags_a_topk_row_only_where_admissible_and_not_known(model):
     assert (ids[flagged] == -1).all() and (ids[~flagged][:, 0] >= 0).all()
 
 
+@pytest.mark.parametrize("side", ["tail", "head"])
+@pytest.mark.parametrize("model", ["transe", "transr"])
+def test_masked_topk_with_two_merge_rounds(model, side):
+    """n_ent = 4,353: 18 source blocks (the 18th holds one entity), so 18 candidate ranges for one or two row chunks and
+    two merge rounds, 18 -> 2 -> 1, through the merge loop that the masked and the unmasked top-k share."""
+    E, d, head = 4353, 8, side == "head"
+    for B in (1, 17):
+        rng = np.random.default_rng(7 * B + head)
+        m = make_model(model, E, True, d, seed=B)
+        tri, fixed, target = make_rows(E, B, rng, side)
+        adm = make_sets(E, rng, target)
+        n_sets = adm.shape[0]
+        mask_t = dev(REF.pack(adm, pad=True).view(I32))
+        row_set = rng.integers(-1, n_sets, B)
+        row_set[:min(B, n_sets)] = rng.permutation(n_sets)[:min(B, n_sets)]
+        known = rng.random((B, E)) < 0.1
+        koff, krc = cells(known)
+        sc = stored(m, tri, head)[3]
+        full_t = dev(REF.pack(np.ones((n_sets, E), bool), pad=True).view(I32))
+        q = dev(np.stack([fixed, tri[:, 2]], 1).astype(I32))
+        for k in (1, 128):
+            check_topk(m, fixed, tri[:, 2], head, k, sc, adm, row_set, mask_t, known, koff, krc)
+            a = m.topk_candidates(q, k, cand_is_head=head, known_off=koff, known_rc=krc, row_set=dev(row_set.astype(I32)),
+                                  mask=full_t)
+            b = m.topk_candidates(q, k, cand_is_head=head, known_off=koff, known_rc=krc)
+            assert torch.equal(a[0], b[0]) and torch.equal(a[1].view(torch.int32), b[1].view(torch.int32))
+
+
 def block_sets(E, rng):
     """Sets with a chosen number of admissible entities in every 256-entity source block (per_block[s][b]); None: the
     whole block."""

@@ -4,8 +4,10 @@ sides): the unmasked sweep, the masked sweep with CandidateSets.from_types over 
 triples), and the masked sweep with every bit set (the cost of the scan and the queue alone).  The rows are sorted by
 relation, as evaluate.translation_ranks passes them; each timed call is rank_counts without known lists (preparation,
 row kernel, sweep).  One JSON line per (model, norm, side).
-    python tools/probes/masked_transx_rank_time.py [--lib PATH] [--runs N] [--unmasked-only] [--models a,b]
+    python tools/probes/masked_transx_rank_time.py [--lib PATH] [--runs N] [--unmasked-only] [--models a,b] [--topk K]
 --lib: time another build of libge_hip.so (an older one without the masked entry points: the unmasked sweep only).
+--topk K: time topk_candidates(k = K) on the same rows' (fixed entity, relation) queries in place of rank_counts; the
+"mean_n_before" fields then hold the mean number of candidates returned.
 --unmasked-only: the loop an older build runs, unmasked sweeps back to back: the like-for-like comparison with --lib."""
 import json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
@@ -16,6 +18,7 @@ lib_path = args[args.index("--lib") + 1] if "--lib" in args else None
 runs = int(args[args.index("--runs") + 1]) if "--runs" in args else 7
 models = args[args.index("--models") + 1].split(",") if "--models" in args else ["transe", "transh", "transd", "transr"]
 masked = "--unmasked-only" not in args
+topk = int(args[args.index("--topk") + 1]) if "--topk" in args else 0
 if lib_path:                     # (torch is imported: one HIP runtime in the process, as _lib.load arranges)
     import ctypes
     lib = ctypes.CDLL(os.path.abspath(lib_path))
@@ -38,6 +41,7 @@ test = test[np.argsort(test[:, 2], kind="stable")]
 seen = np.concatenate([shift(inf.validation_triples), test])
 types = inf.type_arrays()[1][R:]
 tri = torch.as_tensor(test.astype(np.int32)).cuda()
+queries = {head: torch.as_tensor(test[:, [1 if head else 0, 2]].astype(np.int32)).cuda() for head in (False, True)}
 B = len(test)
 sets = {}
 if masked:
@@ -53,11 +57,16 @@ if masked:
 def once(m, head, **kw):
     ev = H.Events(2)
     ev.record(0)
-    nb, _, _ = m.rank_counts(tri, cand_is_head=head, **kw)
+    if topk:
+        nb = m.topk_candidates(queries[head], topk, cand_is_head=head, **kw)[0]
+    else:
+        nb, _, _ = m.rank_counts(tri, cand_is_head=head, **kw)
     ev.record(1)
     torch.cuda.synchronize()
     ms = ev.elapsed_ms(0, 1)
     ev.close()
+    if topk:
+        nb = (nb >= 0).sum(1)
     return ms, float(nb.float().mean())
 for name in models:
     for l1 in (True, False):
@@ -76,6 +85,8 @@ for name in models:
                     if i >= 2:
                         got[v].append(t)
             out = {"lib": lib_path or "this build", "model": name, "l1": l1, "side": side, "rows": B, "n_ent": n_ent, "d": d}
+            if topk:
+                out["topk"] = topk
             for v, ts in got.items():
                 out[v + "_ms"] = [round(t, 3) for t, _ in ts]
                 out[v + "_median_ms"] = round(float(np.median([t for t, _ in ts])), 3)
