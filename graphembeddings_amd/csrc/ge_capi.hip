@@ -735,44 +735,76 @@ int ge_rank_planes(const float* table, int64_t N, int32_t d, const int32_t* cand
   return rank_planes_launch(table, N, d, cand, K, max_norm, model == GE_MODEL_HOLE_SPECTRAL, planes, (hipStream_t)stream);
 }
 
+// The ONE check of what the rank and top-k sweeps, plain and with candidate sets, take: `a` as the entry point packed
+// it (the checker fills a.spec from the model), topk / sets null where the call has none.  Codes and order are what
+// each entry point answered when it had a copy of its own (tests/test_sweep_refusals_host.py).  The forms differ, and
+// stay different -- aligning them would change what callers see:
+//   * ranks refuse K < 0; top-k refuses K < 1, and k < 1, in the first line;
+//   * candidate sets are checked second, ahead of the model, and ask for the split-precision range (GE_ENOTSUP) ahead
+//     of the planes -- and so ahead of B == 0, where the plain forms leave the range to the route;
+//   * sweep_rank: ge_rank_1vK_vs_loss and ge_rank_1vK_masked return 0 for K == 0 once the counts are zeroed;
+//     ge_rank_1vK_planes leaves K == 0 to route_rank, which first refuses an odd or unsupported embedding_dim;
+//   * behind the shape's GE_ENOTSUP the routes of the candidate-set forms refuse a table that is not 16-byte aligned and
+//     more than INT32_MAX / 8 row blocks; route_topk without sets asks neither, so a misaligned table with the caller's
+//     own planes is not refused there.
+static int sweep_args(SweepArgs& a, int model, const void* planes, const TopkOut* topk, const SetArgs* sets) {
+  if (a.B < 0 || a.K < (topk ? 1 : 0) || (topk && topk->k < 1) || !ok_table(a.table, a.N, a.d) || !max_norm_ok(a.max_norm))
+    return GE_EINVAL;
+  if (sets && (!sets->row_set || !sets->mask || sets->n_sets < 1 || !aligned4(sets->row_set) || !aligned4(sets->mask)))
+    return GE_EINVAL;
+  if (int rc = sweep_model_ok(model)) return rc;
+  a.spec = model == GE_MODEL_HOLE_SPECTRAL;
+  if (a.B > 0) {
+    if (!a.hr || (a.K > 0 && !a.cand)) return GE_EINVAL;
+    if (topk ? !topk->out_id || !topk->out_loss : !a.true_id || !a.raw_cnt || !a.skip_cnt) return GE_EINVAL;
+    if ((a.sweep_flags & 2) && !a.true_loss) return GE_EINVAL;   // (ranks against stored losses read them)
+  }
+  if ((a.known_off == nullptr) != (a.known_rc == nullptr)) return GE_EINVAL;
+  if (sets && !f16_sweep_ok(a.d, a.max_norm)) return GE_ENOTSUP;
+  if (planes && (rank_planes_bytes(a.N, a.d, a.K) == 0 || reinterpret_cast<uintptr_t>(planes) % 256 != 0)) return GE_EINVAL;
+  return 0;
+}
+
+// a checked rank sweep: the counters zeroed, then the route's kernel
+static int sweep_rank(const SweepArgs& a, bool k0_returns, const void* planes, const SetArgs* sets, void* stream) {
+  if (a.B == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = zero_counts(a.raw_cnt, a.skip_cnt, a.B, st)) return rc;
+  if (k0_returns && a.K == 0) return 0;
+  if (!sets) return complex_rank_1vK_launch(a, planes, st);
+  const SweepRoute r = route_masked_rank(a.N, a.d, a.B, a.K, a.max_norm, table_mod16(a));
+  return r.kernel == SweepRoute::None ? r.status : masked_rank_launch(a, *sets, planes, st);
+}
+
+// a checked top-k sweep
+static int sweep_topk(const SweepArgs& a, const TopkOut& t, const void* planes, const SetArgs* sets, void* stream) {
+  const SweepRoute r = route_topk(a.N, a.d, a.B, a.K, a.max_norm, table_mod16(a), t.k, sets != nullptr);
+  if (r.kernel == SweepRoute::None) return r.status;
+  return sets ? masked_topk_launch(a, t, *sets, planes, (hipStream_t)stream) : topk_f16_launch(a, t, planes, (hipStream_t)stream);
+}
+
 int ge_rank_1vK_planes(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* true_id,
                        const int32_t* cand, int64_t K, float max_norm, int model, int cand_is_head, const int32_t* known_off,
                        const uint16_t* known_rc, int32_t* n_before, int32_t* n_known_before, float* true_loss,
                        float* scores_out, const void* planes, void* stream) {
-  if (B < 0 || K < 0 || !ok_table(table, N, d) || !max_norm_ok(max_norm)) return GE_EINVAL;
-  if (int rc = sweep_model_ok(model)) return rc;
-  if (B > 0 && (!hr || !true_id || !n_before || !n_known_before)) return GE_EINVAL;
-  if (B > 0 && K > 0 && !cand) return GE_EINVAL;
-  if ((known_off == nullptr) != (known_rc == nullptr)) return GE_EINVAL;
-  if (planes && (rank_planes_bytes(N, d, K) == 0 || reinterpret_cast<uintptr_t>(planes) % 256 != 0)) return GE_EINVAL;
-  if (B == 0) return 0;
-  hipStream_t st = (hipStream_t)stream;
-  if (int rc = zero_counts(n_before, n_known_before, B, st)) return rc;
-  return complex_rank_1vK_launch(table, N, d, hr, B, true_id, cand, K, max_norm, cand_is_head, known_off, known_rc,
-                                 n_before, n_known_before, true_loss, scores_out, model == GE_MODEL_HOLE_SPECTRAL, planes, st);
+  SweepArgs a{table, N, d, hr, B, true_id, cand, K, max_norm, cand_is_head, known_off, known_rc, n_before, n_known_before,
+              true_loss, scores_out, /*spec=*/0, /*scores_only=*/0, /*sweep_flags=*/0};
+  if (int rc = sweep_args(a, model, planes, nullptr, nullptr)) return rc;
+  return sweep_rank(a, /*k0_returns=*/false, planes, nullptr, stream);
 }
 
 int ge_rank_1vK_vs_loss(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* ref_id,
                         const float* ref_loss, const int32_t* cand, int64_t K, float max_norm, int model, int cand_is_head,
                         const int32_t* known_off, const uint16_t* known_rc, int32_t* n_before, int32_t* n_known_before,
                         const void* planes, void* stream) {
-  if (B < 0 || K < 0 || !ok_table(table, N, d) || !max_norm_ok(max_norm)) return GE_EINVAL;
-  if (int rc = sweep_model_ok(model)) return rc;
-  if (B > 0 && (!hr || !ref_id || !ref_loss || !n_before || !n_known_before)) return GE_EINVAL;
-  if (B > 0 && K > 0 && !cand) return GE_EINVAL;
-  if ((known_off == nullptr) != (known_rc == nullptr)) return GE_EINVAL;
-  if (planes && (rank_planes_bytes(N, d, K) == 0 || reinterpret_cast<uintptr_t>(planes) % 256 != 0)) return GE_EINVAL;
-  if (B == 0) return 0;
-  hipStream_t st = (hipStream_t)stream;
-  if (int rc = zero_counts(n_before, n_known_before, B, st)) return rc;
-  if (K == 0) return 0;
-  // (the launchers take the losses through their true_loss argument, which this mode only reads)
-  return complex_rank_1vK_launch(table, N, d, hr, B, ref_id, cand, K, max_norm, cand_is_head, known_off, known_rc, n_before,
-                                 n_known_before, const_cast<float*>(ref_loss), nullptr, model == GE_MODEL_HOLE_SPECTRAL, planes, st,
-                                 /*vs_loss=*/1);
+  // (the launchers take the losses through their true_loss argument, which sweep_flags & 2 only reads)
+  SweepArgs a{table, N, d, hr, B, ref_id, cand, K, max_norm, cand_is_head, known_off, known_rc, n_before, n_known_before,
+              const_cast<float*>(ref_loss), nullptr, /*spec=*/0, /*scores_only=*/0, /*sweep_flags=*/2};
+  if (int rc = sweep_args(a, model, planes, nullptr, nullptr)) return rc;
+  return sweep_rank(a, /*k0_returns=*/true, planes, nullptr, stream);
 }
 
-int ge_topk_max_k(void) { return topk_max_k(); }
+int ge_topk_max_k(void) { return kTopkMaxK; }
 
 size_t ge_topk_workspace_bytes(int64_t B, int64_t K, int32_t k) { return topk_ws_bytes(B, K, k); }
 
@@ -780,13 +812,10 @@ int ge_topk_1vK_planes(const float* table, int64_t N, int32_t d, const int32_t* 
                        int64_t K, float max_norm, int model, int cand_is_head, const int32_t* known_off,
                        const uint16_t* known_rc, int32_t k, int32_t* out_id, float* out_loss, const void* planes,
                        void* workspace, size_t workspace_bytes, void* stream) {
-  if (B < 0 || K < 1 || k < 1 || !ok_table(table, N, d) || !max_norm_ok(max_norm)) return GE_EINVAL;
-  if (int rc = sweep_model_ok(model)) return rc;
-  if (B > 0 && (!hr || !cand || !out_id || !out_loss)) return GE_EINVAL;
-  if ((known_off == nullptr) != (known_rc == nullptr)) return GE_EINVAL;
-  if (planes && (rank_planes_bytes(N, d, K) == 0 || reinterpret_cast<uintptr_t>(planes) % 256 != 0)) return GE_EINVAL;
-  return topk_f16_launch(table, N, d, hr, B, cand, K, max_norm, cand_is_head, known_off, known_rc, k, out_id, out_loss,
-                         model == GE_MODEL_HOLE_SPECTRAL, planes, workspace, workspace_bytes, (hipStream_t)stream);
+  SweepArgs a{table, N, d, hr, B, nullptr, cand, K, max_norm, cand_is_head, known_off, known_rc};
+  const TopkOut t{k, out_id, out_loss, workspace, workspace_bytes};
+  if (int rc = sweep_args(a, model, planes, &t, nullptr)) return rc;
+  return sweep_topk(a, t, planes, nullptr, stream);
 }
 
 int64_t ge_candidate_mask_words(int64_t K) { return candidate_mask_words(K); }
@@ -809,22 +838,11 @@ int ge_rank_1vK_masked(const float* table, int64_t N, int32_t d, const int32_t* 
                        const uint16_t* known_rc, int32_t* n_before, int32_t* n_known_before, float* true_loss,
                        float* scores_out, const void* planes, const int32_t* row_set, const uint32_t* mask, int32_t n_sets,
                        void* stream) {
-  if (B < 0 || K < 0 || !ok_table(table, N, d) || !max_norm_ok(max_norm)) return GE_EINVAL;
-  if (!row_set || !mask || n_sets < 1 || !aligned4(row_set) || !aligned4(mask)) return GE_EINVAL;
-  if (int rc = sweep_model_ok(model)) return rc;
-  if (B > 0 && (!hr || !true_id || !n_before || !n_known_before)) return GE_EINVAL;
-  if (B > 0 && K > 0 && !cand) return GE_EINVAL;
-  if ((known_off == nullptr) != (known_rc == nullptr)) return GE_EINVAL;
-  if (!f16_sweep_ok(d, max_norm)) return GE_ENOTSUP;
-  if (planes && (rank_planes_bytes(N, d, K) == 0 || reinterpret_cast<uintptr_t>(planes) % 256 != 0)) return GE_EINVAL;
-  if (B == 0) return 0;
-  hipStream_t st = (hipStream_t)stream;
-  if (int rc = zero_counts(n_before, n_known_before, B, st)) return rc;
-  if (K == 0) return 0;
-  const SweepArgs a{table, N, d, hr, B, true_id, cand, K, max_norm, cand_is_head, known_off, known_rc, n_before,
-                    n_known_before, true_loss, scores_out, model == GE_MODEL_HOLE_SPECTRAL, /*scores_only=*/0,
-                    /*sweep_flags=*/0};
-  return masked_rank_launch(a, row_set, mask, n_sets, planes, st);
+  SweepArgs a{table, N, d, hr, B, true_id, cand, K, max_norm, cand_is_head, known_off, known_rc, n_before, n_known_before,
+              true_loss, scores_out, /*spec=*/0, /*scores_only=*/0, /*sweep_flags=*/0};
+  const SetArgs sets{row_set, mask, n_sets, 0};
+  if (int rc = sweep_args(a, model, planes, nullptr, &sets)) return rc;
+  return sweep_rank(a, /*k0_returns=*/true, planes, &sets, stream);
 }
 
 int ge_topk_1vK_masked(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* cand,
@@ -832,16 +850,11 @@ int ge_topk_1vK_masked(const float* table, int64_t N, int32_t d, const int32_t* 
                        const uint16_t* known_rc, int32_t k, int32_t* out_id, float* out_loss, const void* planes,
                        void* workspace, size_t workspace_bytes, const int32_t* row_set, const uint32_t* mask,
                        int32_t n_sets, void* stream) {
-  if (B < 0 || K < 1 || k < 1 || !ok_table(table, N, d) || !max_norm_ok(max_norm)) return GE_EINVAL;
-  if (!row_set || !mask || n_sets < 1 || !aligned4(row_set) || !aligned4(mask)) return GE_EINVAL;
-  if (int rc = sweep_model_ok(model)) return rc;
-  if (B > 0 && (!hr || !cand || !out_id || !out_loss)) return GE_EINVAL;
-  if ((known_off == nullptr) != (known_rc == nullptr)) return GE_EINVAL;
-  if (!f16_sweep_ok(d, max_norm)) return GE_ENOTSUP;
-  if (planes && (rank_planes_bytes(N, d, K) == 0 || reinterpret_cast<uintptr_t>(planes) % 256 != 0)) return GE_EINVAL;
-  return masked_topk_launch(table, N, d, hr, B, cand, K, max_norm, cand_is_head, known_off, known_rc, k, out_id, out_loss,
-                            model == GE_MODEL_HOLE_SPECTRAL, row_set, mask, n_sets, planes, workspace, workspace_bytes,
-                            (hipStream_t)stream);
+  SweepArgs a{table, N, d, hr, B, nullptr, cand, K, max_norm, cand_is_head, known_off, known_rc};
+  const TopkOut t{k, out_id, out_loss, workspace, workspace_bytes};
+  const SetArgs sets{row_set, mask, n_sets, 0};
+  if (int rc = sweep_args(a, model, planes, &t, &sets)) return rc;
+  return sweep_topk(a, t, planes, &sets, stream);
 }
 
 int ge_rank_1vK(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* true_id,

@@ -77,21 +77,27 @@ int copy_if_launch(const float* src, float* dst, int64_t n, const int32_t* flag,
 int complex_score_1vK_launch(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* cand,
                              int64_t K, float max_norm, int apply_sigmoid, int cand_is_head, float* out, hipStream_t st);
 
-// ge_rank.hip: link-prediction ranks -- the switch on route_rank (ge_sweep_route.h) and the fp32 kernel
-int complex_rank_1vK_launch(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* true_id,
-                            const int32_t* cand, int64_t K, float max_norm, int cand_is_head, const int32_t* known_off,
-                            const uint16_t* known_rc, int32_t* raw_cnt, int32_t* skip_cnt, float* true_loss,
-                            float* scores_out, int spec, const void* planes_ws, hipStream_t st, int vs_loss = 0);
-
-// What the sweep kernels behind route_rank / route_score take.  spec: the table is a spectral HolE table.
+// What the sweep kernels behind the routes of ge_sweep_route.h take.  spec: the table is a spectral HolE table.
 // scores_only: no ranking, scores_out [B,K] = score (its sigmoid with sweep_flags & 1): ge_complex_score_1vK.
 // Ranks: scores_out may be null; sweep_flags & 2: true_loss is an INPUT, the loss every candidate of row i is ranked
-// against, and true_id the tie-break id (ge_rank_1vK_vs_loss).
+// against, and true_id the tie-break id (ge_rank_1vK_vs_loss).  Top-k: the rank outputs are unused, see TopkOut.
 struct SweepArgs {
   const float* table; int64_t N; int32_t d; const int32_t* hr; int64_t B; const int32_t* true_id; const int32_t* cand;
   int64_t K; float max_norm; int cand_is_head; const int32_t* known_off; const uint16_t* known_rc; int32_t* raw_cnt;
   int32_t* skip_cnt; float* true_loss; float* scores_out; int spec, scores_only, sweep_flags;
 };
+inline int table_mod16(const SweepArgs& a) { return (int)(reinterpret_cast<uintptr_t>(a.table) % 16); }   // (for the routes)
+// what a top-k sweep takes beside them: k <= kTopkMaxK, out_id / out_loss [B][k], a workspace of topk_ws_bytes(B, K, k)
+struct TopkOut { int32_t k; int32_t* out_id; float* out_loss; void* workspace; size_t workspace_bytes; };
+// The candidate sets of a call (include/ge_hip.h): mask [n_sets][candidate_mask_words(candidates)], row_set [B].  The C
+// ABI fills the first three; mw, the words per mask row, is the translation launchers'.
+struct SetArgs {
+  const int32_t* row_set; const uint32_t* mask; int32_t n_sets;
+  int64_t mw;
+};
+
+// ge_rank.hip: link-prediction ranks -- the switch on route_rank (ge_sweep_route.h) and the fp32 kernel
+int complex_rank_1vK_launch(const SweepArgs& a, const void* planes_ws, hipStream_t st);
 
 // ge_rank_pipe.hip: Pipe<cw> of the route, cw in 40, 32, 24 dividing embedding_dim
 int pipe_sweep_launch(int cw, const SweepArgs& a, hipStream_t st);
@@ -102,27 +108,18 @@ int pipe_sweep_launch(int cw, const SweepArgs& a, hipStream_t st);
 int rank_planes_launch(const float* table, int64_t N, int32_t d, const int32_t* cand, int64_t K, float max_norm, int spec,
                        void* planes_ws, hipStream_t st);
 int f16_sweep_launch(const SweepArgs& a, const void* planes_ws, hipStream_t st);
-// the top-k sweep on the same planes (ge_topk_1vK_planes): k <= topk_max_k(), workspace of topk_ws_bytes(B, K, k)
-int topk_max_k();
-size_t topk_ws_bytes(int64_t B, int64_t K, int32_t k);
-int topk_f16_launch(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* cand, int64_t K,
-                    float max_norm, int cand_is_head, const int32_t* known_off, const uint16_t* known_rc, int32_t k,
-                    int32_t* out_id, float* out_loss, int spec, const void* planes_ws, void* workspace,
-                    size_t workspace_bytes, hipStream_t st);
-int64_t topk_splits(int64_t B, int64_t K);
+// the top-k sweep on the same planes, behind route_topk: the workspace's pointer and size (GE_EINVAL, GE_ENOMEM) and
+// topk_grid_ok (GE_ENOTSUP) are the launcher's own
+int topk_f16_launch(const SweepArgs& a, const TopkOut& t, const void* planes_ws, hipStream_t st);
 
-// ge_rank_f16_masked.hip: the same two sweeps with per-row candidate sets (mask [n_sets][candidate_mask_words(K)], row_set
-// [B]; include/ge_hip.h), split-precision shapes only (GE_ENOTSUP otherwise), and the mask builders
+// ge_rank_f16_masked.hip: the same two sweeps with per-row candidate sets, behind route_masked_rank and route_topk, and
+// the mask builders
 int64_t candidate_mask_words(int64_t K);
 int mask_from_classes_launch(const int32_t* cand_class, int64_t K, const uint32_t* allow, int32_t n_sets, int32_t n_class,
                              uint32_t* mask, hipStream_t st);
 int mask_from_cells_launch(const int32_t* cells, int64_t M, int32_t n_sets, int64_t K, uint32_t* mask, hipStream_t st);
-int masked_rank_launch(const SweepArgs& a, const int32_t* row_set, const uint32_t* mask, int32_t n_sets,
-                       const void* planes_ws, hipStream_t st);
-int masked_topk_launch(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* cand, int64_t K,
-                       float max_norm, int cand_is_head, const int32_t* known_off, const uint16_t* known_rc, int32_t k,
-                       int32_t* out_id, float* out_loss, int spec, const int32_t* row_set, const uint32_t* mask,
-                       int32_t n_sets, const void* planes_ws, void* workspace, size_t workspace_bytes, hipStream_t st);
+int masked_rank_launch(const SweepArgs& a, const SetArgs& sets, const void* planes_ws, hipStream_t st);
+int masked_topk_launch(const SweepArgs& a, const TopkOut& t, const SetArgs& sets, const void* planes_ws, hipStream_t st);
 
 // ge_neighbors.hip: nearest-neighbour search (cosine / Euclidean) on the split-precision sweep; embedding_dim 1 ... 288
 int neighbor_max_k();
@@ -262,14 +259,8 @@ size_t trans_topk_ws_bytes(const TransModel& m, int64_t B, int32_t k);
 int trans_topk_launch(const TransModel& m, const int32_t* queries, int64_t B, int cand_is_head,
                       const int32_t* known_off, const uint16_t* known_rc, int32_t k, int32_t* out_id, float* out_dist,
                       void* workspace, size_t workspace_bytes, hipStream_t st);
-// The candidate sets of a call (include/ge_hip.h): mask [n_sets][candidate_mask_words(E)], row_set [B].  The C ABI fills
-// the first three; mw, the words per mask row, is the launcher's.
-struct SetArgs {
-  const int32_t* row_set; const uint32_t* mask; int32_t n_sets;
-  int64_t mw;
-};
-// ge_transx_rank_masked.hip: the same two sweeps with per-row candidate sets over the entities; the workspaces of the
-// unmasked forms; o.scores_out unused
+// ge_transx_rank_masked.hip: the same two sweeps with per-row candidate sets (SetArgs) over the entities; the workspaces
+// of the unmasked forms; o.scores_out unused
 int trans_rank_masked_launch(const TransModel& m, const int32_t* tri, int64_t B, int cand_is_head, const RankOut& o,
                              const SetArgs& sets, void* workspace, size_t workspace_bytes, hipStream_t st);
 int trans_topk_masked_launch(const TransModel& m, const int32_t* queries, int64_t B, int cand_is_head,

@@ -378,13 +378,8 @@ static int rank_f32_launch(const SweepArgs& a, hipStream_t st) {
   return launch_status();
 }
 
-int complex_rank_1vK_launch(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B,
-                            const int32_t* true_id, const int32_t* cand, int64_t K, float max_norm, int cand_is_head,
-                            const int32_t* known_off, const uint16_t* known_rc, int32_t* raw_cnt, int32_t* skip_cnt,
-                            float* true_loss, float* scores_out, int spec, const void* planes_ws, hipStream_t st, int vs_loss) {
-  const SweepRoute r = route_rank(N, d, B, K, max_norm, (int)(reinterpret_cast<uintptr_t>(table) % 16));
-  const SweepArgs a{table, N, d, hr, B, true_id, cand, K, max_norm, cand_is_head, known_off, known_rc, raw_cnt, skip_cnt,
-                    true_loss, scores_out, spec, /*scores_only=*/0, /*sweep_flags=*/vs_loss ? 2 : 0};
+int complex_rank_1vK_launch(const SweepArgs& a, const void* planes_ws, hipStream_t st) {
+  const SweepRoute r = route_rank(a.N, a.d, a.B, a.K, a.max_norm, table_mod16(a));
   switch (r.kernel) {
     case SweepRoute::F16: return f16_sweep_launch(a, planes_ws, st);
     case SweepRoute::Pipe40:

@@ -97,41 +97,7 @@ __global__ __launch_bounds__(256) void rank_planes_kernel(const float* __restric
   }
 }
 
-template <int KKB>
-int f16_launch_kkb(const SweepArgs& a, const void* planes_ws, hipStream_t st) {
-  const int64_t n_rb = (a.B + kRB - 1) / kRB, n_ct = (a.K + kRB - 1) / kRB;
-  assert(n_ct <= INT32_MAX / 8 && n_rb <= INT32_MAX / 8);        // route_main_road
-  const int64_t n_tiles = n_rb * n_ct;
-  const int64_t grid = std::min<int64_t>(n_tiles, GE_PIPE_GRID_M * (int64_t)cu_count());
-  const int32_t* pos_of = reinterpret_cast<const int32_t*>(planes_ws);
-  const _Float16* planes = reinterpret_cast<const _Float16*>(reinterpret_cast<const char*>(planes_ws) + pos_bytes(a.N));
-  auto go = [&](auto kern) -> int {
-    if (int rc = lds_opt_in(kern)) return rc;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kBlk), h_lds_bytes<KKB>(), st, a.table, a.N, a.d, a.hr, a.B, a.true_id,
-                       a.cand, a.K, a.max_norm, a.cand_is_head, a.known_off, a.known_rc, a.raw_cnt, a.skip_cnt, a.true_loss,
-                       a.scores_out, (int)n_ct, n_tiles, a.spec, a.sweep_flags, pos_of, planes, TopkArgs{});
-    return launch_status();
-  };
-  if (a.scores_only) return go(rank_f16_kernel<KKB, 2>);
-  if (a.scores_out) return go(rank_f16_kernel<KKB, 1>);
-  return go(rank_f16_kernel<KKB, 0>);
-}
-
 }  // namespace
-
-// ---- top-k: workgroups per row block.  With fewer than 256 row blocks (one workgroup per CU of the MI355X) the row
-// blocks' candidates are cut into ranges until there are about 256 workgroups (one query against 1.2 M candidates: 256
-// ranges of 37 tiles); the partial lists meet in topk_merge_kernel.  A function of (B, K) alone, so that the workspace is.
-int64_t topk_splits(int64_t B, int64_t K) {
-  const int64_t n_rb = (B + kRB - 1) / kRB, n_ct = (K + kRB - 1) / kRB;
-  if (n_rb >= 256) return 1;
-  return std::max<int64_t>(1, std::min<int64_t>(n_ct, (256 + n_rb - 1) / n_rb));
-}
-
-int64_t topk_ws_rows(int64_t n_rb, int64_t K, int32_t k) {      // bytes for n_rb full row blocks
-  const int64_t ns = topk_splits(n_rb * kRB, K);
-  return n_rb * kRB * ns * (topk_kp(k) + 128 + k) * (int64_t)sizeof(u64);
-}
 
 // planes_ws (rank_planes_bytes, 256-byte aligned) <- the entity -> position map, then the candidates' fp16 planes
 int rank_planes_launch(const float* table, int64_t N, int32_t d, const int32_t* cand, int64_t K, float max_norm, int spec,
@@ -153,76 +119,15 @@ int rank_planes_launch(const float* table, int64_t N, int32_t d, const int32_t* 
 #undef GE_CALL
 }
 
-// The split-precision sweep.  planes_ws: the candidates' planes from rank_planes_launch for the same (table, cand,
-// max_norm, spec), or NULL.
+// The F16 of route_rank / route_score, and of route_topk without candidate sets: the route's conditions are asserted
 int f16_sweep_launch(const SweepArgs& a, const void* planes_ws, hipStream_t st) {
   assert(f16_sweep_ok(a.d, a.max_norm) && rank_planes_bytes(a.N, a.d, a.K) != 0);   // route_main_road
-  static_assert(h_lds_bytes<18>() <= kLdsMax, "LDS of the largest instantiation");
-  return with_planes(a.table, a.N, a.d, a.cand, a.K, a.max_norm, a.spec, planes_ws, st, [&](const void* ws) -> int {
-#define GE_CALL(KKB) return f16_launch_kkb<KKB>(a, ws, st)
-    GE_KKB_SWITCH(a.d, GE_CALL)
-#undef GE_CALL
-  });
+  return f16_sweep_run<false>(a, nullptr, planes_ws, st);
 }
 
-int topk_max_k() { return kTopkMaxK; }
-
-// Workspace of a top-k over B rows and K candidates: the pools, [B][n_split][kp + 128] keys, and the partial lists,
-// [B][n_split][k].  Taken as the largest need of any B' <= B (the ranges shrink as B grows), so that the
-// size is monotone in B, K and k.
-size_t topk_ws_bytes(int64_t B, int64_t K, int32_t k) {
-  if (B <= 0 || K <= 0 || k < 1 || k > kTopkMaxK) return 0;
-  const int64_t n_rb = (B + kRB - 1) / kRB;
-  int64_t need = topk_ws_rows(n_rb, K, k);
-  for (int64_t r = 1; r < std::min<int64_t>(n_rb, 256); ++r) need = std::max(need, topk_ws_rows(r, K, k));
-  return (size_t)need + 256;
-}
-
-// The top-k sweep (rank_f16_kernel MODE 3, grid row blocks x candidate ranges), then the merge of the partial lists.  The same planes
-// and Q staging as the rank sweep, so the losses are MODE 1's.
-int topk_f16_launch(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* cand, int64_t K,
-                    float max_norm, int cand_is_head, const int32_t* known_off, const uint16_t* known_rc, int32_t k,
-                    int32_t* out_id, float* out_loss, int spec, const void* planes_ws, void* workspace,
-                    size_t workspace_bytes, hipStream_t st) {
-  if (!f16_sweep_ok(d, max_norm) || rank_planes_bytes(N, d, K) == 0) return GE_ENOTSUP;   // (incl. planes beyond 32-bit offsets)
-  if (k < 1) return GE_EINVAL;
-  if (k > kTopkMaxK) return GE_ENOTSUP;
-  if (B == 0) return 0;
-  if (!workspace || reinterpret_cast<uintptr_t>(workspace) % 256 != 0) return GE_EINVAL;
-  if (workspace_bytes < topk_ws_bytes(B, K, k)) return GE_ENOMEM;
-  static_assert(topk_lds_bytes<18>() <= kLdsMax, "LDS of the largest top-k instantiation");
-  const int64_t n_rb = (B + kRB - 1) / kRB, n_ct = (K + kRB - 1) / kRB;   // (n_ct < INT32_MAX / 8: the planes' 2^32 bytes)
-  const int64_t ns = topk_splits(B, K);
-  if (n_rb * ns > INT32_MAX) return GE_ENOTSUP;
-  TopkArgs tk;
-  tk.k = k;
-  tk.cap = topk_kp(k) + 128;
-  tk.n_split = (int)ns;
-  tk.pool = reinterpret_cast<u64*>(workspace);
-  tk.part = tk.pool + B * ns * tk.cap;
-  tk.out_id = out_id;
-  tk.out_loss = out_loss;
-  return with_planes(table, N, d, cand, K, max_norm, spec, planes_ws, st, [&](const void* ws) -> int {
-    const int32_t* pos_of = reinterpret_cast<const int32_t*>(ws);
-    const _Float16* planes = reinterpret_cast<const _Float16*>(reinterpret_cast<const char*>(ws) + pos_bytes(N));
-    auto sweep = [&]() -> int {
-#define GE_CALL(KKB)                                                                                                  \
-  {                                                                                                                   \
-    auto kern = rank_f16_kernel<KKB, 3>;                                                                              \
-    if (int rc = lds_opt_in(kern)) return rc;                                                                         \
-    hipLaunchKernelGGL(kern, dim3((unsigned)n_rb, (unsigned)ns), dim3(kBlk), topk_lds_bytes<KKB>(), st, table, N, d, hr, B,   \
-                       nullptr, cand, K, max_norm, cand_is_head, known_off, known_rc, nullptr, nullptr, nullptr,      \
-                       nullptr, (int)n_ct, n_rb * n_ct, spec, 0, pos_of, planes, tk);                                 \
-    return launch_status();                                                                                           \
-  }
-      GE_KKB_SWITCH(d, GE_CALL)
-#undef GE_CALL
-    };
-    const int rc = sweep();
-    if (rc != 0) return rc;
-    hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, hr, B, N, tk);
-    return launch_status();
-  });
+int topk_f16_launch(const SweepArgs& a, const TopkOut& t, const void* planes_ws, hipStream_t st) {
+  assert(route_topk(a.N, a.d, a.B, a.K, a.max_norm, 0, t.k, false).kernel == SweepRoute::F16);
+  return topk_sweep_run<false>(a, t, nullptr, planes_ws, st);
 }
 
 }  // namespace ge

@@ -1,7 +1,8 @@
 // ge_rank_f16_kern.h -- the kernel template of the split-precision sweep (ge_rank_f16.hip: why it has this shape) and
-// what its launchers share: LDS sizes, the top-k arguments and merge, the planes helper.  Included by ge_rank_f16.hip
-// (the unmasked instantiations) and ge_rank_f16_masked.hip (the MASKED ones: per-row candidate sets), so that the two
-// sets of instantiations compile side by side.
+// the host side of its two sweeps, one body each for the plain and the candidate-set form (f16_sweep_run,
+// topk_sweep_run): LDS sizes, the top-k arguments and merge, the planes helper.  Included by ge_rank_f16.hip (the
+// unmasked instantiations) and ge_rank_f16_masked.hip (the MASKED ones: per-row candidate sets), so that the two sets of
+// instantiations compile side by side.
 #pragma once
 #include <algorithm>
 #include <type_traits>
@@ -20,8 +21,8 @@ constexpr size_t h_lds_bytes() {
          sizeof(unsigned) * 8 * 64 + sizeof(int) * (4 * kRB + 4);
 }
 
-// ---- top-k (MODE 3, ge_topk_1vK): keys, pools, thresholds (keys, rank / cut / emit: ge_topk_dev.h)
-constexpr int kTopkMaxK = 128;
+// ---- top-k (MODE 3, ge_topk_1vK): keys, pools, thresholds (keys, rank / cut / emit: ge_topk_dev.h; kTopkMaxK and the
+// workspace: ge_sweep_route.h)
 // Losses are sigmoids in [0, 1] (never NaN for a candidate that survives), so the integer order of topk_key's keys is the
 // reference heap's pop order (ascending loss, ties by id).
 
@@ -647,6 +648,115 @@ int with_planes(const float* table, int64_t N, int32_t d, const int32_t* cand, i
     if (rc == 0 && e != hipSuccess) rc = (int)e;
   }
   return rc;
+}
+
+// ---- the host side of both sweeps, plain (MASKED false: ge_rank_f16.hip, sets null) and with candidate sets (true:
+// ge_rank_f16_masked.hip).  Each unit instantiates its own form alone.
+template <bool MASKED>
+constexpr size_t kSetsLds = MASKED ? kMaskLdsBytes : 0;
+
+template <bool MASKED>
+SweepTk<MASKED> sweep_tk(const TopkArgs& tk, const SetArgs* sets) {
+  SweepTk<MASKED> m;
+  static_cast<TopkArgs&>(m) = tk;
+  if constexpr (MASKED) {
+    m.row_set = sets->row_set;
+    m.mask = sets->mask;
+    m.n_sets = sets->n_sets;
+  }
+  return m;
+}
+
+struct PlanesWs { const int32_t* pos_of; const _Float16* planes; };
+inline PlanesWs planes_at(const void* planes_ws, int64_t N) {
+  return {reinterpret_cast<const int32_t*>(planes_ws),
+          reinterpret_cast<const _Float16*>(reinterpret_cast<const char*>(planes_ws) + pos_bytes(N))};
+}
+
+template <bool MASKED, int KKB>
+int f16_launch_kkb(const SweepArgs& a, const SetArgs* sets, const void* planes_ws, hipStream_t st) {
+  const int64_t n_rb = (a.B + kRB - 1) / kRB, n_ct = (a.K + kRB - 1) / kRB;
+  assert(n_ct <= INT32_MAX / 8 && n_rb <= INT32_MAX / 8);        // route_main_road, f16_only_status
+  const int64_t n_tiles = n_rb * n_ct;
+  const int64_t grid = std::min<int64_t>(n_tiles, GE_PIPE_GRID_M * (int64_t)cu_count());
+  const PlanesWs p = planes_at(planes_ws, a.N);
+  const SweepTk<MASKED> tk = sweep_tk<MASKED>(TopkArgs{}, sets);
+  auto go = [&](auto kern) -> int {
+    if (int rc = lds_opt_in(kern)) return rc;
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kBlk), h_lds_bytes<KKB>() + kSetsLds<MASKED>, st, a.table, a.N, a.d,
+                       a.hr, a.B, a.true_id, a.cand, a.K, a.max_norm, a.cand_is_head, a.known_off, a.known_rc, a.raw_cnt,
+                       a.skip_cnt, a.true_loss, a.scores_out, (int)n_ct, n_tiles, a.spec, a.sweep_flags, p.pos_of, p.planes,
+                       tk);
+    return launch_status();
+  };
+  if constexpr (!MASKED) {                                       // (the score sweep takes no candidate sets)
+    if (a.scores_only) return go(rank_f16_kernel<KKB, 2, MASKED>);
+  }
+  if (a.scores_out) return go(rank_f16_kernel<KKB, 1, MASKED>);
+  return go(rank_f16_kernel<KKB, 0, MASKED>);
+}
+
+// The rank (or score) sweep.  planes_ws: the candidates' planes from rank_planes_launch for the same (table, cand,
+// max_norm, spec), or NULL.
+template <bool MASKED>
+int f16_sweep_run(const SweepArgs& a, const SetArgs* sets, const void* planes_ws, hipStream_t st) {
+  static_assert(h_lds_bytes<18>() + kSetsLds<MASKED> <= kLdsMax, "LDS of the largest instantiation");
+  return with_planes(a.table, a.N, a.d, a.cand, a.K, a.max_norm, a.spec, planes_ws, st, [&](const void* ws) -> int {
+#define GE_CALL(KKB) return f16_launch_kkb<MASKED, KKB>(a, sets, ws, st)
+    GE_KKB_SWITCH(a.d, GE_CALL)
+#undef GE_CALL
+  });
+}
+
+// after topk_merge_kernel in a MASKED top-k: ge_rank_f16_masked.hip
+__global__ void topk_bad_set_rows_kernel(const int32_t* __restrict__ row_set, int64_t B, int32_t n_sets, int k,
+                                         int32_t* __restrict__ out_id, float* __restrict__ out_loss);
+
+// The top-k sweep (rank_f16_kernel MODE 3, grid row blocks x candidate ranges), then the merge of the partial lists.
+// The same planes and Q staging as the rank sweep, so the losses are MODE 1's.  Behind route_topk; the workspace and the
+// grid are checked here, in this order.
+template <bool MASKED>
+int topk_sweep_run(const SweepArgs& a, const TopkOut& t, const SetArgs* sets, const void* planes_ws, hipStream_t st) {
+  if (!t.workspace || reinterpret_cast<uintptr_t>(t.workspace) % 256 != 0) return GE_EINVAL;
+  if (t.workspace_bytes < topk_ws_bytes(a.B, a.K, t.k)) return GE_ENOMEM;
+  if (!topk_grid_ok(a.B, a.K)) return GE_ENOTSUP;
+  static_assert(topk_lds_bytes<18>() + kSetsLds<MASKED> <= kLdsMax, "LDS of the largest top-k instantiation");
+  const int64_t n_rb = (a.B + kRB - 1) / kRB, n_ct = (a.K + kRB - 1) / kRB;   // (n_ct < INT32_MAX / 8: the planes' 2^32 bytes)
+  const int64_t ns = topk_splits(a.B, a.K);
+  TopkArgs tk;
+  tk.k = t.k;
+  tk.cap = topk_kp(t.k) + 128;
+  tk.n_split = (int)ns;
+  tk.pool = reinterpret_cast<u64*>(t.workspace);
+  tk.part = tk.pool + a.B * ns * tk.cap;
+  tk.out_id = t.out_id;
+  tk.out_loss = t.out_loss;
+  const SweepTk<MASKED> stk = sweep_tk<MASKED>(tk, sets);
+  return with_planes(a.table, a.N, a.d, a.cand, a.K, a.max_norm, a.spec, planes_ws, st, [&](const void* ws) -> int {
+    const PlanesWs p = planes_at(ws, a.N);
+    auto sweep = [&]() -> int {
+#define GE_CALL(KKB)                                                                                                  \
+  {                                                                                                                   \
+    auto kern = rank_f16_kernel<KKB, 3, MASKED>;                                                                      \
+    if (int rc = lds_opt_in(kern)) return rc;                                                                         \
+    hipLaunchKernelGGL(kern, dim3((unsigned)n_rb, (unsigned)ns), dim3(kBlk), topk_lds_bytes<KKB>() + kSetsLds<MASKED>, st, \
+                       a.table, a.N, a.d, a.hr, a.B, nullptr, a.cand, a.K, a.max_norm, a.cand_is_head, a.known_off,    \
+                       a.known_rc, nullptr, nullptr, nullptr, nullptr, (int)n_ct, n_rb * n_ct, a.spec, 0, p.pos_of,    \
+                       p.planes, stk);                                                                                \
+    return launch_status();                                                                                           \
+  }
+      GE_KKB_SWITCH(a.d, GE_CALL)
+#undef GE_CALL
+    };
+    const int rc = sweep();
+    if (rc != 0) return rc;
+    hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)((a.B + 3) / 4)), dim3(256), 0, st, a.hr, a.B, a.N, tk);
+    if constexpr (MASKED) {   // a row whose set index is out of range is a bad row
+      hipLaunchKernelGGL(topk_bad_set_rows_kernel, dim3((unsigned)((a.B * t.k + 255) / 256)), dim3(256), 0, st, sets->row_set,
+                         a.B, sets->n_sets, t.k, t.out_id, t.out_loss);
+    }
+    return launch_status();
+  });
 }
 
 }  // namespace

@@ -48,38 +48,6 @@ __global__ __launch_bounds__(256) void topk_bad_set_rows_kernel(const int32_t* _
   if (s < -1 || s >= n_sets) { out_id[i] = -1; out_loss[i] = __builtin_nanf(""); }
 }
 
-MaskedTopkArgs masked_args(const TopkArgs& tk, const int32_t* row_set, const uint32_t* mask, int32_t n_sets) {
-  MaskedTopkArgs m;
-  static_cast<TopkArgs&>(m) = tk;
-  m.row_set = row_set;
-  m.mask = mask;
-  m.n_sets = n_sets;
-  return m;
-}
-
-template <int KKB>
-int masked_launch_kkb(const SweepArgs& a, const MaskedTopkArgs& mk, const void* planes_ws, hipStream_t st) {
-  const int64_t n_rb = (a.B + kRB - 1) / kRB, n_ct = (a.K + kRB - 1) / kRB;
-  const int64_t n_tiles = n_rb * n_ct;
-  const int64_t grid = std::min<int64_t>(n_tiles, GE_PIPE_GRID_M * (int64_t)cu_count());
-  const int32_t* pos_of = reinterpret_cast<const int32_t*>(planes_ws);
-  const _Float16* planes = reinterpret_cast<const _Float16*>(reinterpret_cast<const char*>(planes_ws) + pos_bytes(a.N));
-  auto go = [&](auto kern) -> int {
-    if (int rc = lds_opt_in(kern)) return rc;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kBlk), h_lds_bytes<KKB>() + kMaskLdsBytes, st, a.table, a.N, a.d, a.hr,
-                       a.B, a.true_id, a.cand, a.K, a.max_norm, a.cand_is_head, a.known_off, a.known_rc, a.raw_cnt, a.skip_cnt,
-                       a.true_loss, a.scores_out, (int)n_ct, n_tiles, a.spec, a.sweep_flags, pos_of, planes, mk);
-    return launch_status();
-  };
-  if (a.scores_out) return go(rank_f16_kernel<KKB, 1, true>);
-  return go(rank_f16_kernel<KKB, 0, true>);
-}
-
-// what both masked sweeps ask of the shape: the split-precision range, planes within 32-bit offsets, 32-bit tile counts
-bool masked_shape_ok(int64_t N, int32_t d, int64_t B, int64_t K, float max_norm) {
-  return f16_sweep_ok(d, max_norm) && rank_planes_bytes(N, d, K) != 0 && sweep_tiles(B) <= INT32_MAX / 8;
-}
-
 }  // namespace
 
 int64_t candidate_mask_words(int64_t K) { return K <= 0 ? 0 : planes_slices(K); }
@@ -105,68 +73,17 @@ int mask_from_cells_launch(const int32_t* cells, int64_t M, int32_t n_sets, int6
   return launch_status();
 }
 
-// The rank sweep of f16_sweep_launch with candidate sets (a.scores_only and a.sweep_flags are 0).
-int masked_rank_launch(const SweepArgs& a, const int32_t* row_set, const uint32_t* mask, int32_t n_sets,
-                       const void* planes_ws, hipStream_t st) {
-  if (!masked_shape_ok(a.N, a.d, a.B, a.K, a.max_norm)) return GE_ENOTSUP;
-  if (reinterpret_cast<uintptr_t>(a.table) % 16 != 0) return GE_EINVAL;
-  static_assert(h_lds_bytes<18>() + kMaskLdsBytes <= kLdsMax, "LDS of the largest masked instantiation");
-  const MaskedTopkArgs mk = masked_args(TopkArgs{}, row_set, mask, n_sets);
-  return with_planes(a.table, a.N, a.d, a.cand, a.K, a.max_norm, a.spec, planes_ws, st, [&](const void* ws) -> int {
-#define GE_CALL(KKB) return masked_launch_kkb<KKB>(a, mk, ws, st)
-    GE_KKB_SWITCH(a.d, GE_CALL)
-#undef GE_CALL
-  });
+// f16_sweep_launch and topk_f16_launch with candidate sets (a.scores_only and a.sweep_flags are 0): the route's
+// conditions are asserted
+int masked_rank_launch(const SweepArgs& a, const SetArgs& sets, const void* planes_ws, hipStream_t st) {
+  assert(route_masked_rank(a.N, a.d, a.B, a.K, a.max_norm, table_mod16(a)).kernel == SweepRoute::F16);
+  return f16_sweep_run<true>(a, &sets, planes_ws, st);
 }
 
-// topk_f16_launch with candidate sets: the same workspace, grid and merge.
-int masked_topk_launch(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* cand, int64_t K,
-                       float max_norm, int cand_is_head, const int32_t* known_off, const uint16_t* known_rc, int32_t k,
-                       int32_t* out_id, float* out_loss, int spec, const int32_t* row_set, const uint32_t* mask,
-                       int32_t n_sets, const void* planes_ws, void* workspace, size_t workspace_bytes, hipStream_t st) {
-  if (!masked_shape_ok(N, d, B, K, max_norm)) return GE_ENOTSUP;
-  if (reinterpret_cast<uintptr_t>(table) % 16 != 0) return GE_EINVAL;
-  if (k < 1) return GE_EINVAL;
-  if (k > kTopkMaxK) return GE_ENOTSUP;
-  if (B == 0) return 0;
-  if (!workspace || reinterpret_cast<uintptr_t>(workspace) % 256 != 0) return GE_EINVAL;
-  if (workspace_bytes < topk_ws_bytes(B, K, k)) return GE_ENOMEM;
-  static_assert(topk_lds_bytes<18>() + kMaskLdsBytes <= kLdsMax, "LDS of the largest masked top-k instantiation");
-  const int64_t n_rb = (B + kRB - 1) / kRB, n_ct = (K + kRB - 1) / kRB;
-  const int64_t ns = topk_splits(B, K);
-  if (n_rb * ns > INT32_MAX) return GE_ENOTSUP;
-  TopkArgs tk;
-  tk.k = k;
-  tk.cap = topk_kp(k) + 128;
-  tk.n_split = (int)ns;
-  tk.pool = reinterpret_cast<u64*>(workspace);
-  tk.part = tk.pool + B * ns * tk.cap;
-  tk.out_id = out_id;
-  tk.out_loss = out_loss;
-  const MaskedTopkArgs mk = masked_args(tk, row_set, mask, n_sets);
-  return with_planes(table, N, d, cand, K, max_norm, spec, planes_ws, st, [&](const void* ws) -> int {
-    const int32_t* pos_of = reinterpret_cast<const int32_t*>(ws);
-    const _Float16* planes = reinterpret_cast<const _Float16*>(reinterpret_cast<const char*>(ws) + pos_bytes(N));
-    auto sweep = [&]() -> int {
-#define GE_CALL(KKB)                                                                                                  \
-  {                                                                                                                   \
-    auto kern = rank_f16_kernel<KKB, 3, true>;                                                                        \
-    if (int rc = lds_opt_in(kern)) return rc;                                                                         \
-    hipLaunchKernelGGL(kern, dim3((unsigned)n_rb, (unsigned)ns), dim3(kBlk), topk_lds_bytes<KKB>() + kMaskLdsBytes, st, \
-                       table, N, d, hr, B, nullptr, cand, K, max_norm, cand_is_head, known_off, known_rc, nullptr,    \
-                       nullptr, nullptr, nullptr, (int)n_ct, n_rb * n_ct, spec, 0, pos_of, planes, mk);               \
-    return launch_status();                                                                                           \
-  }
-      GE_KKB_SWITCH(d, GE_CALL)
-#undef GE_CALL
-    };
-    const int rc = sweep();
-    if (rc != 0) return rc;
-    hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, hr, B, N, tk);
-    hipLaunchKernelGGL(topk_bad_set_rows_kernel, dim3((unsigned)((B * k + 255) / 256)), dim3(256), 0, st, row_set, B, n_sets,
-                       k, out_id, out_loss);
-    return launch_status();
-  });
+int masked_topk_launch(const SweepArgs& a, const TopkOut& t, const SetArgs& sets, const void* planes_ws, hipStream_t st) {
+  assert(route_topk(a.N, a.d, a.B, a.K, a.max_norm, table_mod16(a), t.k, true).kernel == SweepRoute::F16);
+  return topk_sweep_run<true>(a, t, &sets, planes_ws, st);
 }
 
 }  // namespace ge
+

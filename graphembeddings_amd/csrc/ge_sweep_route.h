@@ -1,8 +1,9 @@
-// ge_sweep_route.h -- which kernel serves a ComplEx / HolE 1-vs-K candidate sweep (ge_rank_1vK_planes,
-// ge_rank_1vK_vs_loss, ge_complex_score_1vK; ge_topk_1vK_planes has one kernel and uses f16_sweep_ok alone), and the size
-// formulas that decision rests on.  The ONE place that decides: ge_rank.hip, ge_rank_pipe.hip, ge_rank_f16.hip and
-// ge_1vk.hip switch on the route and launch; none refuses a shape for another to catch.  Host only, plain C++17: tested
-// without a GPU (tests/sweep_route_dump.cpp).
+// ge_sweep_route.h -- which kernel serves a ComplEx / HolE 1-vs-K candidate sweep, and the size formulas that decision
+// rests on: route_rank (ge_rank_1vK_planes, ge_rank_1vK_vs_loss), route_score (ge_complex_score_1vK), route_masked_rank
+// (ge_rank_1vK_masked) and route_topk (ge_topk_1vK_planes, ge_topk_1vK_masked), with the top-k workspace (topk_splits,
+// topk_ws_bytes) and its grid limit (topk_grid_ok).  The ONE place that decides: ge_rank.hip, ge_rank_pipe.hip,
+// ge_rank_f16.hip, ge_rank_f16_masked.hip and ge_1vk.hip switch on the route, or assert it, and launch; none refuses a
+// shape for another to catch.  Host only, plain C++17: tested without a GPU (tests/sweep_route_dump.cpp).
 // The route as a table: DESIGN.md section 4.
 #pragma once
 #include <stddef.h>
@@ -98,5 +99,67 @@ inline SweepRoute route_score(int64_t N, int32_t d, int64_t B, int64_t K, float 
   }
   return {SweepRoute::ScoreBasic, 0};
 }
+
+// ---- the top-k sweep and the candidate-set (masked) forms: F16 is their one kernel, so no other road.
+// In order: the split-precision range, addressable planes and -- masked -- 32-bit row-block arithmetic, GE_ENOTSUP; then
+// -- masked -- the table's 16-byte alignment, GE_EINVAL.  The unmasked top-k asks neither of the last two.
+inline int f16_only_status(int64_t N, int32_t d, int64_t B, int64_t K, float max_norm, int table_addr_mod_16, bool masked) {
+  if (!f16_sweep_ok(d, max_norm) || rank_planes_bytes(N, d, K) == 0) return GE_ENOTSUP;
+  if (masked && sweep_tiles(B) > INT32_MAX / 8) return GE_ENOTSUP;
+  return masked && table_addr_mod_16 != 0 ? GE_EINVAL : 0;
+}
+
+// (ge_rank_1vK_masked returns for B == 0 or K == 0 before it asks)
+inline SweepRoute route_masked_rank(int64_t N, int32_t d, int64_t B, int64_t K, float max_norm, int table_addr_mod_16) {
+  if (const int rc = f16_only_status(N, d, B, K, max_norm, table_addr_mod_16, true)) return {SweepRoute::None, rc};
+  if (B == 0) return {SweepRoute::None, 0};
+  return {SweepRoute::F16, 0};
+}
+
+constexpr int kTopkMaxK = 128;             // the longest list of the top-k sweeps, ComplEx / HolE and translation alike
+// a top-k pool past kp entries is cut back to k after a tile (>= 32 appends apart)
+constexpr int topk_kp(int k) { return (k + 95) / 64 * 64; }   // k + 32 rounded up: 64 for k <= 32, 192 for k = 128
+
+inline SweepRoute route_topk(int64_t N, int32_t d, int64_t B, int64_t K, float max_norm, int table_addr_mod_16, int32_t k,
+                             bool masked) {
+  if (const int rc = f16_only_status(N, d, B, K, max_norm, table_addr_mod_16, masked)) return {SweepRoute::None, rc};
+  if (k < 1) return {SweepRoute::None, GE_EINVAL};
+  if (k > kTopkMaxK) return {SweepRoute::None, GE_ENOTSUP};
+  if (B == 0) return {SweepRoute::None, 0};
+  return {SweepRoute::F16, 0};
+}
+
+// Top-k: workgroups per row block.  With fewer than 256 row blocks (one workgroup per CU of the MI355X) the row
+// blocks' candidates are cut into ranges until there are about 256 workgroups (one query against 1.2 M candidates: 256
+// ranges of 37 tiles); the partial lists meet in topk_merge_kernel.  A function of (B, K) alone, so that the workspace is.
+// B > 0.
+constexpr int64_t topk_splits(int64_t B, int64_t K) {
+  const int64_t n_rb = sweep_tiles(B), n_ct = sweep_tiles(K);
+  if (n_rb >= 256) return 1;
+  const int64_t want = (256 + n_rb - 1) / n_rb, ns = n_ct < want ? n_ct : want;
+  return ns < 1 ? 1 : ns;
+}
+
+constexpr int64_t topk_ws_rows(int64_t n_rb, int64_t K, int32_t k) {      // bytes for n_rb full row blocks
+  return n_rb * kRB * topk_splits(n_rb * kRB, K) * (topk_kp(k) + 128 + k) * (int64_t)sizeof(uint64_t);
+}
+
+// Workspace of a top-k over B rows and K candidates: the pools, [B][n_split][kp + 128] keys, and the partial lists,
+// [B][n_split][k].  Taken as the largest need of any B' <= B (the ranges shrink as B grows), so that the
+// size is monotone in B, K and k.
+constexpr size_t topk_ws_bytes(int64_t B, int64_t K, int32_t k) {
+  if (B <= 0 || K <= 0 || k < 1 || k > kTopkMaxK) return 0;
+  const int64_t n_rb = sweep_tiles(B);
+  int64_t need = topk_ws_rows(n_rb, K, k);
+  for (int64_t r = 1; r < n_rb && r < 256; ++r) {
+    const int64_t rows = topk_ws_rows(r, K, k);
+    if (rows > need) need = rows;
+  }
+  return (size_t)need + 256;
+}
+
+// the top-k's grid, row blocks x candidate ranges.  The launcher asks it behind the workspace's pointer and size, so a
+// call too large for the grid answers GE_ENOMEM first when its workspace is short.
+constexpr bool topk_grid_ok(int64_t B, int64_t K) { return sweep_tiles(B) * topk_splits(B, K) <= INT32_MAX; }
 
 }  // namespace ge

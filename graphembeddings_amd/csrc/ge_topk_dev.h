@@ -3,6 +3,7 @@
 // NL: pool entries per lane, so a pool holds at most NL * 64 keys.
 #pragma once
 #include "ge_common.h"
+#include "ge_sweep_route.h"
 
 namespace ge {
 
@@ -13,8 +14,7 @@ constexpr u64 kNoKey = ~0ull;           // (also the padding of a partial list)
 // or NaN the integer order of the keys is the order ascending by (value, id); distinct candidates have distinct keys.
 __device__ __forceinline__ u64 topk_key(float e, int32_t id) { return ((u64)__float_as_uint(e) << 32) | (unsigned)id; }
 
-// a pool past kp entries is cut back to k after a tile (>= 32 appends apart)
-__host__ __device__ constexpr int topk_kp(int k) { return (k + 95) / 64 * 64; }   // k + 32 rounded up: 64 for k <= 32, 192 for k = 128
+// (topk_kp(k), the pool size past which a pool is cut back to k: ge_sweep_route.h, where the workspace size needs it)
 
 __device__ __forceinline__ u64 readlane64(u64 x, int l) {
   const unsigned lo = __builtin_amdgcn_readlane((int)(unsigned)x, l);

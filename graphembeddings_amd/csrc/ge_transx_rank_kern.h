@@ -201,7 +201,7 @@ __global__ __launch_bounds__(kBlock) void rank_filter_kernel(TransTables T, cons
 // ---- top-k (ge_transx_topk / ge_transr_topk): per query row (fixed f, relation r) the first k candidates c in
 // ascending (D_c, c), D_c the rank sweep's own value (GE_SWEEP_DISTS), known cells skipped.  D is a sum of |u| or u^2
 // from +0, never negative or -0.0, so topk_key's integer order is that order.
-constexpr int kTopkMaxK = 128;
+// (k <= kTopkMaxK: ge_sweep_route.h)
 constexpr int kTopkLanes = 7;            // pool entries per lane: cap = kp + 256 <= 448 (a candidate block adds <= 256)
 constexpr int kMergeFan = 16;            // partial lists per merge wave
 

@@ -2,7 +2,8 @@
 the chain of launchers that each tried the one that superseded it and fell back on GE_ENOTSUP (ge_rank.hip ->
 ge_rank_pipe.hip -> ge_rank_f16.hip, and ge_1vk.hip into the same chain), kept in that nested shape on purpose: it shares
 no structure with the route table it checks (tests/test_sweep_route_host.py).  Each launcher returns the name of the
-kernel it launched, or an error code."""
+kernel it launched, or an error code.  Below them, in the same way, the fronts of the top-k and candidate-set launchers
+and the top-k workspace size as they stood before route_topk, route_masked_rank and topk_ws_bytes moved to that header."""
 GE_EINVAL, GE_ENOTSUP = -22, -95
 INT32_MAX = 2 ** 31 - 1
 KERNELS = ["None", "F16", "Pipe40", "Pipe32", "Pipe24", "RankF32", "ScoreTileF16", "ScoreTile", "ScoreFullK",
@@ -106,7 +107,86 @@ def _complex_score_1vK_launch(N, d, B, K, max_norm, mod16):
     return "ScoreBasic"
 
 
-def route(entry, N, d, B, K, max_norm, mod16):
-    """(kernel name, status) of entry "rank" or "score"."""
-    rc = (_complex_rank_1vK_launch if entry == "rank" else _complex_score_1vK_launch)(N, d, B, K, max_norm, mod16)
+# ---- the top-k sweep and the candidate-set (masked) forms, BEFORE route_topk / route_masked_rank existed: each launcher
+# of ge_rank_f16.hip and ge_rank_f16_masked.hip refused shapes at its own front, restated here launcher by launcher.
+# They stop where the launchers first looked at the workspace.
+TOPK_MAX_K = 128
+
+
+def _masked_shape_ok(N, d, B, K, max_norm):
+    f16_sweep_ok = d % 8 == 0 and d >= 56 and d <= 288 and max_norm <= 8.0
+    return f16_sweep_ok and _rank_planes_bytes(N, d, K) != 0 and _tiles(B) <= INT32_MAX // 8
+
+
+def _topk_f16_launch(N, d, B, K, max_norm, mod16, k):
+    f16_sweep_ok = d % 8 == 0 and d >= 56 and d <= 288 and max_norm <= 8.0
+    if not f16_sweep_ok or _rank_planes_bytes(N, d, K) == 0:
+        return GE_ENOTSUP
+    if k < 1:
+        return GE_EINVAL
+    if k > TOPK_MAX_K:
+        return GE_ENOTSUP
+    if B == 0:
+        return 0
+    return "F16"
+
+
+def _masked_topk_launch(N, d, B, K, max_norm, mod16, k):
+    if not _masked_shape_ok(N, d, B, K, max_norm):
+        return GE_ENOTSUP
+    if mod16 != 0:
+        return GE_EINVAL
+    if k < 1:
+        return GE_EINVAL
+    if k > TOPK_MAX_K:
+        return GE_ENOTSUP
+    if B == 0:
+        return 0
+    return "F16"
+
+
+def _masked_rank_launch(N, d, B, K, max_norm, mod16, k):
+    if not _masked_shape_ok(N, d, B, K, max_norm):
+        return GE_ENOTSUP
+    if mod16 != 0:
+        return GE_EINVAL
+    if B == 0:          # (never reached the launcher: ge_rank_1vK_masked returned 0 for B == 0 before calling it)
+        return 0
+    return "F16"
+
+
+def topk_splits(B, K):
+    n_rb, n_ct = _tiles(B), _tiles(K)
+    if n_rb >= 256:
+        return 1
+    return max(1, min(n_ct, (256 + n_rb - 1) // n_rb))
+
+
+def _topk_ws_rows(n_rb, K, k):
+    kp = (k + 95) // 64 * 64
+    return n_rb * 128 * topk_splits(n_rb * 128, K) * (kp + 128 + k) * 8
+
+
+def topk_ws_bytes(B, K, k):
+    if B <= 0 or K <= 0 or k < 1 or k > TOPK_MAX_K:
+        return 0
+    n_rb = _tiles(B)
+    need = _topk_ws_rows(n_rb, K, k)
+    for r in range(1, min(n_rb, 256)):
+        need = max(need, _topk_ws_rows(r, K, k))
+    return need + 256
+
+
+def topk_grid_ok(B, K):
+    """the launchers' last refusal, behind the workspace checks: n_rb * ns > INT32_MAX was GE_ENOTSUP"""
+    return _tiles(B) * topk_splits(B, K) <= INT32_MAX
+
+
+_ENTRIES = {"rank": _complex_rank_1vK_launch, "score": _complex_score_1vK_launch, "topk": _topk_f16_launch,
+            "masked_topk": _masked_topk_launch, "masked_rank": _masked_rank_launch}
+
+
+def route(entry, N, d, B, K, max_norm, mod16, k=None):
+    """(kernel name, status) of entry "rank", "score", "topk", "masked_rank" or "masked_topk" (the last three take k)."""
+    rc = _ENTRIES[entry](N, d, B, K, max_norm, mod16) if k is None else _ENTRIES[entry](N, d, B, K, max_norm, mod16, k)
     return (rc, 0) if isinstance(rc, str) else ("None", rc)
