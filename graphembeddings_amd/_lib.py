@@ -36,6 +36,7 @@ SYMBOLS = {
     "ge_hinge_grad": (C.c_int, [_p, _i64, _i32, _p, _p, _i64, _f, _f, _f, C.c_int, _p, _p, _p, _p]),
     "ge_scatter_add_rows": (C.c_int, [_p, _i64, _i32, _p, _p, _i64, _p]),
     "ge_gather_rows": (C.c_int, [_p, _i64, _i32, _p, _i64, _p, _p]),
+    "ge_adagrad_rows": (C.c_int, [_p, _p, _i64, _i32, _p, _p, _p, _i64, _f, _p]),
     "ge_corrupt_batch": (C.c_int, [_p, _i64, _p, _i64, _p, _i32, _p, _u64, _u64, _i32, _i32, _p, _p]),
     "ge_bernoulli_corrupt_batch": (C.c_int, [_p, _i64, _p, _p, _p, _p, _i64, _p, _i32, _i32, _i32, _u64, _u64, _p, _p]),
     "ge_complex_score_1vK": (C.c_int, [_p, _i64, _i32, _p, _i64, _p, _i64, _f, C.c_int, C.c_int, _p, _p]),
@@ -70,6 +71,9 @@ SYMBOLS = {
     "ge_train_pipeline_destroy": (C.c_int, [_p]),
     "ge_train_steps": (C.c_int, [_p, _i64, _i32, _p, _i64, _i64, _i64, _i64, _p, _p, _i32, _p, _u64, _u64, _i32,
                                  _i32, _f, _f, _f, _f, _f, C.c_int, _p, C.c_int, _p, _p, _sz, _p, C.c_int, _p, _p]),
+    "ge_train_adagrad_workspace_bytes": (_sz, [_i64, _i32]),
+    "ge_train_steps_adagrad": (C.c_int, [_p, _p, _i64, _i32, _p, _i64, _i64, _i64, _i64, _p, _p, _i32, _p, _u64, _u64, _i32,
+                                         _i32, _f, _f, _f, _f, _f, C.c_int, _p, C.c_int, _p, _p, _sz, _p, _p]),
     "ge_train_logloss_workspace_bytes": (_sz, [_i64, _i32, _i32]),
     "ge_train_steps_logloss": (C.c_int, [_p, _i64, _i32, _p, _i64, _i64, _i64, _i64, _p, _p, _i32, _p, _u64, _u64, _i32,
                                          _i32, _i32, _f, _f, _f, _f, _f, _p, C.c_int, _p, _p, _sz, _p, _p]),
@@ -181,7 +185,7 @@ def load():
             fn = getattr(lib, name)  # AttributeError if the ABI and the header diverge
             fn.restype = res
             fn.argtypes = args
-        if lib.ge_version() < 410:
+        if lib.ge_version() < 420:
             raise RuntimeError("libge_hip.so is older than the Python host expects")
         _lib = lib
     return _lib

@@ -185,6 +185,23 @@ int ge_scatter_add_rows(float* table, int64_t N, int32_t d, const int32_t* idx, 
   return scatter_add_rows_launch(table, N, d, idx, val, R, (hipStream_t)stream);
 }
 
+// [a, a + n floats) and [b, b + n floats) share a byte
+static inline bool rows_overlap(const float* a, const float* b, int64_t N, int32_t d) {
+  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+  const uintptr_t n = (uintptr_t)N * (uintptr_t)d * sizeof(float);
+  return x < y + n && y < x + n;
+}
+
+int ge_adagrad_rows(float* table, float* accum, int64_t N, int32_t d, const int32_t* idx, const float* val,
+                    const int32_t* perm, int64_t R, float lr, void* stream) {
+  if (R < 0 || !ok_table(table, N, d) || !accum) return GE_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(table) | reinterpret_cast<uintptr_t>(accum)) % 4 != 0) return GE_EINVAL;
+  if (rows_overlap(table, accum, N, d)) return GE_EINVAL;
+  if (R == 0) return 0;
+  if (!idx || !val || !perm) return GE_EINVAL;
+  return adagrad_rows_launch(table, accum, N, d, idx, val, perm, R, lr, (hipStream_t)stream);
+}
+
 int ge_gather_rows(const float* table, int64_t N, int32_t d, const int32_t* idx, int64_t R, float* out,
                    void* stream) {
   if (R < 0 || !ok_table(table, N, d)) return GE_EINVAL;
@@ -905,6 +922,28 @@ int ge_train_steps(float* table, int64_t N, int32_t d, const int32_t* triples, i
   return train_steps_run(table, d, StepSeq{triples, T, first_row, B, global_step0}, n_steps, ts, margin,
                          StepHyper{lr0, decay_steps, decay_rate, max_norm}, model, loss, keep_all_losses, neg_ws, workspace,
                          workspace_bytes, ev_pairs, ev_kernel, pipeline, (hipStream_t)stream);
+}
+
+size_t ge_train_adagrad_workspace_bytes(int64_t B, int32_t d) { return ge_train_workspace_bytes(B, d); }
+
+int ge_train_steps_adagrad(float* table, float* accum, int64_t N, int32_t d, const int32_t* triples, int64_t T,
+                           int64_t first_row, int64_t B, int64_t n_steps, const int32_t* id_to_type,
+                           const int64_t* type_offsets, int32_t n_types, const int32_t* type_ids, uint64_t seed,
+                           uint64_t global_step0, int32_t padded_size, int32_t mode, float margin, float lr0,
+                           float decay_steps, float decay_rate, float max_norm, int model, float* loss,
+                           int keep_all_losses, int32_t* neg_ws, void* workspace, size_t workspace_bytes, void* pipeline,
+                           void* stream) {
+  if (B <= 0 || n_steps < 0 || T < B || first_row < 0 || !ok_table(table, N, d) || !max_norm_ok(max_norm)) return GE_EINVAL;
+  if (!accum || rows_overlap(table, accum, N, d)) return GE_EINVAL;
+  TypeSampler ts;
+  if (type_sampler(ts, id_to_type, N, type_offsets, n_types, type_ids, seed, padded_size, mode, true)) return GE_EINVAL;
+  if (!triples || !loss || !neg_ws || !workspace) return GE_EINVAL;
+  if (model < 0 || model > 3) return GE_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(table) | reinterpret_cast<uintptr_t>(accum)) % 4 != 0) return GE_EINVAL;
+  if (reinterpret_cast<uintptr_t>(workspace) % 256 != 0) return GE_EINVAL;
+  return train_adagrad_run(table, accum, d, StepSeq{triples, T, first_row, B, global_step0}, n_steps, ts, margin,
+                           StepHyper{lr0, decay_steps, decay_rate, max_norm}, model, loss, keep_all_losses, neg_ws,
+                           workspace, workspace_bytes, pipeline, (hipStream_t)stream);
 }
 
 size_t ge_train_logloss_workspace_bytes(int64_t B, int32_t negative_ratio, int32_t d) {

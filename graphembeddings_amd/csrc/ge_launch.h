@@ -182,9 +182,20 @@ int train_logloss_run(float* table, int32_t d, const StepSeq& q, int64_t n_steps
 size_t train_prepare_bytes(int64_t B, int64_t n_steps);
 int train_prepare_run(const StepSeq& q, int64_t n_steps, const TypeSampler& ts, int direct, int32_t* out, hipStream_t st);
 void train_prepared_layout(int64_t B, int64_t* out);
+// the AdaGrad loop (holE.py:296 with AdagradOptimizer): the prepared path only, its workspace is train_ws_bytes'
+int train_adagrad_run(float* table, float* accum, int32_t d, const StepSeq& q, int64_t n_steps, const TypeSampler& ts,
+                      float margin, const StepHyper& hp, int model, float* loss, int keep_all_losses, int32_t* neg_ws,
+                      void* workspace, size_t workspace_bytes, void* pipe_handle, hipStream_t st);
 int pipeline_create(void** out);
 int pipeline_reset(void* h);
 int pipeline_destroy(void* h);
+
+// ge_adagrad.hip: the AdaGrad update of a prepared step record (items kernel + ordered pass over the split rows; gval
+// holds minus the gradient and is written: split rows park their partial sums there) and of any sorted IndexedSlices
+int adagrad_items_launch(float* table, float* accum, int d, const TileGeom& G, const int32_t* step_rec, const int32_t* gidx,
+                         float* gval, float lr, hipStream_t st);
+int adagrad_rows_launch(float* table, float* accum, int64_t N, int32_t d, const int32_t* idx, const float* val,
+                        const int32_t* perm, int64_t R, float lr, hipStream_t st);
 
 // ge_shard.hip: the row-sharded step's requester and owner planners
 size_t shard_plan_scratch_bytes(int64_t B, int64_t S);

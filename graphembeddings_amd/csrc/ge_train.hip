@@ -1049,6 +1049,47 @@ int train_steps_run(float* table, int32_t d, const StepSeq& q, int64_t n_steps, 
   return 0;
 }
 
+// ------------------------------------------------------------------ the AdaGrad loop (holE.py:296, AdagradOptimizer)
+// The hinge loop on the prepared path with the optimizer exchanged: records without direct tags (every row of a step is
+// listed), the gradient kernel at lr = 1 writing minus the snapshot gradient, then the two kernels of ge_adagrad.hip.
+// HolE runs the direct-correlation kernels on the real table whatever d is: AdaGrad is elementwise and not linear, so
+// unlike SGD it does not commute with the DFT and the table is never carried in the frequency domain.
+int train_adagrad_run(float* table, float* accum, int32_t d, const StepSeq& q, int64_t n_steps, const TypeSampler& ts,
+                      float margin, const StepHyper& hp, int model, float* loss, int keep_all_losses, int32_t* neg_ws,
+                      void* workspace, size_t workspace_bytes, void* pipe_handle, hipStream_t st) {
+  const int64_t N = ts.N, B = q.B;
+  if (model == GE_MODEL_HOLE_SPECTRAL || !train_fast_ok(B, d)) return GE_ENOTSUP;
+  if (workspace_bytes < train_ws_bytes(B, d)) return GE_ENOMEM;
+  if (n_steps <= 0) return 0;
+  const bool hole = model != GE_MODEL_COMPLEX;
+  const TrainWs w = train_ws(workspace, B, d);
+  PrepCursor cur(StepIdentity{q, ts, d, 0, 0, workspace}, static_cast<Pipeline*>(pipe_handle), w.prep, st);
+  const PrepLayout& L = cur.layout();
+  int rc = cur.begin();
+  if (rc) return rc;
+  for (int64_t s = 0; s < n_steps; ++s) {
+    const uint64_t gs = q.global_step0 + (uint64_t)s;
+    const int32_t* pos = q.triples + 3 * step_row(q.first_row, q.T, B, s);
+    float* loss_s = keep_all_losses ? loss + s * B : loss;
+    const int32_t* step_rec = nullptr;
+    rc = cur.step(s, &step_rec);
+    if (rc) return rc;
+    float* gval = w.g.gval + (size_t)(gs % (uint64_t)w.ring) * w.region_floats;   // this step's region of the ring
+    rc = hole ? hole_hinge_grad_launch(table, N, d, pos, step_rec, B, margin, 1.0f, hp.max_norm, loss_s, w.g.gidx, gval, st)
+              : complex_hinge_grad_launch(table, N, d, pos, step_rec, B, margin, 1.0f, hp.max_norm, loss_s, w.g.gidx, gval, st,
+                                          nullptr, nullptr, nullptr, nullptr, 0,
+                                          L.off_order >= 0 ? step_rec + L.off_order : nullptr);
+    if (rc) return rc;
+    rc = adagrad_items_launch(table, accum, d, geom_of(L), step_rec, w.g.gidx, gval, hp.lr_at(gs), st);
+    if (rc) return rc;
+  }
+  const int32_t* last = nullptr;
+  rc = cur.finish(n_steps, &last);
+  if (rc) return rc;
+  GE_HIP_TRY(hipMemcpyAsync(neg_ws, last, sizeof(int32_t) * 3 * (size_t)B, hipMemcpyDeviceToDevice, st));
+  return 0;
+}
+
 // ------------------------------------------------------------------ the --log_loss loop (holE.py:194-196, 206-220, 296)
 // Per step: M = (1+K) B triples -- the positives (label +1) and K corrupted batches (label -1, the k-th drawn
 // with Philox step key global_step * K + k) -- loss_i = log(1 + exp(-y_i s_i)) + l2 * l2_loss(table), and

@@ -295,6 +295,54 @@ def scatter_add_rows(table: torch.Tensor, idx: torch.Tensor, val: torch.Tensor) 
               val.data_ptr(), idx.numel(), _stream())
 
 
+def _accumulator(accumulator: torch.Tensor, table: torch.Tensor) -> torch.Tensor:
+    _need_cuda(accumulator, "accumulator")
+    if accumulator.dtype != torch.float32 or accumulator.shape != table.shape or not accumulator.is_contiguous():
+        raise ValueError("accumulator must be a contiguous float32 tensor of the table's shape")
+    return accumulator
+
+
+def adagrad_rows(table: torch.Tensor, accumulator: torch.Tensor, idx: torch.Tensor, val: torch.Tensor, lr: float) -> None:
+    """The AdaGrad counterpart of scatter_add_rows (ge_adagrad_rows; AdagradOptimizer at holE.py:296): `val` holds MINUS
+    the gradient rows.  Per row named by idx >= 0: s = sum of its val rows, accumulator[row] += s*s,
+    table[row] += lr * s / sqrt(accumulator[row]).  Rows not named are not touched."""
+    table = _table(table)
+    acc = _accumulator(accumulator, table)
+    _need_cuda(idx, "idx"); _need_cuda(val, "val")
+    idx = idx.to(torch.int32).contiguous()
+    val = val.to(torch.float32).contiguous()
+    if val.shape != (idx.numel(), table.shape[1]):
+        raise ValueError("val must be [len(idx), embedding_dim]")
+    # a row's occurrences consecutive and in their original order: the stable argsort, empty slots last
+    key = torch.where(idx < 0, torch.full_like(idx, table.shape[0]), idx)
+    perm = torch.argsort(key, stable=True).to(torch.int32)
+    _lib.call("ge_adagrad_rows", table.data_ptr(), acc.data_ptr(), table.shape[0], table.shape[1], idx.data_ptr(),
+              val.data_ptr(), perm.data_ptr(), idx.numel(), float(lr), _stream())
+
+
+class HingeAdaGrad:
+    """AdagradOptimizer(lr, initial_accumulator_value).minimize(loss) in place of the GradientDescentOptimizer of
+    holE.py:296 for the hinge of holE.py:231: ge_hinge_grad at lr = 1 (minus the gradient of SUM_i loss_i as
+    IndexedSlices), duplicates summed per row, then the AdaGrad update of every row named.  Owns `.accumulator`."""
+
+    def __init__(self, embeddings: torch.Tensor, batch_size: int, *, margin: float = 0.2, model="complex",
+                 max_norm: float = 1.0, initial_accumulator_value: float = 0.1):
+        if not initial_accumulator_value > 0:
+            raise ValueError("initial_accumulator_value must be positive")
+        self.embeddings = _table(embeddings)
+        if _MODELS[model] == MODEL_HOLE_SPECTRAL:
+            raise ValueError("AdaGrad is elementwise: it does not commute with the DFT of a spectral HolE table")
+        self.margin, self.max_norm, self.model = float(margin), float(max_norm), model
+        self.accumulator = torch.full_like(self.embeddings, float(initial_accumulator_value))
+
+    def step(self, pos: torch.Tensor, neg: torch.Tensor, lr: float) -> torch.Tensor:
+        """One training step in place on the table and the accumulator; returns the per-pair hinge [B,1]."""
+        loss, gi, gv = hinge_grad(self.embeddings, pos, neg, 1.0, margin=self.margin, model=self.model,
+                                  max_norm=self.max_norm)
+        adagrad_rows(self.embeddings, self.accumulator, gi, gv, lr)
+        return loss.view(-1, 1)
+
+
 def gather_rows(table: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     """out[i] = table[idx[i]] (zeros where idx[i] < 0)."""
     table = _table(table)
@@ -713,7 +761,22 @@ class Trainer:
                  batch_size: int, *, margin: float = 0.2, learning_rate: float = 0.1,
                  decay_steps: float = 0.0, decay_rate: float = 0.5, model="complex", max_norm: float = 1.0,
                  seed: int = 0, corrupt_mode: int = CORRUPT_BATCH_COIN, prepared: bool = True,
-                 lookahead: bool = True, spectral_resident: bool = False, deterministic: bool = False):
+                 lookahead: bool = True, spectral_resident: bool = False, deterministic: bool = False,
+                 optimizer: str = "sgd", initial_accumulator_value: float = 0.1):
+        # optimizer="adagrad": AdagradOptimizer in place of the GradientDescentOptimizer of holE.py:296 -- run() enqueues
+        # ge_train_steps_adagrad (prepared path only; no float atomics, so bitwise reproducible) and `accumulator` holds
+        # the [N,d] sum of squared gradients, filled with initial_accumulator_value
+        if optimizer not in ("sgd", "adagrad"):
+            raise ValueError("optimizer must be 'sgd' or 'adagrad'")
+        self.optimizer, self.accumulator = optimizer, None
+        if optimizer == "adagrad":
+            if spectral_resident or _MODELS[model] == MODEL_HOLE_SPECTRAL:
+                raise ValueError("AdaGrad is elementwise: it does not commute with the DFT, the table stays real "
+                                 "(spectral_resident=False)")
+            if not prepared:
+                raise ValueError("the AdaGrad loop runs on the prepared path only")
+            if not initial_accumulator_value > 0:
+                raise ValueError("initial_accumulator_value must be positive")
         # deterministic (GE_STEP_DETERMINISTIC): rows with more than 16 gradient slots in a step are reduced in a fixed
         # order instead of by float atomics -- every row bitwise reproducible run to run; one more launch per step
         self.deterministic = bool(deterministic)
@@ -747,6 +810,8 @@ class Trainer:
         self._ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
         self._neg = torch.empty(self.B, 3, dtype=torch.int32, device=dev)
         self.last_loss = torch.zeros(self.B, dtype=torch.float32, device=dev)
+        if optimizer == "adagrad":
+            self.accumulator = torch.full_like(self.embeddings, float(initial_accumulator_value))
         # the prepared-steps pipeline (side stream + look-ahead records that survive between run() calls)
         self._pipe = None
         if prepared and lookahead:
@@ -826,6 +891,8 @@ class Trainer:
         row-sorted update, the dense L2 decay carried as one scalar.  last_loss becomes [(1+K)*B]."""
         if self.model != MODEL_COMPLEX:
             raise NotImplementedError("--log_loss is defined for the ComplEx score (holE.py:191-196)")
+        if self.optimizer == "adagrad":
+            raise ValueError("AdaGrad is not available for --log_loss: its dense L2 term makes every row's gradient non-zero")
         self.K, self.l2 = int(negative_ratio), float(l2_regularization)
         dev = self.embeddings.device
         need = _lib.load().ge_train_logloss_workspace_bytes(self.B, self.K, self.embeddings.shape[1])
@@ -861,7 +928,12 @@ class Trainer:
         table = (emb.data_ptr(), emb.shape[0], emb.shape[1])
         rates = (self.lr0, self.decay_steps, self.decay_rate, self.max_norm)
         out = (loss.data_ptr(), int(keep_losses), self._neg.data_ptr(), self._ws.data_ptr(), self._ws.numel())
-        if K:
+        if self.optimizer == "adagrad":
+            if events is not None:
+                raise ValueError("events= times the kernels of the SGD loop; the AdaGrad loop takes none")
+            _lib.call("ge_train_steps_adagrad", emb.data_ptr(), _accumulator(self.accumulator, emb).data_ptr(), *table[1:],
+                      *self._source(n_steps), self.margin, *rates, self.model, *out, self._pipe, _stream())
+        elif K:
             _lib.call("ge_train_steps_logloss", *table, *self._source(n_steps), K, self.l2, *rates, *out, self._pipe, _stream())
         else:
             evp = None

@@ -12,7 +12,9 @@ which starts at 2.0 (holE.py:329, 357-360); the output directory must not exist 
 checkpoint bundle) are not: the table is saved as `model.ckpt.pt` (embeddings + global_step).
 Between validation ticks the steps are enqueued natively by ge_train_steps (hinge) or
 ge_train_steps_logloss (--log_loss) -- no Python per step.
-Extras: --model hole (README.md:42 score), --seed, --max_steps, --checkpoint_seconds.
+Extras: --model hole (README.md:42 score), --seed, --max_steps, --checkpoint_seconds, --optimizer adagrad
+(AdagradOptimizer in place of holE.py:296's GradientDescentOptimizer: ge_train_steps_adagrad; the checkpoint then also
+holds `adagrad_accumulator`).
 """
 from __future__ import annotations
 
@@ -82,6 +84,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('--max_steps', type=int, default=0, help='Stop after this many steps (0 = epoch limit only).')
     p.add_argument('--checkpoint_seconds', type=float, default=300.,
                    help='Also write the best table found so far this often inside an epoch (0 = once per epoch only).')
+    p.add_argument('--optimizer', choices=['sgd', 'adagrad'], default='sgd',
+                   help='sgd: the plain gradient descent of holE.py:296; adagrad: AdagradOptimizer in its place (hinge loss, '
+                        'one GPU).')
+    p.add_argument('--adagrad_init', type=float, default=0.1,
+                   help='With --optimizer adagrad: initial_accumulator_value.')
     p.add_argument('--gpus', type=int, default=1,
                    help='Ranks (one per GPU) the table is row-sharded over; > 1 without a launcher: this program starts them '
                         '(graphembeddings_amd/launch.py).  --batch_size stays the GLOBAL batch.')
@@ -92,15 +99,36 @@ def checkpoint_path(output_dir: str) -> str:
     return os.path.join(output_dir, 'model.ckpt.pt')
 
 
-def save_checkpoint(output_dir: str, embeddings: torch.Tensor, global_step: int) -> None:
+def save_checkpoint(output_dir: str, embeddings: torch.Tensor, global_step: int, adagrad_accumulator=None) -> None:
+    """adagrad_accumulator (--optimizer adagrad): stored beside the table; without it the file is what it always was."""
     tmp = checkpoint_path(output_dir) + '.tmp'
-    torch.save({'embeddings': embeddings.detach().cpu(), 'global_step': int(global_step)}, tmp)
+    ck = {'embeddings': embeddings.detach().cpu(), 'global_step': int(global_step)}
+    if adagrad_accumulator is not None:
+        ck['adagrad_accumulator'] = adagrad_accumulator.detach().cpu()
+    torch.save(ck, tmp)
     os.replace(tmp, checkpoint_path(output_dir))
 
 
-def load_checkpoint(output_dir: str, device='cuda'):
+def load_checkpoint(output_dir: str, device='cuda', with_accumulator: bool = False):
+    """(embeddings, global_step); with_accumulator: also the AdaGrad accumulator, None when the file holds none."""
     ck = torch.load(checkpoint_path(output_dir), weights_only=True)
-    return ck['embeddings'].to(device).contiguous(), int(ck['global_step'])
+    out = ck['embeddings'].to(device).contiguous(), int(ck['global_step'])
+    if not with_accumulator:
+        return out
+    acc = ck.get('adagrad_accumulator')
+    return (*out, None if acc is None else acc.to(device).contiguous())
+
+
+def check_optimizer_flags(FLAGS, world: int = 1) -> None:
+    """--optimizer adagrad: the hinge loss on one GPU."""
+    if getattr(FLAGS, 'optimizer', 'sgd') != 'adagrad':
+        return
+    if FLAGS.log_loss:
+        raise SystemExit('--optimizer adagrad is not available with --log_loss (its dense L2 term touches every row)')
+    if FLAGS.gpus > 1 or world > 1:
+        raise SystemExit('--optimizer adagrad runs on one GPU (drop --gpus)')
+    if not FLAGS.adagrad_init > 0:
+        raise SystemExit('--adagrad_init must be positive')
 
 
 def run_training(data: D.HolEData, FLAGS, log=print) -> dict:
@@ -120,8 +148,10 @@ def run_training(data: D.HolEData, FLAGS, log=print) -> dict:
     names, id_to_type, offsets, ids = data.type_arrays()
     tt = H.TypeTables.from_host(id_to_type, offsets, ids, padded_size=FLAGS.padded_size)
     global_step = 0
+    adagrad = getattr(FLAGS, 'optimizer', 'sgd') == 'adagrad'
+    accumulator = None
     if FLAGS.resume_checkpoint:
-        embeddings, global_step = load_checkpoint(FLAGS.output_dir)
+        embeddings, global_step, accumulator = load_checkpoint(FLAGS.output_dir, with_accumulator=True)
         if tuple(embeddings.shape) != (data.entity_count, FLAGS.embedding_dim):
             raise ValueError('checkpoint shape does not match the data / --embedding_dim')
     else:
@@ -131,7 +161,15 @@ def run_training(data: D.HolEData, FLAGS, log=print) -> dict:
                         learning_rate=FLAGS.learning_rate,
                         decay_steps=FLAGS.learning_decay_steps * batch_count,
                         decay_rate=FLAGS.learning_decay_rate, model=FLAGS.model, seed=FLAGS.seed,
-                        spectral_resident=(FLAGS.model == 'hole' and FLAGS.embedding_dim % 2 == 0 and not FLAGS.log_loss))
+                        spectral_resident=(FLAGS.model == 'hole' and FLAGS.embedding_dim % 2 == 0 and not FLAGS.log_loss
+                                           and not adagrad),
+                        optimizer='adagrad' if adagrad else 'sgd',
+                        initial_accumulator_value=getattr(FLAGS, 'adagrad_init', 0.1))
+    if adagrad and FLAGS.resume_checkpoint:
+        if accumulator is not None and accumulator.shape == trainer.accumulator.shape:
+            trainer.accumulator.copy_(accumulator)
+        else:
+            log('Checkpoint holds no AdaGrad accumulator: starting it at', FLAGS.adagrad_init)
     # HolE: `embeddings` is held in the frequency domain while training (hole.Trainer); validation scores it
     # there (model 'hole_spectral'), checkpoints store the real-valued table
     eval_model = 'hole_spectral' if trainer.spectral else FLAGS.model
@@ -188,7 +226,7 @@ def run_training(data: D.HolEData, FLAGS, log=print) -> dict:
         table = pocket.clone()
         if trainer.spectral:
             H.hole_from_spectral(table)
-        save_checkpoint(FLAGS.output_dir, table, state['pocket_step'])
+        save_checkpoint(FLAGS.output_dir, table, state['pocket_step'], trainer.accumulator)
         log('Epoch {}, (Model saved with loss {})'.format(epoch, pocket_loss))
 
     t_start = time.time()
@@ -224,7 +262,7 @@ def run_training(data: D.HolEData, FLAGS, log=print) -> dict:
     log('Done training -- epoch limit reached')
     trainer.to_real()
     if not os.path.exists(checkpoint_path(FLAGS.output_dir)):
-        save_checkpoint(FLAGS.output_dir, embeddings, trainer.global_step)
+        save_checkpoint(FLAGS.output_dir, embeddings, trainer.global_step, trainer.accumulator)
     steps = trainer.global_step - global_step
     return {'steps': steps, 'seconds': time.time() - t_start, 'pocket_loss': pocket_loss, 'history': history,
             'global_step': trainer.global_step, 'final_mean_hinge': float(trainer.last_loss.mean())}
@@ -378,6 +416,7 @@ def main(argv=None):
                          '(drop --gpus or --predict_k)')
     check_classify_flags(FLAGS, world)
     check_candidate_set_flags(FLAGS, world)
+    check_optimizer_flags(FLAGS, world)
     if FLAGS.relation_ranks and not FLAGS.infer:
         raise SystemExit('--relation_ranks needs --infer')
     if FLAGS.relation_ranks and (FLAGS.gpus > 1 or world > 1):

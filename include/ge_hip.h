@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define GE_VERSION 410 /* 0.4.1: + ge_rank_1vK_masked / ge_topk_1vK_masked and the mask builders (per-relation candidate sets) */
+#define GE_VERSION 420 /* 0.4.2: + ge_adagrad_rows / ge_train_steps_adagrad (AdaGrad for ComplEx and HolE, holE.py:296) */
 
 /* argument errors (negative, -errno style) */
 #define GE_EINVAL (-22)  /* bad dimension / null pointer / misaligned buffer */
@@ -171,6 +171,18 @@ int ge_scatter_add_rows(float* table, int64_t N, int32_t d, const int32_t* idx, 
                         int64_t R, void* stream);
 int ge_gather_rows(const float* table, int64_t N, int32_t d, const int32_t* idx, int64_t R,
                    float* out, void* stream);
+
+/* --- the optimizer half for AdaGrad: TF1's AdagradOptimizer(lr, initial_accumulator_value) in place of the
+ * GradientDescentOptimizer of holE.py:296, on any IndexedSlices -- the counterpart of ge_scatter_add_rows.  `val` holds
+ * MINUS the gradient (what ge_hinge_grad emits at lr = 1).  For every table row named by an idx[i] in [0, N):
+ *   s = sum of its val rows (duplicates are summed first, in `perm` order),
+ *   accum[row] += s * s,   table[row] += lr * s / sqrt(accum[row])   (the updated accumulator, no epsilon).
+ * accum: the caller's [N,d] fp32 accumulator (filled with initial_accumulator_value before the first step), not
+ * overlapping `table`.  perm [R] int32: the STABLE argsort of (idx[i] < 0 ? N : idx[i]) -- a row's occurrences are
+ * consecutive in that order; an entry outside [0, R) and an id >= N are skipped and never dereferenced.  idx[i] < 0 is
+ * skipped; rows not named are not touched in either array.  No float atomics: bitwise reproducible.  R = 0 returns 0. */
+int ge_adagrad_rows(float* table, float* accum, int64_t N, int32_t d, const int32_t* idx, const float* val,
+                    const int32_t* perm, int64_t R, float lr, void* stream);
 
 /* --- corrupt_batch (holE.py:152-153 -> 136-140 -> 97-133) fused with the per-batch host
  * resample of holE.py:343-347.  id_to_type [N] int32 type code per table row (-1 = unknown, the
@@ -697,6 +709,25 @@ int ge_train_steps_logloss(float* table, int64_t N, int32_t d, const int32_t* tr
                            int32_t padded_size, int32_t mode, int32_t negative_ratio, float l2, float lr0,
                            float decay_steps, float decay_rate, float max_norm, float* loss, int keep_all_losses,
                            int32_t* neg_ws, void* workspace, size_t workspace_bytes, void* pipeline, void* stream);
+
+/* --- the hinge loop of ge_train_steps with AdagradOptimizer(lr_s, initial_accumulator_value) in place of the plain SGD
+ * of holE.py:296 (semantics: ge_adagrad_rows; s is the snapshot gradient of the step, taken through the clip; lr_s the
+ * same inverse_time_decay value).  accum: [N,d] fp32, caller-owned, 4-byte aligned, not overlapping `table`.  The
+ * prepared path only: workspace >= ge_train_adagrad_workspace_bytes(B, d) (never shrinks as B grows), 256-B aligned,
+ * GE_ENOMEM below.  Per step: the gradient kernel at lr = 1, then two update kernels that give every distinct row its
+ * complete sum in a fixed order and one read-modify-write of both arrays -- no float atomics, bitwise reproducible.  A
+ * row that no hinge-active pair names is not touched in either array.  model: GE_MODEL_COMPLEX; GE_MODEL_HOLE and
+ * GE_MODEL_HOLE_DIRECT (both: direct-correlation kernels on the real table, which is never transformed -- AdaGrad is
+ * elementwise and not linear, so it does not commute with the DFT); GE_MODEL_HOLE_SPECTRAL is GE_ENOTSUP.  loss, neg_ws,
+ * pipeline: as for ge_train_steps (a handle used for another loop restarts when it meets this one). */
+size_t ge_train_adagrad_workspace_bytes(int64_t B, int32_t d);
+int ge_train_steps_adagrad(float* table, float* accum, int64_t N, int32_t d, const int32_t* triples, int64_t T,
+                           int64_t first_row, int64_t B, int64_t n_steps, const int32_t* id_to_type,
+                           const int64_t* type_offsets, int32_t n_types, const int32_t* type_ids, uint64_t seed,
+                           uint64_t global_step0, int32_t padded_size, int32_t mode, float margin, float lr0,
+                           float decay_steps, float decay_rate, float max_norm, int model, float* loss,
+                           int keep_all_losses, int32_t* neg_ws, void* workspace, size_t workspace_bytes, void* pipeline,
+                           void* stream);
 
 /* The prepare launch on its own: the records of n_steps consecutive steps, as ge_train_steps builds
  * them, into `out` (ge_train_prepare_bytes(B, n_steps) bytes: n_steps * layout[0] int32 words of records,
