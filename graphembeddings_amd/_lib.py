@@ -97,6 +97,11 @@ SYMBOLS = {
     "ge_transx_draw_batch": (C.c_int, [_p, _i64, _i64, _p, _p, _p, _p, _i64, _p, _i32, _i32, _u64, _u64, _p, _p, _p]),
     "ge_transx_train_steps": (C.c_int, [C.c_int, C.c_int, _p, _i64, _p, _i64, _p, _p, _p, _i32, _p, _i64, _p, _p, _p, _p,
                                         _i64, _p, _u64, _u64, _i64, _i64, _f, _f, _p, _p, _sz, _p]),
+    "ge_transx_adagrad_step": (C.c_int, [C.c_int, C.c_int, _p, _i64, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _p, _p,
+                                         _i64, _f, _f, _p, _p, _sz, _p]),
+    "ge_transx_train_steps_adagrad": (C.c_int, [C.c_int, C.c_int, _p, _i64, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _i32,
+                                                _p, _i64, _p, _p, _p, _p, _i64, _p, _u64, _u64, _i64, _i64, _f, _f, _p, _p,
+                                                _sz, _p]),
     "ge_transr_max_dim": (C.c_int, []),
     "ge_transr_score": (C.c_int, [C.c_int, _p, _i64, _p, _p, _i64, _i32, _i32, _p, _i64, _p, _p]),
     "ge_transr_step_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32, _i64]),
@@ -185,7 +190,7 @@ def load():
             fn = getattr(lib, name)  # AttributeError if the ABI and the header diverge
             fn.restype = res
             fn.argtypes = args
-        if lib.ge_version() < 420:
+        if lib.ge_version() < 430:
             raise RuntimeError("libge_hip.so is older than the Python host expects")
         _lib = lib
     return _lib

@@ -378,6 +378,73 @@ int ge_transx_train_steps(int model, int l1, float* ent, int64_t n_ent, float* r
                                 (hipStream_t)stream);
 }
 
+// The accumulators of an AdaGrad step, after transx_model: every table the model has brings its accumulator, 4-byte
+// aligned, whose [rows * d] floats share no byte with a table of the model or with another accumulator.  An accumulator
+// of a table the model does not have is dropped (as its table is ignored).
+static int transx_accs(TransAccs& c, const TransModel& m, float* acc_ent, float* acc_rel, float* acc_normal,
+                       float* acc_ent_transfer, float* acc_rel_transfer) {
+  struct Span { const float* p; int64_t rows; };
+  const Span tabs[5] = {{m.ent, m.E}, {m.rel, m.R}, {m.model == kTransH ? m.normal : nullptr, m.R},
+                        {m.model == kTransD ? m.ent_transfer : nullptr, m.E}, {m.model == kTransD ? m.rel_transfer : nullptr, m.R}};
+  const float* given[5] = {acc_ent, acc_rel, acc_normal, acc_ent_transfer, acc_rel_transfer};
+  Span accs[5];
+  for (int i = 0; i < 5; ++i) accs[i] = Span{tabs[i].p ? given[i] : nullptr, tabs[i].rows};
+  for (int i = 0; i < 5; ++i)
+    if (tabs[i].p && !accs[i].p) return GE_EINVAL;
+  for (int i = 0; i < 5; ++i)
+    if (accs[i].p && !aligned4(accs[i].p)) return GE_EINVAL;
+  auto overlap = [&](const Span& a, const Span& b) {
+    const uintptr_t x = (uintptr_t)a.p, y = (uintptr_t)b.p;
+    const uintptr_t nx = (uintptr_t)a.rows * (uintptr_t)m.dE * sizeof(float), ny = (uintptr_t)b.rows * (uintptr_t)m.dE * sizeof(float);
+    return x < y + ny && y < x + nx;
+  };
+  for (int i = 0; i < 5; ++i) {
+    if (!accs[i].p) continue;
+    for (int k = 0; k < 5; ++k) {
+      if (tabs[k].p && overlap(accs[i], tabs[k])) return GE_EINVAL;
+      if (k > i && accs[k].p && overlap(accs[i], accs[k])) return GE_EINVAL;
+    }
+  }
+  c = TransAccs{(float*)accs[0].p, (float*)accs[1].p, (float*)accs[2].p, (float*)accs[3].p, (float*)accs[4].p};
+  return 0;
+}
+
+int ge_transx_adagrad_step(int model, int l1, float* ent, int64_t n_ent, float* rel, int64_t n_rel, float* normal,
+                           float* ent_transfer, float* rel_transfer, float* acc_ent, float* acc_rel, float* acc_normal,
+                           float* acc_ent_transfer, float* acc_rel_transfer, int32_t d, const int32_t* pos,
+                           const int32_t* neg, int64_t B, float margin, float lr, float* loss, void* workspace,
+                           size_t workspace_bytes, void* stream) {
+  TransModel m;
+  TransAccs c;
+  if (int rc = transx_model(m, model, l1, ent, n_ent, rel, n_rel, normal, ent_transfer, rel_transfer, d)) return rc;
+  if (int rc = transx_accs(c, m, acc_ent, acc_rel, acc_normal, acc_ent_transfer, acc_rel_transfer)) return rc;
+  if (!transx_batch_ok(B) || !pos || !neg || !loss || !workspace) return GE_EINVAL;
+  if (!aligned4(pos) || !aligned4(neg) || !aligned4(loss) || ((uintptr_t)workspace & 255)) return GE_EINVAL;
+  return transx_adagrad_step_run(model, l1, ent, n_ent, rel, n_rel, normal, ent_transfer, rel_transfer, c, d, pos, neg,
+                                 B, margin, lr, loss, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int ge_transx_train_steps_adagrad(int model, int l1, float* ent, int64_t n_ent, float* rel, int64_t n_rel, float* normal,
+                                  float* ent_transfer, float* rel_transfer, float* acc_ent, float* acc_rel,
+                                  float* acc_normal, float* acc_ent_transfer, float* acc_rel_transfer, int32_t d,
+                                  const int32_t* triples, int64_t T, const int64_t* bh_key, const int32_t* bh_ent,
+                                  const int64_t* bt_key, const int32_t* bt_ent, int64_t n_known,
+                                  const uint32_t* tail_threshold, uint64_t seed, uint64_t first_step, int64_t n_steps,
+                                  int64_t B, float margin, float lr, float* losses, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+  TransModel m;
+  TransAccs c;
+  SamplerArgs s;
+  if (int rc = transx_model(m, model, l1, ent, n_ent, rel, n_rel, normal, ent_transfer, rel_transfer, d)) return rc;
+  if (int rc = transx_accs(c, m, acc_ent, acc_rel, acc_normal, acc_ent_transfer, acc_rel_transfer)) return rc;
+  if (!transx_batch_ok(B) || n_steps < 0 || !losses || !workspace || ((uintptr_t)workspace & 255)) return GE_EINVAL;
+  if (!sampler_ok(s, triples, T, tail_threshold, n_known, bh_key, bh_ent, bt_key, bt_ent, (int32_t)n_rel, (int32_t)n_ent))
+    return GE_EINVAL;
+  return transx_train_steps_adagrad_run(model, l1, ent, n_ent, rel, n_rel, normal, ent_transfer, rel_transfer, c, d, s,
+                                        seed, first_step, n_steps, B, margin, lr, losses, workspace, workspace_bytes,
+                                        (hipStream_t)stream);
+}
+
 // ---------------------------------------------------------------- TransR
 // 4B entity slots and every sorted position fit an int32
 static inline bool transr_batch_ok(int64_t B) { return sweep_batch_ok(B); }

@@ -239,6 +239,19 @@ int transx_train_steps_run(int model, int l1, float* ent, int64_t E, float* rel,
                            float* ent_transfer, float* rel_transfer, int32_t d, const SamplerArgs& sa, uint64_t seed,
                            uint64_t first_step, int64_t n_steps, int64_t B, float margin, float lr, float* losses,
                            void* workspace, size_t workspace_bytes, hipStream_t st);
+// The same step and loop with AdaGrad (acc += s * s, row -= lr * s / sqrt(acc) on each row's summed gradient): one
+// accumulator per table under the table's name, those of tables the model does not have ignored.  The workspace is
+// transx_ws_bytes' for both optimizers.
+struct TransAccs { float *ent, *rel, *normal, *ent_transfer, *rel_transfer; };
+int transx_adagrad_step_run(int model, int l1, float* ent, int64_t E, float* rel, int64_t R, float* normal,
+                            float* ent_transfer, float* rel_transfer, const TransAccs& accs, int32_t d,
+                            const int32_t* pos, const int32_t* neg, int64_t B, float margin, float lr, float* loss,
+                            void* workspace, size_t workspace_bytes, hipStream_t st);
+int transx_train_steps_adagrad_run(int model, int l1, float* ent, int64_t E, float* rel, int64_t R, float* normal,
+                                   float* ent_transfer, float* rel_transfer, const TransAccs& accs, int32_t d,
+                                   const SamplerArgs& sa, uint64_t seed, uint64_t first_step, int64_t n_steps, int64_t B,
+                                   float margin, float lr, float* losses, void* workspace, size_t workspace_bytes,
+                                   hipStream_t st);
 
 // ge_transr.hip: TransR scoring, Adam steps and native loop
 int transr_max_dim();

@@ -20,6 +20,11 @@
 //   4. apply, pass 2: one wave per window that holds the head of a cut segment adds the following windows'
 //      partials in window order and applies; its last block sums the hinge terms into the batch loss.
 // Every sum runs in a fixed order, so a step is bitwise reproducible.
+//
+// AdaGrad (TF1 AdagradOptimizer in place of the SGD line): the same four stages.  The apply hands every row its
+// complete sum in one apply_row call, which is what AdaGrad's s * s needs, so the two apply kernels are instantiated a
+// second time on AdaArgs (the tables' accumulators beside them) and only apply_row differs:
+//   acc[row] += s * s,  row -= lr * s / sqrt(acc[row])      (the updated accumulator, no epsilon).
 #include <cstring>
 #include <type_traits>
 
@@ -299,8 +304,44 @@ __device__ __forceinline__ bool has_plane1(const ApplyArgs& a, uint32_t k) {
   return k < (uint32_t)a.E ? a.ent2 != nullptr : a.rel2 != nullptr;
 }
 
+// The AdaGrad apply: ApplyArgs plus one accumulator per table (acc_ent2 / acc_rel2 null where ent2 / rel2 are).
+struct AdaArgs : ApplyArgs {
+  float* acc_ent; float* acc_rel; float* acc_ent2; float* acc_rel2;
+};
+
+// One row's AdaGrad update from its complete sums.  The table row and the accumulator row of both planes are requested
+// before any arithmetic; then one read-modify-write per array.  Plane 1's arrays are touched only where the key has one.
 template <int VEC>
-__global__ __launch_bounds__(kBlock) void transx_apply_runs_kernel(ApplyArgs a) {
+__device__ __forceinline__ void apply_row(const AdaArgs& a, uint32_t k, int j, const float (&s0)[VEC], const float (&s1)[VEC]) {
+  const bool is_ent = k < (uint32_t)a.E;
+  const int64_t off = (is_ent ? (int64_t)k : (int64_t)k - a.E) * a.d + (int64_t)j * VEC;
+  float* t0 = (is_ent ? a.ent : a.rel) + off;
+  float* c0 = (is_ent ? a.acc_ent : a.acc_rel) + off;
+  const bool p1 = has_plane1(a, k);
+  float* t1 = p1 ? (is_ent ? a.ent2 : a.rel2) + off : nullptr;
+  float* c1 = p1 ? (is_ent ? a.acc_ent2 : a.acc_rel2) + off : nullptr;
+  float v0[VEC], b0[VEC], v1[VEC], b1[VEC];
+  load_vec<VEC>(t0, v0); load_vec<VEC>(c0, b0);
+  if (p1) { load_vec<VEC>(t1, v1); load_vec<VEC>(c1, b1); }
+#pragma unroll
+  for (int q = 0; q < VEC; ++q) {
+    b0[q] = b0[q] + s0[q] * s0[q];
+    v0[q] -= a.lr * s0[q] / sqrtf(b0[q]);
+  }
+  store_vec<VEC>(c0, b0); store_vec<VEC>(t0, v0);
+  if (p1) {
+#pragma unroll
+    for (int q = 0; q < VEC; ++q) {
+      b1[q] = b1[q] + s1[q] * s1[q];
+      v1[q] -= a.lr * s1[q] / sqrtf(b1[q]);
+    }
+    store_vec<VEC>(c1, b1); store_vec<VEC>(t1, v1);
+  }
+}
+
+// Args: ApplyArgs (SGD) or AdaArgs (AdaGrad); it selects apply_row and nothing else.
+template <int VEC, class Args>
+__global__ __launch_bounds__(kBlock) void transx_apply_runs_kernel(Args a) {
   const int lane = threadIdx.x & (kWave - 1);
   const int64_t c = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
   const int64_t nwin = (a.n + kWin - 1) / kWin;
@@ -346,8 +387,8 @@ __global__ __launch_bounds__(kBlock) void transx_apply_runs_kernel(ApplyArgs a) 
 }
 
 // Cut segments (one per window that holds the head of a segment running past its end), then the batch loss.
-template <int VEC>
-__global__ __launch_bounds__(kBlock) void transx_apply_cut_kernel(ApplyArgs a, const float* __restrict__ hinge,
+template <int VEC, class Args>
+__global__ __launch_bounds__(kBlock) void transx_apply_cut_kernel(Args a, const float* __restrict__ hinge,
                                                                   int64_t B, float* __restrict__ loss) {
   const int64_t nwin = (a.n + kWin - 1) / kWin;
   if (blockIdx.x == gridDim.x - 1) {                  // the loss block: fixed-order sum of the hinge terms
@@ -514,11 +555,20 @@ int transx_score_launch(const TransModel& m, const int32_t* tri, int64_t B, floa
   return launch_status();
 }
 
-// One step on caller-given (or drawn) pos/neg; loss = one float.
+// The accumulators of an AdaGrad step as the kernels take them (ent2 / rel2's order); all null: plain SGD.
+struct TxAcc { float *ent = nullptr, *rel = nullptr, *ent2 = nullptr, *rel2 = nullptr; };
+
+template <int VEC, class Args>
+static void launch_apply(const Args& a, int grid_a, const float* hinge, int64_t B, float* loss, hipStream_t st) {
+  hipLaunchKernelGGL((transx_apply_runs_kernel<VEC, Args>), dim3(grid_a), dim3(kBlock), 0, st, a);
+  hipLaunchKernelGGL((transx_apply_cut_kernel<VEC, Args>), dim3(grid_a + 1), dim3(kBlock), 0, st, a, hinge, B, loss);
+}
+
+// One step on caller-given (or drawn) pos/neg; loss = one float.  acc.ent set: the AdaGrad apply.
 static int step_core(int model, int l1, float* ent, int64_t E, float* rel, int64_t R, float* ent2, float* rel2,
                      int32_t d, const int32_t* pos, const int32_t* neg, int64_t B, float margin, float lr, float* loss,
-                     TxWs& w, hipStream_t st) {
-  const bool v4 = d % 4 == 0 && aligned16({ent, rel, ent2, rel2, w.g0, w.g1, w.part});
+                     TxWs& w, hipStream_t st, const TxAcc& acc = TxAcc{}) {
+  const bool v4 = d % 4 == 0 && aligned16({ent, rel, ent2, rel2, w.g0, w.g1, w.part, acc.ent, acc.rel, acc.ent2, acc.rel2});
   const int nvec = v4 ? d / 4 : d, lpt = lpt_for(nvec);
   const int grid = grid_for((B + kWave / lpt - 1) / (kWave / lpt), kBlock / kWave);
   if (v4) dispatch_mn<false, 4>(model, l1, lpt, grid, st, ent, rel, ent2, rel2, E, R, (int)d, pos, neg, B, margin, w);
@@ -530,16 +580,19 @@ static int step_core(int model, int l1, float* ent, int64_t E, float* rel, int64
   hipError_t e = rocprim::radix_sort_pairs(w.sort_tmp, sb, w.keys_in, w.keys_out, w.slots_in, w.slots_out, (size_t)n,
                                            0u, key_bits(E, R), st);
   if (e != hipSuccess) return (int)e;
-  ApplyArgs a{ent, rel, ent2, rel2, E, R, (int)d, n, w.keys_out, w.slots_out, w.g0, w.g1, w.part, lr};
+  const ApplyArgs a{ent, rel, ent2, rel2, E, R, (int)d, n, w.keys_out, w.slots_out, w.g0, w.g1, w.part, lr};
   const int64_t nwin = (n + kWin - 1) / kWin;
   const int wpb = kBlock / kWave;
   const int grid_a = (int)((nwin + wpb - 1) / wpb);
-  if (v4) {
-    hipLaunchKernelGGL(transx_apply_runs_kernel<4>, dim3(grid_a), dim3(kBlock), 0, st, a);
-    hipLaunchKernelGGL(transx_apply_cut_kernel<4>, dim3(grid_a + 1), dim3(kBlock), 0, st, a, w.hinge, B, loss);
+  if (acc.ent) {
+    AdaArgs g;
+    static_cast<ApplyArgs&>(g) = a;
+    g.acc_ent = acc.ent; g.acc_rel = acc.rel; g.acc_ent2 = ent2 ? acc.ent2 : nullptr; g.acc_rel2 = rel2 ? acc.rel2 : nullptr;
+    if (v4) launch_apply<4>(g, grid_a, w.hinge, B, loss, st);
+    else launch_apply<1>(g, grid_a, w.hinge, B, loss, st);
   } else {
-    hipLaunchKernelGGL(transx_apply_runs_kernel<1>, dim3(grid_a), dim3(kBlock), 0, st, a);
-    hipLaunchKernelGGL(transx_apply_cut_kernel<1>, dim3(grid_a + 1), dim3(kBlock), 0, st, a, w.hinge, B, loss);
+    if (v4) launch_apply<4>(a, grid_a, w.hinge, B, loss, st);
+    else launch_apply<1>(a, grid_a, w.hinge, B, loss, st);
   }
   return launch_status();
 }
@@ -577,6 +630,46 @@ int transx_train_steps_run(int model, int l1, float* ent, int64_t E, float* rel,
   extra_tables(model, normal, ent_transfer, rel_transfer, e2, r2);
   return draw_then_step(sa, B, seed, first_step, n_steps, w.pos, w.neg, st, [&](int64_t s) {
     return step_core(model, l1, ent, E, rel, R, (float*)e2, (float*)r2, d, w.pos, w.neg, B, margin, lr, losses + s, w, st);
+  });
+}
+
+// the accumulators of the model's tables in the kernels' order (extra_tables)
+static TxAcc extra_accs(const TransAccs& c, int model) {
+  TxAcc a;
+  a.ent = c.ent; a.rel = c.rel;
+  a.ent2 = model == kTransD ? c.ent_transfer : nullptr;
+  a.rel2 = model == kTransH ? c.normal : model == kTransD ? c.rel_transfer : nullptr;
+  return a;
+}
+
+int transx_adagrad_step_run(int model, int l1, float* ent, int64_t E, float* rel, int64_t R, float* normal,
+                            float* ent_transfer, float* rel_transfer, const TransAccs& accs, int32_t d,
+                            const int32_t* pos, const int32_t* neg, int64_t B, float margin, float lr, float* loss,
+                            void* workspace, size_t workspace_bytes, hipStream_t st) {
+  TxWs w;
+  int rc = ws_layout(E, R, d, B, workspace, w);
+  if (rc) return rc;
+  if (workspace_bytes < w.total) return GE_ENOMEM;
+  const float *e2, *r2;
+  extra_tables(model, normal, ent_transfer, rel_transfer, e2, r2);
+  return step_core(model, l1, ent, E, rel, R, (float*)e2, (float*)r2, d, pos, neg, B, margin, lr, loss, w, st,
+                   extra_accs(accs, model));
+}
+
+int transx_train_steps_adagrad_run(int model, int l1, float* ent, int64_t E, float* rel, int64_t R, float* normal,
+                                   float* ent_transfer, float* rel_transfer, const TransAccs& accs, int32_t d,
+                                   const SamplerArgs& sa, uint64_t seed, uint64_t first_step, int64_t n_steps, int64_t B,
+                                   float margin, float lr, float* losses, void* workspace, size_t workspace_bytes,
+                                   hipStream_t st) {
+  TxWs w;
+  int rc = ws_layout(E, R, d, B, workspace, w);
+  if (rc) return rc;
+  if (workspace_bytes < w.total) return GE_ENOMEM;
+  const float *e2, *r2;
+  extra_tables(model, normal, ent_transfer, rel_transfer, e2, r2);
+  const TxAcc acc = extra_accs(accs, model);
+  return draw_then_step(sa, B, seed, first_step, n_steps, w.pos, w.neg, st, [&](int64_t s) {
+    return step_core(model, l1, ent, E, rel, R, (float*)e2, (float*)r2, d, w.pos, w.neg, B, margin, lr, losses + s, w, st, acc);
   });
 }
 

@@ -4,7 +4,8 @@ margin-hinge SGD step and the native multi-step loop of include/ge_hip.h's ge_tr
 Reference semantics: separate `ent [E,d]` / `rel [R,d]` tables (TransH adds `normal_vector [R,d]`, TransD adds
 `ent_transfer [E,d]` and `rel_transfer [R,d]`), every table xavier_initializer(uniform=False) for its own shape,
 D = sum |h_p + r - t_p| (L1) or sum (h_p + r - t_p)^2, loss = sum_batch max(D+ - D- + margin, 0), plain SGD
-(tf.train.GradientDescentOptimizer) on every table.  There is no CPU path: every call runs a HIP kernel.
+(tf.train.GradientDescentOptimizer) on every table, or TF1's AdagradOptimizer in its place (enable_adagrad,
+adagrad_step, trainer(optimizer="adagrad")).  There is no CPU path: every call runs a HIP kernel.
 """
 from __future__ import annotations
 
@@ -100,7 +101,9 @@ class Trainer:
     """The reference's training loop (getBatch + train_step, transE.py:109-115) as one native call per run():
     each step draws `batch_size` positives uniformly with replacement from `triples` and corrupts each with the
     filtered Bernoulli rule (ent_lo = 0), then takes the model's step.  Step s of the run uses the Philox counter
-    (seed, s): ge_transx_draw_batch(.., seed, s, ..) reproduces any step's batch."""
+    (seed, s): ge_transx_draw_batch(.., seed, s, ..) reproduces any step's batch.  `optimizer` ("sgd", or "adagrad"
+    for a TransX model: _Model.trainer sets it) selects the step; the draws are the same."""
+    optimizer = "sgd"
 
     def __init__(self, model: TransX, triples, batch_size: int, *, margin: float = 1.0, learning_rate: float = 0.001,
                  seed: int = 0):
@@ -327,8 +330,21 @@ class _Model:
         return triple_classification(self, valid_pos, test_pos, valid_neg, test_neg, known=known, seed=seed, mode=mode)
 
     def trainer(self, triples, batch_size: int, *, margin: float = 1.0, learning_rate: float = 0.001,
-                seed: int = 0) -> Trainer:
-        return self._trainer(self, triples, batch_size, margin=margin, learning_rate=learning_rate, seed=seed)
+                seed: int = 0, optimizer: str = "sgd", initial_accumulator_value: float = 0.1) -> Trainer:
+        """The model's native loop.  optimizer="sgd" (the default) is the model's own step: plain SGD for TransX, Adam
+        for TransR.  optimizer="adagrad" (TransX only) enables AdaGrad with initial_accumulator_value unless the model
+        already has accumulators, which are kept; its run(n) is one ge_transx_train_steps_adagrad call."""
+        if optimizer not in ("sgd", "adagrad"):
+            raise ValueError(f"optimizer must be 'sgd' or 'adagrad', got {optimizer!r}")
+        if optimizer == "adagrad":
+            self._trainer_adagrad(initial_accumulator_value)
+        tr = self._trainer(self, triples, batch_size, margin=margin, learning_rate=learning_rate, seed=seed)
+        tr.optimizer = optimizer
+        return tr
+
+    def _trainer_adagrad(self, initial_accumulator_value: float) -> None:
+        raise ValueError(f"{type(self).__name__} has no AdaGrad step: TransR trains with Adam, which optimizer='sgd' "
+                         "(the default) leaves in place")
 
     def _state_tensors(self) -> Dict[str, torch.Tensor]:
         return self.tables
@@ -386,14 +402,79 @@ class TransX(_Model):
                   float(lr), self._loss.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
         return self._loss[0].clone()
 
+    # --- AdaGrad (ge_transx_adagrad_step / ge_transx_train_steps_adagrad): one accumulator per table
+    accumulators: Optional[Dict[str, torch.Tensor]] = None
+    adagrad_init: Optional[float] = None
+
+    def enable_adagrad(self, initial_accumulator_value: float = 0.1) -> None:
+        """Create (or refill) `accumulators`: one fp32 tensor per table under the table's name, filled with
+        initial_accumulator_value, TF1's AdagradOptimizer(lr, initial_accumulator_value) slots."""
+        a0 = float(initial_accumulator_value)
+        if not a0 > 0:
+            raise ValueError(f"initial_accumulator_value must be positive, got {initial_accumulator_value}")
+        self.accumulators = {k: torch.full_like(v, a0) for k, v in self.tables.items()}
+        self.adagrad_init = a0
+
+    def _trainer_adagrad(self, initial_accumulator_value: float) -> None:
+        if not float(initial_accumulator_value) > 0:
+            raise ValueError(f"initial_accumulator_value must be positive, got {initial_accumulator_value}")
+        if self.accumulators is None:
+            self.enable_adagrad(initial_accumulator_value)
+
+    def _adagrad_ptrs(self):
+        """_ptrs() with the five accumulator arguments in front of d, as the two AdaGrad entry points take them."""
+        if self.accumulators is None:
+            raise RuntimeError("AdaGrad is not enabled: call enable_adagrad() first")
+        a = self.accumulators
+        p = lambda name: a[name].data_ptr() if name in a else None
+        base = self._ptrs()
+        return (*base[:-1], p("ent"), p("rel"), p("normal_vector"), p("ent_transfer"), p("rel_transfer"), base[-1])
+
+    def adagrad_step(self, pos: torch.Tensor, neg: torch.Tensor, lr: float, margin: float) -> torch.Tensor:
+        """One AdaGrad step on sum max(D(pos) - D(neg) + margin, 0): per row an active pair names, s = its summed
+        gradient, accumulator += s * s, row -= lr * s / sqrt(accumulator).  Returns the batch loss as step() does."""
+        ptrs = self._adagrad_ptrs()
+        pb, nb, ws = self._step_batch(pos, neg)
+        _lib.call("ge_transx_adagrad_step", *ptrs, pb.data_ptr(), nb.data_ptr(), pb.shape[0], float(margin), float(lr),
+                  self._loss.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+        return self._loss[0].clone()
+
     def _train_steps(self, tr: Trainer, n: int, losses: torch.Tensor, ws: torch.Tensor) -> None:
-        _lib.call("ge_transx_train_steps", *self._ptrs(), *tr._sampler_args(), tr.seed & (2**64 - 1), tr.step_count, n,
-                  tr.B, tr.margin, tr.lr, losses.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+        ada = tr.optimizer == "adagrad"
+        _lib.call("ge_transx_train_steps_adagrad" if ada else "ge_transx_train_steps",
+                  *(self._adagrad_ptrs() if ada else self._ptrs()), *tr._sampler_args(), tr.seed & (2**64 - 1),
+                  tr.step_count, n, tr.B, tr.margin, tr.lr, losses.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
 
     def state_dict(self) -> Dict[str, object]:
-        return {"model": self.model, "l1": self.l1, "n_ent": self.n_ent, "n_rel": self.n_rel, "d": self.d,
-                **{k: v.detach().cpu().clone() for k, v in self.tables.items()}}
+        state = {"model": self.model, "l1": self.l1, "n_ent": self.n_ent, "n_rel": self.n_rel, "d": self.d,
+                 **{k: v.detach().cpu().clone() for k, v in self.tables.items()}}
+        if self.accumulators is not None:                # adagrad_init and one adagrad_<table> per table
+            state["adagrad_init"] = self.adagrad_init
+            state.update({"adagrad_" + k: v.detach().cpu().clone() for k, v in self.accumulators.items()})
+        return state
 
     def load_state_dict(self, state: Dict[str, object]) -> None:
+        """Every shape is checked before anything is copied.  A state with accumulators enables AdaGrad and restores
+        them; one without, loaded into a model with AdaGrad enabled, refills the accumulators with its adagrad_init."""
         self._check_state(state, ("model", "n_ent", "n_rel", "d"), "table")
+        has = "adagrad_init" in state
+        if has:
+            a0 = float(state["adagrad_init"])
+            if not a0 > 0:
+                raise ValueError(f"state_dict adagrad_init={a0} must be positive")
+            for name, t in self.tables.items():
+                if "adagrad_" + name not in state:
+                    raise ValueError(f"state_dict has adagrad_init but no adagrad_{name}")
+                src = state["adagrad_" + name]
+                if tuple(src.shape) != tuple(t.shape):
+                    raise ValueError(f"state_dict accumulator adagrad_{name} has shape {tuple(src.shape)}, "
+                                     f"expected {tuple(t.shape)}")
         self._copy_state(state)
+        if has:
+            if self.accumulators is None:
+                self.enable_adagrad(a0)
+            self.adagrad_init = a0
+            for name, acc in self.accumulators.items():
+                acc.copy_(state["adagrad_" + name].to(device=acc.device, dtype=torch.float32))
+        elif self.accumulators is not None:
+            self.enable_adagrad(self.adagrad_init)

@@ -133,9 +133,14 @@ def run(a, driver: str, make_model, name: str) -> int:
     if not torch.cuda.is_available():
         raise RuntimeError(f"{driver} needs an MI355X: graphembeddings_amd has no CPU path")
     m = make_model(E, R)
+    adagrad = getattr(a, "optimizer", "sgd") == "adagrad"      # (transx_train alone has the flag)
     if a.load:
-        m.load_state_dict(torch.load(a.load, map_location="cpu"))
-    tr = m.trainer(tri, B, margin=a.margin, learning_rate=a.learning_rate, seed=a.seed)
+        state = torch.load(a.load, map_location="cpu")
+        m.load_state_dict(state)
+        if adagrad and "adagrad_init" not in state:
+            print(f"{a.load} holds no AdaGrad accumulators: they start at --adagrad_init {a.adagrad_init}")
+    kw = dict(optimizer="adagrad", initial_accumulator_value=getattr(a, "adagrad_init", 0.1)) if adagrad else {}
+    tr = m.trainer(tri, B, margin=a.margin, learning_rate=a.learning_rate, seed=a.seed, **kw)
     for epoch in range(a.train_times):
         res = float(tr.run(a.nbatches).double().sum())
         print(epoch)
@@ -197,6 +202,12 @@ def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(prog="python -m graphembeddings_amd.transx_train", description=__doc__.splitlines()[0])
     p.add_argument("--model", choices=("transe", "transh", "transd"), default="transe")
     add_common_flags(p, ("hidden_size",), "<model>")
+    p.add_argument("--optimizer", choices=("sgd", "adagrad"), default="sgd",
+                   help="sgd: the reference's GradientDescentOptimizer (the default); adagrad: TF1's AdagradOptimizer on "
+                        "every table (try --learning_rate 0.05); the saved file then carries the accumulators and --load "
+                        "restores them")
+    p.add_argument("--adagrad_init", type=float, default=0.1,
+                   help="AdagradOptimizer's initial_accumulator_value (with --optimizer adagrad)")
     return p
 
 
@@ -204,6 +215,11 @@ def check_args(a) -> None:
     """Everything that can be wrong with the flags, before any GPU call."""
     if not 1 <= a.hidden_size <= 1024:
         raise ValueError(f"--hidden_size must lie in [1, 1024], got {a.hidden_size}")
+    optimizer, a0 = getattr(a, "optimizer", "sgd"), getattr(a, "adagrad_init", 0.1)   # (a Namespace built without them)
+    if optimizer not in ("sgd", "adagrad"):
+        raise ValueError(f"--optimizer must be 'sgd' or 'adagrad', got {optimizer!r}")
+    if not a0 > 0:
+        raise ValueError(f"--adagrad_init must be positive, got {a0}")
     check_training_args(a)
     check_eval_args(a)
 

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define GE_VERSION 420 /* 0.4.2: + ge_adagrad_rows / ge_train_steps_adagrad (AdaGrad for ComplEx and HolE, holE.py:296) */
+#define GE_VERSION 430 /* 0.4.3: + ge_transx_adagrad_step / ge_transx_train_steps_adagrad (AdaGrad for TransE / TransH / TransD) */
 
 /* argument errors (negative, -errno style) */
 #define GE_EINVAL (-22)  /* bad dimension / null pointer / misaligned buffer */
@@ -254,6 +254,40 @@ int ge_transx_train_steps(int model, int l1, float* ent, int64_t n_ent, float* r
                           int64_t n_known, const uint32_t* tail_threshold, uint64_t seed, uint64_t first_step,
                           int64_t n_steps, int64_t B, float margin, float lr, float* losses, void* workspace,
                           size_t workspace_bytes, void* stream);
+/* ge_transx_hinge_step with TF1's AdagradOptimizer(lr, initial_accumulator_value).minimize(loss) in place of the
+ * GradientDescentOptimizer of transE.py:76 / transH.py:91 / transD.py:94, on the IndexedSlices of every table's lookups.
+ * Each table X of the model has an accumulator acc_X of X's shape (fp32, filled by the caller with
+ * initial_accumulator_value > 0 before the first step).  For every row that an ACTIVE pair names, in every table:
+ *   s = the sum of its gradient rows (the gradient, not minus it; duplicates summed first, in the order
+ *       ge_transx_hinge_step sums them),
+ *   acc_X[row] += s * s,   X[row] -= lr * s / sqrtf(acc_X[row])   (the updated accumulator, no epsilon: the element
+ *   rule of ge_adagrad_rows).
+ * A row no active pair names is not touched in either array.  The loss, the activity rule, sign(0) = 0, the TransH clamp
+ * branch and the skipping of invalid pairs are ge_transx_hinge_step's.  No float atomics: two calls from one state give
+ * the same bits in tables, accumulators and loss.
+ * Refused before any launch, in this order: whatever ge_transx_hinge_step refuses about the model and its tables;
+ * GE_EINVAL for a missing accumulator of a table the model has, then for an accumulator that is not 4-byte aligned, then
+ * for an accumulator whose [rows * d] floats share a byte with a table of the model or with another accumulator; then
+ * everything else ge_transx_hinge_step refuses; GE_ENOMEM below ge_transx_step_workspace_bytes(n_ent, n_rel, d, B), which
+ * serves both optimizers.  An accumulator of a table the model does not have is ignored, as its table is.  d % 4 == 0
+ * takes the vectorised path when the accumulators are 16-byte aligned too. */
+int ge_transx_adagrad_step(int model, int l1, float* ent, int64_t n_ent, float* rel, int64_t n_rel, float* normal,
+                           float* ent_transfer, float* rel_transfer, float* acc_ent, float* acc_rel, float* acc_normal,
+                           float* acc_ent_transfer, float* acc_rel_transfer, int32_t d, const int32_t* pos,
+                           const int32_t* neg, int64_t B, float margin, float lr, float* loss, void* workspace,
+                           size_t workspace_bytes, void* stream);
+/* ge_transx_train_steps with that step: step s draws its batch as ge_transx_draw_batch(.., seed, first_step + s, ..)
+ * (the SGD loop's draw) and runs ge_transx_adagrad_step on it; losses[s] (device) = its batch loss.  Refusals: those of
+ * ge_transx_adagrad_step about the accumulators, in its order, then those of ge_transx_train_steps (the sampler checks
+ * included), then GE_ENOMEM.  n_steps = 0 returns 0 after the checks.  No host synchronisation inside. */
+int ge_transx_train_steps_adagrad(int model, int l1, float* ent, int64_t n_ent, float* rel, int64_t n_rel, float* normal,
+                                  float* ent_transfer, float* rel_transfer, float* acc_ent, float* acc_rel,
+                                  float* acc_normal, float* acc_ent_transfer, float* acc_rel_transfer, int32_t d,
+                                  const int32_t* triples, int64_t T, const int64_t* bh_key, const int32_t* bh_ent,
+                                  const int64_t* bt_key, const int32_t* bt_ent, int64_t n_known,
+                                  const uint32_t* tail_threshold, uint64_t seed, uint64_t first_step, int64_t n_steps,
+                                  int64_t B, float margin, float lr, float* losses, void* workspace,
+                                  size_t workspace_bytes, void* stream);
 
 /* --- TransR (transR.py).  Row-major fp32 tables: ent [n_ent,dim_e], rel [n_rel,dim_r] and rel_matrix
  * [n_rel, dim_r*dim_e], whose row r read as [dim_r][dim_e] is M_r.  Triples are int32 [B,3] (h, t, r).

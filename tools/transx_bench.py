@@ -2,9 +2,12 @@
 (`Trainer.run`, 100 steps per call) for each model and norm, and the same step in torch eager fp32 on the host.
 
     python tools/transx_bench.py [--calls 5] [--steps 100] [--cpu_steps 5] [--threads 16] [--out FILE]
+                                 [--optimizer sgd|adagrad|both]
 
-Prints one JSON line per configuration.  Synthetic triples with FB15k's shape; a relation column drawn with a
-Zipf-like skew so the busiest relation gets hundreds of slots per step, as FB15k's do."""
+Prints one JSON line per configuration.  --optimizer both times the SGD loop and the AdaGrad loop
+(ge_transx_train_steps_adagrad) of one shape alternated call by call in one process, each on its own model, at the same
+learning rate, so that the two lines of a shape compare like with like.  Synthetic triples with FB15k's shape; a
+relation column drawn with a Zipf-like skew so the busiest relation gets hundreds of slots per step, as FB15k's do."""
 import argparse
 import json
 import os
@@ -60,27 +63,31 @@ def main():
     ap.add_argument("--cpu_steps", type=int, default=5)
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--optimizer", choices=("sgd", "adagrad", "both"), default="sgd")
     a = ap.parse_args()
+    opts = ("sgd", "adagrad") if a.optimizer == "both" else (a.optimizer,)
     tri = fb15k_like()
     B = len(tri) // 100
     lines = []
     torch.set_num_threads(a.threads)
     for model in ("transe", "transh", "transd"):
         for l1 in (True, False):
-            m = X.TransX(model, E, R, D, l1=l1, seed=0)
-            tr = m.trainer(tri, B, margin=1.0, learning_rate=0.001, seed=1)
-            tr.run(a.steps)                                   # warm-up call
+            ms = {o: X.TransX(model, E, R, D, l1=l1, seed=0) for o in opts}
+            trs = {o: ms[o].trainer(tri, B, margin=1.0, learning_rate=0.001, seed=1, optimizer=o) for o in opts}
+            for o in opts:
+                trs[o].run(a.steps)                           # warm-up call
             torch.cuda.synchronize()
             t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            per = []
+            pers, last = {o: [] for o in opts}, {}
             for _ in range(a.calls):
-                t0.record()
-                losses = tr.run(a.steps)
-                t1.record()
-                t1.synchronize()
-                per.append(t0.elapsed_time(t1) * 1e3 / a.steps)
-            assert torch.isfinite(losses).all()
-            us = float(np.median(per))
+                for o in opts:
+                    t0.record()
+                    last[o] = trs[o].run(a.steps)
+                    t1.record()
+                    t1.synchronize()
+                    pers[o].append(t0.elapsed_time(t1) * 1e3 / a.steps)
+            assert all(torch.isfinite(x).all() for x in last.values())
+            m, tr = ms[opts[0]], trs[opts[0]]
             cpu_us = None
             if a.cpu_steps > 0:
                 tabs = {k: v.cpu().clone() for k, v in m.tables.items()}
@@ -90,13 +97,18 @@ def main():
                 for _ in range(a.cpu_steps):
                     cpu_step(model, tabs, pos, neg, 0.001, 1.0, l1)
                 cpu_us = (time.perf_counter() - t) * 1e6 / a.cpu_steps
-            rec = {"model": model, "norm": "L1" if l1 else "L2", "E": E, "R": R, "d": D, "B": B,
-                   "steps_per_call": a.steps, "us_per_step": round(us, 2), "us_per_step_all_calls": [round(x, 2) for x in per],
-                   "scored_triples_per_s": round(2 * B / (us * 1e-6)), "cpu_eager_us_per_step": None if cpu_us is None else round(cpu_us, 1),
-                   "cpu_threads": a.threads, "last_loss": float(losses[-1])}
-            print(json.dumps(rec), flush=True)
-            lines.append(rec)
-            del m, tr
+            for o in opts:
+                per, losses = pers[o], last[o]
+                us = float(np.median(per))
+                rec = {"model": model, "norm": "L1" if l1 else "L2", "E": E, "R": R, "d": D, "B": B,
+                       "steps_per_call": a.steps, "us_per_step": round(us, 2), "us_per_step_all_calls": [round(x, 2) for x in per],
+                       "scored_triples_per_s": round(2 * B / (us * 1e-6)), "cpu_eager_us_per_step": None if cpu_us is None else round(cpu_us, 1),
+                       "cpu_threads": a.threads, "last_loss": float(losses[-1])}
+                if a.optimizer != "sgd":
+                    rec["optimizer"] = o
+                print(json.dumps(rec), flush=True)
+                lines.append(rec)
+            del m, tr, ms, trs
     if a.out:
         with open(a.out, "w") as f:
             for rec in lines:
