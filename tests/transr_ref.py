@@ -163,12 +163,18 @@ def random_tables(E, R, dim_e, dim_r, rng, scale=1.0):
             "rel_matrix": rng.normal(size=(R, dim_e * dim_r)) * scale}
 
 
-def integer_tables(E, R, dim_e, dim_r, seed=0, amp=2):
-    """Tables of small integers in [-amp, amp] (fp64 holding integers)."""
+def integer_tables(E, R, dim_e, dim_r, seed=0, amp=2, density=None):
+    """Tables of small integers in [-amp, amp] (fp64 holding integers).  With `density`, each entry is kept with
+    that probability and is zero otherwise (the keep draws follow the tables', so None gives the same tables as
+    ever): sparser tables keep large dims inside the exact range."""
     rng = np.random.default_rng(seed)
-    return {"ent": rng.integers(-amp, amp + 1, size=(E, dim_e)).astype(np.float64),
+    tabs = {"ent": rng.integers(-amp, amp + 1, size=(E, dim_e)).astype(np.float64),
             "rel": rng.integers(-amp, amp + 1, size=(R, dim_r)).astype(np.float64),
             "rel_matrix": rng.integers(-amp, amp + 1, size=(R, dim_e * dim_r)).astype(np.float64)}
+    if density is not None:
+        for k, x in tabs.items():
+            tabs[k] = np.where(rng.random(x.shape) < density, x, 0.0)
+    return tabs
 
 
 def skewed_batch(rng, E, R, B, s=1.1, hot=None):
