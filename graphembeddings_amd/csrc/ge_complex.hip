@@ -822,7 +822,17 @@ static bool pick_shape(int d, const void* base, int max_niter, Shape& s, int64_t
   return true;
 }
 
-#define GE_DISPATCH_SHAPE(S, MAXN, CALL)                                               \
+// whether the kernels of this file take an embedding_dim on a table at this address (dense rows): what a caller that
+// must not fail half way -- the training loops -- asks before it launches anything
+bool complex_shape_ok(int32_t d, const void* table) {
+  Shape s;
+  return pick_shape(d, table, 2, s);
+}
+
+// The keys 4162 and 4322 are listed but no embedding_dim reaches them: pick_shape widens the lane group to 64 before it
+// takes a second iteration, so NITER = 2 comes with LPT = 64 only (tests/test_complex_shape_cases_host.py enumerates
+// every even d <= 1024 at every alignment).
+#define GE_DISPATCH_SHAPE(S, MAXN, CALL)                                            \
   do {                                                                                 \
     const int key_ = (S).vec * 1000 + (S).lpt * 10 + (S).niter;                        \
     switch (key_) {                                                                    \

@@ -437,7 +437,7 @@ static inline size_t hole_lds_bytes(int d, int nch) {
   return sizeof(float) * (size_t)(kBlock / kWave) * (size_t)(2 * d4 + d4 + nch * 256);
 }
 
-static int hole_max_dim() { return 512; }
+int hole_max_dim() { return 512; }
 
 int hole_score_launch(const float* table, int64_t N, int32_t d, const int32_t* triples, int64_t B,
                       float max_norm, int apply_sigmoid, float* out, hipStream_t st) {

@@ -20,6 +20,9 @@ struct ShardOut;
 
 // ge_complex.hip: ComplEx scoring, hinge and log-loss steps, the row-sharded grad step, table reductions
 int complex_max_dim();
+// the kernels below take this embedding_dim on a table at this address (the vector width follows its alignment); where
+// they do not, their launchers answer GE_ENOTSUP (GE_EINVAL for an odd or non-positive d)
+bool complex_shape_ok(int32_t d, const void* table);
 int complex_score_launch(const float* table, int64_t N, int32_t d, const int32_t* triples, int64_t B, float max_norm,
                          int apply_sigmoid, float* out, hipStream_t st, int spectral = 0, float label = 0.f, float l2 = 0.f,
                          const float* table_sumsq = nullptr, int64_t ld = 0);
@@ -44,6 +47,7 @@ int table_sumsq_launch(const float* table, int64_t n, float* out, hipStream_t st
 int table_scale_launch(float* table, int64_t n, float factor, hipStream_t st);
 
 // ge_hole.hip: HolE scoring and hinge steps
+int hole_max_dim();           // widest embedding_dim of the direct-correlation kernels (GE_ENOTSUP beyond)
 int hole_score_launch(const float* table, int64_t N, int32_t d, const int32_t* triples, int64_t B, float max_norm,
                       int apply_sigmoid, float* out, hipStream_t st);
 int hole_hinge_loss_launch(const float* table, int64_t N, int32_t d, const int32_t* pos, const int32_t* neg, int64_t B,

@@ -987,10 +987,21 @@ int train_steps_run(float* table, int32_t d, const StepSeq& q, int64_t n_steps, 
   // it, and README.md:42's r . ifft(conj(fft h) fft t) is the ComplEx-shaped trilinear form on the half
   // spectrum (ge_complex_dev.h, SPEC).  Model 2: the table already IS spectral (ge_hole_to_spectral).
   // Model 3 (and odd d): the direct-correlation kernels of ge_hole.hip on the real table.
-  const bool transform = model == GE_MODEL_HOLE && !(d & 1);
+  // The shape is decided HERE, before the first launch: a step refused inside the loop would leave records prepared on
+  // the side stream and -- model 1 -- the caller's table in the frequency domain.  An even d the ComplEx-shaped kernels
+  // do not take at this table's alignment (d = 2 mod 4 from 258, d > 256 on a 4-byte boundary, ...) runs HolE on the
+  // direct kernels while they reach (hole_max_dim) and is GE_ENOTSUP, with nothing launched, beyond.
+  const bool shape_ok = complex_shape_ok(d, table);
+  const bool transform = model == GE_MODEL_HOLE && shape_ok;
   const bool spectral = transform || model == GE_MODEL_HOLE_SPECTRAL;
-  const bool hole_direct = (model == GE_MODEL_HOLE && (d & 1)) || model == GE_MODEL_HOLE_DIRECT;
+  const bool hole_direct = (model == GE_MODEL_HOLE && !shape_ok) || model == GE_MODEL_HOLE_DIRECT;
+  if (hole_direct ? d > hole_max_dim() : !shape_ok) return (!hole_direct && (d & 1)) ? GE_EINVAL : GE_ENOTSUP;
   if (transform) { int rc = hole_spectral_launch(table, N, d, /*inverse=*/0, st); if (rc) return rc; }
+  // a return with an error from here on still hands the table back real-valued (the steps enqueued so far stay applied)
+  struct BackToReal {
+    float* table; int64_t N; int32_t d; hipStream_t st; bool armed;
+    ~BackToReal() { if (armed) (void)hole_spectral_launch(table, N, d, /*inverse=*/1, st); }
+  } back{table, N, d, st, transform};
   const bool fast = train_fast_ok(B, d) && workspace_bytes >= train_ws_bytes(B, d);
   // without the prepared path: the hinge step's workspace alone -- one region, no records
   const TrainWs w = fast ? train_ws(workspace, B, d) : TrainWs{hinge_ws(workspace, B, d), 1, 0, nullptr, 0};
@@ -1045,6 +1056,7 @@ int train_steps_run(float* table, int32_t d, const StepSeq& q, int64_t n_steps, 
     if (rc) return rc;
     GE_HIP_TRY(hipMemcpyAsync(neg_ws, last, sizeof(int32_t) * 3 * (size_t)B, hipMemcpyDeviceToDevice, st));
   }
+  back.armed = false;
   if (transform) { int rc = hole_spectral_launch(table, N, d, /*inverse=*/1, st); if (rc) return rc; }
   return 0;
 }
@@ -1062,6 +1074,8 @@ int train_adagrad_run(float* table, float* accum, int32_t d, const StepSeq& q, i
   if (workspace_bytes < train_ws_bytes(B, d)) return GE_ENOMEM;
   if (n_steps <= 0) return 0;
   const bool hole = model != GE_MODEL_COMPLEX;
+  // a width the step's gradient kernel refuses is refused here, with nothing launched (no prepare, no side-stream work)
+  if (hole ? d > hole_max_dim() : !complex_shape_ok(d, table)) return (!hole && (d & 1)) ? GE_EINVAL : GE_ENOTSUP;
   const TrainWs w = train_ws(workspace, B, d);
   PrepCursor cur(StepIdentity{q, ts, d, 0, 0, workspace}, static_cast<Pipeline*>(pipe_handle), w.prep, st);
   const PrepLayout& L = cur.layout();
@@ -1136,6 +1150,8 @@ int train_logloss_run(float* table, int32_t d, const StepSeq& q, int64_t n_steps
   const float max_norm = hp.max_norm;
   if (n_steps <= 0) return 0;
   if (workspace_bytes < train_logloss_ws_bytes(B, negs, d)) return GE_ENOMEM;
+  // a width the step's gradient kernel refuses is refused here, with nothing launched (no prepare, no side-stream work)
+  if (!complex_shape_ok(d, table)) return GE_ENOTSUP;
   const size_t M = (size_t)(1 + negs) * (size_t)B;
   const LoglossLoopWs w = train_logloss_ws(workspace, B, negs, d);
   float* const sumsq = w.g.sumsq;

@@ -703,6 +703,14 @@ int ge_known_cells(int pass, const int64_t* known_key, const int64_t* known_ent,
  * and transforms back on exit -- two O(N d^2) passes per call, so prefer long calls or keep the table
  * spectral); GE_MODEL_HOLE_SPECTRAL (table already spectral, no transforms); GE_MODEL_HOLE_DIRECT
  * (direct-correlation kernels on the real table, O(d^2) per triple).
+ * The width is decided before anything is launched.  The ComplEx-shaped kernels (models 0 and 2, and model 1's
+ * spectral steps) take an even d whose d / 2 complex elements fit 128 lane vectors of the widest width (4, 2 or 1
+ * elements) that divides d / 2 and that the table's alignment allows (16, 8, 4 bytes): every d = 0 (mod 8) up to
+ * ge_max_dim() on a 16-byte boundary, but d = 4 (mod 8) only up to 512 and d = 2 (mod 4) only up to 256, less on a
+ * table off the boundary.  Elsewhere models 0 and 2 are GE_ENOTSUP; GE_MODEL_HOLE then runs the direct-correlation
+ * kernels on the real table (as it does for odd d) up to d = 512 and is GE_ENOTSUP beyond.  A refused call has launched
+ * nothing and changed nothing; a call that fails later hands a GE_MODEL_HOLE table back real-valued.  The log-loss and
+ * AdaGrad loops below decide the same way.
  * ev_pairs (nullable, HOST array of 2*n_steps events from ge_event_create): the events ride on the
  * dispatch of kernel `ev_kernel` of every step (1 = gather+score+hinge+grad, 2 = row update; 0 =
  * the per-step sampler of the fallback path) and report that kernel's own begin/end -- the hook

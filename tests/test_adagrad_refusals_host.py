@@ -94,6 +94,12 @@ def test_train_steps_adagrad_refuses_bad_arguments_without_launching():
     # the spectral table is not supported, with or without steps
     assert call(n, model=2) == ENOTSUP and call(n, model=2, n_steps=1) == ENOTSUP
     assert call(n, d=1 << 20, accum=A + (1 << 40)) == ENOTSUP   # wider than the update kernels
+    # widths the gradient kernel of the step refuses (tests/complex_shape_cases.py REFUSED): before anything is launched
+    for bad in (dict(d=258), dict(d=1022), dict(d=512, table=A + 4), dict(d=520, table=A + 8)):
+        assert call(n, n_steps=1, **bad) == ENOTSUP, bad
+        assert call(n, **bad) == 0 and call(n, n_steps=1, workspace_bytes="NEED-1", **bad) == ENOMEM, bad
+    assert call(n, n_steps=1, model=1, d=1022) == ENOTSUP and call(n, n_steps=1, model=3, d=520) == ENOTSUP
+    assert call(n, n_steps=1, d=7) == EINVAL               # the ComplEx pairs take no odd width
     # the prepared path only: one byte short is refused, whatever the step count
     assert call(n, workspace_bytes="NEED-1") == ENOMEM and call(n, workspace_bytes="NEED-1", n_steps=1) == ENOMEM
     assert call(n, workspace_bytes=0, n_steps=1) == ENOMEM

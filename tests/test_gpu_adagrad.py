@@ -211,8 +211,19 @@ def compare_loop(H, what, model, B, d, steps=20, one_relation=False, margin=0.2,
     tr = make_trainer(H, table_of(d, n=n), tri, B, model, margin, types=types)
     if warm_up:
         tr.run(warm_up)
+    live, counts, crossing = follow_loop(what, tr, tri, types, B, steps, margin, "complex" if model == "complex" else "hole")
+    if live_range:
+        assert all(live_range[0] <= v <= live_range[1] for v in live), live
+    tr.close()
+    return live, counts, crossing
+
+
+def follow_loop(what, tr, tri, types, B, steps, margin, omodel, seed=SEED, padded=PADDED, lr_at=lr_at):
+    """compare_loop's comparison on a trainer someone else built (test_gpu_complex_shapes.py): tri, types and the
+    schedule lr_at are what it was built from.  Returns (hinge-active share per step, the last step's slot counts,
+    whether a hot row crossed the first tile boundary)."""
+    n, T = tr.embeddings.shape[0], len(tri)
     row, live, crossing = tr.row, [], False
-    omodel = "complex" if model == "complex" else "hole"
     for _ in range(steps):
         gs = tr.global_step
         before_t, before_a = state(tr)
@@ -222,7 +233,7 @@ def compare_loop(H, what, model, B, d, steps=20, one_relation=False, margin=0.2,
             row = 0
         pos = tri[row:row + B]
         row += B
-        neg = O.corrupt_batch(pos, *types, SEED, gs, PADDED, 0)
+        neg = O.corrupt_batch(pos, *types, seed, gs, padded, 0)
         assert np.array_equal(tr._neg.cpu().numpy(), neg)
         ref_t, ref_a = before_t.astype(np.float64), before_a.astype(np.float64)
         oloss, s, named = AR.step(ref_t, ref_a, pos, neg, lr_at(gs), margin, model=omodel)
@@ -235,9 +246,6 @@ def compare_loop(H, what, model, B, d, steps=20, one_relation=False, margin=0.2,
         start = np.cumsum(counts) - counts
         crossing |= bool(np.any((counts > 16) & (start < 16384) & (start + counts > 16384)))
     assert tr.row == row
-    if live_range:
-        assert all(live_range[0] <= v <= live_range[1] for v in live), live
-    tr.close()
     return live, counts, crossing
 
 

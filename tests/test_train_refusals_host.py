@@ -23,6 +23,8 @@ pytestmark = pytest.mark.skipif(torch.cuda.is_available(), reason="fake pointers
 EINVAL, ENOTSUP, ENOMEM = _lib.GE_EINVAL, _lib.GE_ENOTSUP, _lib.GE_ENOMEM
 A = 1 << 12                                   # a fake, 256-byte aligned, never-dereferenced address
 P24 = 1 << 24
+# (d, table alignment) no ComplEx-shaped kernel takes; the odd entries are beyond HolE's direct kernels (d > 512) as well
+REFUSED_SHAPES = (dict(d=258), dict(d=1022), dict(d=512, table=A + 4), dict(d=520, table=A + 8))
 
 TABLE = ["table", "N", "d"]
 TYPES = ["id_to_type", "type_offsets", "n_types", "type_ids"]
@@ -240,7 +242,23 @@ def _cases(name):
         add(EINVAL, model=4, **SHORT)
         add(EINVAL, ev_pairs=A, ev_kernel=3, mode=4)
         add(0, d=1 << 20, **zero)                             # no step, no kernel: the width is not looked at
+        # widths the shape switch of ge_complex.hip does not take (tests/complex_shape_cases.py REFUSED): decided before
+        # the first launch -- and, model 1, before the forward transform -- whatever the mode
+        for bad in REFUSED_SHAPES:
+            for m in (0, 2, 0x100, 0x100 | 2):
+                add(ENOTSUP, model=m, **bad)
+            add(0, **bad, **zero)
+            add(ENOMEM, **bad, **SHORT)                       # the size before the width
+        for bad in REFUSED_SHAPES[1::2]:                      # wider than the direct-correlation kernels too: HolE
+            add(ENOTSUP, model=1, **bad)
+            add(ENOTSUP, model=0x100 | 1, **bad)
+            add(ENOTSUP, model=3, **bad)
+        add(EINVAL, d=7, model=0)                             # the ComplEx pairs take no odd width
     elif name == "ge_train_steps_logloss":
+        for bad in REFUSED_SHAPES:
+            add(ENOTSUP, **bad)
+            add(0, **bad, **zero)
+            add(ENOMEM, **bad, **SHORT)
         add(EINVAL, workspace=None)
         add(EINVAL, workspace=A + 128)
         add(ENOMEM, **SHORT)
