@@ -201,6 +201,16 @@ int adagrad_items_launch(float* table, float* accum, int d, const TileGeom& G, c
 int adagrad_rows_launch(float* table, float* accum, int64_t N, int32_t d, const int32_t* idx, const float* val,
                         const int32_t* perm, int64_t R, float lr, hipStream_t st);
 
+// ge_softmax.hip: 1-vs-all softmax loss and gradients of ComplEx (d % 8 == 0 in 8 ... kRankMaxDim, table 16-byte aligned:
+// asserted).  The workspace: Q' [B,d] | C' [K,d] | query keys [B] | candidate keys [K] | (max, log sum) [2][B] | (max, sum, z_true,
+// found) partials [8][B] | dL/dQ' partials [8][B,d], each padded to 256 B.  grad_idx == null: the loss alone.
+struct SoftmaxWs { float* qp; float* cp; int32_t* qkey; int32_t* ckey; float* lse; float4* part; float* gq; size_t bytes; };
+SoftmaxWs softmax_ws(void* base, int64_t B, int64_t K, int32_t d);
+size_t softmax_ws_bytes(int64_t B, int64_t K, int32_t d);
+int softmax_launch(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* true_id,
+                   const int32_t* cand, int64_t K, float max_norm, float scale, float lr, int cand_is_head, float* loss,
+                   int32_t* grad_idx, float* grad_val, void* workspace, hipStream_t st);
+
 // ge_shard.hip: the row-sharded step's requester and owner planners
 size_t shard_plan_scratch_bytes(int64_t B, int64_t S);
 int shard_plan_launch(const int32_t* pos, const int32_t* neg, int64_t S, int64_t B, int64_t N, int32_t G, int32_t rank,

@@ -343,6 +343,182 @@ class HingeAdaGrad:
         return loss.view(-1, 1)
 
 
+def _softmax_args(embeddings, fixed_and_relation, true_ids, candidates, scale, max_norm, side, who):
+    """The host checks of the softmax calls: (emb, hr [B,2] int32, true ids [B] int32, candidates [K] int32, side code)."""
+    emb = _table(embeddings)
+    for name, t in (("fixed_and_relation", fixed_and_relation), ("true_ids", true_ids), ("candidates", candidates)):
+        _need_cuda(t, name)
+    if side not in ("tail", "head"):
+        raise ValueError(f"{who}: side must be 'tail' or 'head'")
+    if not (scale > 0 and np.isfinite(scale)):
+        raise ValueError(f"{who}: scale must be positive and finite")
+    if not max_norm > 0:
+        raise ValueError(f"{who}: max_norm must be positive")
+    hr = fixed_and_relation.to(torch.int32).contiguous()
+    tid = true_ids.to(torch.int32).contiguous().view(-1)
+    cand = candidates.to(torch.int32).contiguous().view(-1)
+    if hr.dim() != 2 or hr.shape[1] != 2 or tid.numel() != hr.shape[0]:
+        raise ValueError(f"{who}: fixed_and_relation must be [B,2] (entity, relation) and true_ids [B]")
+    if hr.shape[0] < 1 or cand.numel() < 1:
+        raise ValueError(f"{who}: at least one query row and one candidate")
+    d = emb.shape[1]
+    if d % 8 != 0 or d < 8 or d > rank_max_dim():
+        raise ValueError(f"{who}: embedding_dim must be a multiple of 8 in 8 ... {rank_max_dim()}")
+    return emb, hr, tid, cand, int(side == "head")
+
+
+def softmax_workspace(embeddings: torch.Tensor, B: int, K: int) -> torch.Tensor:
+    """A workspace for softmax_loss / softmax_grad at this shape (ge_softmax_workspace_bytes)."""
+    need = _lib.load().ge_softmax_workspace_bytes(B, K, embeddings.shape[1])
+    return torch.empty(max(need, 256), dtype=torch.uint8, device=embeddings.device)
+
+
+def softmax_loss(embeddings: torch.Tensor, fixed_and_relation: torch.Tensor, true_ids: torch.Tensor,
+                 candidates: torch.Tensor, *, scale: float, max_norm: float = 1.0, side: str = "tail",
+                 workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The 1-vs-all objective (ge_softmax_loss): loss_i = logsumexp_j(-scale * s_ij) - (-scale * s_i,true) over all
+    `candidates` (distinct ids), s the ComplEx score of score_candidates without the sigmoid.  side="tail": row i is
+    (head_i, relation_i) and the candidates are tails; "head": (tail_i, relation_i), candidates are heads.  NaN for a row
+    with an id outside the table or whose true id is not a candidate.  ComplEx only."""
+    emb, hr, tid, cand, head = _softmax_args(embeddings, fixed_and_relation, true_ids, candidates, scale, max_norm, side,
+                                             "softmax_loss")
+    B, K = hr.shape[0], cand.numel()
+    ws = workspace if workspace is not None else softmax_workspace(emb, B, K)
+    loss = torch.empty(B, dtype=torch.float32, device=emb.device)
+    _lib.call("ge_softmax_loss", emb.data_ptr(), emb.shape[0], emb.shape[1], hr.data_ptr(), B, tid.data_ptr(), cand.data_ptr(),
+              K, float(max_norm), float(scale), MODEL_COMPLEX, head, loss.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+    return loss
+
+
+def softmax_grad(embeddings: torch.Tensor, fixed_and_relation: torch.Tensor, true_ids: torch.Tensor,
+                 candidates: torch.Tensor, lr: float, *, scale: float, max_norm: float = 1.0, side: str = "tail",
+                 workspace: Optional[torch.Tensor] = None, out=None):
+    """The counterpart of hinge_grad for the 1-vs-all objective (ge_softmax_grad): (loss [B], grad_idx [K + 2B] int32,
+    grad_val [K + 2B, d]) with grad_val = -lr * the gradient of SUM_i loss_i.  Slot j < K is candidates[j], slots K + 2i
+    and K + 2i + 1 the fixed entity and the relation of row i; -1 and a zero row for an empty slot.  out: (grad_idx,
+    grad_val) views to write into."""
+    emb, hr, tid, cand, head = _softmax_args(embeddings, fixed_and_relation, true_ids, candidates, scale, max_norm, side,
+                                             "softmax_grad")
+    B, K, d = hr.shape[0], cand.numel(), emb.shape[1]
+    R = K + 2 * B
+    ws = workspace if workspace is not None else softmax_workspace(emb, B, K)
+    loss = torch.empty(B, dtype=torch.float32, device=emb.device)
+    if out is None:
+        gi = torch.empty(R, dtype=torch.int32, device=emb.device)
+        gv = torch.empty(R, d, dtype=torch.float32, device=emb.device)
+    else:
+        gi, gv = out
+        if gi.dtype != torch.int32 or gv.dtype != torch.float32 or gi.numel() != R or tuple(gv.shape) != (R, d) \
+                or not gi.is_contiguous() or not gv.is_contiguous():
+            raise ValueError("softmax_grad: out must be (int32 [K + 2B], float32 [K + 2B, d]), contiguous")
+    _lib.call("ge_softmax_grad", emb.data_ptr(), emb.shape[0], d, hr.data_ptr(), B, tid.data_ptr(), cand.data_ptr(), K,
+              float(max_norm), float(scale), float(lr), MODEL_COMPLEX, head, loss.data_ptr(), gi.data_ptr(), gv.data_ptr(),
+              ws.data_ptr(), ws.numel(), _stream())
+    return loss, gi, gv
+
+
+class SoftmaxAdaGrad:
+    """AdagradOptimizer(lr, initial_accumulator_value) on the 1-vs-all objective, both sides of every triple against ONE
+    snapshot of the table: two ge_softmax_grad calls at lr = 1 (tails, then heads) into one slices buffer of
+    2 (K + 2B) slots, one stable argsort, one ge_adagrad_rows -- an entity that is a candidate, a tail and a head in the
+    same step gets one update from its summed gradient.  Owns `.accumulator`; workspace and slices are reserved once."""
+
+    def __init__(self, embeddings: torch.Tensor, candidates: torch.Tensor, batch_size: int, *, scale: float,
+                 max_norm: float = 1.0, initial_accumulator_value: float = 0.1):
+        if not initial_accumulator_value > 0:
+            raise ValueError("initial_accumulator_value must be positive")
+        self.embeddings = _table(embeddings)
+        _need_cuda(candidates, "candidates")
+        self.candidates = candidates.to(torch.int32).contiguous().view(-1)
+        self.B, self.scale, self.max_norm = int(batch_size), float(scale), float(max_norm)
+        if self.B < 1 or self.candidates.numel() < 1:
+            raise ValueError("SoftmaxAdaGrad: at least one row a batch and one candidate")
+        dev, d = self.embeddings.device, self.embeddings.shape[1]
+        self.accumulator = torch.full_like(self.embeddings, float(initial_accumulator_value))
+        R = self.candidates.numel() + 2 * self.B
+        self._ws = softmax_workspace(self.embeddings, self.B, self.candidates.numel())
+        self._gi = torch.empty(2 * R, dtype=torch.int32, device=dev)
+        self._gv = torch.empty(2 * R, d, dtype=torch.float32, device=dev)
+
+    def step(self, triples: torch.Tensor, lr: float) -> torch.Tensor:
+        """One step in place on the table and the accumulator for triples [B,3] (head, tail, relation); returns the
+        per-row losses [B,2] (tail side, head side)."""
+        emb = self.embeddings
+        tri = _triples(triples, "triples")
+        if tri.shape[0] != self.B:
+            raise ValueError("SoftmaxAdaGrad.step: triples must be [batch_size, 3]")
+        R = self.candidates.numel() + 2 * self.B
+        losses = []
+        for s, (fixed, true, side) in enumerate(((0, 1, "tail"), (1, 0, "head"))):
+            hr = tri[:, [fixed, 2]].contiguous()
+            loss, _, _ = softmax_grad(emb, hr, tri[:, true].contiguous(), self.candidates, 1.0, scale=self.scale,
+                                      max_norm=self.max_norm, side=side, workspace=self._ws,
+                                      out=(self._gi[s * R:(s + 1) * R], self._gv[s * R:(s + 1) * R]))
+            losses.append(loss)
+        # a row's occurrences consecutive and in slot order: the stable argsort, empty slots last (adagrad_rows)
+        key = torch.where(self._gi < 0, torch.full_like(self._gi, emb.shape[0]), self._gi)
+        perm = torch.argsort(key, stable=True).to(torch.int32)
+        _lib.call("ge_adagrad_rows", emb.data_ptr(), _accumulator(self.accumulator, emb).data_ptr(), emb.shape[0],
+                  emb.shape[1], self._gi.data_ptr(), self._gv.data_ptr(), perm.data_ptr(), 2 * R, float(lr), _stream())
+        return torch.stack(losses, 1)
+
+
+class SoftmaxTrainer:
+    """The training loop of the 1-vs-all objective: per step a batch of `triples` [T,3] (head, tail, relation) drawn on
+    the device -- without replacement within an epoch, every epoch a new permutation from a generator seeded with
+    `seed` --, lr from inverse_time_decay as in Trainer, one SoftmaxAdaGrad.step.  A Python loop: a step is milliseconds
+    of GPU work, which the host's few launches per step stay ahead of."""
+
+    def __init__(self, embeddings: torch.Tensor, triples: torch.Tensor, candidates: torch.Tensor, batch_size: int, *,
+                 scale: float, learning_rate: float = 0.1, learning_decay_steps: float = 0.0,
+                 learning_decay_rate: float = 0.5, seed: int = 0, max_norm: float = 1.0,
+                 initial_accumulator_value: float = 0.1):
+        self.opt = SoftmaxAdaGrad(embeddings, candidates, batch_size, scale=scale, max_norm=max_norm,
+                                  initial_accumulator_value=initial_accumulator_value)
+        self.embeddings = self.opt.embeddings
+        self.triples = _triples(triples, "triples")
+        self.B = int(batch_size)
+        if self.triples.shape[0] < self.B:
+            raise ValueError("fewer triples than batch_size (no short batches)")
+        self.lr0, self.decay_steps, self.decay_rate = float(learning_rate), float(learning_decay_steps), float(learning_decay_rate)
+        self.global_step = 0
+        self._gen = torch.Generator(device=self.embeddings.device)
+        self._gen.manual_seed(int(seed))
+        self._perm, self._row = None, 0
+
+    @property
+    def accumulator(self) -> torch.Tensor:
+        return self.opt.accumulator
+
+    @accumulator.setter
+    def accumulator(self, value: torch.Tensor):
+        self.opt.accumulator = _accumulator(value, self.embeddings)
+
+    def learning_rate(self, step=None) -> float:
+        s = self.global_step if step is None else step
+        return inverse_time_decay(self.lr0, s, self.decay_steps, self.decay_rate) if self.decay_steps > 0 else self.lr0
+
+    def next_batch(self) -> torch.Tensor:
+        """The next [B,3] batch of the epoch order (a new permutation when fewer than B rows are left)."""
+        T = self.triples.shape[0]
+        if self._perm is None or self._row + self.B > T:
+            self._perm = torch.randperm(T, device=self.triples.device, generator=self._gen)
+            self._row = 0
+        rows = self._perm[self._row:self._row + self.B]
+        self._row += self.B
+        return self.triples[rows].contiguous()
+
+    def run(self, n_steps: int, keep_losses: bool = False) -> torch.Tensor:
+        """n_steps steps on the current stream; the losses [n_steps, B, 2] if keep_losses, else the last step's [B,2]."""
+        kept, loss = [], None
+        for _ in range(n_steps):
+            loss = self.opt.step(self.next_batch(), self.learning_rate())
+            self.global_step += 1
+            if keep_losses:
+                kept.append(loss)
+        return torch.stack(kept, 0) if keep_losses else loss
+
+
 def gather_rows(table: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     """out[i] = table[idx[i]] (zeros where idx[i] < 0)."""
     table = _table(table)

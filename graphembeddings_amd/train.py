@@ -14,7 +14,8 @@ Between validation ticks the steps are enqueued natively by ge_train_steps (hing
 ge_train_steps_logloss (--log_loss) -- no Python per step.
 Extras: --model hole (README.md:42 score), --seed, --max_steps, --checkpoint_seconds, --optimizer adagrad
 (AdagradOptimizer in place of holE.py:296's GradientDescentOptimizer: ge_train_steps_adagrad; the checkpoint then also
-holds `adagrad_accumulator`).
+holds `adagrad_accumulator`), --objective softmax (1-vs-all multiclass log-loss over all entities, both sides:
+hole.SoftmaxTrainer on ge_softmax_grad; ComplEx with AdaGrad on one GPU, no validation ticks).
 """
 from __future__ import annotations
 
@@ -89,6 +90,11 @@ def build_parser() -> argparse.ArgumentParser:
                         'one GPU).')
     p.add_argument('--adagrad_init', type=float, default=0.1,
                    help='With --optimizer adagrad: initial_accumulator_value.')
+    p.add_argument('--objective', choices=['hinge', 'softmax'], default='hinge',
+                   help='hinge: the pairwise ranking loss of holE.py:231 (or --log_loss); softmax: multiclass log-loss of the '
+                        'true entity over ALL entities, both sides ("1vsAll"; ComplEx, --optimizer adagrad, one GPU).')
+    p.add_argument('--softmax_scale', type=float, default=20.0,
+                   help='With --objective softmax: the logit scale (rows are clipped to norm 1, so |score| <= 1).')
     p.add_argument('--gpus', type=int, default=1,
                    help='Ranks (one per GPU) the table is row-sharded over; > 1 without a launcher: this program starts them '
                         '(graphembeddings_amd/launch.py).  --batch_size stays the GLOBAL batch.')
@@ -131,7 +137,81 @@ def check_optimizer_flags(FLAGS, world: int = 1) -> None:
         raise SystemExit('--adagrad_init must be positive')
 
 
+def check_objective_flags(FLAGS, world: int = 1) -> None:
+    """--objective softmax: ComplEx with AdaGrad on one GPU, no --log_loss."""
+    if getattr(FLAGS, 'objective', 'hinge') != 'softmax':
+        return
+    if getattr(FLAGS, 'optimizer', 'sgd') != 'adagrad':
+        raise SystemExit('--objective softmax needs --optimizer adagrad')
+    if FLAGS.log_loss:
+        raise SystemExit('--objective softmax is an objective of its own: drop --log_loss')
+    if FLAGS.model != 'complex':
+        raise SystemExit('--objective softmax is defined for the ComplEx score (drop --model hole)')
+    if FLAGS.gpus > 1 or world > 1:
+        raise SystemExit('--objective softmax runs on one GPU (drop --gpus)')
+    if not (FLAGS.softmax_scale > 0 and np.isfinite(FLAGS.softmax_scale)):
+        raise SystemExit('--softmax_scale must be positive and finite')
+
+
+def run_softmax_training(data: D.HolEData, FLAGS, log=print) -> dict:
+    """--objective softmax: hole.SoftmaxTrainer over the entity rows relation_count .. entity_count - 1, with the epoch
+    and learning-rate bookkeeping of run_training (an epoch is batch_count - 1 steps).  The checkpoint holds the table
+    and the AdaGrad accumulator and is written every --checkpoint_seconds, at the end of each epoch and at the end."""
+    batch_count = data.triple_count // FLAGS.batch_size
+    log('Embedding dimension: ', FLAGS.embedding_dim, 'Batch size: ', FLAGS.batch_size, 'Batch count: ', batch_count)
+    if batch_count < 2:
+        raise ValueError('need at least 2 batches of training triples')
+    if not FLAGS.resume_checkpoint and os.path.isdir(FLAGS.output_dir):
+        raise Exception("WARNING: " + FLAGS.output_dir + " already exists!")   # holE.py:254-255
+    os.makedirs(FLAGS.output_dir, exist_ok=True)
+    global_step, accumulator = 0, None
+    if FLAGS.resume_checkpoint:
+        embeddings, global_step, accumulator = load_checkpoint(FLAGS.output_dir, with_accumulator=True)
+        if tuple(embeddings.shape) != (data.entity_count, FLAGS.embedding_dim):
+            raise ValueError('checkpoint shape does not match the data / --embedding_dim')
+    else:
+        embeddings = H.init_embeddings(data.entity_count, FLAGS.embedding_dim, seed=FLAGS.seed)
+    triples = torch.as_tensor(np.ascontiguousarray(data.triples)).cuda()
+    candidates = torch.arange(data.relation_count, data.entity_count, dtype=torch.int32, device='cuda')
+    trainer = H.SoftmaxTrainer(embeddings, triples, candidates, FLAGS.batch_size, scale=FLAGS.softmax_scale,
+                               learning_rate=FLAGS.learning_rate,
+                               learning_decay_steps=FLAGS.learning_decay_steps * batch_count,
+                               learning_decay_rate=FLAGS.learning_decay_rate, seed=FLAGS.seed,
+                               initial_accumulator_value=FLAGS.adagrad_init)
+    if accumulator is not None and accumulator.shape == trainer.accumulator.shape:
+        trainer.accumulator.copy_(accumulator)
+    elif FLAGS.resume_checkpoint:
+        log('Checkpoint holds no AdaGrad accumulator: starting it at', FLAGS.adagrad_init)
+    trainer.global_step = global_step
+    log('Objective softmax: no validation ticks (the hinge tick measures another objective); the mean loss of the last '
+        'step is logged per epoch')
+    t_start, last_write, loss = time.time(), time.time(), None
+    left = FLAGS.max_steps if FLAGS.max_steps else None
+    for epoch in range(1, FLAGS.num_epochs + 1):
+        log('Training epoch {}...'.format(epoch))
+        n = batch_count - 1 if left is None else min(batch_count - 1, left)
+        for _ in range(n):
+            loss = trainer.run(1)
+            if FLAGS.checkpoint_seconds > 0 and time.time() - last_write >= FLAGS.checkpoint_seconds:
+                save_checkpoint(FLAGS.output_dir, embeddings, trainer.global_step, trainer.accumulator)
+                last_write = time.time()
+        save_checkpoint(FLAGS.output_dir, embeddings, trainer.global_step, trainer.accumulator)
+        last_write = time.time()
+        log('Epoch {}, mean softmax loss {}'.format(epoch, float(loss.mean()) if loss is not None else float('nan')))
+        if left is not None:
+            left -= n
+            if left <= 0:
+                break
+    torch.cuda.synchronize()
+    log('Done training -- epoch limit reached')
+    return {'steps': trainer.global_step - global_step, 'seconds': time.time() - t_start, 'global_step': trainer.global_step,
+            'final_mean_softmax_loss': float(loss.mean()) if loss is not None else float('nan')}
+
+
 def run_training(data: D.HolEData, FLAGS, log=print) -> dict:
+    if getattr(FLAGS, 'objective', 'hinge') == 'softmax':
+        check_objective_flags(FLAGS)
+        return run_softmax_training(data, FLAGS, log)
     if FLAGS.log_loss and FLAGS.model != 'complex':
         raise NotImplementedError('--log_loss is implemented for the ComplEx score (holE.py:191-196)')
     batch_count = data.triple_count // FLAGS.batch_size
@@ -417,6 +497,7 @@ def main(argv=None):
     check_classify_flags(FLAGS, world)
     check_candidate_set_flags(FLAGS, world)
     check_optimizer_flags(FLAGS, world)
+    check_objective_flags(FLAGS, world)
     if FLAGS.relation_ranks and not FLAGS.infer:
         raise SystemExit('--relation_ranks needs --infer')
     if FLAGS.relation_ranks and (FLAGS.gpus > 1 or world > 1):

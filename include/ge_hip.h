@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define GE_VERSION 430 /* 0.4.3: + ge_transx_adagrad_step / ge_transx_train_steps_adagrad (AdaGrad for TransE / TransH / TransD) */
+#define GE_VERSION 440 /* 0.4.4: + ge_softmax_loss / ge_softmax_grad (1-vs-all softmax training for ComplEx) */
 
 /* argument errors (negative, -errno style) */
 #define GE_EINVAL (-22)  /* bad dimension / null pointer / misaligned buffer */
@@ -183,6 +183,32 @@ int ge_gather_rows(const float* table, int64_t N, int32_t d, const int32_t* idx,
  * skipped; rows not named are not touched in either array.  No float atomics: bitwise reproducible.  R = 0 returns 0. */
 int ge_adagrad_rows(float* table, float* accum, int64_t N, int32_t d, const int32_t* idx, const float* val,
                     const int32_t* perm, int64_t R, float lr, void* stream);
+
+/* --- 1-vs-all softmax training of ComplEx: the multiclass log-loss over all candidates ("1vsAll", Lacroix et al. 2018)
+ * in place of the hinge of holE.py:231, on the candidate sweep of ge_complex_score_1vK (holE.py:564-569) -- extends
+ * ge_hinge_loss / ge_hinge_grad to an objective the reference does not have.  hr [B,2] (fixed entity, relation),
+ * true_id [B], cand [K] (distinct ids), loss [B] as for ge_rank_1vK.  With s_ij the un-squashed score of
+ * ge_complex_score_1vK (rows clipped to max_norm on lookup) and z_ij = -scale * s_ij (lower score = more plausible):
+ *   loss_i = logsumexp_j(z_ij) - z_i,true     (running maximum subtracted; no [B,K] array is ever formed)
+ * A row whose fixed, relation or true id lies outside [0,N), or whose true id is not among the candidates, is invalid:
+ * loss = NaN, no contribution to any gradient.  A candidate id outside [0,N) is left out of every softmax.
+ * ge_softmax_grad is the counterpart of ge_hinge_grad: IndexedSlices of R = K + 2B slots, grad_idx [R] int32 and
+ * grad_val [R,d] fp32 = -lr * the gradient of SUM_i loss_i taken through the three clips, against the table as it is:
+ *   slot j < K: cand[j] (-1 for an id outside [0,N)); slot K + 2i: fixed_i; slot K + 2i + 1: rel_i (both -1 for an
+ *   invalid row); an empty slot's row is zeros.  At lr = 1 the slices are what ge_adagrad_rows takes, scaled by lr what
+ *   ge_scatter_add_rows takes.  Exact-fp32 MFMA, no float atomics: two identical calls give identical bits.
+ * model: GE_MODEL_COMPLEX only (any other code GE_ENOTSUP).  embedding_dim % 8 == 0 in 8 ... ge_rank_max_dim(), else
+ * GE_ENOTSUP; table 16-byte aligned.  GE_EINVAL: a null pointer; N, B, K or d < 1; scale <= 0 or not finite;
+ * max_norm <= 0; a table off 16 bytes; a workspace off 256 bytes.  GE_ENOMEM: workspace_bytes below
+ * ge_softmax_workspace_bytes(B, K, d) (monotone in each argument, a multiple of 256, 0 for sizes the calls refuse).
+ * Nothing is allocated and the host never waits. */
+size_t ge_softmax_workspace_bytes(int64_t B, int64_t K, int32_t d);
+int ge_softmax_loss(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* true_id,
+                    const int32_t* cand, int64_t K, float max_norm, float scale, int model, int cand_is_head,
+                    float* loss, void* workspace, size_t workspace_bytes, void* stream);
+int ge_softmax_grad(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* true_id,
+                    const int32_t* cand, int64_t K, float max_norm, float scale, float lr, int model, int cand_is_head,
+                    float* loss, int32_t* grad_idx, float* grad_val, void* workspace, size_t workspace_bytes, void* stream);
 
 /* --- corrupt_batch (holE.py:152-153 -> 136-140 -> 97-133) fused with the per-batch host
  * resample of holE.py:343-347.  id_to_type [N] int32 type code per table row (-1 = unknown, the
