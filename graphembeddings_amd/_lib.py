@@ -73,6 +73,7 @@ SYMBOLS = {
     "ge_train_pipeline_create": (C.c_int, [C.POINTER(C.c_void_p)]),
     "ge_train_pipeline_reset": (C.c_int, [_p]),
     "ge_train_pipeline_destroy": (C.c_int, [_p]),
+    "ge_train_max_chunk_steps": (_i64, [_i64, _i64]),
     "ge_train_steps": (C.c_int, [_p, _i64, _i32, _p, _i64, _i64, _i64, _i64, _p, _p, _i32, _p, _u64, _u64, _i32,
                                  _i32, _f, _f, _f, _f, _f, C.c_int, _p, C.c_int, _p, _p, _sz, _p, C.c_int, _p, _p]),
     "ge_train_adagrad_workspace_bytes": (_sz, [_i64, _i32]),

@@ -1079,6 +1079,8 @@ int ge_train_pipeline_create(void** pipeline) { return pipeline ? pipeline_creat
 int ge_train_pipeline_reset(void* pipeline) { return pipeline_reset(pipeline); }
 int ge_train_pipeline_destroy(void* pipeline) { return pipeline_destroy(pipeline); }
 
+int64_t ge_train_max_chunk_steps(int64_t B, int64_t negs) { return (B <= 0 || negs < 0) ? 0 : train_chunk_steps(B, negs); }
+
 int ge_train_prepared_layout(int64_t B, int64_t* out8) {
   if (B <= 0 || !out8) return GE_EINVAL;
   train_prepared_layout(B, out8);

@@ -186,6 +186,7 @@ int train_logloss_run(float* table, int32_t d, const StepSeq& q, int64_t n_steps
 size_t train_prepare_bytes(int64_t B, int64_t n_steps);
 int train_prepare_run(const StepSeq& q, int64_t n_steps, const TypeSampler& ts, int direct, int32_t* out, hipStream_t st);
 void train_prepared_layout(int64_t B, int64_t* out);
+int64_t train_chunk_steps(int64_t B, int64_t negs);   // steps per prepare launch of the native loops (negs = 0: hinge, AdaGrad)
 // the AdaGrad loop (holE.py:296 with AdagradOptimizer): the prepared path only, its workspace is train_ws_bytes'
 int train_adagrad_run(float* table, float* accum, int32_t d, const StepSeq& q, int64_t n_steps, const TypeSampler& ts,
                       float margin, const StepHyper& hp, int model, float* loss, int keep_all_losses, int32_t* neg_ws,

@@ -24,7 +24,8 @@
 // pipeline handle (ge_train_pipeline_create) the prepare launches run on the handle's side stream one
 // chunk AHEAD of the steps that consume them -- across ge_train_steps calls too: a call that continues
 // where the previous one stopped finds its records already built.  Without a handle the launches go
-// to the caller's stream (one ~20 us launch per chunk of steps) and the library keeps no state at all.
+// to the caller's stream (one launch per chunk of steps: ~120 us at B = 4096, measured alone, profiles/r23_*) and the
+// library keeps no state at all.
 #include "ge_prep.h"
 #include "ge_launch.h"
 #include <algorithm>
@@ -727,10 +728,28 @@ HingeWs hinge_ws(void* base, int64_t B, int32_t d) {
 
 static bool train_fast_ok(int64_t B, int32_t d) { return B >= 1 && B <= (int64_t)1 << 24 && d <= 1024; }
 
-// steps prepared per launch: 32 at B <= 4096 (one record is ~1.2 MB there), fewer for large batches
+// Steps prepared per launch.  Up to 4096 units (one tile) a launch of n steps is n independent 1024-thread workgroups of
+// train_prepare_kernel, each with a CU's LDS to itself: up to one workgroup per CU it lasts the same whatever n is --
+// 119-120 us at B = 4096 on FB15k's tables, beside training or alone (rocprofv3, profiles/r23_*) -- and for that long the
+// one-round training kernels share CUs with it: the gradient kernel of the 5-9 steps behind a chunk entry takes 9.2-11.5
+// us instead of 8.6 (profiles/r23_step_periods_b4096_parent.json).  The share of steps that run beside a launch is
+// t_prepare / (chunk x t_step): 28 % at 32 steps, 7 % at 128, 3.5 % at 256, so the chunk is LONG.  Step time at config 2,
+// margin 0.2 / 5.0, three alternations on one box (profiles/r23_ab_prepare_chunks.log): 32 steps 13.3-13.8 / 15.0-15.2
+// us, 64: 13.3-13.4 / 14.6-14.7, 128: 12.9-13.4 / 14.4-14.6, 256: 12.8-14.1 / 14.3-15.1 -- 128 is the shortest within
+// the spread of the best (a gain of 0.4-0.8 us, the size of the process-to-process spread at margin 0.2; bench.py's own
+// line 13.6-13.7 -> 12.6-12.9 us; the alternatives that lost: DESIGN.md 9(k)).  The price is workspace: two buffers of
+// chunk x stride words, at B = 4096 records of 1.18 MB (about 0.3 MB of each ever touched): 302 MB where 32 steps took
+// 75 MB.
+#ifndef GE_ONE_TILE_CHUNK_STEPS
+#define GE_ONE_TILE_CHUNK_STEPS 128
+#endif
+// largest_need_up_to relies on a chunk length that never rises with the unit count: 31 steps at 4097 units
+static_assert(GE_ONE_TILE_CHUNK_STEPS >= 32, "the one-tile chunk must not be shorter than the first multi-tile one");
+
 static int64_t prep_chunk_steps(int64_t B, int64_t negs = 0) {
   const int64_t u = negs > 0 ? (1 + negs) * B : B;
-  int64_t c = (32 * kSub) / (u < kSub ? kSub : u);
+  if (u <= kSub) return GE_ONE_TILE_CHUNK_STEPS;
+  int64_t c = (32 * kSub) / u;
   // the multi-tile sorts (slot keys, relation order) are ~16 short launches whose latency is the same for 2 steps
   // or 16: a chunk holds enough steps that the sequence (~0.3-0.5 ms) hides behind them -- 16 up to 32,768 units
   // (42 us steps at 16,384), 8 up to 262,144 (19 MB of records each at B = 65,536), 2 beyond
@@ -1226,6 +1245,8 @@ int train_prepare_run(const StepSeq& q, int64_t n_steps, const TypeSampler& ts, 
   from.first_row = norm_row(q.first_row, q.T, q.B);
   return prepare_launch(from, 0, n_steps, ts, direct ? 1 : 0, out, ws_at<void>(out, prepared_records_bytes(q.B, n_steps)), st);
 }
+
+int64_t train_chunk_steps(int64_t B, int64_t negs) { return prep_chunk_steps(B, negs); }
 
 void train_prepared_layout(int64_t B, int64_t* out) {
   const PrepLayout L = prep_layout(B);

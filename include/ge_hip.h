@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define GE_VERSION 440 /* 0.4.4: + ge_softmax_loss / ge_softmax_grad (1-vs-all softmax training for ComplEx) */
+#define GE_VERSION 441 /* 0.4.4.1: + ge_train_max_chunk_steps; longer prepare chunks (larger workspace) for steps of <= 4096 units */
 
 /* argument errors (negative, -errno style) */
 #define GE_EINVAL (-22)  /* bad dimension / null pointer / misaligned buffer */
@@ -715,7 +715,7 @@ int ge_known_cells(int pass, const int64_t* known_key, const int64_t* known_ent,
  * call continues exactly where the previous call with the same handle stopped (same arrays, sizes,
  * seed, mode, workspace; global_step0 and first_row advanced by the steps already run) its records
  * are already built and nothing but the two per-step kernels is on the critical path.  Any other
- * call restarts the sequence (its first prepare launch, ~20 us, is then exposed).  While a handle
+ * call restarts the sequence (its first prepare launch, ~120 us at B = 4096, is then exposed).  While a handle
  * is live the caller must not modify `triples`, the type tables or the workspace between calls
  * without ge_train_pipeline_reset; the streams are ordered by events only, the host never blocks,
  * and before returning every call makes `stream` wait for the look-ahead launch, so work enqueued
@@ -745,8 +745,16 @@ int ge_known_cells(int pass, const int64_t* known_key, const int64_t* known_ent,
  * largest batch serves every smaller one on the prepared path.  ge_train_logloss_workspace_bytes is NOT monotone in
  * negative_ratio: the steps prepared per chunk and the gradient ring shrink as (1 + negative_ratio) * B grows, so a
  * larger ratio can need fewer bytes (B = 1024, d = 8: ratio 31 needs more than ratio 32).  Size the workspace for the
- * ratio the loop is called with; a call with another ratio than it was sized for may be GE_ENOMEM. */
+ * ratio the loop is called with; a call with another ratio than it was sized for may be GE_ENOMEM.
+ * ge_train_max_chunk_steps(B, negative_ratio; 0 = the hinge and AdaGrad loops): the steps one prepare launch holds, i.e.
+ * where the chunk boundaries of a sequence lie (step s of a sequence is in chunk s / that number).  128 steps while
+ * (1 + negative_ratio) * B <= 4096, where a launch is one workgroup per step and lasts the same for 32 steps or 128 but
+ * slows the steps it runs beside, so fewer and longer launches cost less; 31 and falling beyond, never rising with B;
+ * 0 for B <= 0 or a negative ratio.  The two chunk buffers dominate the workspace of small steps: B = 4096, d = 200
+ * needs 419 MB (ge_train_workspace_bytes), 302 MB of it records (1.18 MB each, about 0.3 MB of which is ever touched;
+ * 32-step chunks took 75 MB), the rest the gradient ring. */
 size_t ge_train_workspace_bytes(int64_t B, int32_t d);
+int64_t ge_train_max_chunk_steps(int64_t B, int64_t negative_ratio);
 int ge_train_pipeline_create(void** pipeline);
 int ge_train_pipeline_reset(void* pipeline);
 int ge_train_pipeline_destroy(void* pipeline); /* waits for the side stream, then frees */
