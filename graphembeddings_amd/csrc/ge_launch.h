@@ -212,6 +212,21 @@ int softmax_launch(const float* table, int64_t N, int32_t d, const int32_t* hr, 
                    const int32_t* cand, int64_t K, float max_norm, float scale, float lr, int cand_is_head, float* loss,
                    int32_t* grad_idx, float* grad_val, void* workspace, hipStream_t st);
 
+// ge_softmax_sampled.hip: the same objective over candidates that need not hold the true entity (its logit is the row's
+// own; slots that hold it are left out), gradients in K + 3B slots.  The workspace: Q' [B,d] | C' [K,d] | T' [B,d] (the
+// clipped true rows) | query keys [B] | candidate keys [K] | z_true [B] | (max, log sum) [2][B] | (max, sum, row of the max, -) partials
+// [8][B] | dL/dQ' partials [8][B,d] | dL/dC' partials [ranges][K,d] (sized for every number of query ranges the launch
+// can choose), each padded to 256 B.  grad_idx == null: the loss alone.
+struct SoftmaxSampledWs {
+  float* qp; float* cp; float* tp; int32_t* qkey; int32_t* ckey; float* zt; float* lse; float4* part; float* gq; float* gc;
+  size_t bytes;
+};
+SoftmaxSampledWs softmax_sampled_ws(void* base, int64_t B, int64_t K, int32_t d);
+size_t softmax_sampled_ws_bytes(int64_t B, int64_t K, int32_t d);
+int softmax_sampled_launch(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* true_id,
+                           const int32_t* cand, int64_t K, float max_norm, float scale, float lr, int cand_is_head,
+                           float* loss, int32_t* grad_idx, float* grad_val, void* workspace, hipStream_t st);
+
 // ge_shard.hip: the row-sharded step's requester and owner planners
 size_t shard_plan_scratch_bytes(int64_t B, int64_t S);
 int shard_plan_launch(const int32_t* pos, const int32_t* neg, int64_t S, int64_t B, int64_t N, int32_t G, int32_t rank,

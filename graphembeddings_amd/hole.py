@@ -463,18 +463,132 @@ class SoftmaxAdaGrad:
         return torch.stack(losses, 1)
 
 
+def softmax_sampled_workspace(embeddings: torch.Tensor, B: int, K: int) -> torch.Tensor:
+    """A workspace for softmax_sampled_loss / softmax_sampled_grad at this shape (ge_softmax_sampled_workspace_bytes)."""
+    need = _lib.load().ge_softmax_sampled_workspace_bytes(B, K, embeddings.shape[1])
+    return torch.empty(max(need, 256), dtype=torch.uint8, device=embeddings.device)
+
+
+def softmax_sampled_loss(embeddings: torch.Tensor, fixed_and_relation: torch.Tensor, true_ids: torch.Tensor,
+                         candidates: torch.Tensor, *, scale: float, max_norm: float = 1.0, side: str = "tail",
+                         workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Sampled softmax with shared negatives (ge_softmax_sampled_loss): softmax_loss over `candidates` that need not hold
+    the true entity and may repeat.  The true entity has a logit of its own and every slot that holds it is left out of
+    the row's softmax: loss_i = log(exp(z_i,true) + sum_{j: cand_j != true_i} exp(z_ij)) - z_i,true.  NaN for a row with an
+    id outside the table.  ComplEx only."""
+    emb, hr, tid, cand, head = _softmax_args(embeddings, fixed_and_relation, true_ids, candidates, scale, max_norm, side,
+                                             "softmax_sampled_loss")
+    B, K = hr.shape[0], cand.numel()
+    ws = workspace if workspace is not None else softmax_sampled_workspace(emb, B, K)
+    loss = torch.empty(B, dtype=torch.float32, device=emb.device)
+    _lib.call("ge_softmax_sampled_loss", emb.data_ptr(), emb.shape[0], emb.shape[1], hr.data_ptr(), B, tid.data_ptr(),
+              cand.data_ptr(), K, float(max_norm), float(scale), MODEL_COMPLEX, head, loss.data_ptr(), ws.data_ptr(),
+              ws.numel(), _stream())
+    return loss
+
+
+def softmax_sampled_grad(embeddings: torch.Tensor, fixed_and_relation: torch.Tensor, true_ids: torch.Tensor,
+                         candidates: torch.Tensor, lr: float, *, scale: float, max_norm: float = 1.0, side: str = "tail",
+                         workspace: Optional[torch.Tensor] = None, out=None):
+    """The gradients of softmax_sampled_loss (ge_softmax_sampled_grad): (loss [B], grad_idx [K + 3B] int32, grad_val
+    [K + 3B, d]) with grad_val = -lr * the gradient of SUM_i loss_i.  Slot j < K is candidates[j]; slots K + 3i, K + 3i + 1
+    and K + 3i + 2 the fixed entity, the relation and the true entity of row i; -1 and a zero row for an empty slot.
+    out: (grad_idx, grad_val) views to write into."""
+    emb, hr, tid, cand, head = _softmax_args(embeddings, fixed_and_relation, true_ids, candidates, scale, max_norm, side,
+                                             "softmax_sampled_grad")
+    B, K, d = hr.shape[0], cand.numel(), emb.shape[1]
+    R = K + 3 * B
+    ws = workspace if workspace is not None else softmax_sampled_workspace(emb, B, K)
+    loss = torch.empty(B, dtype=torch.float32, device=emb.device)
+    if out is None:
+        gi = torch.empty(R, dtype=torch.int32, device=emb.device)
+        gv = torch.empty(R, d, dtype=torch.float32, device=emb.device)
+    else:
+        gi, gv = out
+        if gi.dtype != torch.int32 or gv.dtype != torch.float32 or gi.numel() != R or tuple(gv.shape) != (R, d) \
+                or not gi.is_contiguous() or not gv.is_contiguous():
+            raise ValueError("softmax_sampled_grad: out must be (int32 [K + 3B], float32 [K + 3B, d]), contiguous")
+    _lib.call("ge_softmax_sampled_grad", emb.data_ptr(), emb.shape[0], d, hr.data_ptr(), B, tid.data_ptr(), cand.data_ptr(), K,
+              float(max_norm), float(scale), float(lr), MODEL_COMPLEX, head, loss.data_ptr(), gi.data_ptr(), gv.data_ptr(),
+              ws.data_ptr(), ws.numel(), _stream())
+    return loss, gi, gv
+
+
+class SampledSoftmaxAdaGrad:
+    """SoftmaxAdaGrad on the sampled objective: per step `n_samples` candidates, shared by all rows and both sides.  Two
+    ge_softmax_sampled_grad calls at lr = 1 (tails, then heads) against the same candidates and ONE snapshot of the table
+    into one slices buffer of 2 (n_samples + 3B) slots, one stable argsort, one ge_adagrad_rows.  Owns `.accumulator`;
+    workspace and slices are reserved once."""
+
+    def __init__(self, embeddings: torch.Tensor, batch_size: int, n_samples: int, *, scale: float, max_norm: float = 1.0,
+                 initial_accumulator_value: float = 0.1):
+        if not initial_accumulator_value > 0:
+            raise ValueError("initial_accumulator_value must be positive")
+        self.embeddings = _table(embeddings)
+        self.B, self.K, self.scale, self.max_norm = int(batch_size), int(n_samples), float(scale), float(max_norm)
+        if self.B < 1 or self.K < 1:
+            raise ValueError("SampledSoftmaxAdaGrad: at least one row a batch and one sample")
+        dev, d = self.embeddings.device, self.embeddings.shape[1]
+        self.accumulator = torch.full_like(self.embeddings, float(initial_accumulator_value))
+        R = self.K + 3 * self.B
+        self._ws = softmax_sampled_workspace(self.embeddings, self.B, self.K)
+        self._gi = torch.empty(2 * R, dtype=torch.int32, device=dev)
+        self._gv = torch.empty(2 * R, d, dtype=torch.float32, device=dev)
+
+    def step(self, triples: torch.Tensor, candidates: torch.Tensor, lr: float) -> torch.Tensor:
+        """One step in place on the table and the accumulator for triples [B,3] (head, tail, relation) against
+        candidates [n_samples]; returns the per-row losses [B,2] (tail side, head side)."""
+        emb = self.embeddings
+        tri = _triples(triples, "triples")
+        if tri.shape[0] != self.B:
+            raise ValueError("SampledSoftmaxAdaGrad.step: triples must be [batch_size, 3]")
+        _need_cuda(candidates, "candidates")
+        cand = candidates.to(torch.int32).contiguous().view(-1)
+        if cand.numel() != self.K:
+            raise ValueError("SampledSoftmaxAdaGrad.step: candidates must be [n_samples]")
+        R = self.K + 3 * self.B
+        losses = []
+        for s, (fixed, true, side) in enumerate(((0, 1, "tail"), (1, 0, "head"))):
+            hr = tri[:, [fixed, 2]].contiguous()
+            loss, _, _ = softmax_sampled_grad(emb, hr, tri[:, true].contiguous(), cand, 1.0, scale=self.scale,
+                                              max_norm=self.max_norm, side=side, workspace=self._ws,
+                                              out=(self._gi[s * R:(s + 1) * R], self._gv[s * R:(s + 1) * R]))
+            losses.append(loss)
+        # a row's occurrences consecutive and in slot order: the stable argsort, empty slots last (adagrad_rows)
+        key = torch.where(self._gi < 0, torch.full_like(self._gi, emb.shape[0]), self._gi)
+        perm = torch.argsort(key, stable=True).to(torch.int32)
+        _lib.call("ge_adagrad_rows", emb.data_ptr(), _accumulator(self.accumulator, emb).data_ptr(), emb.shape[0],
+                  emb.shape[1], self._gi.data_ptr(), self._gv.data_ptr(), perm.data_ptr(), 2 * R, float(lr), _stream())
+        return torch.stack(losses, 1)
+
+
 class SoftmaxTrainer:
     """The training loop of the 1-vs-all objective: per step a batch of `triples` [T,3] (head, tail, relation) drawn on
     the device -- without replacement within an epoch, every epoch a new permutation from a generator seeded with
     `seed` --, lr from inverse_time_decay as in Trainer, one SoftmaxAdaGrad.step.  A Python loop: a step is milliseconds
-    of GPU work, which the host's few launches per step stay ahead of."""
+    of GPU work, which the host's few launches per step stay ahead of.
+
+    n_samples: the sampled objective (SampledSoftmaxAdaGrad).  `candidates` is then the pool: every step draws
+    pool[randint(len(pool), n_samples)], with replacement, one draw for both sides, from a second generator seeded with
+    seed + 1 -- so the batches are the ones drawn without sampling."""
 
     def __init__(self, embeddings: torch.Tensor, triples: torch.Tensor, candidates: torch.Tensor, batch_size: int, *,
                  scale: float, learning_rate: float = 0.1, learning_decay_steps: float = 0.0,
                  learning_decay_rate: float = 0.5, seed: int = 0, max_norm: float = 1.0,
-                 initial_accumulator_value: float = 0.1):
-        self.opt = SoftmaxAdaGrad(embeddings, candidates, batch_size, scale=scale, max_norm=max_norm,
-                                  initial_accumulator_value=initial_accumulator_value)
+                 initial_accumulator_value: float = 0.1, n_samples: Optional[int] = None):
+        self.n_samples = None if n_samples is None else int(n_samples)
+        if self.n_samples is None:
+            self.opt = SoftmaxAdaGrad(embeddings, candidates, batch_size, scale=scale, max_norm=max_norm,
+                                      initial_accumulator_value=initial_accumulator_value)
+        else:
+            _need_cuda(candidates, "candidates")
+            self.pool = candidates.to(torch.int32).contiguous().view(-1)
+            if self.pool.numel() < 1:
+                raise ValueError("SoftmaxTrainer: an empty candidate pool")
+            self.opt = SampledSoftmaxAdaGrad(embeddings, batch_size, self.n_samples, scale=scale, max_norm=max_norm,
+                                             initial_accumulator_value=initial_accumulator_value)
+            self._cand_gen = torch.Generator(device=self.opt.embeddings.device)
+            self._cand_gen.manual_seed(int(seed) + 1)
         self.embeddings = self.opt.embeddings
         self.triples = _triples(triples, "triples")
         self.B = int(batch_size)
@@ -508,11 +622,21 @@ class SoftmaxTrainer:
         self._row += self.B
         return self.triples[rows].contiguous()
 
+    def next_candidates(self) -> torch.Tensor:
+        """The next step's [n_samples] candidates: a uniform draw from the pool, with replacement."""
+        if self.n_samples is None:
+            raise ValueError("SoftmaxTrainer.next_candidates: built without n_samples, every candidate is used")
+        at = torch.randint(self.pool.numel(), (self.n_samples,), device=self.pool.device, generator=self._cand_gen)
+        return self.pool[at]
+
     def run(self, n_steps: int, keep_losses: bool = False) -> torch.Tensor:
         """n_steps steps on the current stream; the losses [n_steps, B, 2] if keep_losses, else the last step's [B,2]."""
         kept, loss = [], None
         for _ in range(n_steps):
-            loss = self.opt.step(self.next_batch(), self.learning_rate())
+            if self.n_samples is None:
+                loss = self.opt.step(self.next_batch(), self.learning_rate())
+            else:
+                loss = self.opt.step(self.next_batch(), self.next_candidates(), self.learning_rate())
             self.global_step += 1
             if keep_losses:
                 kept.append(loss)

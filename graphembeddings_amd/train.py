@@ -15,7 +15,8 @@ ge_train_steps_logloss (--log_loss) -- no Python per step.
 Extras: --model hole (README.md:42 score), --seed, --max_steps, --checkpoint_seconds, --optimizer adagrad
 (AdagradOptimizer in place of holE.py:296's GradientDescentOptimizer: ge_train_steps_adagrad; the checkpoint then also
 holds `adagrad_accumulator`), --objective softmax (1-vs-all multiclass log-loss over all entities, both sides:
-hole.SoftmaxTrainer on ge_softmax_grad; ComplEx with AdaGrad on one GPU, no validation ticks).
+hole.SoftmaxTrainer on ge_softmax_grad; ComplEx with AdaGrad on one GPU, no validation ticks; --softmax_samples K': sampled
+softmax, K' shared candidates a step on ge_softmax_sampled_grad).
 """
 from __future__ import annotations
 
@@ -95,6 +96,10 @@ def build_parser() -> argparse.ArgumentParser:
                         'true entity over ALL entities, both sides ("1vsAll"; ComplEx, --optimizer adagrad, one GPU).')
     p.add_argument('--softmax_scale', type=float, default=20.0,
                    help='With --objective softmax: the logit scale (rows are clipped to norm 1, so |score| <= 1).')
+    p.add_argument('--softmax_samples', type=int, default=0,
+                   help='With --objective softmax: candidates drawn per step from the entity rows (uniform, with '
+                        'replacement, shared by the batch and both sides; the true entity has a logit of its own).  '
+                        '0: all entity rows, the 1-vs-all objective.')
     p.add_argument('--gpus', type=int, default=1,
                    help='Ranks (one per GPU) the table is row-sharded over; > 1 without a launcher: this program starts them '
                         '(graphembeddings_amd/launch.py).  --batch_size stays the GLOBAL batch.')
@@ -138,8 +143,13 @@ def check_optimizer_flags(FLAGS, world: int = 1) -> None:
 
 
 def check_objective_flags(FLAGS, world: int = 1) -> None:
-    """--objective softmax: ComplEx with AdaGrad on one GPU, no --log_loss."""
+    """--objective softmax: ComplEx with AdaGrad on one GPU, no --log_loss; --softmax_samples belongs to it."""
+    samples = getattr(FLAGS, 'softmax_samples', 0)
+    if samples < 0:
+        raise SystemExit('--softmax_samples must not be negative (0: all entity rows)')
     if getattr(FLAGS, 'objective', 'hinge') != 'softmax':
+        if samples > 0:
+            raise SystemExit('--softmax_samples needs --objective softmax')
         return
     if getattr(FLAGS, 'optimizer', 'sgd') != 'adagrad':
         raise SystemExit('--objective softmax needs --optimizer adagrad')
@@ -177,7 +187,10 @@ def run_softmax_training(data: D.HolEData, FLAGS, log=print) -> dict:
                                learning_rate=FLAGS.learning_rate,
                                learning_decay_steps=FLAGS.learning_decay_steps * batch_count,
                                learning_decay_rate=FLAGS.learning_decay_rate, seed=FLAGS.seed,
-                               initial_accumulator_value=FLAGS.adagrad_init)
+                               initial_accumulator_value=FLAGS.adagrad_init, n_samples=FLAGS.softmax_samples or None)
+    if FLAGS.softmax_samples:
+        log('Sampled softmax: {} candidates a step, drawn from the {} entity rows'.format(FLAGS.softmax_samples,
+                                                                                      candidates.numel()))
     if accumulator is not None and accumulator.shape == trainer.accumulator.shape:
         trainer.accumulator.copy_(accumulator)
     elif FLAGS.resume_checkpoint:

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define GE_VERSION 441 /* 0.4.4.1: + ge_train_max_chunk_steps; longer prepare chunks (larger workspace) for steps of <= 4096 units */
+#define GE_VERSION 442 /* 0.4.4.2: + ge_softmax_sampled_loss / _grad / _workspace_bytes (sampled softmax with shared negatives) */
 
 /* argument errors (negative, -errno style) */
 #define GE_EINVAL (-22)  /* bad dimension / null pointer / misaligned buffer */
@@ -209,6 +209,30 @@ int ge_softmax_loss(const float* table, int64_t N, int32_t d, const int32_t* hr,
 int ge_softmax_grad(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* true_id,
                     const int32_t* cand, int64_t K, float max_norm, float scale, float lr, int model, int cand_is_head,
                     float* loss, int32_t* grad_idx, float* grad_val, void* workspace, size_t workspace_bytes, void* stream);
+
+/* --- sampled softmax with shared negatives: the objective above over K candidates that need NOT hold the true entity,
+ * so that a step's work follows K and not the table.  Arguments, clips, s, z, cand_is_head and model as for
+ * ge_softmax_loss / ge_softmax_grad.  cand [K] may hold any ids: duplicates are allowed and each slot is a term of its
+ * own; an id outside [0,N) is an empty slot.  A row is valid iff its fixed, relation and true ids all lie in [0,N).  The
+ * true entity counts once, through a logit of its own, z_i,true = -scale * (Q'_i . clip(true_i)), and every slot with
+ * cand[j] == true_id[i] is left out of row i's softmax (accidental-hit removal):
+ *   loss_i = log(exp(z_i,true) + SUM_{j: cand_j in [0,N), cand_j != true_i} exp(z_ij)) - z_i,true   (>= 0; NaN if invalid)
+ * A row whose slots are all empty or left out has loss exactly 0 and exact zero gradient rows.
+ * ge_softmax_sampled_grad emits IndexedSlices of R = K + 3B slots, grad_idx [R] int32 and grad_val [R,d] fp32 = -lr * the
+ * gradient of SUM_i loss_i through all four clips, against the table as it is:
+ *   slot j < K: cand[j] (-1 and a zero row for an empty slot); slot K + 3i: fixed_i; K + 3i + 1: rel_i; K + 3i + 2:
+ *   true_i (all three -1 with zero rows for an invalid row).  At lr = 1 the slices are what ge_adagrad_rows takes.
+ * No float atomics: two identical calls give identical bits.  Refusals as for ge_softmax_loss / ge_softmax_grad, in the
+ * same order, against ge_softmax_sampled_workspace_bytes(B, K, d) (monotone in each argument, a multiple of 256, 0 for
+ * sizes the calls refuse).  Nothing is allocated and the host never waits. */
+size_t ge_softmax_sampled_workspace_bytes(int64_t B, int64_t K, int32_t d);
+int ge_softmax_sampled_loss(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* true_id,
+                            const int32_t* cand, int64_t K, float max_norm, float scale, int model, int cand_is_head,
+                            float* loss, void* workspace, size_t workspace_bytes, void* stream);
+int ge_softmax_sampled_grad(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* true_id,
+                            const int32_t* cand, int64_t K, float max_norm, float scale, float lr, int model,
+                            int cand_is_head, float* loss, int32_t* grad_idx, float* grad_val, void* workspace,
+                            size_t workspace_bytes, void* stream);
 
 /* --- corrupt_batch (holE.py:152-153 -> 136-140 -> 97-133) fused with the per-batch host
  * resample of holE.py:343-347.  id_to_type [N] int32 type code per table row (-1 = unknown, the
