@@ -211,17 +211,25 @@ size_t ge_softmax_workspace_bytes(int64_t B, int64_t K, int32_t d) {
   return softmax_ws_bytes(B, K, d);
 }
 
-// the one check of the four softmax entry points; grad: the gradient outputs are asked for; sampled: ge_softmax_sampled_*
+// the one check of the six softmax entry points; grad: the gradient outputs are asked for; sampled: ge_softmax_sampled_*;
+// sets: ge_softmax_masked_* (its pointers and n_sets join the GE_EINVAL groups, its size function is the one checked)
 static int softmax_call(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* true_id,
                         const int32_t* cand, int64_t K, float max_norm, float scale, float lr, int model, int cand_is_head,
                         float* loss, bool grad, int32_t* grad_idx, float* grad_val, void* workspace, size_t workspace_bytes,
-                        void* stream, bool sampled = false) {
+                        void* stream, bool sampled = false, const SetArgs* sets = nullptr) {
   if (B < 1 || K < 1 || !ok_table(table, N, d) || !max_norm_ok(max_norm) || !(scale > 0.f) || !std::isfinite(scale))
     return GE_EINVAL;
   if (!hr || !true_id || !cand || !loss || !workspace || (grad && (!grad_idx || !grad_val))) return GE_EINVAL;
+  if (sets && (!sets->row_set || !sets->mask || sets->n_sets < 1)) return GE_EINVAL;
   if (model != GE_MODEL_COMPLEX || !softmax_dim_ok(d)) return GE_ENOTSUP;
   if (reinterpret_cast<uintptr_t>(table) % 16 != 0 || reinterpret_cast<uintptr_t>(workspace) % 256 != 0) return GE_EINVAL;
   if (grad && reinterpret_cast<uintptr_t>(grad_val) % 4 != 0) return GE_EINVAL;
+  if (sets && reinterpret_cast<uintptr_t>(sets->mask) % 4 != 0) return GE_EINVAL;
+  if (sets) {
+    if (workspace_bytes < softmax_masked_ws_bytes(B, K, d)) return GE_ENOMEM;
+    return softmax_masked_launch(table, N, d, hr, B, true_id, cand, K, max_norm, scale, lr, cand_is_head, loss,
+                                 grad ? grad_idx : nullptr, grad_val, workspace, *sets, (hipStream_t)stream);
+  }
   if (workspace_bytes < (sampled ? softmax_sampled_ws_bytes(B, K, d) : softmax_ws_bytes(B, K, d))) return GE_ENOMEM;
   if (sampled)
     return softmax_sampled_launch(table, N, d, hr, B, true_id, cand, K, max_norm, scale, lr, cand_is_head, loss,
@@ -262,6 +270,30 @@ int ge_softmax_sampled_grad(const float* table, int64_t N, int32_t d, const int3
                             size_t workspace_bytes, void* stream) {
   return softmax_call(table, N, d, hr, B, true_id, cand, K, max_norm, scale, lr, model, cand_is_head, loss, true, grad_idx,
                       grad_val, workspace, workspace_bytes, stream, true);
+}
+
+size_t ge_softmax_masked_workspace_bytes(int64_t B, int64_t K, int32_t d) {
+  if (B < 1 || K < 1 || !softmax_dim_ok(d)) return 0;
+  return softmax_masked_ws_bytes(B, K, d);
+}
+
+int ge_softmax_masked_loss(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* true_id,
+                           const int32_t* cand, int64_t K, float max_norm, float scale, int model, int cand_is_head,
+                           float* loss, void* workspace, size_t workspace_bytes, const int32_t* row_set,
+                           const uint32_t* mask, int32_t n_sets, void* stream) {
+  const SetArgs sets{row_set, mask, n_sets, 0};
+  return softmax_call(table, N, d, hr, B, true_id, cand, K, max_norm, scale, 0.f, model, cand_is_head, loss, false, nullptr,
+                      nullptr, workspace, workspace_bytes, stream, false, &sets);
+}
+
+int ge_softmax_masked_grad(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* true_id,
+                           const int32_t* cand, int64_t K, float max_norm, float scale, float lr, int model,
+                           int cand_is_head, float* loss, int32_t* grad_idx, float* grad_val, void* workspace,
+                           size_t workspace_bytes, const int32_t* row_set, const uint32_t* mask, int32_t n_sets,
+                           void* stream) {
+  const SetArgs sets{row_set, mask, n_sets, 0};
+  return softmax_call(table, N, d, hr, B, true_id, cand, K, max_norm, scale, lr, model, cand_is_head, loss, true, grad_idx,
+                      grad_val, workspace, workspace_bytes, stream, false, &sets);
 }
 
 int ge_gather_rows(const float* table, int64_t N, int32_t d, const int32_t* idx, int64_t R, float* out,

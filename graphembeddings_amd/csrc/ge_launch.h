@@ -211,6 +211,25 @@ size_t softmax_ws_bytes(int64_t B, int64_t K, int32_t d);
 int softmax_launch(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* true_id,
                    const int32_t* cand, int64_t K, float max_norm, float scale, float lr, int cand_is_head, float* loss,
                    int32_t* grad_idx, float* grad_val, void* workspace, hipStream_t st);
+// its prepare (row_set non-null: a row whose set id is neither -1 nor in [0, n_sets) gets key -1 too), merge and finish
+// stages on a carved workspace, for the masked form
+int softmax_prepare_launch(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* true_id,
+                           const int32_t* cand, int64_t K, float max_norm, int cand_is_head, const int32_t* row_set,
+                           int32_t n_sets, const SoftmaxWs& w, hipStream_t st);
+int softmax_merge_launch(const SoftmaxWs& w, int n_ranges, int64_t B, float* loss, hipStream_t st);
+int softmax_finish_launch(const float* table, int32_t d, const int32_t* hr, int64_t B, int64_t K, float max_norm, float lr,
+                          int cand_is_head, const SoftmaxWs& w, int n_ranges, int32_t* grad_idx, float* grad_val,
+                          hipStream_t st);
+
+// ge_softmax_masked.hip: ge_softmax.hip's objective with per-row candidate sets (SetArgs; mw is not read).  The workspace:
+// SoftmaxWs' parts | the live-tile bitmap [query tiles][sm_live_words(K)] uint32, padded to 256 B.
+struct SoftmaxMaskedWs { SoftmaxWs base; uint32_t* live; size_t bytes; };
+SoftmaxMaskedWs softmax_masked_ws(void* base, int64_t B, int64_t K, int32_t d);
+size_t softmax_masked_ws_bytes(int64_t B, int64_t K, int32_t d);
+int softmax_masked_launch(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* true_id,
+                          const int32_t* cand, int64_t K, float max_norm, float scale, float lr, int cand_is_head,
+                          float* loss, int32_t* grad_idx, float* grad_val, void* workspace, const SetArgs& sets,
+                          hipStream_t st);
 
 // ge_softmax_sampled.hip: the same objective over candidates that need not hold the true entity (its logit is the row's
 // own; slots that hold it are left out), gradients in K + 3B slots.  The workspace: Q' [B,d] | C' [K,d] | T' [B,d] (the

@@ -22,6 +22,7 @@
 //
 // The scalar x . g the clip's beta needs is a dot product in the finish kernel, not a second sum in the sweep.
 // The sweep template, its constants and the helpers the sampled form (ge_softmax_sampled.hip) shares are in ge_softmax_kern.h.
+// The masked form (ge_softmax_masked.hip) runs this file's prepare, merge and finish kernels through their launchers.
 #include "ge_softmax_kern.h"
 
 namespace ge {
@@ -42,10 +43,13 @@ SoftmaxWs softmax_ws(void* base, int64_t B, int64_t K, int32_t d) {
 }
 
 // ------------------------------------------------------------------ prepare
+// SETS (the masked form, ge_softmax_masked.hip): a row whose set id is neither -1 nor in [0, n_sets) is invalid too.
+template <bool SETS>
 __global__ __launch_bounds__(kBlock) void softmax_prepare_kernel(
     const float* __restrict__ table, int64_t N, int d, const int32_t* __restrict__ hr, int64_t B,
     const int32_t* __restrict__ true_id, const int32_t* __restrict__ cand, int64_t K, float max_norm, int cand_is_head,
-    float* __restrict__ qp, float* __restrict__ cp, int32_t* __restrict__ qkey, int32_t* __restrict__ ckey) {
+    float* __restrict__ qp, float* __restrict__ cp, int32_t* __restrict__ qkey, int32_t* __restrict__ ckey,
+    const int32_t* __restrict__ row_set, int32_t n_sets) {
   const int lane = threadIdx.x & (kWave - 1);
   const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
@@ -53,7 +57,8 @@ __global__ __launch_bounds__(kBlock) void softmax_prepare_kernel(
   for (int64_t u = wave; u < B + K; u += nwaves) {      // (wave-uniform)
     if (u < B) {
       const int32_t f = hr[2 * u], r = hr[2 * u + 1], tr = true_id[u];
-      const bool ok = f >= 0 && f < N && r >= 0 && r < N && tr >= 0 && tr < N;
+      bool ok = f >= 0 && f < N && r >= 0 && r < N && tr >= 0 && tr < N;
+      if constexpr (SETS) { const int32_t sid = row_set[u]; ok = ok && sid >= -1 && sid < n_sets; }
       float* dst = qp + u * d;
       if (!ok) {
         for (int c = lane; c < d; c += kWave) dst[c] = 0.f;
@@ -207,27 +212,48 @@ __global__ __launch_bounds__(kBlock) void softmax_finish_kernel(
 // ------------------------------------------------------------------ host
 size_t softmax_ws_bytes(int64_t B, int64_t K, int32_t d) { return softmax_ws(nullptr, B, K, d).bytes; }
 
+int softmax_prepare_launch(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* true_id,
+                           const int32_t* cand, int64_t K, float max_norm, int cand_is_head, const int32_t* row_set,
+                           int32_t n_sets, const SoftmaxWs& w, hipStream_t st) {
+  const dim3 grid(grid_for(B + K, kBlock / kWave));
+  if (row_set)
+    hipLaunchKernelGGL(softmax_prepare_kernel<true>, grid, dim3(kBlock), 0, st, table, N, d, hr, B, true_id, cand, K, max_norm,
+                       cand_is_head, w.qp, w.cp, w.qkey, w.ckey, row_set, n_sets);
+  else
+    hipLaunchKernelGGL(softmax_prepare_kernel<false>, grid, dim3(kBlock), 0, st, table, N, d, hr, B, true_id, cand, K, max_norm,
+                       cand_is_head, w.qp, w.cp, w.qkey, w.ckey, row_set, n_sets);
+  return launch_status();
+}
+
+int softmax_merge_launch(const SoftmaxWs& w, int n_ranges, int64_t B, float* loss, hipStream_t st) {
+  hipLaunchKernelGGL(softmax_merge_kernel, dim3((unsigned)((B + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, w.part, n_ranges,
+                     B, w.qkey, w.lse, loss);
+  return launch_status();
+}
+
+int softmax_finish_launch(const float* table, int32_t d, const int32_t* hr, int64_t B, int64_t K, float max_norm, float lr,
+                          int cand_is_head, const SoftmaxWs& w, int n_ranges, int32_t* grad_idx, float* grad_val,
+                          hipStream_t st) {
+  hipLaunchKernelGGL(softmax_finish_kernel, dim3(grid_for(B + K, kBlock / kWave)), dim3(kBlock), 0, st, table, d, hr, B, K,
+                     max_norm, lr, cand_is_head, w.qkey, w.ckey, w.gq, n_ranges, grad_idx, grad_val);
+  return launch_status();
+}
+
 int softmax_launch(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* true_id,
                    const int32_t* cand, int64_t K, float max_norm, float scale, float lr, int cand_is_head, float* loss,
                    int32_t* grad_idx, float* grad_val, void* workspace, hipStream_t st) {
   assert(d % 8 == 0 && d >= 8 && d <= kRankMaxDim);
   const SoftmaxWs w = softmax_ws(workspace, B, K, d);
-  hipLaunchKernelGGL(softmax_prepare_kernel, dim3(grid_for(B + K, kBlock / kWave)), dim3(kBlock), 0, st, table, N, d, hr, B,
-                     true_id, cand, K, max_norm, cand_is_head, w.qp, w.cp, w.qkey, w.ckey);
-  if (int rc = launch_status()) return rc;
+  if (int rc = softmax_prepare_launch(table, N, d, hr, B, true_id, cand, K, max_norm, cand_is_head, nullptr, 0, w, st)) return rc;
   const int ns = sm_split(B, K);
   if (int rc = sm_sweep<0, true, false>(w.qp, w.qkey, B, w.cp, w.ckey, K, d, scale, nullptr, ns, reinterpret_cast<float*>(w.part), st))
     return rc;
-  hipLaunchKernelGGL(softmax_merge_kernel, dim3((unsigned)((B + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, w.part, ns, B,
-                     w.qkey, w.lse, loss);
-  if (int rc = launch_status()) return rc;
+  if (int rc = softmax_merge_launch(w, ns, B, loss, st)) return rc;
   if (!grad_idx) return 0;
   // dL/dC' over all queries, straight into the candidates' slots; dL/dQ' per candidate range
   if (int rc = sm_sweep<1, false, false>(w.cp, w.ckey, K, w.qp, w.qkey, B, d, scale, w.lse, 1, grad_val, st)) return rc;
   if (int rc = sm_sweep<1, true, false>(w.qp, w.qkey, B, w.cp, w.ckey, K, d, scale, w.lse, ns, w.gq, st)) return rc;
-  hipLaunchKernelGGL(softmax_finish_kernel, dim3(grid_for(B + K, kBlock / kWave)), dim3(kBlock), 0, st, table, d, hr, B, K,
-                     max_norm, lr, cand_is_head, w.qkey, w.ckey, w.gq, ns, grad_idx, grad_val);
-  return launch_status();
+  return softmax_finish_launch(table, d, hr, B, K, max_norm, lr, cand_is_head, w, ns, grad_idx, grad_val, st);
 }
 
 }  // namespace ge

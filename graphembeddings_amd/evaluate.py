@@ -386,6 +386,27 @@ def link_prediction_ranks(embeddings: torch.Tensor, test_triples: np.ndarray, ca
     return out
 
 
+def constrained_sets(data, kind: str, candidates=None, device="cuda"):
+    """(known, {side: CandidateSets}) of the type-constrained protocol: the sets of both sides over `candidates` (default
+    the entity rows in id order) -- kind "types": every entity whose type was seen on that side of the relation;
+    "observed": the entities seen there -- built from train + valid (`known`, the evaluation's filter too).  What
+    evaluate_constrained ranks against and what train.py --softmax_candidate_sets trains against."""
+    if kind not in ("types", "observed"):
+        raise ValueError("kind must be 'types' or 'observed'")
+    R, N = data.relation_count, data.entity_count
+    cand = np.arange(R, N, dtype=np.int32) if candidates is None else np.asarray(candidates, dtype=np.int32)
+    parts = [a for a in (data.triples, data.validation_triples) if a is not None]
+    if not parts:
+        raise ValueError("candidate sets are built from the train / valid triples: none found")
+    known = np.concatenate(parts, 0)
+    id_to_type = data.type_arrays()[1] if kind == "types" else None
+    sets = {}
+    for side in ("tail", "head"):
+        sets[side] = (CandidateSets.from_types(cand, id_to_type, known, R, side, device=device) if kind == "types"
+                      else CandidateSets.from_observed(cand, known, R, side, device=device))
+    return known, sets
+
+
 def evaluate_constrained(embeddings: torch.Tensor, data, kind: str, model: str = "complex", verbose: bool = True):
     """Type-constrained link prediction over data.test_array, both sides: each row is ranked against its relation's
     candidate set -- kind "types": every entity whose type was seen on that side of the relation; "observed": the
@@ -396,20 +417,15 @@ def evaluate_constrained(embeddings: torch.Tensor, data, kind: str, model: str =
         raise ValueError("kind must be 'types' or 'observed'")
     R, N = data.relation_count, data.entity_count
     cand = np.arange(R, N, dtype=np.int32)
-    parts = [a for a in (data.triples, data.validation_triples) if a is not None]
-    if not parts:
-        raise ValueError("candidate sets are built from the train / valid triples: none found")
-    known = np.concatenate(parts, 0)
+    known, sets = constrained_sets(data, kind, device=embeddings.device)
     if model == "hole":
         embeddings, model = H.hole_to_spectral(embeddings.detach().clone()), "hole_spectral"
     dev = embeddings.device
     planes = H.RankPlanes(embeddings, torch.as_tensor(cand).to(dev), model=model) if H.rank_fused_ok(embeddings.shape[1], 1.0) else None
-    id_to_type = data.type_arrays()[1] if kind == "types" else None
-    sets, raw, fil, adm, size = {}, [], [], [], []
+    raw, fil, adm, size = [], [], [], []
     test = np.asarray(data.test_array, dtype=np.int64)
     for side in ("tail", "head"):
-        sets[side] = cs = (CandidateSets.from_types(cand, id_to_type, known, R, side, device=dev) if kind == "types"
-                           else CandidateSets.from_observed(cand, known, R, side, device=dev))
+        cs = sets[side]
         r, f, a = link_prediction_ranks(embeddings, test, cand, known, side, model=model, planes=planes, candidate_sets=cs,
                                         return_admissible=True)
         raw.append(r); fil.append(f); adm.append(a); size.append(cs.counts[test[:, 2]])

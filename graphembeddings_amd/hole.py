@@ -10,6 +10,7 @@ plausible; the hinge max(E(pos) - E(neg) + margin, 0) pushes positive scores dow
 """
 from __future__ import annotations
 
+import types
 from dataclasses import dataclass
 from typing import Optional
 
@@ -373,18 +374,34 @@ def softmax_workspace(embeddings: torch.Tensor, B: int, K: int) -> torch.Tensor:
     return torch.empty(max(need, 256), dtype=torch.uint8, device=embeddings.device)
 
 
+def softmax_masked_workspace(embeddings: torch.Tensor, B: int, K: int) -> torch.Tensor:
+    """A workspace for softmax_loss / softmax_grad with candidate_sets at this shape (ge_softmax_masked_workspace_bytes)."""
+    need = _lib.load().ge_softmax_masked_workspace_bytes(B, K, embeddings.shape[1])
+    return torch.empty(max(need, 256), dtype=torch.uint8, device=embeddings.device)
+
+
 def softmax_loss(embeddings: torch.Tensor, fixed_and_relation: torch.Tensor, true_ids: torch.Tensor,
                  candidates: torch.Tensor, *, scale: float, max_norm: float = 1.0, side: str = "tail",
-                 workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 workspace: Optional[torch.Tensor] = None, candidate_sets=None, row_sets=None) -> torch.Tensor:
     """The 1-vs-all objective (ge_softmax_loss): loss_i = logsumexp_j(-scale * s_ij) - (-scale * s_i,true) over all
     `candidates` (distinct ids), s the ComplEx score of score_candidates without the sigmoid.  side="tail": row i is
     (head_i, relation_i) and the candidates are tails; "head": (tail_i, relation_i), candidates are heads.  NaN for a row
-    with an id outside the table or whose true id is not a candidate.  ComplEx only."""
+    with an id outside the table or whose true id is not a candidate.  ComplEx only.
+    candidate_sets (an evaluate.CandidateSets built for these very `candidates` and this side) / row_sets ([B], default
+    the row's relation id; -1: unrestricted): ge_softmax_masked_loss -- row i's softmax runs over the candidates its set
+    admits, and a row whose true candidate is inadmissible is NaN too.  The workspace is then softmax_masked_workspace's."""
     emb, hr, tid, cand, head = _softmax_args(embeddings, fixed_and_relation, true_ids, candidates, scale, max_norm, side,
                                              "softmax_loss")
     B, K = hr.shape[0], cand.numel()
-    ws = workspace if workspace is not None else softmax_workspace(emb, B, K)
+    sets, _rs = _sets_args(candidate_sets, row_sets, hr, cand, "softmax_loss")
     loss = torch.empty(B, dtype=torch.float32, device=emb.device)
+    if sets:
+        ws = workspace if workspace is not None else softmax_masked_workspace(emb, B, K)
+        _lib.call("ge_softmax_masked_loss", emb.data_ptr(), emb.shape[0], emb.shape[1], hr.data_ptr(), B, tid.data_ptr(),
+                  cand.data_ptr(), K, float(max_norm), float(scale), MODEL_COMPLEX, head, loss.data_ptr(), ws.data_ptr(),
+                  ws.numel(), *sets, _stream())
+        return loss
+    ws = workspace if workspace is not None else softmax_workspace(emb, B, K)
     _lib.call("ge_softmax_loss", emb.data_ptr(), emb.shape[0], emb.shape[1], hr.data_ptr(), B, tid.data_ptr(), cand.data_ptr(),
               K, float(max_norm), float(scale), MODEL_COMPLEX, head, loss.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
     return loss
@@ -392,16 +409,22 @@ def softmax_loss(embeddings: torch.Tensor, fixed_and_relation: torch.Tensor, tru
 
 def softmax_grad(embeddings: torch.Tensor, fixed_and_relation: torch.Tensor, true_ids: torch.Tensor,
                  candidates: torch.Tensor, lr: float, *, scale: float, max_norm: float = 1.0, side: str = "tail",
-                 workspace: Optional[torch.Tensor] = None, out=None):
+                 workspace: Optional[torch.Tensor] = None, out=None, candidate_sets=None, row_sets=None):
     """The counterpart of hinge_grad for the 1-vs-all objective (ge_softmax_grad): (loss [B], grad_idx [K + 2B] int32,
     grad_val [K + 2B, d]) with grad_val = -lr * the gradient of SUM_i loss_i.  Slot j < K is candidates[j], slots K + 2i
     and K + 2i + 1 the fixed entity and the relation of row i; -1 and a zero row for an empty slot.  out: (grad_idx,
-    grad_val) views to write into."""
+    grad_val) views to write into.
+    candidate_sets / row_sets (as softmax_loss takes them): ge_softmax_masked_grad, same slots; a candidate that no valid
+    row admits keeps its id and gets an exact zero row."""
     emb, hr, tid, cand, head = _softmax_args(embeddings, fixed_and_relation, true_ids, candidates, scale, max_norm, side,
                                              "softmax_grad")
     B, K, d = hr.shape[0], cand.numel(), emb.shape[1]
     R = K + 2 * B
-    ws = workspace if workspace is not None else softmax_workspace(emb, B, K)
+    sets, _rs = _sets_args(candidate_sets, row_sets, hr, cand, "softmax_grad")
+    if workspace is not None:
+        ws = workspace
+    else:
+        ws = softmax_masked_workspace(emb, B, K) if sets else softmax_workspace(emb, B, K)
     loss = torch.empty(B, dtype=torch.float32, device=emb.device)
     if out is None:
         gi = torch.empty(R, dtype=torch.int32, device=emb.device)
@@ -411,6 +434,11 @@ def softmax_grad(embeddings: torch.Tensor, fixed_and_relation: torch.Tensor, tru
         if gi.dtype != torch.int32 or gv.dtype != torch.float32 or gi.numel() != R or tuple(gv.shape) != (R, d) \
                 or not gi.is_contiguous() or not gv.is_contiguous():
             raise ValueError("softmax_grad: out must be (int32 [K + 2B], float32 [K + 2B, d]), contiguous")
+    if sets:
+        _lib.call("ge_softmax_masked_grad", emb.data_ptr(), emb.shape[0], d, hr.data_ptr(), B, tid.data_ptr(), cand.data_ptr(),
+                  K, float(max_norm), float(scale), float(lr), MODEL_COMPLEX, head, loss.data_ptr(), gi.data_ptr(),
+                  gv.data_ptr(), ws.data_ptr(), ws.numel(), *sets, _stream())
+        return loss, gi, gv
     _lib.call("ge_softmax_grad", emb.data_ptr(), emb.shape[0], d, hr.data_ptr(), B, tid.data_ptr(), cand.data_ptr(), K,
               float(max_norm), float(scale), float(lr), MODEL_COMPLEX, head, loss.data_ptr(), gi.data_ptr(), gv.data_ptr(),
               ws.data_ptr(), ws.numel(), _stream())
@@ -421,10 +449,15 @@ class SoftmaxAdaGrad:
     """AdagradOptimizer(lr, initial_accumulator_value) on the 1-vs-all objective, both sides of every triple against ONE
     snapshot of the table: two ge_softmax_grad calls at lr = 1 (tails, then heads) into one slices buffer of
     2 (K + 2B) slots, one stable argsort, one ge_adagrad_rows -- an entity that is a candidate, a tail and a head in the
-    same step gets one update from its summed gradient.  Owns `.accumulator`; workspace and slices are reserved once."""
+    same step gets one update from its summed gradient.  Owns `.accumulator`; workspace and slices are reserved once.
+
+    candidate_sets={"tail": sets, "head": sets} (evaluate.CandidateSets built for `candidates`, one per side): the
+    type-constrained objective (ge_softmax_masked_grad).  The step then orders the batch rows by set id (a stable sort) before
+    the two gradient calls, so that the rows of a 64-row tile share sets and the tile pairs nobody admits are skipped;
+    the losses come back in the caller's order."""
 
     def __init__(self, embeddings: torch.Tensor, candidates: torch.Tensor, batch_size: int, *, scale: float,
-                 max_norm: float = 1.0, initial_accumulator_value: float = 0.1):
+                 max_norm: float = 1.0, initial_accumulator_value: float = 0.1, candidate_sets=None):
         if not initial_accumulator_value > 0:
             raise ValueError("initial_accumulator_value must be positive")
         self.embeddings = _table(embeddings)
@@ -436,24 +469,50 @@ class SoftmaxAdaGrad:
         dev, d = self.embeddings.device, self.embeddings.shape[1]
         self.accumulator = torch.full_like(self.embeddings, float(initial_accumulator_value))
         R = self.candidates.numel() + 2 * self.B
-        self._ws = softmax_workspace(self.embeddings, self.B, self.candidates.numel())
+        self.candidate_sets, self._sets = candidate_sets, {}
+        if candidate_sets is not None:
+            if not isinstance(candidate_sets, dict) or any(s not in candidate_sets for s in ("tail", "head")):
+                raise ValueError("SoftmaxAdaGrad: candidate_sets must be a dict with a CandidateSets per side ('tail', 'head')")
+            # checked against the candidates once, here: the step's calls then see the optimizer's own tensor
+            for side in ("tail", "head"):
+                cs = candidate_sets[side]
+                _sets_args(cs, None, torch.zeros(1, 2, dtype=torch.int32, device=dev), self.candidates, "SoftmaxAdaGrad")
+                self._sets[side] = types.SimpleNamespace(mask=cs.mask, n_sets=int(cs.n_sets), cand=self.candidates)
+            self._ws = softmax_masked_workspace(self.embeddings, self.B, self.candidates.numel())
+        else:
+            self._ws = softmax_workspace(self.embeddings, self.B, self.candidates.numel())
         self._gi = torch.empty(2 * R, dtype=torch.int32, device=dev)
         self._gv = torch.empty(2 * R, d, dtype=torch.float32, device=dev)
 
-    def step(self, triples: torch.Tensor, lr: float) -> torch.Tensor:
+    def step(self, triples: torch.Tensor, lr: float, row_sets=None) -> torch.Tensor:
         """One step in place on the table and the accumulator for triples [B,3] (head, tail, relation); returns the
-        per-row losses [B,2] (tail side, head side)."""
+        per-row losses [B,2] (tail side, head side).  row_sets ([B], with candidate_sets only; default the rows' relation
+        ids): the set of each row, the same on both sides."""
         emb = self.embeddings
         tri = _triples(triples, "triples")
         if tri.shape[0] != self.B:
             raise ValueError("SoftmaxAdaGrad.step: triples must be [batch_size, 3]")
         R = self.candidates.numel() + 2 * self.B
+        order, rs = None, None
+        if self.candidate_sets is None:
+            if row_sets is not None:
+                raise ValueError("SoftmaxAdaGrad.step: row_sets without candidate_sets")
+        else:
+            rs = tri[:, 2] if row_sets is None else torch.as_tensor(row_sets).to(tri.device)
+            if rs.dim() != 1 or rs.numel() != self.B or rs.dtype.is_floating_point:
+                raise ValueError("SoftmaxAdaGrad.step: row_sets must be [B] integers")
+            order = torch.argsort(rs, stable=True)
+            tri, rs = tri[order].contiguous(), rs[order].contiguous()
         losses = []
         for s, (fixed, true, side) in enumerate(((0, 1, "tail"), (1, 0, "head"))):
             hr = tri[:, [fixed, 2]].contiguous()
+            sets = self._sets.get(side)
             loss, _, _ = softmax_grad(emb, hr, tri[:, true].contiguous(), self.candidates, 1.0, scale=self.scale,
                                       max_norm=self.max_norm, side=side, workspace=self._ws,
-                                      out=(self._gi[s * R:(s + 1) * R], self._gv[s * R:(s + 1) * R]))
+                                      out=(self._gi[s * R:(s + 1) * R], self._gv[s * R:(s + 1) * R]),
+                                      candidate_sets=sets, row_sets=rs)
+            if order is not None:
+                loss = torch.empty_like(loss).index_copy_(0, order, loss)
             losses.append(loss)
         # a row's occurrences consecutive and in slot order: the stable argsort, empty slots last (adagrad_rows)
         key = torch.where(self._gi < 0, torch.full_like(self._gi, emb.shape[0]), self._gi)
@@ -570,16 +629,21 @@ class SoftmaxTrainer:
 
     n_samples: the sampled objective (SampledSoftmaxAdaGrad).  `candidates` is then the pool: every step draws
     pool[randint(len(pool), n_samples)], with replacement, one draw for both sides, from a second generator seeded with
-    seed + 1 -- so the batches are the ones drawn without sampling."""
+    seed + 1 -- so the batches are the ones drawn without sampling.
+
+    candidate_sets ({"tail": sets, "head": sets}, without n_samples): passed through to SoftmaxAdaGrad; every row's set is
+    its relation id."""
 
     def __init__(self, embeddings: torch.Tensor, triples: torch.Tensor, candidates: torch.Tensor, batch_size: int, *,
                  scale: float, learning_rate: float = 0.1, learning_decay_steps: float = 0.0,
                  learning_decay_rate: float = 0.5, seed: int = 0, max_norm: float = 1.0,
-                 initial_accumulator_value: float = 0.1, n_samples: Optional[int] = None):
+                 initial_accumulator_value: float = 0.1, n_samples: Optional[int] = None, candidate_sets=None):
         self.n_samples = None if n_samples is None else int(n_samples)
+        if self.n_samples is not None and candidate_sets is not None:
+            raise ValueError("SoftmaxTrainer: candidate_sets belong to the 1-vs-all objective (drop n_samples)")
         if self.n_samples is None:
             self.opt = SoftmaxAdaGrad(embeddings, candidates, batch_size, scale=scale, max_norm=max_norm,
-                                      initial_accumulator_value=initial_accumulator_value)
+                                      initial_accumulator_value=initial_accumulator_value, candidate_sets=candidate_sets)
         else:
             _need_cuda(candidates, "candidates")
             self.pool = candidates.to(torch.int32).contiguous().view(-1)

@@ -16,7 +16,8 @@ Extras: --model hole (README.md:42 score), --seed, --max_steps, --checkpoint_sec
 (AdagradOptimizer in place of holE.py:296's GradientDescentOptimizer: ge_train_steps_adagrad; the checkpoint then also
 holds `adagrad_accumulator`), --objective softmax (1-vs-all multiclass log-loss over all entities, both sides:
 hole.SoftmaxTrainer on ge_softmax_grad; ComplEx with AdaGrad on one GPU, no validation ticks; --softmax_samples K': sampled
-softmax, K' shared candidates a step on ge_softmax_sampled_grad).
+softmax, K' shared candidates a step on ge_softmax_sampled_grad; --softmax_candidate_sets types|observed: each row's
+softmax over its relation's candidate set, ge_softmax_masked_grad).
 """
 from __future__ import annotations
 
@@ -100,6 +101,10 @@ def build_parser() -> argparse.ArgumentParser:
                    help='With --objective softmax: candidates drawn per step from the entity rows (uniform, with '
                         'replacement, shared by the batch and both sides; the true entity has a logit of its own).  '
                         '0: all entity rows, the 1-vs-all objective.')
+    p.add_argument('--softmax_candidate_sets', choices=['none', 'types', 'observed'], default='none',
+                   help='With --objective softmax (1-vs-all, --softmax_samples 0): each row\'s softmax runs over the candidate '
+                        'set of its relation and side -- the sets of --infer --candidate_sets, from train + valid -- instead '
+                        'of over all entity rows.')
     p.add_argument('--gpus', type=int, default=1,
                    help='Ranks (one per GPU) the table is row-sharded over; > 1 without a launcher: this program starts them '
                         '(graphembeddings_amd/launch.py).  --batch_size stays the GLOBAL batch.')
@@ -147,10 +152,15 @@ def check_objective_flags(FLAGS, world: int = 1) -> None:
     samples = getattr(FLAGS, 'softmax_samples', 0)
     if samples < 0:
         raise SystemExit('--softmax_samples must not be negative (0: all entity rows)')
+    sets = getattr(FLAGS, 'softmax_candidate_sets', 'none') or 'none'
     if getattr(FLAGS, 'objective', 'hinge') != 'softmax':
         if samples > 0:
             raise SystemExit('--softmax_samples needs --objective softmax')
+        if sets != 'none':
+            raise SystemExit('--softmax_candidate_sets needs --objective softmax')
         return
+    if sets != 'none' and samples > 0:
+        raise SystemExit('--softmax_candidate_sets belongs to the 1-vs-all objective: drop --softmax_samples')
     if getattr(FLAGS, 'optimizer', 'sgd') != 'adagrad':
         raise SystemExit('--objective softmax needs --optimizer adagrad')
     if FLAGS.log_loss:
@@ -183,11 +193,24 @@ def run_softmax_training(data: D.HolEData, FLAGS, log=print) -> dict:
         embeddings = H.init_embeddings(data.entity_count, FLAGS.embedding_dim, seed=FLAGS.seed)
     triples = torch.as_tensor(np.ascontiguousarray(data.triples)).cuda()
     candidates = torch.arange(data.relation_count, data.entity_count, dtype=torch.int32, device='cuda')
+    kind, candidate_sets = getattr(FLAGS, 'softmax_candidate_sets', 'none') or 'none', None
+    if kind != 'none':
+        cand = np.arange(data.relation_count, data.entity_count, dtype=np.int32)
+        if kind == 'types':
+            # candidates of one type next to each other: 64-candidate tiles are then admitted or not as a whole
+            cand = cand[np.lexsort((cand, np.asarray(data.type_arrays()[1])[cand]))]
+        candidates = torch.as_tensor(np.ascontiguousarray(cand)).cuda()
+        _, candidate_sets = E.constrained_sets(data, kind, candidates=cand, device='cuda')
+        rel = np.asarray(data.triples)[:, 2]
+        log('Softmax candidate sets: {} (from train + valid); mean set size of a training row {:.1f} tails, {:.1f} heads '
+            'of {} entity rows'.format(kind, float(candidate_sets['tail'].counts[rel].mean()),
+                                       float(candidate_sets['head'].counts[rel].mean()), candidates.numel()))
     trainer = H.SoftmaxTrainer(embeddings, triples, candidates, FLAGS.batch_size, scale=FLAGS.softmax_scale,
                                learning_rate=FLAGS.learning_rate,
                                learning_decay_steps=FLAGS.learning_decay_steps * batch_count,
                                learning_decay_rate=FLAGS.learning_decay_rate, seed=FLAGS.seed,
-                               initial_accumulator_value=FLAGS.adagrad_init, n_samples=FLAGS.softmax_samples or None)
+                               initial_accumulator_value=FLAGS.adagrad_init, n_samples=FLAGS.softmax_samples or None,
+                               candidate_sets=candidate_sets)
     if FLAGS.softmax_samples:
         log('Sampled softmax: {} candidates a step, drawn from the {} entity rows'.format(FLAGS.softmax_samples,
                                                                                       candidates.numel()))

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define GE_VERSION 442 /* 0.4.4.2: + ge_softmax_sampled_loss / _grad / _workspace_bytes (sampled softmax with shared negatives) */
+#define GE_VERSION 443 /* 0.4.4.3: + ge_softmax_masked_loss / _grad / _workspace_bytes (1-vs-all softmax over per-row candidate sets) */
 
 /* argument errors (negative, -errno style) */
 #define GE_EINVAL (-22)  /* bad dimension / null pointer / misaligned buffer */
@@ -233,6 +233,36 @@ int ge_softmax_sampled_grad(const float* table, int64_t N, int32_t d, const int3
                             const int32_t* cand, int64_t K, float max_norm, float scale, float lr, int model,
                             int cand_is_head, float* loss, int32_t* grad_idx, float* grad_val, void* workspace,
                             size_t workspace_bytes, void* stream);
+
+/* --- type-constrained 1-vs-all softmax: ge_softmax_loss / ge_softmax_grad with each row's softmax taken over the
+ * candidates its set admits -- the training counterpart of the candidate sets of ge_rank_1vK_masked.  Everything is as
+ * for ge_softmax_loss / ge_softmax_grad (clips, s, z, cand_is_head, model, validity, the R = K + 2B slots, grad_val = -lr *
+ * the gradient of SUM_i loss_i, no float atomics, two identical calls give identical bits) except:
+ *   row_set [B] int32, mask uint32 [n_sets][W], W = ge_candidate_mask_words(K): the sets in the format described at
+ *   ge_candidate_mask_words -- a bit is addressed by candidate POSITION, bits at positions >= K are ignored,
+ *   row_set[i] = -1 means unrestricted.
+ *   loss_i = logsumexp_{j admissible for row i} z_ij - z_i,true;  w_ij = 0 exactly for an inadmissible pair.
+ * A row is valid iff it is valid for ge_softmax_loss AND row_set[i] is -1 or in [0, n_sets) AND the position of its true
+ * candidate is admissible; any other row (a row with an empty set among them) is invalid as there: loss = NaN, grad_idx
+ * -1, zero rows, no contribution anywhere.  Candidate slot j keeps grad_idx[j] = cand[j] for an id in the table; a
+ * candidate that no valid row admits gets an exact zero row (ge_adagrad_rows then leaves its table and accumulator bits
+ * as they are).  With every bit set, or every row_set = -1, loss, grad_idx and grad_val equal ge_softmax_loss /
+ * ge_softmax_grad's bit for bit.  A (64-row, 64-candidate) tile pair that no valid row admits is not computed: on sets
+ * that follow the order of cand, the work follows the sets' sizes.  Non-finite table rows: unspecified, as there.
+ * Refusals as for ge_softmax_loss / ge_softmax_grad, in the same order: a null row_set or mask and n_sets < 1 with the
+ * null pointers, a mask off 4 bytes with the other alignments; GE_ENOMEM against ge_softmax_masked_workspace_bytes(B, K,
+ * d) (ge_softmax_workspace_bytes' parts plus one bit per tile pair; monotone in each argument, a multiple of 256, 0 for
+ * sizes the calls refuse).  Nothing is allocated and the host never waits. */
+size_t ge_softmax_masked_workspace_bytes(int64_t B, int64_t K, int32_t d);
+int ge_softmax_masked_loss(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* true_id,
+                           const int32_t* cand, int64_t K, float max_norm, float scale, int model, int cand_is_head,
+                           float* loss, void* workspace, size_t workspace_bytes, const int32_t* row_set,
+                           const uint32_t* mask, int32_t n_sets, void* stream);
+int ge_softmax_masked_grad(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* true_id,
+                           const int32_t* cand, int64_t K, float max_norm, float scale, float lr, int model,
+                           int cand_is_head, float* loss, int32_t* grad_idx, float* grad_val, void* workspace,
+                           size_t workspace_bytes, const int32_t* row_set, const uint32_t* mask, int32_t n_sets,
+                           void* stream);
 
 /* --- corrupt_batch (holE.py:152-153 -> 136-140 -> 97-133) fused with the per-batch host
  * resample of holE.py:343-347.  id_to_type [N] int32 type code per table row (-1 = unknown, the
