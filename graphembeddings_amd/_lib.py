@@ -50,6 +50,11 @@ SYMBOLS = {
                                          _i32, _p]),
     "ge_softmax_masked_grad": (C.c_int, [_p, _i64, _i32, _p, _i64, _p, _p, _i64, _f, _f, _f, C.c_int, C.c_int, _p, _p, _p, _p,
                                          _sz, _p, _p, _i32, _p]),
+    "ge_softmax_labels_workspace_bytes": (_sz, [_i64, _i64, _i32, _i64]),
+    "ge_softmax_labels_loss": (C.c_int, [_p, _i64, _i32, _p, _i64, _p, _p, _i64, _p, _i64, _f, _f, C.c_int, C.c_int, _p, _p, _sz,
+                                         _p]),
+    "ge_softmax_labels_grad": (C.c_int, [_p, _i64, _i32, _p, _i64, _p, _p, _i64, _p, _i64, _f, _f, _f, C.c_int, C.c_int, _p, _p,
+                                         _p, _p, _sz, _p]),
     "ge_corrupt_batch": (C.c_int, [_p, _i64, _p, _i64, _p, _i32, _p, _u64, _u64, _i32, _i32, _p, _p]),
     "ge_bernoulli_corrupt_batch": (C.c_int, [_p, _i64, _p, _p, _p, _p, _i64, _p, _i32, _i32, _i32, _u64, _u64, _p, _p]),
     "ge_complex_score_1vK": (C.c_int, [_p, _i64, _i32, _p, _i64, _p, _i64, _f, C.c_int, C.c_int, _p, _p]),
@@ -204,7 +209,7 @@ def load():
             fn = getattr(lib, name)  # AttributeError if the ABI and the header diverge
             fn.restype = res
             fn.argtypes = args
-        if lib.ge_version() < 443:
+        if lib.ge_version() < 444:
             raise RuntimeError("libge_hip.so is older than the Python host expects")
         _lib = lib
     return _lib

@@ -296,6 +296,42 @@ int ge_softmax_masked_grad(const float* table, int64_t N, int32_t d, const int32
                       grad_val, workspace, workspace_bytes, stream, false, &sets);
 }
 
+size_t ge_softmax_labels_workspace_bytes(int64_t B, int64_t K, int32_t d, int64_t L) {
+  if (B < 1 || K < 1 || L < 0 || !softmax_dim_ok(d)) return 0;
+  return softmax_labels_ws_bytes(B, K, d, L);
+}
+
+// softmax_call's checks, in its order, with the labels' arguments in their groups
+static int softmax_labels_call(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* label_off,
+                               const int32_t* label_pos, int64_t L, const int32_t* cand, int64_t K, float max_norm, float scale,
+                               float lr, int model, int cand_is_head, float* loss, bool grad, int32_t* grad_idx, float* grad_val,
+                               void* workspace, size_t workspace_bytes, void* stream) {
+  if (B < 1 || K < 1 || L < 0 || !ok_table(table, N, d) || !max_norm_ok(max_norm) || !(scale > 0.f) || !std::isfinite(scale))
+    return GE_EINVAL;
+  if (!hr || !label_off || !label_pos || !cand || !loss || !workspace || (grad && (!grad_idx || !grad_val))) return GE_EINVAL;
+  if (model != GE_MODEL_COMPLEX || !softmax_dim_ok(d) || N > INT32_MAX) return GE_ENOTSUP;
+  if (reinterpret_cast<uintptr_t>(table) % 16 != 0 || reinterpret_cast<uintptr_t>(workspace) % 256 != 0) return GE_EINVAL;
+  if (grad && reinterpret_cast<uintptr_t>(grad_val) % 4 != 0) return GE_EINVAL;
+  if (workspace_bytes < softmax_labels_ws_bytes(B, K, d, L)) return GE_ENOMEM;
+  return softmax_labels_launch(table, N, d, hr, B, label_off, label_pos, L, cand, K, max_norm, scale, lr, cand_is_head, loss,
+                               grad ? grad_idx : nullptr, grad_val, workspace, (hipStream_t)stream);
+}
+
+int ge_softmax_labels_loss(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* label_off,
+                           const int32_t* label_pos, int64_t L, const int32_t* cand, int64_t K, float max_norm, float scale,
+                           int model, int cand_is_head, float* loss, void* workspace, size_t workspace_bytes, void* stream) {
+  return softmax_labels_call(table, N, d, hr, B, label_off, label_pos, L, cand, K, max_norm, scale, 0.f, model, cand_is_head,
+                             loss, false, nullptr, nullptr, workspace, workspace_bytes, stream);
+}
+
+int ge_softmax_labels_grad(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* label_off,
+                           const int32_t* label_pos, int64_t L, const int32_t* cand, int64_t K, float max_norm, float scale,
+                           float lr, int model, int cand_is_head, float* loss, int32_t* grad_idx, float* grad_val,
+                           void* workspace, size_t workspace_bytes, void* stream) {
+  return softmax_labels_call(table, N, d, hr, B, label_off, label_pos, L, cand, K, max_norm, scale, lr, model, cand_is_head,
+                             loss, true, grad_idx, grad_val, workspace, workspace_bytes, stream);
+}
+
 int ge_gather_rows(const float* table, int64_t N, int32_t d, const int32_t* idx, int64_t R, float* out,
                    void* stream) {
   if (R < 0 || !ok_table(table, N, d)) return GE_EINVAL;

@@ -220,6 +220,22 @@ int softmax_merge_launch(const SoftmaxWs& w, int n_ranges, int64_t B, float* los
 int softmax_finish_launch(const float* table, int32_t d, const int32_t* hr, int64_t B, int64_t K, float max_norm, float lr,
                           int cand_is_head, const SoftmaxWs& w, int n_ranges, int32_t* grad_idx, float* grad_val,
                           hipStream_t st);
+// its three sweeps: the LSE sweep into w.part, and the two gradient sweeps (dL/dC' into grad_val's first K rows, dL/dQ'
+// into w.gq's first n_ranges partials) -- the instantiations softmax_launch runs, for ge_softmax_labels.hip
+int softmax_lse_launch(const SoftmaxWs& w, int64_t B, int64_t K, int32_t d, float scale, int n_ranges, hipStream_t st);
+int softmax_grad_sweeps_launch(const SoftmaxWs& w, int64_t B, int64_t K, int32_t d, float scale, int n_ranges, float* grad_val,
+                               hipStream_t st);
+
+// ge_softmax_labels.hip: multi-label (K-vs-all) softmax: row i is a query whose labels are the candidate positions
+// label_pos[label_off[i] .. label_off[i + 1]), the target uniform over them; gradients in K + 2B + L slots.  The workspace:
+// SoftmaxWs' parts with a ninth dL/dQ' partial [B,d] (the label term) | label means [B] double | row of entry [L] int32.
+struct SoftmaxLabelsWs { SoftmaxWs base; float* lsum; double* mean; int32_t* row_of; size_t bytes; };
+SoftmaxLabelsWs softmax_labels_ws(void* base, int64_t B, int64_t K, int32_t d, int64_t L);
+size_t softmax_labels_ws_bytes(int64_t B, int64_t K, int32_t d, int64_t L);
+int softmax_labels_launch(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* label_off,
+                          const int32_t* label_pos, int64_t L, const int32_t* cand, int64_t K, float max_norm, float scale,
+                          float lr, int cand_is_head, float* loss, int32_t* grad_idx, float* grad_val, void* workspace,
+                          hipStream_t st);
 
 // ge_softmax_masked.hip: ge_softmax.hip's objective with per-row candidate sets (SetArgs; mw is not read).  The workspace:
 // SoftmaxWs' parts | the live-tile bitmap [query tiles][sm_live_words(K)] uint32, padded to 256 B.

@@ -22,7 +22,8 @@
 //
 // The scalar x . g the clip's beta needs is a dot product in the finish kernel, not a second sum in the sweep.
 // The sweep template, its constants and the helpers the sampled form (ge_softmax_sampled.hip) shares are in ge_softmax_kern.h.
-// The masked form (ge_softmax_masked.hip) runs this file's prepare, merge and finish kernels through their launchers.
+// The masked form (ge_softmax_masked.hip) runs this file's prepare, merge and finish kernels through their launchers; the
+// multi-label form (ge_softmax_labels.hip) runs its prepare, its three sweeps and its finish kernel through theirs.
 #include "ge_softmax_kern.h"
 
 namespace ge {
@@ -239,6 +240,17 @@ int softmax_finish_launch(const float* table, int32_t d, const int32_t* hr, int6
   return launch_status();
 }
 
+int softmax_lse_launch(const SoftmaxWs& w, int64_t B, int64_t K, int32_t d, float scale, int n_ranges, hipStream_t st) {
+  return sm_sweep<0, true, false>(w.qp, w.qkey, B, w.cp, w.ckey, K, d, scale, nullptr, n_ranges, reinterpret_cast<float*>(w.part), st);
+}
+
+int softmax_grad_sweeps_launch(const SoftmaxWs& w, int64_t B, int64_t K, int32_t d, float scale, int n_ranges, float* grad_val,
+                               hipStream_t st) {
+  // dL/dC' over all queries, straight into the candidates' slots; dL/dQ' per candidate range
+  if (int rc = sm_sweep<1, false, false>(w.cp, w.ckey, K, w.qp, w.qkey, B, d, scale, w.lse, 1, grad_val, st)) return rc;
+  return sm_sweep<1, true, false>(w.qp, w.qkey, B, w.cp, w.ckey, K, d, scale, w.lse, n_ranges, w.gq, st);
+}
+
 int softmax_launch(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* true_id,
                    const int32_t* cand, int64_t K, float max_norm, float scale, float lr, int cand_is_head, float* loss,
                    int32_t* grad_idx, float* grad_val, void* workspace, hipStream_t st) {
@@ -246,13 +258,10 @@ int softmax_launch(const float* table, int64_t N, int32_t d, const int32_t* hr, 
   const SoftmaxWs w = softmax_ws(workspace, B, K, d);
   if (int rc = softmax_prepare_launch(table, N, d, hr, B, true_id, cand, K, max_norm, cand_is_head, nullptr, 0, w, st)) return rc;
   const int ns = sm_split(B, K);
-  if (int rc = sm_sweep<0, true, false>(w.qp, w.qkey, B, w.cp, w.ckey, K, d, scale, nullptr, ns, reinterpret_cast<float*>(w.part), st))
-    return rc;
+  if (int rc = softmax_lse_launch(w, B, K, d, scale, ns, st)) return rc;
   if (int rc = softmax_merge_launch(w, ns, B, loss, st)) return rc;
   if (!grad_idx) return 0;
-  // dL/dC' over all queries, straight into the candidates' slots; dL/dQ' per candidate range
-  if (int rc = sm_sweep<1, false, false>(w.cp, w.ckey, K, w.qp, w.qkey, B, d, scale, w.lse, 1, grad_val, st)) return rc;
-  if (int rc = sm_sweep<1, true, false>(w.qp, w.qkey, B, w.cp, w.ckey, K, d, scale, w.lse, ns, w.gq, st)) return rc;
+  if (int rc = softmax_grad_sweeps_launch(w, B, K, d, scale, ns, grad_val, st)) return rc;
   return softmax_finish_launch(table, d, hr, B, K, max_norm, lr, cand_is_head, w, ns, grad_idx, grad_val, st);
 }
 

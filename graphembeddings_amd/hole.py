@@ -522,6 +522,180 @@ class SoftmaxAdaGrad:
         return torch.stack(losses, 1)
 
 
+class QueryLabels:
+    """The rows of the multi-label objective for one side: the distinct queries (fixed, relation) of `triples` and, per
+    query, the candidate POSITIONS of all its known answers, as a CSR on the device.
+    queries [Q,2] int32, label_off [Q + 1] int64, label_pos [sum n_i] int32 (ascending and distinct within a query)."""
+
+    def __init__(self, queries: torch.Tensor, label_off: torch.Tensor, label_pos: torch.Tensor, side: str):
+        self.queries, self.label_off, self.label_pos, self.side = queries, label_off, label_pos, side
+        self.counts = label_off[1:] - label_off[:-1]
+
+    def __len__(self) -> int:
+        return self.queries.shape[0]
+
+    @classmethod
+    def from_triples(cls, triples: torch.Tensor, candidates: torch.Tensor, side: str) -> "QueryLabels":
+        """side="tail": the queries are (head, relation) and the answers tails; "head": (tail, relation), answers heads.
+        `candidates` are distinct ids; a triple whose answer is none of them is refused."""
+        if side not in ("tail", "head"):
+            raise ValueError("QueryLabels: side must be 'tail' or 'head'")
+        tri = _triples(triples, "triples").to(torch.int64)
+        _need_cuda(candidates, "candidates")
+        cand = candidates.to(torch.int64).view(-1)
+        K = cand.numel()
+        if tri.shape[0] < 1 or K < 1:
+            raise ValueError("QueryLabels: at least one triple and one candidate")
+        if int(tri.min()) < 0 or int(cand.min()) < 0:
+            raise ValueError("QueryLabels: negative ids")
+        fixed, answer, rel = tri[:, 0 if side == "tail" else 1], tri[:, 1 if side == "tail" else 0], tri[:, 2]
+        where = torch.full((int(max(cand.max(), answer.max())) + 1,), -1, dtype=torch.int64, device=tri.device)
+        where[cand] = torch.arange(K, device=tri.device)
+        if int((where >= 0).sum()) != K:
+            raise ValueError("QueryLabels: candidates must be distinct")
+        pos = where[answer]
+        if bool((pos < 0).any()):
+            raise ValueError("QueryLabels: a triple's answer is not among the candidates")
+        n_rel = int(rel.max()) + 1
+        # one key per (query, position), sorted and distinct: the queries in (fixed, relation) order, each one's positions ascending
+        pair = torch.unique((fixed * n_rel + rel) * K + pos)
+        qkey, counts = torch.unique_consecutive(torch.div(pair, K, rounding_mode="floor"), return_counts=True)
+        off = torch.zeros(qkey.numel() + 1, dtype=torch.int64, device=tri.device)
+        off[1:] = torch.cumsum(counts, 0)
+        queries = torch.stack([torch.div(qkey, n_rel, rounding_mode="floor"), qkey % n_rel], 1).to(torch.int32)
+        return cls(queries.contiguous(), off, (pair % K).to(torch.int32).contiguous(), side)
+
+    def take(self, rows: torch.Tensor):
+        """(hr [b,2] int32, label_off [b + 1] int32, label_pos [L] int32) of the queries `rows` (indices on the device), in
+        that order.  The host waits once, for L."""
+        rows = rows.to(torch.int64).view(-1)
+        n = self.counts[rows]
+        off = torch.zeros(rows.numel() + 1, dtype=torch.int64, device=rows.device)
+        off[1:] = torch.cumsum(n, 0)
+        L = int(off[-1])
+        src = torch.repeat_interleave(self.label_off[rows] - off[:-1], n, output_size=L) + torch.arange(L, device=rows.device)
+        return self.queries[rows].contiguous(), off.to(torch.int32), self.label_pos[src].contiguous()
+
+
+def _labels_args(fixed_and_relation, label_off, label_pos, who):
+    for name, t in (("fixed_and_relation", fixed_and_relation), ("label_off", label_off), ("label_pos", label_pos)):
+        _need_cuda(t, name)
+    off = label_off.to(torch.int32).contiguous().view(-1)
+    pos = label_pos.to(torch.int32).contiguous().view(-1)
+    if off.numel() != fixed_and_relation.shape[0] + 1:
+        raise ValueError(f"{who}: label_off must be [B + 1]")
+    return off, pos
+
+
+def softmax_labels_workspace(embeddings: torch.Tensor, B: int, K: int, L: int) -> torch.Tensor:
+    """A workspace for softmax_labels_loss / softmax_labels_grad at this shape (ge_softmax_labels_workspace_bytes)."""
+    need = _lib.load().ge_softmax_labels_workspace_bytes(B, K, embeddings.shape[1], L)
+    return torch.empty(max(need, 256), dtype=torch.uint8, device=embeddings.device)
+
+
+def softmax_labels_loss(embeddings: torch.Tensor, fixed_and_relation: torch.Tensor, label_off: torch.Tensor,
+                        label_pos: torch.Tensor, candidates: torch.Tensor, *, scale: float, max_norm: float = 1.0,
+                        side: str = "tail", workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The multi-label (K-vs-all) objective (ge_softmax_labels_loss): row i is a query (fixed, relation) whose labels are the
+    candidate positions label_pos[label_off[i] : label_off[i + 1]], n_i of them, and
+    loss_i = logsumexp_j(-scale * s_ij) - mean over the labels of (-scale * s_i,l).  NaN for a row with an id outside the
+    table, without labels, or with a label that is no position of a candidate in the table.  ComplEx only."""
+    off, pos = _labels_args(fixed_and_relation, label_off, label_pos, "softmax_labels_loss")
+    # (the offsets behind the first stand in for the true ids of the shared checks: one per row)
+    emb, hr, _, cand, head = _softmax_args(embeddings, fixed_and_relation, off[1:], candidates, scale, max_norm, side,
+                                           "softmax_labels_loss")
+    B, K, L = hr.shape[0], cand.numel(), pos.numel()
+    ws = workspace if workspace is not None else softmax_labels_workspace(emb, B, K, L)
+    loss = torch.empty(B, dtype=torch.float32, device=emb.device)
+    _lib.call("ge_softmax_labels_loss", emb.data_ptr(), emb.shape[0], emb.shape[1], hr.data_ptr(), B, off.data_ptr(),
+              pos.data_ptr() if L else off.data_ptr(), L, cand.data_ptr(), K, float(max_norm), float(scale), MODEL_COMPLEX,
+              head, loss.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+    return loss
+
+
+def softmax_labels_grad(embeddings: torch.Tensor, fixed_and_relation: torch.Tensor, label_off: torch.Tensor,
+                        label_pos: torch.Tensor, candidates: torch.Tensor, lr: float, *, scale: float, max_norm: float = 1.0,
+                        side: str = "tail", workspace: Optional[torch.Tensor] = None, out=None):
+    """The gradients of softmax_labels_loss (ge_softmax_labels_grad): (loss [B], grad_idx [K + 2B + L] int32, grad_val
+    [K + 2B + L, d]) with grad_val = -lr * the gradient of SUM_i loss_i.  Slot j < K is candidates[j] with the softmax term of
+    its gradient, slots K + 2i and K + 2i + 1 the fixed entity and the relation of row i, slot K + 2B + x the candidate of
+    label entry x with the label term of its gradient; -1 and a zero row for an empty slot.  The slices of one table row
+    sum to its gradient.  out: (grad_idx, grad_val) views to write into."""
+    off, pos = _labels_args(fixed_and_relation, label_off, label_pos, "softmax_labels_grad")
+    # (the offsets behind the first stand in for the true ids of the shared checks: one per row)
+    emb, hr, _, cand, head = _softmax_args(embeddings, fixed_and_relation, off[1:], candidates, scale, max_norm, side,
+                                           "softmax_labels_grad")
+    B, K, L, d = hr.shape[0], cand.numel(), pos.numel(), emb.shape[1]
+    R = K + 2 * B + L
+    ws = workspace if workspace is not None else softmax_labels_workspace(emb, B, K, L)
+    loss = torch.empty(B, dtype=torch.float32, device=emb.device)
+    if out is None:
+        gi = torch.empty(R, dtype=torch.int32, device=emb.device)
+        gv = torch.empty(R, d, dtype=torch.float32, device=emb.device)
+    else:
+        gi, gv = out
+        if gi.dtype != torch.int32 or gv.dtype != torch.float32 or gi.numel() != R or tuple(gv.shape) != (R, d) \
+                or not gi.is_contiguous() or not gv.is_contiguous():
+            raise ValueError("softmax_labels_grad: out must be (int32 [K + 2B + L], float32 [K + 2B + L, d]), contiguous")
+    _lib.call("ge_softmax_labels_grad", emb.data_ptr(), emb.shape[0], d, hr.data_ptr(), B, off.data_ptr(),
+              pos.data_ptr() if L else off.data_ptr(), L, cand.data_ptr(), K, float(max_norm), float(scale), float(lr),
+              MODEL_COMPLEX, head, loss.data_ptr(), gi.data_ptr(), gv.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+    return loss, gi, gv
+
+
+class LabelSoftmaxAdaGrad:
+    """SoftmaxAdaGrad on the multi-label objective: per step a batch of tail-side queries and one of head-side queries,
+    each (hr [b,2], label_off [b + 1], label_pos [L]) as QueryLabels.take gives them, with b <= batch_size and
+    L <= max_labels a side (a side may be None: no rows).  Two ge_softmax_labels_grad calls at lr = 1 (tails, then heads)
+    against ONE snapshot of the table into one slices buffer, one stable argsort, one ge_adagrad_rows.  Owns
+    `.accumulator`; workspace and slices are reserved once, for the largest step."""
+
+    def __init__(self, embeddings: torch.Tensor, candidates: torch.Tensor, batch_size: int, max_labels: int, *, scale: float,
+                 max_norm: float = 1.0, initial_accumulator_value: float = 0.1):
+        if not initial_accumulator_value > 0:
+            raise ValueError("initial_accumulator_value must be positive")
+        self.embeddings = _table(embeddings)
+        _need_cuda(candidates, "candidates")
+        self.candidates = candidates.to(torch.int32).contiguous().view(-1)
+        self.B, self.L, self.scale, self.max_norm = int(batch_size), int(max_labels), float(scale), float(max_norm)
+        if self.B < 1 or self.L < 1 or self.candidates.numel() < 1:
+            raise ValueError("LabelSoftmaxAdaGrad: at least one row a batch, one label and one candidate")
+        dev, d = self.embeddings.device, self.embeddings.shape[1]
+        self.accumulator = torch.full_like(self.embeddings, float(initial_accumulator_value))
+        R = self.candidates.numel() + 2 * self.B + self.L
+        self._ws = softmax_labels_workspace(self.embeddings, self.B, self.candidates.numel(), self.L)
+        self._gi = torch.empty(2 * R, dtype=torch.int32, device=dev)
+        self._gv = torch.empty(2 * R, d, dtype=torch.float32, device=dev)
+
+    def step(self, tail_batch, head_batch, lr: float):
+        """One step in place on the table and the accumulator; returns (tail losses [b_tail] or None, head losses [b_head]
+        or None)."""
+        emb, K = self.embeddings, self.candidates.numel()
+        at, losses = 0, []
+        for batch, side in ((tail_batch, "tail"), (head_batch, "head")):
+            if batch is None or batch[0].shape[0] == 0:
+                losses.append(None)
+                continue
+            hr, off, pos = batch
+            b, L = hr.shape[0], pos.numel()
+            if b > self.B or L > self.L:
+                raise ValueError("LabelSoftmaxAdaGrad.step: more rows than batch_size or more labels than max_labels")
+            R = K + 2 * b + L
+            loss, _, _ = softmax_labels_grad(emb, hr, off, pos, self.candidates, 1.0, scale=self.scale, max_norm=self.max_norm,
+                                             side=side, workspace=self._ws, out=(self._gi[at:at + R], self._gv[at:at + R]))
+            losses.append(loss)
+            at += R
+        if at == 0:
+            raise ValueError("LabelSoftmaxAdaGrad.step: no rows on either side")
+        gi = self._gi[:at]
+        # a row's occurrences consecutive and in slot order: the stable argsort, empty slots last (adagrad_rows)
+        key = torch.where(gi < 0, torch.full_like(gi, emb.shape[0]), gi)
+        perm = torch.argsort(key, stable=True).to(torch.int32)
+        _lib.call("ge_adagrad_rows", emb.data_ptr(), _accumulator(self.accumulator, emb).data_ptr(), emb.shape[0],
+                  emb.shape[1], gi.data_ptr(), self._gv.data_ptr(), perm.data_ptr(), at, float(lr), _stream())
+        return tuple(losses)
+
+
 def softmax_sampled_workspace(embeddings: torch.Tensor, B: int, K: int) -> torch.Tensor:
     """A workspace for softmax_sampled_loss / softmax_sampled_grad at this shape (ge_softmax_sampled_workspace_bytes)."""
     need = _lib.load().ge_softmax_sampled_workspace_bytes(B, K, embeddings.shape[1])
@@ -632,16 +806,38 @@ class SoftmaxTrainer:
     seed + 1 -- so the batches are the ones drawn without sampling.
 
     candidate_sets ({"tail": sets, "head": sets}, without n_samples): passed through to SoftmaxAdaGrad; every row's set is
-    its relation id."""
+    its relation id.
+
+    labels="all" (without n_samples or candidate_sets): the multi-label objective (LabelSoftmaxAdaGrad).  The rows are the
+    distinct QUERIES of both sides (QueryLabels.from_triples, built once), each with all its answers in `triples` as
+    labels.  An epoch is one permutation of all Q_tail + Q_head queries from the seeded generator; a step takes the next
+    batch_size of them and splits them by side (a side without rows is skipped); the last short batch is dropped.  The
+    step's losses come back as one [batch_size] tensor, tail-side rows first."""
 
     def __init__(self, embeddings: torch.Tensor, triples: torch.Tensor, candidates: torch.Tensor, batch_size: int, *,
                  scale: float, learning_rate: float = 0.1, learning_decay_steps: float = 0.0,
                  learning_decay_rate: float = 0.5, seed: int = 0, max_norm: float = 1.0,
-                 initial_accumulator_value: float = 0.1, n_samples: Optional[int] = None, candidate_sets=None):
+                 initial_accumulator_value: float = 0.1, n_samples: Optional[int] = None, candidate_sets=None,
+                 labels: str = "one"):
         self.n_samples = None if n_samples is None else int(n_samples)
         if self.n_samples is not None and candidate_sets is not None:
             raise ValueError("SoftmaxTrainer: candidate_sets belong to the 1-vs-all objective (drop n_samples)")
-        if self.n_samples is None:
+        if labels not in ("one", "all"):
+            raise ValueError("SoftmaxTrainer: labels must be 'one' or 'all'")
+        self.labels = labels
+        if labels == "all":
+            if self.n_samples is not None or candidate_sets is not None:
+                raise ValueError("SoftmaxTrainer: labels='all' runs over all candidates (drop n_samples and candidate_sets)")
+            tri = _triples(triples, "triples")
+            self.queries = {s: QueryLabels.from_triples(tri, candidates, s) for s in ("tail", "head")}
+            self.Q = len(self.queries["tail"]) + len(self.queries["head"])
+            if self.Q < int(batch_size):
+                raise ValueError("fewer queries than batch_size (no short batches)")
+            # the most labels batch_size rows of one side can have
+            most = max(int(torch.sort(q.counts, descending=True).values[:int(batch_size)].sum()) for q in self.queries.values())
+            self.opt = LabelSoftmaxAdaGrad(embeddings, candidates, batch_size, most, scale=scale, max_norm=max_norm,
+                                           initial_accumulator_value=initial_accumulator_value)
+        elif self.n_samples is None:
             self.opt = SoftmaxAdaGrad(embeddings, candidates, batch_size, scale=scale, max_norm=max_norm,
                                       initial_accumulator_value=initial_accumulator_value, candidate_sets=candidate_sets)
         else:
@@ -686,6 +882,20 @@ class SoftmaxTrainer:
         self._row += self.B
         return self.triples[rows].contiguous()
 
+    def next_queries(self):
+        """labels="all": the next step's (tail batch or None, head batch or None), each as QueryLabels.take gives it."""
+        if self.labels != "all":
+            raise ValueError("SoftmaxTrainer.next_queries: built with labels='one', the rows are triples")
+        if self._perm is None or self._row + self.B > self.Q:
+            self._perm = torch.randperm(self.Q, device=self.embeddings.device, generator=self._gen)
+            self._row = 0
+        rows = self._perm[self._row:self._row + self.B]
+        self._row += self.B
+        n_tail = len(self.queries["tail"])
+        is_tail = rows < n_tail
+        t, h = rows[is_tail], rows[~is_tail] - n_tail
+        return (self.queries["tail"].take(t) if t.numel() else None, self.queries["head"].take(h) if h.numel() else None)
+
     def next_candidates(self) -> torch.Tensor:
         """The next step's [n_samples] candidates: a uniform draw from the pool, with replacement."""
         if self.n_samples is None:
@@ -694,10 +904,13 @@ class SoftmaxTrainer:
         return self.pool[at]
 
     def run(self, n_steps: int, keep_losses: bool = False) -> torch.Tensor:
-        """n_steps steps on the current stream; the losses [n_steps, B, 2] if keep_losses, else the last step's [B,2]."""
+        """n_steps steps on the current stream; the losses [n_steps, B, 2] if keep_losses, else the last step's [B,2]
+        (labels="all": [n_steps, B] and [B])."""
         kept, loss = [], None
         for _ in range(n_steps):
-            if self.n_samples is None:
+            if self.labels == "all":
+                loss = torch.cat([l for l in self.opt.step(*self.next_queries(), self.learning_rate()) if l is not None])
+            elif self.n_samples is None:
                 loss = self.opt.step(self.next_batch(), self.learning_rate())
             else:
                 loss = self.opt.step(self.next_batch(), self.next_candidates(), self.learning_rate())

@@ -17,7 +17,8 @@ Extras: --model hole (README.md:42 score), --seed, --max_steps, --checkpoint_sec
 holds `adagrad_accumulator`), --objective softmax (1-vs-all multiclass log-loss over all entities, both sides:
 hole.SoftmaxTrainer on ge_softmax_grad; ComplEx with AdaGrad on one GPU, no validation ticks; --softmax_samples K': sampled
 softmax, K' shared candidates a step on ge_softmax_sampled_grad; --softmax_candidate_sets types|observed: each row's
-softmax over its relation's candidate set, ge_softmax_masked_grad).
+softmax over its relation's candidate set, ge_softmax_masked_grad; --softmax_labels all: one row per distinct query with
+all its training answers as labels, ge_softmax_labels_grad).
 """
 from __future__ import annotations
 
@@ -101,6 +102,11 @@ def build_parser() -> argparse.ArgumentParser:
                    help='With --objective softmax: candidates drawn per step from the entity rows (uniform, with '
                         'replacement, shared by the batch and both sides; the true entity has a logit of its own).  '
                         '0: all entity rows, the 1-vs-all objective.')
+    p.add_argument('--softmax_labels', choices=['one', 'all'], default='one',
+                   help='With --objective softmax (1-vs-all, --softmax_samples 0, --softmax_candidate_sets none): one: a row per '
+                        'training triple with its answer as the one label; all: a row per distinct (entity, relation) query '
+                        'of each side with ALL its answers among the training triples as labels, the target uniform over '
+                        'them (the "KvsAll" training type).')
     p.add_argument('--softmax_candidate_sets', choices=['none', 'types', 'observed'], default='none',
                    help='With --objective softmax (1-vs-all, --softmax_samples 0): each row\'s softmax runs over the candidate '
                         'set of its relation and side -- the sets of --infer --candidate_sets, from train + valid -- instead '
@@ -153,14 +159,21 @@ def check_objective_flags(FLAGS, world: int = 1) -> None:
     if samples < 0:
         raise SystemExit('--softmax_samples must not be negative (0: all entity rows)')
     sets = getattr(FLAGS, 'softmax_candidate_sets', 'none') or 'none'
+    labels = getattr(FLAGS, 'softmax_labels', 'one') or 'one'
     if getattr(FLAGS, 'objective', 'hinge') != 'softmax':
         if samples > 0:
             raise SystemExit('--softmax_samples needs --objective softmax')
         if sets != 'none':
             raise SystemExit('--softmax_candidate_sets needs --objective softmax')
+        if labels != 'one':
+            raise SystemExit('--softmax_labels needs --objective softmax')
         return
     if sets != 'none' and samples > 0:
         raise SystemExit('--softmax_candidate_sets belongs to the 1-vs-all objective: drop --softmax_samples')
+    if labels != 'one' and samples > 0:
+        raise SystemExit('--softmax_labels all runs over all entity rows: drop --softmax_samples')
+    if labels != 'one' and sets != 'none':
+        raise SystemExit('--softmax_labels all runs over all entity rows: drop --softmax_candidate_sets')
     if getattr(FLAGS, 'optimizer', 'sgd') != 'adagrad':
         raise SystemExit('--objective softmax needs --optimizer adagrad')
     if FLAGS.log_loss:
@@ -210,7 +223,11 @@ def run_softmax_training(data: D.HolEData, FLAGS, log=print) -> dict:
                                learning_decay_steps=FLAGS.learning_decay_steps * batch_count,
                                learning_decay_rate=FLAGS.learning_decay_rate, seed=FLAGS.seed,
                                initial_accumulator_value=FLAGS.adagrad_init, n_samples=FLAGS.softmax_samples or None,
-                               candidate_sets=candidate_sets)
+                               candidate_sets=candidate_sets, labels=getattr(FLAGS, 'softmax_labels', 'one') or 'one')
+    if trainer.labels == 'all':
+        log('Softmax labels: all -- {} tail queries and {} head queries (labels from the training triples only) against {} '
+            'triples, {} triple sides'.format(len(trainer.queries['tail']), len(trainer.queries['head']),
+                                              data.triple_count, 2 * data.triple_count))
     if FLAGS.softmax_samples:
         log('Sampled softmax: {} candidates a step, drawn from the {} entity rows'.format(FLAGS.softmax_samples,
                                                                                       candidates.numel()))

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define GE_VERSION 443 /* 0.4.4.3: + ge_softmax_masked_loss / _grad / _workspace_bytes (1-vs-all softmax over per-row candidate sets) */
+#define GE_VERSION 444 /* 0.4.4.4: + ge_softmax_labels_loss / _grad / _workspace_bytes (multi-label softmax: one row per query, all its answers) */
 
 /* argument errors (negative, -errno style) */
 #define GE_EINVAL (-22)  /* bad dimension / null pointer / misaligned buffer */
@@ -263,6 +263,39 @@ int ge_softmax_masked_grad(const float* table, int64_t N, int32_t d, const int32
                            int cand_is_head, float* loss, int32_t* grad_idx, float* grad_val, void* workspace,
                            size_t workspace_bytes, const int32_t* row_set, const uint32_t* mask, int32_t n_sets,
                            void* stream);
+
+/* --- multi-label (K-vs-all) softmax: one row per distinct QUERY (fixed, relation) with ALL its known answers as labels and
+ * a target uniform over them, where ge_softmax_loss has one row per triple and one true candidate.  Clips, s, z, Q', C',
+ * cand_is_head, model and empty candidate slots as for ge_softmax_loss / ge_softmax_grad.  Row i's labels are the candidate
+ * POSITIONS label_pos[label_off[i] .. label_off[i + 1]) (label_off [B + 1], label_pos [L], int32, on the device), n_i of
+ * them; a position named twice counts as two labels.
+ *   loss_i = logsumexp_j z_ij - (1 / n_i) SUM_{l in labels_i} z_i,l
+ *   dL/ds_ij = -scale * (softmax_j(z_ij) - y_ij / n_i),   y_ij = the number of labels of row i at position j
+ * A row is valid iff its fixed and relation ids lie in [0,N), 0 <= label_off[i] < label_off[i + 1] <= L, and every label
+ * is a position in [0,K) whose candidate id lies in [0,N); any other row has loss = NaN and contributes to no gradient.
+ * Offsets that decrease or point past L invalidate rows and are never followed out of bounds.
+ * ge_softmax_labels_grad emits IndexedSlices of R = K + 2B + L slots, grad_val [R,d] = -lr * the gradient of SUM_i loss_i
+ * through the clips, against the table as it is:
+ *   slot j < K: cand[j], the dense part (the softmax term) of the candidate's gradient; slot K + 2i: fixed_i;
+ *   K + 2i + 1: rel_i, both with the label term included (-1 and zero rows for an invalid row);
+ *   slot K + 2B + x: the candidate id of label entry x, with the label term of that candidate's gradient from the row the
+ *   entry belongs to: the clip derivative of the candidate row applied to (scale / n_i) Q'_i, which is linear in its
+ *   argument, so the slices of one table row sum to its gradient (-1 and a zero row for an entry of an invalid row or of
+ *   none).  At lr = 1 the slices are what ge_adagrad_rows takes.  No [B,K] array, no float atomics: two identical calls
+ *   give identical bits.
+ * Refusals as for ge_softmax_loss / ge_softmax_grad, in the same order: a null label_off or label_pos and L < 0 with the
+ * null pointers (L = 0 is taken: every row is then invalid); N > INT32_MAX with GE_ENOTSUP; GE_ENOMEM against
+ * ge_softmax_labels_workspace_bytes(B, K, d, L) (ge_softmax_workspace_bytes' parts plus the label-sum rows [B,d], the label
+ * means [B] and a row-of-entry array [L]; monotone in each argument, a multiple of 256, 0 for sizes the calls refuse).
+ * Nothing is allocated and the host never waits. */
+size_t ge_softmax_labels_workspace_bytes(int64_t B, int64_t K, int32_t d, int64_t L);
+int ge_softmax_labels_loss(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* label_off,
+                           const int32_t* label_pos, int64_t L, const int32_t* cand, int64_t K, float max_norm, float scale,
+                           int model, int cand_is_head, float* loss, void* workspace, size_t workspace_bytes, void* stream);
+int ge_softmax_labels_grad(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* label_off,
+                           const int32_t* label_pos, int64_t L, const int32_t* cand, int64_t K, float max_norm, float scale,
+                           float lr, int model, int cand_is_head, float* loss, int32_t* grad_idx, float* grad_val,
+                           void* workspace, size_t workspace_bytes, void* stream);
 
 /* --- corrupt_batch (holE.py:152-153 -> 136-140 -> 97-133) fused with the per-batch host
  * resample of holE.py:343-347.  id_to_type [N] int32 type code per table row (-1 = unknown, the
