@@ -83,6 +83,10 @@ SYMBOLS = {
                                      _p, _p, _i32, _p]),
     "ge_topk_1vK_masked": (C.c_int, [_p, _i64, _i32, _p, _i64, _p, _i64, _f, C.c_int, C.c_int, _p, _p, _i32, _p, _p, _p,
                                      _p, _sz, _p, _p, _i32, _p]),
+    "ge_rank_metrics": (C.c_int, [_p, _p, _p, _i64, _p, _p, _p, _p]),
+    "ge_rank_tick_workspace_bytes": (_sz, [_i64]),
+    "ge_rank_validation_tick": (C.c_int, [_p, _i64, _i32, _p, _p, _i64, _p, _i64, _f, C.c_int, _p, _p, _p, _p, _p, _p, _p, _p,
+                                          _i32, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "ge_train_workspace_bytes": (_sz, [_i64, _i32]),
     "ge_train_pipeline_create": (C.c_int, [C.POINTER(C.c_void_p)]),
     "ge_train_pipeline_reset": (C.c_int, [_p]),
@@ -209,7 +213,7 @@ def load():
             fn = getattr(lib, name)  # AttributeError if the ABI and the header diverge
             fn.restype = res
             fn.argtypes = args
-        if lib.ge_version() < 444:
+        if lib.ge_version() < 445:
             raise RuntimeError("libge_hip.so is older than the Python host expects")
         _lib = lib
     return _lib

@@ -1090,6 +1090,75 @@ int ge_known_cells(int pass, const int64_t* known_key, const int64_t* known_ent,
                             known_rc, (hipStream_t)stream);
 }
 
+// ---------------------------------------------------------------- rank metrics and the rank validation tick
+constexpr int64_t kRankMetricsMaxRows = (int64_t)1 << 24;   // the counted rows stay exact in metrics_out[7]
+
+int ge_rank_metrics(const int32_t* n_before, const int32_t* n_known_before, const float* true_loss, int64_t M,
+                    float* metrics_out, float* best, int32_t* improved, void* stream) {
+  if (!n_before || !n_known_before || !metrics_out || M < 1) return GE_EINVAL;
+  if (M > kRankMetricsMaxRows) return GE_ENOTSUP;
+  return rank_metrics_launch(n_before, n_known_before, true_loss, M, metrics_out, best, improved, (hipStream_t)stream);
+}
+
+// the tick's workspace: n_before [2V] | n_known_before [2V] | true_loss [2V] | flag -- the tail side's V rows first, so
+// that the three vectors are what ge_rank_metrics takes for M = 2V
+struct RankTickWs { int32_t* raw; int32_t* skip; float* true_loss; int32_t* flag; size_t bytes; };
+static RankTickWs rank_tick_ws(void* base, int64_t V) {
+  const size_t m = 2 * (size_t)V;
+  return RankTickWs{ws_at<int32_t>(base, 0), ws_at<int32_t>(base, 4 * m), ws_at<float>(base, 8 * m),
+                    ws_at<int32_t>(base, 12 * m), (12 * m + 16 + 255) / 256 * 256};
+}
+size_t ge_rank_tick_workspace_bytes(int64_t V) { return V < 1 ? 0 : rank_tick_ws(nullptr, V).bytes; }
+
+// Every check of both sides comes before the first launch: the tick's own, then sweep_args for the tail rows and the
+// head rows (the codes and the order of ge_rank_1vK_planes / ge_rank_1vK_masked), then what their routes and
+// copy_if_launch would refuse behind a launch, then the workspace's size.
+int ge_rank_validation_tick(const float* table, int64_t N, int32_t d, const int32_t* hr, const int32_t* true_id, int64_t V,
+                            const int32_t* cand, int64_t K, float max_norm, int model, const int32_t* known_off_tail,
+                            const uint16_t* known_rc_tail, const int32_t* known_off_head, const uint16_t* known_rc_head,
+                            void* planes, const int32_t* row_set, const uint32_t* mask_tail, const uint32_t* mask_head,
+                            int32_t n_sets, const float* accumulator, float* metrics_out, float* best, float* pocket,
+                            float* pocket_accumulator, void* workspace, size_t workspace_bytes, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (V < 1 || K < 1 || !metrics_out || !best || !workspace) return GE_EINVAL;
+  const bool masked = row_set || mask_tail || mask_head;
+  if (masked && (!row_set || !mask_tail || !mask_head)) return GE_EINVAL;
+  if (!masked && n_sets != 0) return GE_EINVAL;
+  if (pocket_accumulator && !accumulator) return GE_EINVAL;
+  if (reinterpret_cast<uintptr_t>(workspace) % 256 != 0) return GE_EINVAL;
+  if (2 * V > kRankMetricsMaxRows) return GE_ENOTSUP;
+  const RankTickWs w = rank_tick_ws(workspace, V);
+  SweepArgs tail{table, N, d, hr, V, true_id, cand, K, max_norm, /*cand_is_head=*/0, known_off_tail, known_rc_tail, w.raw,
+                 w.skip, w.true_loss, nullptr, /*spec=*/0, /*scores_only=*/0, /*sweep_flags=*/0};
+  SweepArgs head{table, N, d, hr ? hr + 2 * V : nullptr, V, true_id ? true_id + V : nullptr, cand, K, max_norm,
+                 /*cand_is_head=*/1, known_off_head, known_rc_head, w.raw + V, w.skip + V, w.true_loss + V, nullptr,
+                 /*spec=*/0, /*scores_only=*/0, /*sweep_flags=*/0};
+  const SetArgs sets_tail{row_set, mask_tail, n_sets, 0}, sets_head{row_set ? row_set + V : nullptr, mask_head, n_sets, 0};
+  if (int rc = sweep_args(tail, model, planes, nullptr, masked ? &sets_tail : nullptr)) return rc;
+  if (int rc = sweep_args(head, model, planes, nullptr, masked ? &sets_head : nullptr)) return rc;
+  const SweepRoute r = masked ? route_masked_rank(N, d, V, K, max_norm, table_mod16(tail))
+                              : route_rank(N, d, V, K, max_norm, table_mod16(tail));
+  if (r.kernel == SweepRoute::None) return r.status ? r.status : GE_EINVAL;
+  const bool f16 = r.kernel == SweepRoute::F16;
+  if (f16 && !planes) return GE_EINVAL;     // (no allocation in a tick: the split-precision sweep runs on the caller's planes)
+  const int64_t n = N * (int64_t)d;
+  if (pocket && !copy_if_ok(table, pocket, n)) return GE_EINVAL;
+  if (pocket_accumulator && !copy_if_ok(accumulator, pocket_accumulator, n)) return GE_EINVAL;
+  if (workspace_bytes < w.bytes) return GE_ENOMEM;
+
+  if (f16)
+    if (int rc = rank_planes_launch(table, N, d, cand, K, max_norm, tail.spec, planes, st)) return rc;
+  const void* pl = f16 ? planes : nullptr;
+  if (int rc = sweep_rank(tail, /*k0_returns=*/true, pl, masked ? &sets_tail : nullptr, stream)) return rc;
+  if (int rc = sweep_rank(head, /*k0_returns=*/true, pl, masked ? &sets_head : nullptr, stream)) return rc;
+  if (int rc = rank_metrics_launch(w.raw, w.skip, w.true_loss, 2 * V, metrics_out, best, w.flag, st)) return rc;
+  if (pocket)
+    if (int rc = copy_if_launch(table, pocket, n, w.flag, st)) return rc;
+  if (pocket_accumulator)
+    if (int rc = copy_if_launch(accumulator, pocket_accumulator, n, w.flag, st)) return rc;
+  return 0;
+}
+
 int ge_complex_rank_1vK(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* true_id,
                         const int32_t* cand, int64_t K, float max_norm, int cand_is_head, const int32_t* known_off,
                         const uint16_t* known_rc, int32_t* n_before, int32_t* n_known_before, float* true_loss,

@@ -76,6 +76,10 @@ int select_rows_launch(const int32_t* valid, int64_t V, int64_t B, uint64_t seed
                        hipStream_t st);
 int mean_pocket_launch(const float* loss, int64_t B, float* mean_out, float* best, int32_t* flag, hipStream_t st);
 int copy_if_launch(const float* src, float* dst, int64_t n, const int32_t* flag, hipStream_t st);
+bool copy_if_ok(const float* src, const float* dst, int64_t n);   // false: copy_if_launch would refuse these buffers
+// the summary of a rank sweep's counts (metrics_out [8]) and the pocket decision on its filtered MRR: one workgroup
+int rank_metrics_launch(const int32_t* n_before, const int32_t* n_known_before, const float* true_loss, int64_t M,
+                        float* metrics_out, float* best, int32_t* improved, hipStream_t st);
 
 // ge_1vk.hip: 1-vs-K candidate scoring
 int complex_score_1vK_launch(const float* table, int64_t N, int32_t d, const int32_t* hr, int64_t B, const int32_t* cand,

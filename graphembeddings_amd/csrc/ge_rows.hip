@@ -173,6 +173,78 @@ __global__ __launch_bounds__(1024) void mean_pocket_kernel(const float* __restri
   }
 }
 
+// one workgroup: the summary of holE.py:475-490 from the counts of a rank sweep, and the pocket bookkeeping on the
+// filtered MRR (higher is better).  Row i counts iff its true_loss is not NaN (the sweeps' bad rows: counts 0, true_loss
+// NaN -- they must not score as rank 1) and 0 <= n_known_before[i] <= n_before[i].  Every sum has one fixed order
+// (thread-strided, xor shuffles, the 16 wave partials in turn): two calls agree bitwise.  The rank sums and the hit
+// counts are integers, added as 64-bit integers and converted once; each output is one double division rounded to float.
+// n = 0: 0.0 / 0.0 = NaN in entries 0-6.
+__global__ __launch_bounds__(1024) void rank_metrics_kernel(const int32_t* __restrict__ n_before,
+                                                            const int32_t* __restrict__ n_known_before,
+                                                            const float* __restrict__ true_loss, int64_t M,
+                                                            float* __restrict__ metrics_out, float* __restrict__ best,
+                                                            int32_t* __restrict__ improved) {
+  __shared__ double part_d[2][16];
+  __shared__ long long part_i[6][16];
+  double inv_fil = 0.0, inv_raw = 0.0;
+  long long v[6] = {0, 0, 0, 0, 0, 0};      // sum of filtered ranks, of raw ranks, hits at 1 / 3 / 10, counted rows
+  for (int64_t i = threadIdx.x; i < M; i += 1024) {
+    const int32_t nb = n_before[i], nk = n_known_before[i];
+    if (nk < 0 || nk > nb) continue;
+    if (true_loss) {
+      const float tl = true_loss[i];
+      if (tl != tl) continue;
+    }
+    const long long raw = 1ll + nb, fil = raw - nk;
+    inv_fil += 1.0 / (double)fil;
+    inv_raw += 1.0 / (double)raw;
+    v[0] += fil;
+    v[1] += raw;
+    v[2] += fil <= 1;
+    v[3] += fil <= 3;
+    v[4] += fil <= 10;
+    v[5] += 1;
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    inv_fil += __shfl_xor(inv_fil, m, kWave);
+    inv_raw += __shfl_xor(inv_raw, m, kWave);
+#pragma unroll
+    for (int j = 0; j < 6; ++j) v[j] += __shfl_xor(v[j], m, kWave);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    part_d[0][threadIdx.x >> 6] = inv_fil;
+    part_d[1][threadIdx.x >> 6] = inv_raw;
+    for (int j = 0; j < 6; ++j) part_i[j][threadIdx.x >> 6] = v[j];
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double sf = 0.0, sr = 0.0;
+    long long t[6] = {0, 0, 0, 0, 0, 0};
+    for (int w = 0; w < 16; ++w) {
+      sf += part_d[0][w];
+      sr += part_d[1][w];
+      for (int j = 0; j < 6; ++j) t[j] += part_i[j][w];
+    }
+    const double n = (double)t[5];
+    const float mrr = (float)(sf / n);
+    metrics_out[0] = mrr;
+    metrics_out[1] = (float)(sr / n);
+    metrics_out[2] = (float)((double)t[0] / n);
+    metrics_out[3] = (float)((double)t[1] / n);
+    metrics_out[4] = (float)((100.0 * (double)t[2]) / n);
+    metrics_out[5] = (float)((100.0 * (double)t[3]) / n);
+    metrics_out[6] = (float)((100.0 * (double)t[4]) / n);
+    metrics_out[7] = (float)n;
+    bool better = false;
+    if (best) {
+      better = mrr > *best;                 // a NaN never improves, an equal value keeps the first best
+      if (better) *best = mrr;
+    }
+    if (improved) *improved = better ? 1 : 0;
+  }
+}
+
 // pocket <- table iff *flag (the flag is read on the device: no host decision, no synchronisation)
 __global__ __launch_bounds__(kBlock) void copy_if_kernel(const float4* __restrict__ src, float4* __restrict__ dst,
                                                          int64_t n4, const float* __restrict__ src_tail,
@@ -193,6 +265,19 @@ int select_rows_launch(const int32_t* valid, int64_t V, int64_t B, uint64_t seed
 int mean_pocket_launch(const float* loss, int64_t B, float* mean_out, float* best, int32_t* flag, hipStream_t st) {
   hipLaunchKernelGGL(mean_pocket_kernel, dim3(1), dim3(1024), 0, st, loss, B, mean_out, best, flag);
   return launch_status();
+}
+
+int rank_metrics_launch(const int32_t* n_before, const int32_t* n_known_before, const float* true_loss, int64_t M,
+                        float* metrics_out, float* best, int32_t* improved, hipStream_t st) {
+  hipLaunchKernelGGL(rank_metrics_kernel, dim3(1), dim3(1024), 0, st, n_before, n_known_before, true_loss, M, metrics_out,
+                     best, improved);
+  return launch_status();
+}
+
+// what copy_if_launch takes: 16-byte aligned buffers, or no more floats than its tail path copies
+bool copy_if_ok(const float* src, const float* dst, int64_t n) {
+  const bool vec = reinterpret_cast<uintptr_t>(src) % 16 == 0 && reinterpret_cast<uintptr_t>(dst) % 16 == 0;
+  return vec || n <= kBlock;
 }
 
 int copy_if_launch(const float* src, float* dst, int64_t n, const int32_t* flag, hipStream_t st) {

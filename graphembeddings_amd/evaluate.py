@@ -487,6 +487,111 @@ def evaluate_fb15k_style(embeddings: torch.Tensor, data, both_sides: bool = True
     return out
 
 
+class RankPocket:
+    """Validation ticks on the evaluation's own metric without a host round trip per tick (ge_rank_validation_tick): each
+    tick rebuilds the candidates' planes from the table as it is now, ranks every validation triple's tail and head among
+    `candidates` (filtered by known_triples; with candidate_sets = {"tail": CandidateSets, "head": CandidateSets} each
+    row against its relation's set, the constrained protocol of evaluate_constrained), takes the summary of mrr_and_hits
+    into `hist`, and copies the table into `pocket` -- and `accumulator` into `pocket_accumulator` -- iff the filtered
+    MRR is the best so far (`best`, a device scalar that starts at 0; a tie keeps the first).  The constructor does all
+    that does not depend on the table; tick() enqueues one native call; read() synchronises once for all pending ticks.
+    ValueError on the host: an empty validation set, a true entity that is no candidate, candidate sets outside the
+    masked sweep's embedding_dim range, a relation without a set."""
+
+    KEYS = ("filtered_mrr", "raw_mrr", "mean_filtered_pos", "mean_raw_pos", "hits1", "hits3", "hits10", "counted")
+
+    def __init__(self, embeddings: torch.Tensor, validation_triples, candidates, known_triples=None, *, accumulator=None,
+                 candidate_sets=None, max_norm: float = 1.0, keep_table: bool = True, capacity: int = 4096,
+                 model: str = "complex"):
+        self.model = H._sweep_model(model, "RankPocket", H._TRANSFORM_FIRST)
+        self.emb = emb = H._table(embeddings)
+        dev, (N, d) = emb.device, emb.shape
+        self.max_norm = float(max_norm)
+        valid = np.asarray(validation_triples.cpu() if isinstance(validation_triples, torch.Tensor) else validation_triples,
+                           dtype=np.int64).reshape(-1, 3)
+        if len(valid) == 0:
+            raise ValueError("RankPocket: the validation set is empty")
+        cand_np = CandidateSets._candidates(candidates)
+        if cand_np.max() >= N:
+            raise ValueError("RankPocket: a candidate id is outside the table")
+        if valid.min() < 0 or valid.max() >= N:
+            raise ValueError("RankPocket: a validation triple holds an id outside the table")
+        if (CandidateSets.positions_of(cand_np, valid[:, :2].reshape(-1)) < 0).any():
+            raise ValueError("a validation triple's true entity is not in the candidate list")
+        self.V, self.K = len(valid), cand_np.size
+        self.cand = torch.as_tensor(cand_np.astype(np.int32)).to(dev)
+        self.sets = None
+        if candidate_sets is not None:
+            if not H.split_sweep_ok(d, self.max_norm):
+                raise ValueError("RankPocket: candidate sets need the masked sweep: embedding_dim % 8 == 0 in 56 ... 288, "
+                                 "max_norm <= 8")
+            tail, head = candidate_sets["tail"], candidate_sets["head"]
+            for cs in (tail, head):
+                cs._check(self.cand, "RankPocket")
+            if tail.n_sets != head.n_sets:
+                raise ValueError("RankPocket: the tail and head candidate sets must hold the same number of sets")
+            if valid[:, 2].max() >= tail.n_sets:
+                raise ValueError("RankPocket: a validation relation has no candidate set")
+            self.sets = (tail, head)
+        q = torch.as_tensor(valid).to(dev)
+        self.hr = torch.cat([q[:, [0, 2]], q[:, [1, 2]]], 0).to(torch.int32).contiguous()
+        self.true_id = torch.cat([q[:, 1], q[:, 0]]).to(torch.int32).contiguous()
+        self.row_set = torch.cat([q[:, 2], q[:, 2]]).to(torch.int32).contiguous() if self.sets else None
+        self.known = (None, None, None, None)
+        if known_triples is not None and len(known_triples):
+            pos_of = torch.full((N,), -1, dtype=torch.int64, device=dev)
+            pos_of[self.cand.to(torch.int64)] = torch.arange(self.K, device=dev)
+            cells = []
+            for side, col in (("tail", 0), ("head", 1)):
+                index = known_triples[side] if isinstance(known_triples, dict) else KnownIndex(known_triples, N, side, dev)
+                cells += list(index.cells(q[:, col], q[:, 2], pos_of, self.K))
+            self.known = tuple(cells)
+        lib = H._lib.load()
+        nbytes = int(lib.ge_rank_planes_bytes(N, d, self.K)) if H.split_sweep_ok(d, self.max_norm) else 0
+        self.planes = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+        self._ws = torch.empty(max(int(lib.ge_rank_tick_workspace_bytes(self.V)), 256), dtype=torch.uint8, device=dev)
+        self.hist = torch.zeros(int(capacity), 8, dtype=torch.float32, device=dev)
+        self.best = torch.zeros((), dtype=torch.float32, device=dev)
+        self.accumulator = None
+        if accumulator is not None:
+            H._need_cuda(accumulator, "accumulator")
+            if accumulator.shape != emb.shape or accumulator.dtype != torch.float32 or not accumulator.is_contiguous():
+                raise ValueError("RankPocket: accumulator must be a contiguous float32 tensor of the table's shape")
+            self.accumulator = accumulator
+        self.pocket = torch.empty_like(emb) if keep_table else None
+        self.pocket_accumulator = torch.empty_like(accumulator) if keep_table and accumulator is not None else None
+        self._steps = []        # global step of each tick since the last read()
+
+    def tick(self, global_step: int) -> None:
+        if len(self._steps) >= self.hist.shape[0]:
+            raise RuntimeError("RankPocket: read() the pending ticks first (capacity %d)" % self.hist.shape[0])
+        ptr = lambda t: None if t is None else t.data_ptr()
+        sets = (ptr(self.row_set), self.sets[0].mask.data_ptr(), self.sets[1].mask.data_ptr(), self.sets[0].n_sets) \
+            if self.sets else (None, None, None, 0)
+        emb = self.emb
+        H._lib.call("ge_rank_validation_tick", emb.data_ptr(), emb.shape[0], emb.shape[1], self.hr.data_ptr(),
+                    self.true_id.data_ptr(), self.V, self.cand.data_ptr(), self.K, self.max_norm, self.model,
+                    *[ptr(t) for t in self.known], ptr(self.planes), *sets, ptr(self.accumulator),
+                    self.hist.data_ptr() + 32 * len(self._steps), self.best.data_ptr(), ptr(self.pocket),
+                    ptr(self.pocket_accumulator), self._ws.data_ptr(), self._ws.numel(), H._stream())
+        self._steps.append(int(global_step))
+
+    def read(self):
+        """[(global_step, metrics)] of the ticks since the last read, in order (synchronises): the keys of mrr_and_hits
+        plus `counted`, the number of rows that had a rank."""
+        n = len(self._steps)
+        if n == 0:
+            return []
+        rows = self.hist[:n].cpu().tolist()
+        out = []
+        for step, row in zip(self._steps, rows):
+            m = dict(zip(self.KEYS, row))
+            m["counted"] = int(m["counted"])
+            out.append((step, m))
+        self._steps = []
+        return out
+
+
 # ------------------------------------------------------------------ top-k prediction
 def _known_cells_rc(off: torch.Tensor, rc: torch.Tensor, n_cand: int):
     """(rows, columns) int64 of the per-tile known-cell lists of KnownIndex.cells."""

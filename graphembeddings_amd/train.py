@@ -15,10 +15,14 @@ ge_train_steps_logloss (--log_loss) -- no Python per step.
 Extras: --model hole (README.md:42 score), --seed, --max_steps, --checkpoint_seconds, --optimizer adagrad
 (AdagradOptimizer in place of holE.py:296's GradientDescentOptimizer: ge_train_steps_adagrad; the checkpoint then also
 holds `adagrad_accumulator`), --objective softmax (1-vs-all multiclass log-loss over all entities, both sides:
-hole.SoftmaxTrainer on ge_softmax_grad; ComplEx with AdaGrad on one GPU, no validation ticks; --softmax_samples K': sampled
-softmax, K' shared candidates a step on ge_softmax_sampled_grad; --softmax_candidate_sets types|observed: each row's
-softmax over its relation's candidate set, ge_softmax_masked_grad; --softmax_labels all: one row per distinct query with
-all its training answers as labels, ge_softmax_labels_grad).
+hole.SoftmaxTrainer on ge_softmax_grad; ComplEx with AdaGrad on one GPU, no validation ticks by default; --softmax_samples
+K': sampled softmax, K' shared candidates a step on ge_softmax_sampled_grad; --softmax_candidate_sets types|observed: each
+row's softmax over its relation's candidate set, ge_softmax_masked_grad; --softmax_labels all: one row per distinct query
+with all its training answers as labels, ge_softmax_labels_grad; --softmax_validation_ticks T: T ticks per epoch on the
+filtered MRR of --infer over the validation triples (of --infer --candidate_sets with --softmax_candidate_sets), each one
+native call -- evaluate.RankPocket on ge_rank_validation_tick -- that keeps the best table and accumulator in a device
+pocket, which model.ckpt.pt then follows (key `validation_mrr`); --softmax_validation_rows n ranks a seeded sample of
+the validation triples; --softmax_patience P stops after P ticks in a row without an improvement).
 """
 from __future__ import annotations
 
@@ -111,6 +115,17 @@ def build_parser() -> argparse.ArgumentParser:
                    help='With --objective softmax (1-vs-all, --softmax_samples 0): each row\'s softmax runs over the candidate '
                         'set of its relation and side -- the sets of --infer --candidate_sets, from train + valid -- instead '
                         'of over all entity rows.')
+    p.add_argument('--softmax_validation_ticks', type=int, default=0,
+                   help='With --objective softmax: validation ticks per epoch, evenly spaced, the last at the epoch\'s end.  '
+                        'Each takes the filtered MRR of --infer (of --infer --candidate_sets with '
+                        '--softmax_candidate_sets) over the validation triples on the device and keeps the best table; '
+                        'model.ckpt.pt then follows that table.  0: no ticks, the last table is saved.')
+    p.add_argument('--softmax_validation_rows', type=int, default=0,
+                   help='With --softmax_validation_ticks: rank only this many validation triples, the first of a '
+                        'permutation seeded by --seed (0: all of them).')
+    p.add_argument('--softmax_patience', type=int, default=0,
+                   help='With --softmax_validation_ticks: stop after this many consecutive ticks without an improvement '
+                        '(the host then reads every tick).  0: never stop early.')
     p.add_argument('--gpus', type=int, default=1,
                    help='Ranks (one per GPU) the table is row-sharded over; > 1 without a launcher: this program starts them '
                         '(graphembeddings_amd/launch.py).  --batch_size stays the GLOBAL batch.')
@@ -121,14 +136,24 @@ def checkpoint_path(output_dir: str) -> str:
     return os.path.join(output_dir, 'model.ckpt.pt')
 
 
-def save_checkpoint(output_dir: str, embeddings: torch.Tensor, global_step: int, adagrad_accumulator=None) -> None:
-    """adagrad_accumulator (--optimizer adagrad): stored beside the table; without it the file is what it always was."""
+def save_checkpoint(output_dir: str, embeddings: torch.Tensor, global_step: int, adagrad_accumulator=None,
+                    validation_mrr=None) -> None:
+    """adagrad_accumulator (--optimizer adagrad): stored beside the table; without it the file is what it always was.
+    validation_mrr (--softmax_validation_ticks): the filtered validation MRR of the tick whose table this is."""
     tmp = checkpoint_path(output_dir) + '.tmp'
     ck = {'embeddings': embeddings.detach().cpu(), 'global_step': int(global_step)}
     if adagrad_accumulator is not None:
         ck['adagrad_accumulator'] = adagrad_accumulator.detach().cpu()
+    if validation_mrr is not None:
+        ck['validation_mrr'] = float(validation_mrr)
     torch.save(ck, tmp)
     os.replace(tmp, checkpoint_path(output_dir))
+
+
+def checkpoint_validation_mrr(output_dir: str) -> float:
+    """The validation MRR a --softmax_validation_ticks run stored with its best table; 0 when the file holds none."""
+    v = torch.load(checkpoint_path(output_dir), weights_only=True).get('validation_mrr')
+    return 0.0 if v is None or not v > 0 else float(v)
 
 
 def load_checkpoint(output_dir: str, device='cuda', with_accumulator: bool = False):
@@ -160,6 +185,11 @@ def check_objective_flags(FLAGS, world: int = 1) -> None:
         raise SystemExit('--softmax_samples must not be negative (0: all entity rows)')
     sets = getattr(FLAGS, 'softmax_candidate_sets', 'none') or 'none'
     labels = getattr(FLAGS, 'softmax_labels', 'one') or 'one'
+    tick_flags = ('softmax_validation_ticks', 'softmax_validation_rows', 'softmax_patience')
+    ticks, rows, patience = (getattr(FLAGS, f, 0) or 0 for f in tick_flags)
+    for flag, value in zip(tick_flags, (ticks, rows, patience)):
+        if value < 0:
+            raise SystemExit('--{} must not be negative'.format(flag))
     if getattr(FLAGS, 'objective', 'hinge') != 'softmax':
         if samples > 0:
             raise SystemExit('--softmax_samples needs --objective softmax')
@@ -167,6 +197,10 @@ def check_objective_flags(FLAGS, world: int = 1) -> None:
             raise SystemExit('--softmax_candidate_sets needs --objective softmax')
         if labels != 'one':
             raise SystemExit('--softmax_labels needs --objective softmax')
+        for flag, value in zip(tick_flags, (ticks, rows, patience)):
+            if value > 0:
+                raise SystemExit('--{} needs --objective softmax (the hinge and log-loss loops have ticks of their '
+                                 'own)'.format(flag))
         return
     if sets != 'none' and samples > 0:
         raise SystemExit('--softmax_candidate_sets belongs to the 1-vs-all objective: drop --softmax_samples')
@@ -184,6 +218,33 @@ def check_objective_flags(FLAGS, world: int = 1) -> None:
         raise SystemExit('--objective softmax runs on one GPU (drop --gpus)')
     if not (FLAGS.softmax_scale > 0 and np.isfinite(FLAGS.softmax_scale)):
         raise SystemExit('--softmax_scale must be positive and finite')
+    if ticks == 0:
+        if rows > 0:
+            raise SystemExit('--softmax_validation_rows needs --softmax_validation_ticks')
+        if patience > 0:
+            raise SystemExit('--softmax_patience needs --softmax_validation_ticks')
+    elif sets != 'none' and not H.split_sweep_ok(FLAGS.embedding_dim, 1.0):
+        raise SystemExit('--softmax_validation_ticks with --softmax_candidate_sets ranks on the masked sweep: '
+                         '--embedding_dim must be a multiple of 8 in 56 ... 288')
+
+
+def ticks_since_best(mrrs, best: float = 0.0) -> int:
+    """How many of the latest ticks in a row did not improve, by the device pocket's rule replayed over the ticks' MRRs in
+    order: a tick improves iff its MRR is above the best so far (`best` to start with); a tie keeps the first best, a
+    NaN never improves.  What --softmax_patience compares against."""
+    since = 0
+    for m in mrrs:
+        if m > best:
+            best, since = m, 0
+        else:
+            since += 1
+    return since
+
+
+def tick_steps(steps_per_epoch: int, ticks: int) -> set:
+    """The steps of an epoch (counted from 1) after which a tick comes: `ticks` of them evenly spaced, the last at the
+    epoch's end; fewer where an epoch has fewer steps."""
+    return {-(-j * steps_per_epoch // ticks) for j in range(1, ticks + 1)} - {0}
 
 
 def run_softmax_training(data: D.HolEData, FLAGS, log=print) -> dict:
@@ -236,29 +297,114 @@ def run_softmax_training(data: D.HolEData, FLAGS, log=print) -> dict:
     elif FLAGS.resume_checkpoint:
         log('Checkpoint holds no AdaGrad accumulator: starting it at', FLAGS.adagrad_init)
     trainer.global_step = global_step
-    log('Objective softmax: no validation ticks (the hinge tick measures another objective); the mean loss of the last '
-        'step is logged per epoch')
-    t_start, last_write, loss = time.time(), time.time(), None
+    ticks = getattr(FLAGS, 'softmax_validation_ticks', 0) or 0
+    patience = getattr(FLAGS, 'softmax_patience', 0) or 0
+    # --softmax_validation_ticks: the tick is one native call (evaluate.RankPocket / ge_rank_validation_tick) -- planes,
+    # both sides' rank sweeps, the MRR and the pocket copies of the table and the accumulator all happen on the device;
+    # the host reads the numbers when it writes the file (after every tick only with --softmax_patience).  What ends up in
+    # model.ckpt.pt is the table, accumulator and global step of the best tick, as the hinge loop's write_pocket keeps it.
+    vp, best0, at = None, 0.0, set()
+    if ticks:
+        vp = softmax_rank_pocket(data, FLAGS, embeddings, trainer.accumulator, kind, log)
+        if FLAGS.resume_checkpoint:
+            best0 = checkpoint_validation_mrr(FLAGS.output_dir)
+            vp.best.fill_(best0)
+        at = tick_steps(batch_count - 1, ticks)
+    else:
+        log('Objective softmax: no validation ticks (the hinge tick measures another objective); the mean loss of the last '
+            'step is logged per epoch')
+    history = []
+    state = {'pocket_mrr': best0, 'pocket_step': global_step, 'best_logged': best0, 'last_write': time.time(),
+             'stopped': False}
+
+    def drain():
+        """Log the ticks since the last call, in order (one synchronisation).  The host sees every MRR in tick order, so it
+        knows which tick the device pocket holds: the first one with the highest MRR."""
+        for step, m in vp.read():
+            log('\tStep {} Validation MRR: {:.6f} (hits@10 {:.2f} %, mean rank {:.1f}, {} rows)...'.format(
+                step, m['filtered_mrr'], m['hits10'], m['mean_filtered_pos'], m['counted']))
+            history.append((step, m['filtered_mrr']))
+            if m['filtered_mrr'] > state['pocket_mrr']:
+                state['pocket_mrr'], state['pocket_step'] = m['filtered_mrr'], step
+
+    def write(epoch):
+        """Without ticks: the table as it is.  With ticks the file follows the device pocket: once per epoch, every
+        --checkpoint_seconds in between, and at the end."""
+        state['last_write'] = time.time()
+        if vp is None:
+            save_checkpoint(FLAGS.output_dir, embeddings, trainer.global_step, trainer.accumulator)
+            return
+        drain()
+        if not state['pocket_mrr'] > state['best_logged']:
+            return
+        state['best_logged'] = state['pocket_mrr']
+        save_checkpoint(FLAGS.output_dir, vp.pocket, state['pocket_step'], vp.pocket_accumulator,
+                        validation_mrr=state['pocket_mrr'])
+        log('Epoch {}, (Model saved with validation MRR {:.6f})'.format(epoch, state['pocket_mrr']))
+
+    t_start, loss = time.time(), None
     left = FLAGS.max_steps if FLAGS.max_steps else None
     for epoch in range(1, FLAGS.num_epochs + 1):
         log('Training epoch {}...'.format(epoch))
         n = batch_count - 1 if left is None else min(batch_count - 1, left)
-        for _ in range(n):
+        for i in range(1, n + 1):
             loss = trainer.run(1)
-            if FLAGS.checkpoint_seconds > 0 and time.time() - last_write >= FLAGS.checkpoint_seconds:
-                save_checkpoint(FLAGS.output_dir, embeddings, trainer.global_step, trainer.accumulator)
-                last_write = time.time()
-        save_checkpoint(FLAGS.output_dir, embeddings, trainer.global_step, trainer.accumulator)
-        last_write = time.time()
+            if i in at:
+                vp.tick(trainer.global_step)
+                if patience:
+                    drain()
+                    if ticks_since_best([m for _, m in history], best0) >= patience:
+                        state['stopped'] = True
+                        break
+            if FLAGS.checkpoint_seconds > 0 and time.time() - state['last_write'] >= FLAGS.checkpoint_seconds:
+                write(epoch)
+        write(epoch)
         log('Epoch {}, mean softmax loss {}'.format(epoch, float(loss.mean()) if loss is not None else float('nan')))
+        if state['stopped']:
+            break
         if left is not None:
             left -= n
             if left <= 0:
                 break
     torch.cuda.synchronize()
-    log('Done training -- epoch limit reached')
-    return {'steps': trainer.global_step - global_step, 'seconds': time.time() - t_start, 'global_step': trainer.global_step,
-            'final_mean_softmax_loss': float(loss.mean()) if loss is not None else float('nan')}
+    if state['stopped']:
+        log('Done training -- no improvement in {} validation ticks'.format(patience))
+    else:
+        log('Done training -- epoch limit reached')
+    res = {'steps': trainer.global_step - global_step, 'seconds': time.time() - t_start, 'global_step': trainer.global_step,
+           'final_mean_softmax_loss': float(loss.mean()) if loss is not None else float('nan')}
+    if vp is not None:
+        if not os.path.exists(checkpoint_path(FLAGS.output_dir)):      # no tick improved: the table as it is
+            save_checkpoint(FLAGS.output_dir, embeddings, trainer.global_step, trainer.accumulator)
+        res.update(pocket_mrr=state['pocket_mrr'], pocket_step=state['pocket_step'], history=history,
+                   stopped_early=state['stopped'])
+    return res
+
+
+def softmax_rank_pocket(data: D.HolEData, FLAGS, embeddings: torch.Tensor, accumulator: torch.Tensor, kind: str, log=print):
+    """The evaluate.RankPocket of a --softmax_validation_ticks run: the validation triples (the first
+    --softmax_validation_rows of a permutation seeded by --seed) ranked over every entity row in id order, filtered by
+    train + valid -- the candidates and the filter of --infer -- and, with --softmax_candidate_sets, against the sets of
+    --infer --candidate_sets."""
+    valid = data.validation_triples
+    if valid is None or len(valid) == 0:
+        raise ValueError('--softmax_validation_ticks needs validation triples (triples-valid.txt): none found')
+    valid = np.asarray(valid, dtype=np.int64)
+    rows = getattr(FLAGS, 'softmax_validation_rows', 0) or 0
+    if 0 < rows < len(valid):
+        valid = valid[np.random.default_rng(FLAGS.seed).permutation(len(valid))[:rows]]
+    cand = np.arange(data.relation_count, data.entity_count, dtype=np.int32)
+    known = np.concatenate([np.asarray(data.triples), np.asarray(data.validation_triples)], 0)
+    sets = None
+    if kind != 'none':
+        _, sets = E.constrained_sets(data, kind, device='cuda')
+    ticks = FLAGS.softmax_validation_ticks
+    vp = E.RankPocket(embeddings, valid, cand, known, accumulator=accumulator, candidate_sets=sets,
+                      capacity=max(64, 2 * (ticks + 2)))
+    log('Objective softmax: {} validation ticks per epoch on the filtered MRR of {} validation triples, both sides{}; '
+        'the checkpoint follows the best tick'.format(ticks, len(valid),
+                                                      '' if sets is None else ' ({} candidate sets)'.format(kind)))
+    return vp
 
 
 def run_training(data: D.HolEData, FLAGS, log=print) -> dict:

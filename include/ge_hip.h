@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define GE_VERSION 444 /* 0.4.4.4: + ge_softmax_labels_loss / _grad / _workspace_bytes (multi-label softmax: one row per query, all its answers) */
+#define GE_VERSION 445 /* 0.4.4.5: + ge_rank_metrics, ge_rank_validation_tick / ge_rank_tick_workspace_bytes (filtered-MRR validation ticks with a pocket) */
 
 /* argument errors (negative, -errno style) */
 #define GE_EINVAL (-22)  /* bad dimension / null pointer / misaligned buffer */
@@ -722,6 +722,51 @@ int ge_topk_1vK_masked(const float* table, int64_t N, int32_t d, const int32_t* 
                        const uint16_t* known_rc, int32_t k, int32_t* out_id, float* out_loss, const void* planes,
                        void* workspace, size_t workspace_bytes, const int32_t* row_set, const uint32_t* mask,
                        int32_t n_sets, void* stream);
+
+/* --- the summary of holE.py:475-490 from a rank sweep's counts, and a pocket decision on it, on the device.
+ * Row i of the M rows COUNTS iff true_loss is NULL or true_loss[i] is not NaN (the sweeps report a bad row as counts 0
+ * with true_loss NaN: it must not score as rank 1) and 0 <= n_known_before[i] <= n_before[i].  For a counted row raw =
+ * 1 + n_before, fil = raw - n_known_before; with n the number of counted rows, metrics_out [8] receives
+ *     [0] filtered MRR = mean 1 / fil    [1] raw MRR    [2] mean fil    [3] mean raw
+ *     [4] [5] [6] 100 * #{fil <= 1 / 3 / 10} / n        [7] n
+ * n = 0: entries 0-6 are NaN, entry 7 is 0.  Arithmetic: one workgroup; the reciprocal sums in double in one fixed
+ * order (two calls agree bitwise, no atomics), the rank sums and hit counts as 64-bit integers; each output is one
+ * double division rounded once to float ((100.0 * count) / n, sum / n).
+ * Pocket: improved = metrics_out[0] > *best (a NaN never improves, an equal value does not: the first best is kept, as
+ * ge_validation_tick keeps it); if improved, *best = metrics_out[0]; *improved (nullable) = 1 or 0.  best NULL: no
+ * decision, *improved = 0.
+ * GE_EINVAL: n_before, n_known_before or metrics_out NULL, M < 1.  GE_ENOTSUP: M > 2^24 (n stays exact in entry 7). */
+int ge_rank_metrics(const int32_t* n_before, const int32_t* n_known_before, const float* true_loss, int64_t M,
+                    float* metrics_out, float* best, int32_t* improved, void* stream);
+
+/* --- one validation tick on the evaluation's own metric, enqueued on `stream` without a host decision, a
+ * synchronisation or an allocation: `planes` rebuilt from the table as it is now (ge_rank_planes), the V tail-side rows
+ * ranked (cand_is_head = 0), the V head-side rows ranked (cand_is_head = 1), ge_rank_metrics over the 2V rows into
+ * metrics_out [8] and *best (device scalar, start it at 0), and -- iff this tick improved on *best -- pocket <- table
+ * and pocket_accumulator <- accumulator (each nullable; otherwise neither is touched).
+ *     hr [2V,2]       V rows (head, relation), then V rows (tail, relation);  true_id [2V]: their tails, then their heads
+ *     known_*_tail / known_*_head   ge_known_cells' lists of each side's V rows, as ge_rank_1vK takes them for B = V
+ *                     (both of a side NULL: unfiltered)
+ *     planes          ge_rank_planes_bytes(N, d, K) bytes, 256-byte aligned, overwritten by every call; NULL iff that
+ *                     size is 0 (the fp32 kernels then rank, and take no candidate sets)
+ *     row_set [2V], mask_tail, mask_head, n_sets   per-relation candidate sets as ge_rank_1vK_masked takes them, one
+ *                     mask per side; all NULL / 0: unmasked.  Every row is ranked against its set whether or not its
+ *                     true entity is admissible.
+ *     workspace       ge_rank_tick_workspace_bytes(V) bytes (the counts and true losses of the 2V rows and the flag;
+ *                     a multiple of 256, monotone, 0 for V < 1), 256-byte aligned
+ * The counts are ge_rank_1vK_planes' (ge_rank_1vK_masked's with masks), bit for bit; bad rows do not count.
+ * Refusals, all before the first launch, in this order: GE_EINVAL for V < 1, K < 1, metrics_out, best or workspace NULL;
+ * masks without row_set, row_set without both masks, n_sets != 0 without them; pocket_accumulator without accumulator;
+ * a workspace off 256 bytes.  GE_ENOTSUP for 2V > 2^24.  Then everything ge_rank_1vK_planes / ge_rank_1vK_masked refuse,
+ * with their codes (the masked form outside embedding_dim 56 ... 288 included); GE_EINVAL for planes NULL where the
+ * split-precision sweep runs, and for a pocket that is not 16-byte aligned; GE_ENOMEM for a workspace below the size. */
+size_t ge_rank_tick_workspace_bytes(int64_t V);
+int ge_rank_validation_tick(const float* table, int64_t N, int32_t d, const int32_t* hr, const int32_t* true_id, int64_t V,
+                            const int32_t* cand, int64_t K, float max_norm, int model, const int32_t* known_off_tail,
+                            const uint16_t* known_rc_tail, const int32_t* known_off_head, const uint16_t* known_rc_head,
+                            void* planes, const int32_t* row_set, const uint32_t* mask_tail, const uint32_t* mask_head,
+                            int32_t n_sets, const float* accumulator, float* metrics_out, float* best, float* pocket,
+                            float* pocket_accumulator, void* workspace, size_t workspace_bytes, void* stream);
 
 /* --- per-relation candidate sets on the translation models' sweeps over every entity (ge_transx_rank / ge_transr_rank,
  * ge_transx_topk / ge_transr_topk): the same type-constrained protocol (holE.py:493-499, 533-541), with candidate
