@@ -575,6 +575,100 @@ int ge_transx_train_steps_adagrad(int model, int l1, float* ent, int64_t n_ent, 
                                         (hipStream_t)stream);
 }
 
+// ---------------------------------------------------------------- RotatE
+// The shape and the two tables checked, in transx_model's order: present, sizes >= 1, ids fit the sort's 32-bit keys
+// (GE_EINVAL); d even and at most rotate_max_dim() (GE_ENOTSUP); 4-byte aligned (GE_EINVAL).
+static int rotate_model(const float* ent, int64_t E, const float* rel, int64_t R, int32_t d) {
+  if (!ent || !rel || E <= 0 || R <= 0 || E + R >= ((int64_t)1 << 31)) return GE_EINVAL;
+  if (d <= 0) return GE_EINVAL;
+  if (d % 2 || d > rotate_max_dim()) return GE_ENOTSUP;
+  if (!aligned4(ent) || !aligned4(rel)) return GE_EINVAL;
+  return 0;
+}
+// The two accumulators of an AdaGrad step, after rotate_model: present, 4-byte aligned, and their [E, d] and [R, d / 2]
+// floats share no byte with a table or with each other.
+static int rotate_accs(const float* ent, int64_t E, const float* rel, int64_t R, int32_t d, const float* acc_ent,
+                       const float* acc_rel) {
+  if (!acc_ent || !acc_rel || !aligned4(acc_ent) || !aligned4(acc_rel)) return GE_EINVAL;
+  struct Span { uintptr_t p, n; };
+  const uintptr_t ne = (uintptr_t)E * (uintptr_t)d * sizeof(float), nr = (uintptr_t)R * (uintptr_t)(d / 2) * sizeof(float);
+  const Span tabs[2] = {{(uintptr_t)ent, ne}, {(uintptr_t)rel, nr}}, accs[2] = {{(uintptr_t)acc_ent, ne}, {(uintptr_t)acc_rel, nr}};
+  auto overlap = [](const Span& a, const Span& b) { return a.p < b.p + b.n && b.p < a.p + a.n; };
+  for (const Span& a : accs)
+    for (const Span& t : tabs)
+      if (overlap(a, t)) return GE_EINVAL;
+  return overlap(accs[0], accs[1]) ? GE_EINVAL : 0;
+}
+static int rotate_step_args_ok(int64_t B, const int32_t* pos, const int32_t* neg, const float* loss, const void* workspace) {
+  if (!transx_batch_ok(B) || !pos || !neg || !loss || !workspace) return GE_EINVAL;
+  if (!aligned4(pos) || !aligned4(neg) || !aligned4(loss) || ((uintptr_t)workspace & 255)) return GE_EINVAL;
+  return 0;
+}
+
+int ge_rotate_max_dim(void) { return rotate_max_dim(); }
+
+int ge_rotate_score(int l1, const float* ent, int64_t n_ent, const float* rel, int64_t n_rel, int32_t d,
+                    const int32_t* triples, int64_t B, float* out, void* stream) {
+  if (int rc = rotate_model(ent, n_ent, rel, n_rel, d)) return rc;
+  if (B < 0) return GE_EINVAL;
+  if (B > 0 && (!triples || !out || !aligned4(triples) || !aligned4(out))) return GE_EINVAL;
+  return rotate_score_launch(l1, ent, n_ent, rel, n_rel, d, triples, B, out, (hipStream_t)stream);
+}
+
+size_t ge_rotate_step_workspace_bytes(int64_t n_ent, int64_t n_rel, int32_t d, int64_t B) {
+  if (n_ent <= 0 || n_rel <= 0 || d <= 0 || d % 2 || d > rotate_max_dim() || !transx_batch_ok(B)) return 0;
+  return rotate_ws_bytes(n_ent, n_rel, d, B);
+}
+
+int ge_rotate_hinge_step(int l1, float* ent, int64_t n_ent, float* rel, int64_t n_rel, int32_t d, const int32_t* pos,
+                         const int32_t* neg, int64_t B, float margin, float lr, float* loss, void* workspace,
+                         size_t workspace_bytes, void* stream) {
+  if (int rc = rotate_model(ent, n_ent, rel, n_rel, d)) return rc;
+  if (int rc = rotate_step_args_ok(B, pos, neg, loss, workspace)) return rc;
+  return rotate_step_run(l1, ent, n_ent, rel, n_rel, nullptr, nullptr, d, pos, neg, B, margin, lr, loss, workspace,
+                         workspace_bytes, (hipStream_t)stream);
+}
+
+int ge_rotate_adagrad_step(int l1, float* ent, int64_t n_ent, float* rel, int64_t n_rel, float* acc_ent, float* acc_rel,
+                           int32_t d, const int32_t* pos, const int32_t* neg, int64_t B, float margin, float lr,
+                           float* loss, void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = rotate_model(ent, n_ent, rel, n_rel, d)) return rc;
+  if (int rc = rotate_accs(ent, n_ent, rel, n_rel, d, acc_ent, acc_rel)) return rc;
+  if (int rc = rotate_step_args_ok(B, pos, neg, loss, workspace)) return rc;
+  return rotate_step_run(l1, ent, n_ent, rel, n_rel, acc_ent, acc_rel, d, pos, neg, B, margin, lr, loss, workspace,
+                         workspace_bytes, (hipStream_t)stream);
+}
+
+int ge_rotate_train_steps(int l1, float* ent, int64_t n_ent, float* rel, int64_t n_rel, int32_t d, const int32_t* triples,
+                          int64_t T, const int64_t* bh_key, const int32_t* bh_ent, const int64_t* bt_key,
+                          const int32_t* bt_ent, int64_t n_known, const uint32_t* tail_threshold, uint64_t seed,
+                          uint64_t first_step, int64_t n_steps, int64_t B, float margin, float lr, float* losses,
+                          void* workspace, size_t workspace_bytes, void* stream) {
+  SamplerArgs s;
+  if (int rc = rotate_model(ent, n_ent, rel, n_rel, d)) return rc;
+  if (!transx_batch_ok(B) || n_steps < 0 || !losses || !workspace || ((uintptr_t)workspace & 255)) return GE_EINVAL;
+  if (!sampler_ok(s, triples, T, tail_threshold, n_known, bh_key, bh_ent, bt_key, bt_ent, (int32_t)n_rel, (int32_t)n_ent))
+    return GE_EINVAL;
+  return rotate_train_steps_run(l1, ent, n_ent, rel, n_rel, nullptr, nullptr, d, s, seed, first_step, n_steps, B, margin,
+                                lr, losses, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int ge_rotate_train_steps_adagrad(int l1, float* ent, int64_t n_ent, float* rel, int64_t n_rel, float* acc_ent,
+                                  float* acc_rel, int32_t d, const int32_t* triples, int64_t T, const int64_t* bh_key,
+                                  const int32_t* bh_ent, const int64_t* bt_key, const int32_t* bt_ent, int64_t n_known,
+                                  const uint32_t* tail_threshold, uint64_t seed, uint64_t first_step, int64_t n_steps,
+                                  int64_t B, float margin, float lr, float* losses, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+  SamplerArgs s;
+  if (int rc = rotate_model(ent, n_ent, rel, n_rel, d)) return rc;
+  if (int rc = rotate_accs(ent, n_ent, rel, n_rel, d, acc_ent, acc_rel)) return rc;
+  if (!transx_batch_ok(B) || n_steps < 0 || !losses || !workspace || ((uintptr_t)workspace & 255)) return GE_EINVAL;
+  if (!sampler_ok(s, triples, T, tail_threshold, n_known, bh_key, bh_ent, bt_key, bt_ent, (int32_t)n_rel, (int32_t)n_ent))
+    return GE_EINVAL;
+  return rotate_train_steps_run(l1, ent, n_ent, rel, n_rel, acc_ent, acc_rel, d, s, seed, first_step, n_steps, B, margin,
+                                lr, losses, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
 // ---------------------------------------------------------------- TransR
 // 4B entity slots and every sorted position fit an int32
 static inline bool transr_batch_ok(int64_t B) { return sweep_batch_ok(B); }
@@ -708,6 +802,24 @@ int ge_transx_rank(int model, int l1, const float* ent, int64_t n_ent, const flo
   if (int rc = transx_model(m, model, l1, ent, n_ent, rel, n_rel, normal, ent_transfer, rel_transfer, d)) return rc;
   return trans_rank(m, triples, B, cand_is_head, {known_off, known_rc, n_before, n_known_before, true_dist, scores_out},
                     workspace, workspace_bytes, stream);
+}
+
+// RotatE's ranks over every entity (ge_rotate.hip): the tables, the outputs, B == 0 (returns 0), the launcher's GE_ENOMEM
+size_t ge_rotate_rank_workspace_bytes(int64_t n_ent, int64_t n_rel, int32_t d, int64_t B) {
+  if (n_ent <= 0 || n_rel <= 0 || d <= 0 || d % 2 || d > rotate_max_dim() || !sweep_batch_ok(B)) return 0;
+  return rotate_rank_ws_bytes(d, B);
+}
+
+int ge_rotate_rank(int l1, const float* ent, int64_t n_ent, const float* rel, int64_t n_rel, int32_t d,
+                   const int32_t* triples, int64_t B, int cand_is_head, const int32_t* known_off,
+                   const uint16_t* known_rc, int32_t* n_before, int32_t* n_known_before, float* true_dist,
+                   float* scores_out, void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = rotate_model(ent, n_ent, rel, n_rel, d)) return rc;
+  const RankOut o{known_off, known_rc, n_before, n_known_before, true_dist, scores_out};
+  if (int rc = rank_outputs_ok(B, triples, o, workspace)) return rc;
+  if (B == 0) return 0;
+  return rotate_rank_launch(l1, ent, n_ent, rel, n_rel, d, triples, B, cand_is_head, o, workspace, workspace_bytes,
+                            (hipStream_t)stream);
 }
 
 size_t ge_transr_rank_workspace_bytes(int64_t n_ent, int64_t n_rel, int32_t dim_e, int32_t dim_r, int64_t B) {

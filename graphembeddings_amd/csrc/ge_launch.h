@@ -366,6 +366,25 @@ size_t trans_relrank_ws_bytes(const TransModel& m, int64_t B);
 int trans_relrank_launch(const TransModel& m, const int32_t* tri, int64_t B, const RankOut& o, void* workspace,
                          size_t workspace_bytes, hipStream_t st);
 
+// ge_rotate.hip: RotatE (ent [E,d] as [Re | Im], rel [R,d/2] phases; d even, at most rotate_max_dim()): scoring, the
+// hinge step and native loop (acc_ent / acc_rel both null: SGD; both set: AdaGrad), ranks over every entity.  One
+// workspace size serves both optimizers and the loops.
+int rotate_max_dim();
+size_t rotate_ws_bytes(int64_t E, int64_t R, int32_t d, int64_t B);
+int rotate_score_launch(int l1, const float* ent, int64_t E, const float* rel, int64_t R, int32_t d, const int32_t* tri,
+                        int64_t B, float* out, hipStream_t st);
+int rotate_step_run(int l1, float* ent, int64_t E, float* rel, int64_t R, float* acc_ent, float* acc_rel, int32_t d,
+                    const int32_t* pos, const int32_t* neg, int64_t B, float margin, float lr, float* loss,
+                    void* workspace, size_t workspace_bytes, hipStream_t st);
+int rotate_train_steps_run(int l1, float* ent, int64_t E, float* rel, int64_t R, float* acc_ent, float* acc_rel,
+                           int32_t d, const SamplerArgs& sa, uint64_t seed, uint64_t first_step, int64_t n_steps,
+                           int64_t B, float margin, float lr, float* losses, void* workspace, size_t workspace_bytes,
+                           hipStream_t st);
+size_t rotate_rank_ws_bytes(int32_t d, int64_t B);
+int rotate_rank_launch(int l1, const float* ent, int64_t E, const float* rel, int64_t R, int32_t d, const int32_t* tri,
+                       int64_t B, int cand_is_head, const RankOut& o, void* workspace, size_t workspace_bytes,
+                       hipStream_t st);
+
 // ge_classify.hip: triple classification -- per-segment thresholds fitted from sorted labelled scores, the decision
 size_t threshold_fit_ws_bytes(int64_t M, int32_t n_seg);
 int threshold_fit_launch(const float* score, const int32_t* seg, const uint8_t* label, int64_t M, int32_t n_seg,

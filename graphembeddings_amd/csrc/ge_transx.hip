@@ -33,15 +33,12 @@
 #include "ge_common.h"
 #include "ge_bernoulli_dev.h"
 #include "ge_launch.h"
+#include "ge_transx_apply.h"   // stages 3 and 4: the apply kernels, shared with ge_rotate.hip
 
 namespace ge {
 
 constexpr int kTxMaxDim = 1024;
-constexpr int kWin = 32;                  // sorted slots per wave in the apply's first pass
 constexpr float kNormEps = 1e-12f;        // tf.nn.l2_normalize epsilon
-
-template <int VEC>
-__device__ __forceinline__ void ld(const float* __restrict__ row, int j, float (&v)[VEC]) { load_vec<VEC>(row + j * VEC, v); }
 
 template <bool L1>
 __device__ __forceinline__ float dist_term(float u) { return L1 ? fabsf(u) : u * u; }
@@ -272,172 +269,6 @@ __global__ __launch_bounds__(kBlock) void transx_grad_kernel(
   }
 }
 
-// ------------------------------------------------------------------------------------------- apply
-struct ApplyArgs {
-  float* ent; float* rel; float* ent2; float* rel2;
-  int64_t E, R; int d; int64_t n;               // n = 5B sorted slots
-  const uint32_t* keys; const uint32_t* slots;
-  const float* g0; const float* g1;
-  float* part;                                  // [nwin][2 (first, last run)][2 (plane)][d]
-  float lr;
-};
-
-template <int VEC>
-__device__ __forceinline__ void apply_row(const ApplyArgs& a, uint32_t k, int j, const float (&s0)[VEC], const float (&s1)[VEC]) {
-  const bool is_ent = k < (uint32_t)a.E;
-  float* t0 = is_ent ? a.ent + (int64_t)k * a.d : a.rel + ((int64_t)k - a.E) * a.d;
-  float* t1 = is_ent ? (a.ent2 ? a.ent2 + (int64_t)k * a.d : nullptr) : (a.rel2 ? a.rel2 + ((int64_t)k - a.E) * a.d : nullptr);
-  float v[VEC];
-  ld<VEC>(t0, j, v);
-#pragma unroll
-  for (int q = 0; q < VEC; ++q) v[q] -= a.lr * s0[q];
-  store_vec<VEC>(t0 + j * VEC, v);
-  if (t1) {
-    ld<VEC>(t1, j, v);
-#pragma unroll
-    for (int q = 0; q < VEC; ++q) v[q] -= a.lr * s1[q];
-    store_vec<VEC>(t1 + j * VEC, v);
-  }
-}
-
-__device__ __forceinline__ bool has_plane1(const ApplyArgs& a, uint32_t k) {
-  return k < (uint32_t)a.E ? a.ent2 != nullptr : a.rel2 != nullptr;
-}
-
-// The AdaGrad apply: ApplyArgs plus one accumulator per table (acc_ent2 / acc_rel2 null where ent2 / rel2 are).
-struct AdaArgs : ApplyArgs {
-  float* acc_ent; float* acc_rel; float* acc_ent2; float* acc_rel2;
-};
-
-// One row's AdaGrad update from its complete sums.  The table row and the accumulator row of both planes are requested
-// before any arithmetic; then one read-modify-write per array.  Plane 1's arrays are touched only where the key has one.
-template <int VEC>
-__device__ __forceinline__ void apply_row(const AdaArgs& a, uint32_t k, int j, const float (&s0)[VEC], const float (&s1)[VEC]) {
-  const bool is_ent = k < (uint32_t)a.E;
-  const int64_t off = (is_ent ? (int64_t)k : (int64_t)k - a.E) * a.d + (int64_t)j * VEC;
-  float* t0 = (is_ent ? a.ent : a.rel) + off;
-  float* c0 = (is_ent ? a.acc_ent : a.acc_rel) + off;
-  const bool p1 = has_plane1(a, k);
-  float* t1 = p1 ? (is_ent ? a.ent2 : a.rel2) + off : nullptr;
-  float* c1 = p1 ? (is_ent ? a.acc_ent2 : a.acc_rel2) + off : nullptr;
-  float v0[VEC], b0[VEC], v1[VEC], b1[VEC];
-  load_vec<VEC>(t0, v0); load_vec<VEC>(c0, b0);
-  if (p1) { load_vec<VEC>(t1, v1); load_vec<VEC>(c1, b1); }
-#pragma unroll
-  for (int q = 0; q < VEC; ++q) {
-    b0[q] = b0[q] + s0[q] * s0[q];
-    v0[q] -= a.lr * s0[q] / sqrtf(b0[q]);
-  }
-  store_vec<VEC>(c0, b0); store_vec<VEC>(t0, v0);
-  if (p1) {
-#pragma unroll
-    for (int q = 0; q < VEC; ++q) {
-      b1[q] = b1[q] + s1[q] * s1[q];
-      v1[q] -= a.lr * s1[q] / sqrtf(b1[q]);
-    }
-    store_vec<VEC>(c1, b1); store_vec<VEC>(t1, v1);
-  }
-}
-
-// Args: ApplyArgs (SGD) or AdaArgs (AdaGrad); it selects apply_row and nothing else.
-template <int VEC, class Args>
-__global__ __launch_bounds__(kBlock) void transx_apply_runs_kernel(Args a) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int64_t c = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
-  const int64_t nwin = (a.n + kWin - 1) / kWin;
-  if (c >= nwin) return;
-  const uint32_t sentinel = (uint32_t)(a.E + a.R);
-  const int64_t w0 = c * kWin, w1 = min(w0 + kWin, a.n);
-  const int nvec = a.d / VEC;
-  for (int j = lane; j < nvec; j += kWave) {
-    float s0[VEC], s1[VEC];
-#pragma unroll
-    for (int q = 0; q < VEC; ++q) s0[q] = s1[q] = 0.f;
-    int64_t rs = w0;                                    // start of the current run
-    for (int64_t p = w0; p < w1; ++p) {
-      const uint32_t k = a.keys[p];
-      if (k >= sentinel) break;                         // inactive slots sort last
-      const int64_t slot = a.slots[p];
-      const bool p1 = has_plane1(a, k);
-      float v[VEC];
-      ld<VEC>(a.g0 + slot * a.d, j, v);
-#pragma unroll
-      for (int q = 0; q < VEC; ++q) s0[q] += v[q];
-      if (p1) {
-        ld<VEC>(a.g1 + slot * a.d, j, v);
-#pragma unroll
-        for (int q = 0; q < VEC; ++q) s1[q] += v[q];
-      }
-      const bool seg_end = p + 1 == a.n || a.keys[p + 1] != k;
-      if (seg_end || p + 1 == w1) {
-        const bool head = rs == 0 || a.keys[rs - 1] != k;
-        if (head && seg_end) {
-          apply_row<VEC>(a, k, j, s0, s1);
-        } else {
-          float* dst = a.part + ((c * 2 + (head ? 1 : 0)) * 2) * a.d;
-          store_vec<VEC>(dst + j * VEC, s0);
-          if (p1) store_vec<VEC>(dst + a.d + j * VEC, s1);
-        }
-#pragma unroll
-        for (int q = 0; q < VEC; ++q) s0[q] = s1[q] = 0.f;
-        rs = p + 1;
-      }
-    }
-  }
-}
-
-// Cut segments (one per window that holds the head of a segment running past its end), then the batch loss.
-template <int VEC, class Args>
-__global__ __launch_bounds__(kBlock) void transx_apply_cut_kernel(Args a, const float* __restrict__ hinge,
-                                                                  int64_t B, float* __restrict__ loss) {
-  const int64_t nwin = (a.n + kWin - 1) / kWin;
-  if (blockIdx.x == gridDim.x - 1) {                  // the loss block: fixed-order sum of the hinge terms
-    __shared__ float red[kBlock];
-    float s = 0.f;
-    for (int64_t i = threadIdx.x; i < B; i += kBlock) s += hinge[i];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = kBlock / 2; w > 0; w >>= 1) {
-      if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) *loss = red[0];
-    return;
-  }
-  const int lane = threadIdx.x & (kWave - 1);
-  const int64_t c = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
-  if (c >= nwin) return;
-  const uint32_t sentinel = (uint32_t)(a.E + a.R);
-  const int64_t w0 = c * kWin, q = min(w0 + kWin, a.n) - 1;
-  const uint32_t k = a.keys[q];
-  if (k >= sentinel || q + 1 >= a.n || a.keys[q + 1] != k) return;      // the last run ends inside this window
-  if (a.keys[w0] == k && w0 > 0 && a.keys[w0 - 1] == k) return;       // ...or its head lies in an earlier window
-  const bool p1 = has_plane1(a, k);
-  const int nvec = a.d / VEC;
-  for (int j = lane; j < nvec; j += kWave) {
-    float s0[VEC], s1[VEC], v[VEC];
-    const float* src = a.part + ((c * 2 + 1) * 2) * a.d;
-    ld<VEC>(src, j, s0);
-    if (p1) ld<VEC>(src + a.d, j, s1);
-    else {
-#pragma unroll
-      for (int e = 0; e < VEC; ++e) s1[e] = 0.f;
-    }
-    for (int64_t cc = c + 1; cc < nwin && a.keys[cc * kWin] == k; ++cc) {
-      const float* pp = a.part + ((cc * 2 + 0) * 2) * a.d;
-      ld<VEC>(pp, j, v);
-#pragma unroll
-      for (int e = 0; e < VEC; ++e) s0[e] += v[e];
-      if (p1) {
-        ld<VEC>(pp + a.d, j, v);
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) s1[e] += v[e];
-      }
-    }
-    apply_row<VEC>(a, k, j, s0, s1);
-  }
-}
-
 // ------------------------------------------------------------------------------------------- draw (loop)
 #define GE_TAG_TXDRAW 0x74786472u
 
@@ -462,7 +293,6 @@ __global__ __launch_bounds__(kBlock) void transx_draw_kernel(
 
 // ------------------------------------------------------------------------------------------- host side
 static inline int lpt_for(int nvec) { return nvec <= 8 ? 8 : nvec <= 16 ? 16 : nvec <= 32 ? 32 : 64; }
-static inline unsigned key_bits(int64_t E, int64_t R) { return sort_key_bits(E + R); }   // the sentinel E + R
 
 struct TxWs {
   uint32_t *keys_in, *keys_out, *slots_in, *slots_out;
@@ -558,12 +388,6 @@ int transx_score_launch(const TransModel& m, const int32_t* tri, int64_t B, floa
 // The accumulators of an AdaGrad step as the kernels take them (ent2 / rel2's order); all null: plain SGD.
 struct TxAcc { float *ent = nullptr, *rel = nullptr, *ent2 = nullptr, *rel2 = nullptr; };
 
-template <int VEC, class Args>
-static void launch_apply(const Args& a, int grid_a, const float* hinge, int64_t B, float* loss, hipStream_t st) {
-  hipLaunchKernelGGL((transx_apply_runs_kernel<VEC, Args>), dim3(grid_a), dim3(kBlock), 0, st, a);
-  hipLaunchKernelGGL((transx_apply_cut_kernel<VEC, Args>), dim3(grid_a + 1), dim3(kBlock), 0, st, a, hinge, B, loss);
-}
-
 // One step on caller-given (or drawn) pos/neg; loss = one float.  acc.ent set: the AdaGrad apply.
 static int step_core(int model, int l1, float* ent, int64_t E, float* rel, int64_t R, float* ent2, float* rel2,
                      int32_t d, const int32_t* pos, const int32_t* neg, int64_t B, float margin, float lr, float* loss,
@@ -580,10 +404,8 @@ static int step_core(int model, int l1, float* ent, int64_t E, float* rel, int64
   hipError_t e = rocprim::radix_sort_pairs(w.sort_tmp, sb, w.keys_in, w.keys_out, w.slots_in, w.slots_out, (size_t)n,
                                            0u, key_bits(E, R), st);
   if (e != hipSuccess) return (int)e;
-  const ApplyArgs a{ent, rel, ent2, rel2, E, R, (int)d, n, w.keys_out, w.slots_out, w.g0, w.g1, w.part, lr};
-  const int64_t nwin = (n + kWin - 1) / kWin;
-  const int wpb = kBlock / kWave;
-  const int grid_a = (int)((nwin + wpb - 1) / wpb);
+  const ApplyArgs a{ent, rel, ent2, rel2, E, R, (int)d, n, w.keys_out, w.slots_out, w.g0, w.g1, w.part, lr, (int)d};
+  const int grid_a = apply_grid(n);
   if (acc.ent) {
     AdaArgs g;
     static_cast<ApplyArgs&>(g) = a;

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define GE_VERSION 445 /* 0.4.4.5: + ge_rank_metrics, ge_rank_validation_tick / ge_rank_tick_workspace_bytes (filtered-MRR validation ticks with a pocket) */
+#define GE_VERSION 446 /* 0.4.4.6: + ge_rotate_* (RotatE: scoring, hinge step with SGD / AdaGrad, native loops, ranks over every entity) */
 
 /* argument errors (negative, -errno style) */
 #define GE_EINVAL (-22)  /* bad dimension / null pointer / misaligned buffer */
@@ -401,6 +401,70 @@ int ge_transx_train_steps_adagrad(int model, int l1, float* ent, int64_t n_ent, 
                                   const uint32_t* tail_threshold, uint64_t seed, uint64_t first_step, int64_t n_steps,
                                   int64_t B, float margin, float lr, float* losses, void* workspace,
                                   size_t workspace_bytes, void* stream);
+
+/* --- RotatE (Sun et al., ICLR 2019): the translation model in the complex plane, t ~ h o r with |r_j| = 1.
+ * Row-major fp32 tables: ent [n_ent,d], d even, k = d / 2, a row [Re (k) | Im (k)] (the ComplEx table's split);
+ * rel [n_rel,k] holds PHASES theta in radians, unconstrained: never wrapped, never normalised.  The rotation is
+ * (c, s) = (cosf theta, sinf theta) from the accurate sincosf.  With u_j = h_j e^{i theta_j} - t_j (complex) and
+ * m_j = sqrtf(Re u_j^2 + Im u_j^2):
+ *   D = sum_j m_j (l1 != 0, the paper's norm)  or  D = sum_j m_j^2 (l1 = 0, no square root).
+ * Gradients: dD/du_j = g_j = u_j / m_j (0 where m_j == 0; 2 u_j for the squared norm), dD/dh_j = g_j conj(e^{i theta_j}),
+ * dD/dt_j = -g_j, dD/dtheta_j = Re g_j (-Im w_j) + Im g_j Re w_j with w_j = h_j e^{i theta_j}.
+ * Triples are int32 [B,3] (h, t, r).  The arguments follow the ge_transx_* entry points without `model`, with
+ * (ent, n_ent, rel, n_rel, d) in place of the five tables and (acc_ent, acc_rel) as the AdaGrad accumulators
+ * (acc_rel is [n_rel,k]).  Refused before any launch, in this order: GE_EINVAL for a null table, n_ent or n_rel < 1,
+ * n_ent + n_rel >= 2^31 or d < 1; GE_ENOTSUP for an odd d or d > ge_rotate_max_dim() (1024); GE_EINVAL for a table
+ * that is not 4-byte aligned; (AdaGrad) GE_EINVAL for an accumulator that is missing, not 4-byte aligned, or shares a
+ * byte with a table or the other accumulator; then whatever the ge_transx_* counterpart refuses about its other
+ * arguments; GE_ENOMEM below the size function, which answers 0 for a refused shape.  d % 8 == 0 with 16-byte aligned
+ * buffers takes the vectorised path, every other even d the scalar one.
+ * Not provided for this model: top-k prediction, candidate sets, relation prediction, the paper's self-adversarial
+ * loss, multi-GPU. */
+int ge_rotate_max_dim(void);
+/* out[i] = D of triple i ([B] fp32); NaN for a triple with an id out of range. */
+int ge_rotate_score(int l1, const float* ent, int64_t n_ent, const float* rel, int64_t n_rel, int32_t d,
+                    const int32_t* triples, int64_t B, float* out, void* stream);
+/* Workspace of one step (either optimizer) / of either native loop for B pairs: one size serves all four. */
+size_t ge_rotate_step_workspace_bytes(int64_t n_ent, int64_t n_rel, int32_t d, int64_t B);
+/* ge_transx_hinge_step's step on the two tables: loss = sum_i max(D(pos_i) - D(neg_i) + margin, 0), a pair active iff
+ * that argument is >= 0, gradients on the pre-step tables, duplicates summed in slot order (4i..4i+3 = pos h, pos t,
+ * neg h, neg t; 4B+i = the relation), row -= lr * sum.  neg_i must keep pos_i's relation; a pair with an id out of
+ * range or another relation is skipped.  *loss (device, one float) = the batch loss before the step.  No float atomics:
+ * two calls from one state give the same bits. */
+int ge_rotate_hinge_step(int l1, float* ent, int64_t n_ent, float* rel, int64_t n_rel, int32_t d, const int32_t* pos,
+                         const int32_t* neg, int64_t B, float margin, float lr, float* loss, void* workspace,
+                         size_t workspace_bytes, void* stream);
+/* The same step with ge_transx_adagrad_step's update: per row an active pair names, s = its summed gradient,
+ * acc[row] += s * s, row -= lr * s / sqrtf(acc[row]), on ent and on rel.  A row no active pair names is untouched in
+ * either array. */
+int ge_rotate_adagrad_step(int l1, float* ent, int64_t n_ent, float* rel, int64_t n_rel, float* acc_ent, float* acc_rel,
+                           int32_t d, const int32_t* pos, const int32_t* neg, int64_t B, float margin, float lr,
+                           float* loss, void* workspace, size_t workspace_bytes, void* stream);
+/* n_steps steps in one call: step s draws its batch as ge_transx_draw_batch(.., seed, first_step + s, ..) and runs
+ * ge_rotate_hinge_step (ge_rotate_adagrad_step) on it; losses[s] (device) = its batch loss.  n_steps = 0 returns 0 after
+ * the checks.  No host synchronisation inside. */
+int ge_rotate_train_steps(int l1, float* ent, int64_t n_ent, float* rel, int64_t n_rel, int32_t d, const int32_t* triples,
+                          int64_t T, const int64_t* bh_key, const int32_t* bh_ent, const int64_t* bt_key,
+                          const int32_t* bt_ent, int64_t n_known, const uint32_t* tail_threshold, uint64_t seed,
+                          uint64_t first_step, int64_t n_steps, int64_t B, float margin, float lr, float* losses,
+                          void* workspace, size_t workspace_bytes, void* stream);
+int ge_rotate_train_steps_adagrad(int l1, float* ent, int64_t n_ent, float* rel, int64_t n_rel, float* acc_ent,
+                                  float* acc_rel, int32_t d, const int32_t* triples, int64_t T, const int64_t* bh_key,
+                                  const int32_t* bh_ent, const int64_t* bt_key, const int32_t* bt_ent, int64_t n_known,
+                                  const uint32_t* tail_threshold, uint64_t seed, uint64_t first_step, int64_t n_steps,
+                                  int64_t B, float margin, float lr, float* losses, void* workspace,
+                                  size_t workspace_bytes, void* stream);
+/* Link-prediction ranks over every entity, ge_transx_rank's contract: candidates c in [0, n_ent) replace the tail
+ * (cand_is_head = 0) or the head; ascending (D, entity id); n_before, n_known_before (known_off / known_rc:
+ * ge_known_cells' lists, or both NULL), true_dist, optional scores_out [B, n_ent]; -1 / -1 / NaN for a row with an id out
+ * of range.  A row kernel stores q = h o e^{i theta} (tail side) or t o e^{-i theta} (head side) once; the sweep, the
+ * true distance and the filter pass evaluate one arithmetic on it, so the target never ranks before itself and the
+ * filter counts exactly the cells the sweep counted. */
+size_t ge_rotate_rank_workspace_bytes(int64_t n_ent, int64_t n_rel, int32_t d, int64_t B);
+int ge_rotate_rank(int l1, const float* ent, int64_t n_ent, const float* rel, int64_t n_rel, int32_t d,
+                   const int32_t* triples, int64_t B, int cand_is_head, const int32_t* known_off,
+                   const uint16_t* known_rc, int32_t* n_before, int32_t* n_known_before, float* true_dist,
+                   float* scores_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* --- TransR (transR.py).  Row-major fp32 tables: ent [n_ent,dim_e], rel [n_rel,dim_r] and rel_matrix
  * [n_rel, dim_r*dim_e], whose row r read as [dim_r][dim_e] is M_r.  Triples are int32 [B,3] (h, t, r).
