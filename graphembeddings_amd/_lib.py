@@ -137,6 +137,19 @@ SYMBOLS = {
     "ge_rotate_rank_workspace_bytes": (_sz, [_i64, _i64, _i32, _i64]),
     "ge_rotate_rank": (C.c_int, [C.c_int, _p, _i64, _p, _i64, _i32, _p, _i64, C.c_int, _p, _p, _p, _p, _p, _p, _p, _sz,
                                  _p]),
+    "ge_rotate_adv_max_negatives": (C.c_int, []),
+    "ge_rotate_adv_step_workspace_bytes": (_sz, [_i64, _i64, _i32, _i64, _i32]),
+    "ge_rotate_adv_loss": (C.c_int, [C.c_int, _p, _i64, _p, _i64, _i32, _p, _p, _p, _i64, _i32, _f, _f, _p, _p]),
+    "ge_rotate_adv_step": (C.c_int, [C.c_int, _p, _i64, _p, _i64, _i32, _p, _p, _p, _i64, _i32, _f, _f, _f, _p, _p, _sz,
+                                     _p]),
+    "ge_rotate_adv_adagrad_step": (C.c_int, [C.c_int, _p, _i64, _p, _i64, _p, _p, _i32, _p, _p, _p, _i64, _i32, _f, _f, _f,
+                                             _p, _p, _sz, _p]),
+    "ge_rotate_adv_draw_batch": (C.c_int, [_p, _i64, _i64, _p, _p, _p, _p, _i64, _p, _i32, _i32, _u64, _u64, _i32, _p, _p,
+                                           _p, _p]),
+    "ge_rotate_adv_train_steps": (C.c_int, [C.c_int, _p, _i64, _p, _i64, _i32, _p, _i64, _p, _p, _p, _p, _i64, _p, _u64,
+                                            _u64, _i64, _i64, _i32, _f, _f, _f, _p, _p, _sz, _p]),
+    "ge_rotate_adv_train_steps_adagrad": (C.c_int, [C.c_int, _p, _i64, _p, _i64, _p, _p, _i32, _p, _i64, _p, _p, _p, _p,
+                                                    _i64, _p, _u64, _u64, _i64, _i64, _i32, _f, _f, _f, _p, _p, _sz, _p]),
     "ge_transr_max_dim": (C.c_int, []),
     "ge_transr_score": (C.c_int, [C.c_int, _p, _i64, _p, _p, _i64, _i32, _i32, _p, _i64, _p, _p]),
     "ge_transr_step_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32, _i64]),
@@ -225,7 +238,7 @@ def load():
             fn = getattr(lib, name)  # AttributeError if the ABI and the header diverge
             fn.restype = res
             fn.argtypes = args
-        if lib.ge_version() < 446:
+        if lib.ge_version() < 447:
             raise RuntimeError("libge_hip.so is older than the Python host expects")
         _lib = lib
     return _lib

@@ -669,6 +669,116 @@ int ge_rotate_train_steps_adagrad(int l1, float* ent, int64_t n_ent, float* rel,
                                 lr, losses, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
+// ---------------------------------------------------------------- RotatE, the self-adversarial loss
+// What this loss adds to a step's or a loop's refusals, after the tables (and accumulators) and in front of the batch,
+// the output and the workspace checks, in this order: K < 1 (GE_EINVAL), K > the maximum (GE_ENOTSUP), (K + 3) B >= 2^31
+// (GE_EINVAL), then -- where the call takes them (rows = true) -- a null side or neg_ent (GE_EINVAL), a margin or alpha
+// that is not finite, alpha < 0 (GE_EINVAL).
+static inline bool adv_count_ok(int64_t B, int32_t K) { return B <= (((int64_t)1 << 31) - 1) / ((int64_t)K + 3); }
+static int rotate_adv_args(int32_t K, int64_t B, bool rows, const int32_t* side, const int32_t* neg_ent, float margin,
+                           float alpha) {
+  if (K < 1) return GE_EINVAL;
+  if (K > rotate_adv_max_negatives()) return GE_ENOTSUP;
+  if (!adv_count_ok(B, K)) return GE_EINVAL;
+  if (rows && (!side || !neg_ent)) return GE_EINVAL;
+  if (!std::isfinite(margin) || !std::isfinite(alpha) || alpha < 0.f) return GE_EINVAL;
+  return 0;
+}
+static int rotate_adv_step_args_ok(int64_t B, const int32_t* pos, const int32_t* side, const int32_t* neg_ent,
+                                   const float* loss, const void* workspace) {
+  if (B <= 0 || !pos || !loss || !workspace) return GE_EINVAL;
+  if (!aligned4(pos) || !aligned4(side) || !aligned4(neg_ent) || !aligned4(loss) || ((uintptr_t)workspace & 255)) return GE_EINVAL;
+  return 0;
+}
+
+int ge_rotate_adv_max_negatives(void) { return rotate_adv_max_negatives(); }
+
+size_t ge_rotate_adv_step_workspace_bytes(int64_t n_ent, int64_t n_rel, int32_t d, int64_t B, int32_t K) {
+  if (n_ent <= 0 || n_rel <= 0 || d <= 0 || d % 2 || d > rotate_max_dim() || B <= 0) return 0;
+  if (K < 1 || K > rotate_adv_max_negatives() || !adv_count_ok(B, K)) return 0;
+  return rotate_adv_ws_bytes(n_ent, n_rel, d, B, K);
+}
+
+int ge_rotate_adv_loss(int l1, const float* ent, int64_t n_ent, const float* rel, int64_t n_rel, int32_t d,
+                       const int32_t* pos, const int32_t* side, const int32_t* neg_ent, int64_t B, int32_t K,
+                       float margin, float alpha, float* out, void* stream) {
+  if (int rc = rotate_model(ent, n_ent, rel, n_rel, d)) return rc;
+  if (int rc = rotate_adv_args(K, B, B > 0, side, neg_ent, margin, alpha)) return rc;
+  if (B < 0) return GE_EINVAL;
+  if (B > 0 && (!pos || !out || !aligned4(pos) || !aligned4(side) || !aligned4(neg_ent) || !aligned4(out))) return GE_EINVAL;
+  return rotate_adv_loss_launch(l1, ent, n_ent, rel, n_rel, d, pos, side, neg_ent, B, K, margin, alpha, out,
+                                (hipStream_t)stream);
+}
+
+int ge_rotate_adv_step(int l1, float* ent, int64_t n_ent, float* rel, int64_t n_rel, int32_t d, const int32_t* pos,
+                       const int32_t* side, const int32_t* neg_ent, int64_t B, int32_t K, float margin, float alpha,
+                       float lr, float* loss, void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = rotate_model(ent, n_ent, rel, n_rel, d)) return rc;
+  if (int rc = rotate_adv_args(K, B, true, side, neg_ent, margin, alpha)) return rc;
+  if (int rc = rotate_adv_step_args_ok(B, pos, side, neg_ent, loss, workspace)) return rc;
+  return rotate_adv_step_run(l1, ent, n_ent, rel, n_rel, nullptr, nullptr, d, pos, side, neg_ent, B, K, margin, alpha, lr,
+                             loss, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int ge_rotate_adv_adagrad_step(int l1, float* ent, int64_t n_ent, float* rel, int64_t n_rel, float* acc_ent,
+                               float* acc_rel, int32_t d, const int32_t* pos, const int32_t* side,
+                               const int32_t* neg_ent, int64_t B, int32_t K, float margin, float alpha, float lr,
+                               float* loss, void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = rotate_model(ent, n_ent, rel, n_rel, d)) return rc;
+  if (int rc = rotate_accs(ent, n_ent, rel, n_rel, d, acc_ent, acc_rel)) return rc;
+  if (int rc = rotate_adv_args(K, B, true, side, neg_ent, margin, alpha)) return rc;
+  if (int rc = rotate_adv_step_args_ok(B, pos, side, neg_ent, loss, workspace)) return rc;
+  return rotate_adv_step_run(l1, ent, n_ent, rel, n_rel, acc_ent, acc_rel, d, pos, side, neg_ent, B, K, margin, alpha, lr,
+                             loss, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int ge_rotate_adv_draw_batch(const int32_t* triples, int64_t T, int64_t B, const int64_t* bh_key, const int32_t* bh_ent,
+                             const int64_t* bt_key, const int32_t* bt_ent, int64_t n_known,
+                             const uint32_t* tail_threshold, int32_t n_rel, int32_t n_ent, uint64_t seed, uint64_t step,
+                             int32_t K, int32_t* pos, int32_t* side, int32_t* neg_ent, void* stream) {
+  SamplerArgs s;
+  if (!sampler_ok(s, triples, T, tail_threshold, n_known, bh_key, bh_ent, bt_key, bt_ent, n_rel, n_ent)) return GE_EINVAL;
+  if (B < 0 || n_rel <= 0 || n_ent <= 0) return GE_EINVAL;
+  if (K < 1) return GE_EINVAL;
+  if (K > rotate_adv_max_negatives()) return GE_ENOTSUP;
+  if (!adv_count_ok(B, K) || (B > 0 && (!pos || !side || !neg_ent))) return GE_EINVAL;
+  return rotate_adv_draw_launch(s, B, K, seed, step, pos, side, neg_ent, (hipStream_t)stream);
+}
+
+int ge_rotate_adv_train_steps(int l1, float* ent, int64_t n_ent, float* rel, int64_t n_rel, int32_t d,
+                              const int32_t* triples, int64_t T, const int64_t* bh_key, const int32_t* bh_ent,
+                              const int64_t* bt_key, const int32_t* bt_ent, int64_t n_known,
+                              const uint32_t* tail_threshold, uint64_t seed, uint64_t first_step, int64_t n_steps,
+                              int64_t B, int32_t K, float margin, float alpha, float lr, float* losses, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+  SamplerArgs s;
+  if (int rc = rotate_model(ent, n_ent, rel, n_rel, d)) return rc;
+  if (int rc = rotate_adv_args(K, B, false, nullptr, nullptr, margin, alpha)) return rc;
+  if (B <= 0 || n_steps < 0 || !losses || !workspace || ((uintptr_t)workspace & 255)) return GE_EINVAL;
+  if (!sampler_ok(s, triples, T, tail_threshold, n_known, bh_key, bh_ent, bt_key, bt_ent, (int32_t)n_rel, (int32_t)n_ent))
+    return GE_EINVAL;
+  return rotate_adv_train_steps_run(l1, ent, n_ent, rel, n_rel, nullptr, nullptr, d, s, seed, first_step, n_steps, B, K,
+                                    margin, alpha, lr, losses, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int ge_rotate_adv_train_steps_adagrad(int l1, float* ent, int64_t n_ent, float* rel, int64_t n_rel, float* acc_ent,
+                                      float* acc_rel, int32_t d, const int32_t* triples, int64_t T,
+                                      const int64_t* bh_key, const int32_t* bh_ent, const int64_t* bt_key,
+                                      const int32_t* bt_ent, int64_t n_known, const uint32_t* tail_threshold,
+                                      uint64_t seed, uint64_t first_step, int64_t n_steps, int64_t B, int32_t K,
+                                      float margin, float alpha, float lr, float* losses, void* workspace,
+                                      size_t workspace_bytes, void* stream) {
+  SamplerArgs s;
+  if (int rc = rotate_model(ent, n_ent, rel, n_rel, d)) return rc;
+  if (int rc = rotate_accs(ent, n_ent, rel, n_rel, d, acc_ent, acc_rel)) return rc;
+  if (int rc = rotate_adv_args(K, B, false, nullptr, nullptr, margin, alpha)) return rc;
+  if (B <= 0 || n_steps < 0 || !losses || !workspace || ((uintptr_t)workspace & 255)) return GE_EINVAL;
+  if (!sampler_ok(s, triples, T, tail_threshold, n_known, bh_key, bh_ent, bt_key, bt_ent, (int32_t)n_rel, (int32_t)n_ent))
+    return GE_EINVAL;
+  return rotate_adv_train_steps_run(l1, ent, n_ent, rel, n_rel, acc_ent, acc_rel, d, s, seed, first_step, n_steps, B, K,
+                                    margin, alpha, lr, losses, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
 // ---------------------------------------------------------------- TransR
 // 4B entity slots and every sorted position fit an int32
 static inline bool transr_batch_ok(int64_t B) { return sweep_batch_ok(B); }

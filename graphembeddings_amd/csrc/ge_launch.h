@@ -385,6 +385,26 @@ int rotate_rank_launch(int l1, const float* ent, int64_t E, const float* rel, in
                        int64_t B, int cand_is_head, const RankOut& o, void* workspace, size_t workspace_bytes,
                        hipStream_t st);
 
+// ge_rotate_adv.hip: RotatE's self-adversarial negative-sampling loss on the same tables: B positives pos [B,3] with K
+// replacing entities each (neg_ent [B,K], side [B]: 0 replaces the tail, 1 the head).  Per-row losses, the step (acc_ent /
+// acc_rel both null: SGD; both set: AdaGrad), the draw of a step's (pos, side, neg_ent) and the native loop, which keeps
+// them in the workspace.  One workspace size serves both optimizers and the loops.
+int rotate_adv_max_negatives();
+size_t rotate_adv_ws_bytes(int64_t E, int64_t R, int32_t d, int64_t B, int32_t K);
+int rotate_adv_loss_launch(int l1, const float* ent, int64_t E, const float* rel, int64_t R, int32_t d,
+                           const int32_t* pos, const int32_t* side, const int32_t* neg_ent, int64_t B, int32_t K,
+                           float margin, float alpha, float* out, hipStream_t st);
+int rotate_adv_step_run(int l1, float* ent, int64_t E, float* rel, int64_t R, float* acc_ent, float* acc_rel, int32_t d,
+                        const int32_t* pos, const int32_t* side, const int32_t* neg_ent, int64_t B, int32_t K,
+                        float margin, float alpha, float lr, float* loss, void* workspace, size_t workspace_bytes,
+                        hipStream_t st);
+int rotate_adv_draw_launch(const SamplerArgs& s, int64_t B, int32_t K, uint64_t seed, uint64_t step, int32_t* pos,
+                           int32_t* side, int32_t* neg_ent, hipStream_t st);
+int rotate_adv_train_steps_run(int l1, float* ent, int64_t E, float* rel, int64_t R, float* acc_ent, float* acc_rel,
+                               int32_t d, const SamplerArgs& sa, uint64_t seed, uint64_t first_step, int64_t n_steps,
+                               int64_t B, int32_t K, float margin, float alpha, float lr, float* losses, void* workspace,
+                               size_t workspace_bytes, hipStream_t st);
+
 // ge_classify.hip: triple classification -- per-segment thresholds fitted from sorted labelled scores, the decision
 size_t threshold_fit_ws_bytes(int64_t M, int32_t n_seg);
 int threshold_fit_launch(const float* score, const int32_t* seg, const uint8_t* label, int64_t M, int32_t n_seg,

@@ -26,45 +26,16 @@
 
 #include "ge_common.h"
 #include "ge_launch.h"
+#include "ge_rotate_dev.h"     // Coord, coord, dist_term, dist_grad, kRotMaxDim
 #include "ge_transx_apply.h"
 
 namespace ge {
 namespace {
 
-constexpr int kRotMaxDim = 1024;
 constexpr int kRows = 16;                 // rows per sweep workgroup
 constexpr int kKnownTile = 128;           // ge_known_cells' tile edge
 
 __device__ __forceinline__ bool id_ok(int32_t x, int64_t n) { return x >= 0 && x < n; }
-
-// One complex coordinate of one triple under the rotation (c, s): w = h e^{i theta}, u = w - t, m2 = |u|^2.
-struct Coord { float wre, wim, ure, uim, m2; };
-
-__device__ __forceinline__ Coord coord(float hre, float him, float tre, float tim, float c, float s) {
-  Coord x;
-  x.wre = hre * c - him * s;
-  x.wim = hre * s + him * c;
-  x.ure = x.wre - tre;
-  x.uim = x.wim - tim;
-  x.m2 = x.ure * x.ure + x.uim * x.uim;
-  return x;
-}
-
-template <bool L1>
-__device__ __forceinline__ float dist_term(const Coord& x) { return L1 ? sqrtf(x.m2) : x.m2; }
-
-// g = dD/du of one coordinate
-template <bool L1>
-__device__ __forceinline__ void dist_grad(const Coord& x, float& gre, float& gim) {
-  if constexpr (L1) {
-    const float m = sqrtf(x.m2);
-    gre = m > 0.f ? x.ure / m : 0.f;
-    gim = m > 0.f ? x.uim / m : 0.f;
-  } else {
-    gre = 2.f * x.ure;
-    gim = 2.f * x.uim;
-  }
-}
 
 // ------------------------------------------------------------------------------------------- score
 // One group of LPT lanes per triple; a lane takes chunks of VEC complex coordinates.

@@ -270,8 +270,6 @@ __global__ __launch_bounds__(kBlock) void transx_grad_kernel(
 }
 
 // ------------------------------------------------------------------------------------------- draw (loop)
-#define GE_TAG_TXDRAW 0x74786472u
-
 // Positive i of step `step`: a uniform row of the triple list, with replacement (getBatch, init.cpp:229);
 // then the Bernoulli corruption of the same (seed, step, row).
 __global__ __launch_bounds__(kBlock) void transx_draw_kernel(

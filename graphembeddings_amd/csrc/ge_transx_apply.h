@@ -1,6 +1,7 @@
-// ge_transx_apply.h -- the apply stage of the translation family's hinge step, shared by ge_transx.hip (TransE /
-// TransH / TransD) and ge_rotate.hip (RotatE): the sorted (key, slot) list summed per destination row in slot order and
-// applied, as SGD (ApplyArgs) or AdaGrad (AdaArgs).
+// ge_transx_apply.h -- the apply stage of the translation family's steps, shared by ge_transx.hip (TransE / TransH /
+// TransD), ge_rotate.hip (RotatE's hinge step) and ge_rotate_adv.hip (RotatE's self-adversarial step, whose per-row losses
+// take the hinge terms' place): the sorted (key, slot) list summed per destination row in slot order and applied, as SGD
+// (ApplyArgs) or AdaGrad (AdaArgs).
 //   pass 1: one wave per window of kWin sorted positions sums each run of equal keys in slot order; a run that is a
 //           whole segment (its row's every slot) is applied at once, a run cut by a window edge is stored as a partial.
 //   pass 2: one wave per window that holds the head of a cut segment adds the following windows' partials in window
@@ -20,7 +21,7 @@ __device__ __forceinline__ void ld(const float* __restrict__ row, int j, float (
 
 struct ApplyArgs {
   float* ent; float* rel; float* ent2; float* rel2;
-  int64_t E, R; int d; int64_t n;               // n = 5B sorted slots
+  int64_t E, R; int d; int64_t n;               // n sorted slots: 5B (hinge), (K+3)B (self-adversarial)
   const uint32_t* keys; const uint32_t* slots;
   const float* g0; const float* g1;
   float* part;                                  // [nwin][2 (first, last run)][2 (plane)][d]

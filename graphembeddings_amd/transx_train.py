@@ -116,13 +116,13 @@ def check_eval_args(a) -> None:
             raise ValueError(f"no such file: {path}")
 
 
-def run(a, driver: str, make_model, name: str) -> int:
+def run(a, driver: str, make_model, name: str, trainer_kw=None) -> int:
     """Everything after the flags are checked: read --data_dir, build make_model(E, R), --load, train, save
     <name>.pt (with --neighbors_k, <name>_neighbors.tsv) and, with --test_file, rank it (heads and tails, printed)
     into <name>_test.json (with --relation_ranks, relations too; with --candidate_sets, the `constrained` block and
     line); with --predict_k, write <name>_predict.tsv (from the relation's set with --candidate_sets); with
     --predict_relations_k, <name>_predict_relations.tsv; with --classify, <name>_classify.json and
-    <name>_thresholds.tsv."""
+    <name>_thresholds.tsv.  trainer_kw: further keywords of the model's trainer() (rotate_train's loss)."""
     import numpy as np
     from .transx import read_kg, read_triples
     E, R, tri = read_kg(a.data_dir)
@@ -140,7 +140,7 @@ def run(a, driver: str, make_model, name: str) -> int:
         if adagrad and "adagrad_init" not in state:
             print(f"{a.load} holds no AdaGrad accumulators: they start at --adagrad_init {a.adagrad_init}")
     kw = dict(optimizer="adagrad", initial_accumulator_value=getattr(a, "adagrad_init", 0.1)) if adagrad else {}
-    tr = m.trainer(tri, B, margin=a.margin, learning_rate=a.learning_rate, seed=a.seed, **kw)
+    tr = m.trainer(tri, B, margin=a.margin, learning_rate=a.learning_rate, seed=a.seed, **kw, **(trainer_kw or {}))
     for epoch in range(a.train_times):
         res = float(tr.run(a.nbatches).double().sum())
         print(epoch)

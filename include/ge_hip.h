@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define GE_VERSION 446 /* 0.4.4.6: + ge_rotate_* (RotatE: scoring, hinge step with SGD / AdaGrad, native loops, ranks over every entity) */
+#define GE_VERSION 447 /* 0.4.4.7: + ge_rotate_adv_* (RotatE: the self-adversarial negative-sampling loss, its step with SGD / AdaGrad, draw and native loops) */
 
 /* argument errors (negative, -errno style) */
 #define GE_EINVAL (-22)  /* bad dimension / null pointer / misaligned buffer */
@@ -418,8 +418,7 @@ int ge_transx_train_steps_adagrad(int model, int l1, float* ent, int64_t n_ent, 
  * byte with a table or the other accumulator; then whatever the ge_transx_* counterpart refuses about its other
  * arguments; GE_ENOMEM below the size function, which answers 0 for a refused shape.  d % 8 == 0 with 16-byte aligned
  * buffers takes the vectorised path, every other even d the scalar one.
- * Not provided for this model: top-k prediction, candidate sets, relation prediction, the paper's self-adversarial
- * loss, multi-GPU. */
+ * Not provided for this model: top-k prediction, candidate sets, relation prediction, multi-GPU. */
 int ge_rotate_max_dim(void);
 /* out[i] = D of triple i ([B] fp32); NaN for a triple with an id out of range. */
 int ge_rotate_score(int l1, const float* ent, int64_t n_ent, const float* rel, int64_t n_rel, int32_t d,
@@ -465,6 +464,83 @@ int ge_rotate_rank(int l1, const float* ent, int64_t n_ent, const float* rel, in
                    const int32_t* triples, int64_t B, int cand_is_head, const int32_t* known_off,
                    const uint16_t* known_rc, int32_t* n_before, int32_t* n_known_before, float* true_dist,
                    float* scores_out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* --- RotatE, the self-adversarial negative-sampling loss (Sun et al., ICLR 2019, eq. 5-6) on the same tables.
+ * A batch has B positives pos [B,3] (h, t, r) with K negatives each; row i's negatives all replace the same side:
+ * side [B] int32 (0: the tail is replaced, 1: the head), neg_ent [B,K] int32 the replacing entity ids; negative j of row i
+ * is (h, neg_ent[i,j], r) or (neg_ent[i,j], t, r).  D = ge_rotate_score's distance in either norm, gamma = margin,
+ * alpha = adversarial_temperature >= 0:
+ *   p_ij   = softmax_j(-alpha D-_ij) over row i's live slots, a constant for the gradient (not differentiated)
+ *   loss_i = softplus(D+_i - gamma) + sum_j p_ij softplus(gamma - D-_ij)       softplus(x) = log(1 + e^x) = -log sigma(-x)
+ *   loss   = sum_i loss_i
+ *   dloss/dD+_i = sigma(D+_i - gamma)        dloss/dD-_ij = -p_ij sigma(gamma - D-_ij)
+ * The batch loss is a sum, as in every step of this family; the paper's (mean + mean) / 2 is this divided by 2B, a factor
+ * on lr.  alpha = 0 gives p = 1 / n_i, the paper's uniform baseline.
+ * Live slots and invalid rows: a slot whose id is outside [0, n_ent) is empty -- left out of the softmax, no gradient, its
+ * sort key the sentinel n_ent + n_rel; a row whose slots are all empty keeps its positive term alone; a slot that holds
+ * the true entity is an ordinary negative.  A row is invalid if a positive id is out of range or side is outside {0, 1}:
+ * it contributes 0 and names no row (ge_rotate_adv_loss writes NaN for it).  There are no inactive pairs: every valid row
+ * names its rows.
+ * Arithmetic: fp32 with the accurate expf / log1pf; softplus(x) = fmaxf(x, 0) + log1pf(expf(-fabsf(x))); sigma in the
+ * form that never overflows; the softmax max-subtracted (at alpha = 0 the exponent is 0 whatever D is); every sum in a
+ * fixed order.  On the head side the distances are evaluated as |h' - t e^{-i theta}| (the rank sweep's identity), on
+ * the tail side as |h e^{i theta} - t'|.
+ * The update is ge_rotate_hinge_step's / ge_rotate_adagrad_step's: gradients on the pre-step tables, duplicates summed in
+ * slot order by the same sort-and-apply stage, relation rows k = d / 2 wide.  Gradient slots of row i: (K+2) i + 0 and
+ * + 1 the positive's head and tail, (K+2) i + 2 + j negative j's replacing entity, (K+2) B + i the relation;
+ * n = (K+3) B slots in all.  The fixed entity of row i (h on the tail side, t on the head side) and its relation are the
+ * same table rows in the positive and in all K negatives: the negatives' contributions are added into the positive's slot
+ * for that entity and into the relation's slot in a fixed order (groups of j = q mod NT ascending, then a fixed tree),
+ * not written as K more rows.  No float atomics: two calls from one state give the same bits in the tables, the
+ * accumulators and the loss.
+ * Refused before any launch, in this order: what ge_rotate_hinge_step (ge_rotate_adagrad_step) refuses about the shape,
+ * the tables and the accumulators; GE_EINVAL for K < 1; GE_ENOTSUP for K > ge_rotate_adv_max_negatives() (1024);
+ * GE_EINVAL for (K + 3) B >= 2^31; GE_EINVAL for a null side or neg_ent (steps and ge_rotate_adv_loss with B > 0);
+ * GE_EINVAL for a margin or alpha that is not finite, then for alpha < 0; then GE_EINVAL for B < 1 (ge_rotate_adv_loss:
+ * B < 0; its B = 0 returns 0), a null or misaligned pos / side / neg_ent / loss(es) / workspace, n_steps < 0 and a bad
+ * sampler, as the hinge counterpart; GE_ENOMEM below the size function. */
+int ge_rotate_adv_max_negatives(void);
+/* Workspace of one step (either optimizer) / of either native loop: one size serves all four; 0 for a refused shape
+ * (the tables' sizes, d, B < 1, K outside [1, max], (K + 3) B >= 2^31). */
+size_t ge_rotate_adv_step_workspace_bytes(int64_t n_ent, int64_t n_rel, int32_t d, int64_t B, int32_t K);
+/* out[i] = loss_i ([B] fp32); NaN for an invalid row. */
+int ge_rotate_adv_loss(int l1, const float* ent, int64_t n_ent, const float* rel, int64_t n_rel, int32_t d,
+                       const int32_t* pos, const int32_t* side, const int32_t* neg_ent, int64_t B, int32_t K,
+                       float margin, float alpha, float* out, void* stream);
+/* One SGD step (row -= lr * sum) / one AdaGrad step (acc += s * s, row -= lr * s / sqrtf(acc)) on the loss above; *loss
+ * (device, one float) = the batch loss before the step. */
+int ge_rotate_adv_step(int l1, float* ent, int64_t n_ent, float* rel, int64_t n_rel, int32_t d, const int32_t* pos,
+                       const int32_t* side, const int32_t* neg_ent, int64_t B, int32_t K, float margin, float alpha,
+                       float lr, float* loss, void* workspace, size_t workspace_bytes, void* stream);
+int ge_rotate_adv_adagrad_step(int l1, float* ent, int64_t n_ent, float* rel, int64_t n_rel, float* acc_ent,
+                               float* acc_rel, int32_t d, const int32_t* pos, const int32_t* side,
+                               const int32_t* neg_ent, int64_t B, int32_t K, float margin, float alpha, float lr,
+                               float* loss, void* workspace, size_t workspace_bytes, void* stream);
+/* The batch of (seed, step): pos and the replaced side are ge_transx_draw_batch's of the same (seed, step) -- the same
+ * Philox words -- and neg_ent[i,j] is the entity that the word at row index i K + j under the tag 'advp' draws among
+ * those that are not known completions of (fixed entity, r): ge_bernoulli_corrupt_batch's pick with ent_lo = 0.  Picks
+ * may repeat.  A key with no free entity gives -1 in all K slots.  Refused: what ge_transx_draw_batch refuses, then K as
+ * above, then null outputs with B > 0. */
+int ge_rotate_adv_draw_batch(const int32_t* triples, int64_t T, int64_t B, const int64_t* bh_key, const int32_t* bh_ent,
+                             const int64_t* bt_key, const int32_t* bt_ent, int64_t n_known,
+                             const uint32_t* tail_threshold, int32_t n_rel, int32_t n_ent, uint64_t seed, uint64_t step,
+                             int32_t K, int32_t* pos, int32_t* side, int32_t* neg_ent, void* stream);
+/* n_steps steps in one call: step s draws ge_rotate_adv_draw_batch(.., seed, first_step + s, K, ..) into the workspace and
+ * runs ge_rotate_adv_step (ge_rotate_adv_adagrad_step) on it; losses[s] (device) = its batch loss.  n_steps = 0 returns 0
+ * after the checks.  No host synchronisation inside. */
+int ge_rotate_adv_train_steps(int l1, float* ent, int64_t n_ent, float* rel, int64_t n_rel, int32_t d,
+                              const int32_t* triples, int64_t T, const int64_t* bh_key, const int32_t* bh_ent,
+                              const int64_t* bt_key, const int32_t* bt_ent, int64_t n_known,
+                              const uint32_t* tail_threshold, uint64_t seed, uint64_t first_step, int64_t n_steps,
+                              int64_t B, int32_t K, float margin, float alpha, float lr, float* losses, void* workspace,
+                              size_t workspace_bytes, void* stream);
+int ge_rotate_adv_train_steps_adagrad(int l1, float* ent, int64_t n_ent, float* rel, int64_t n_rel, float* acc_ent,
+                                      float* acc_rel, int32_t d, const int32_t* triples, int64_t T,
+                                      const int64_t* bh_key, const int32_t* bh_ent, const int64_t* bt_key,
+                                      const int32_t* bt_ent, int64_t n_known, const uint32_t* tail_threshold,
+                                      uint64_t seed, uint64_t first_step, int64_t n_steps, int64_t B, int32_t K,
+                                      float margin, float alpha, float lr, float* losses, void* workspace,
+                                      size_t workspace_bytes, void* stream);
 
 /* --- TransR (transR.py).  Row-major fp32 tables: ent [n_ent,dim_e], rel [n_rel,dim_r] and rel_matrix
  * [n_rel, dim_r*dim_e], whose row r read as [dim_r][dim_e] is M_r.  Triples are int32 [B,3] (h, t, r).
