@@ -150,6 +150,19 @@ SYMBOLS = {
                                             _u64, _i64, _i64, _i32, _f, _f, _f, _p, _p, _sz, _p]),
     "ge_rotate_adv_train_steps_adagrad": (C.c_int, [C.c_int, _p, _i64, _p, _i64, _p, _p, _i32, _p, _i64, _p, _p, _p, _p,
                                                     _i64, _p, _u64, _u64, _i64, _i64, _i32, _f, _f, _f, _p, _p, _sz, _p]),
+    "ge_transx_adv_max_negatives": (C.c_int, []),
+    "ge_transx_adv_step_workspace_bytes": (_sz, [C.c_int, _i64, _i64, _i32, _i64, _i32]),
+    "ge_transx_adv_loss": (C.c_int, [C.c_int, C.c_int, _p, _i64, _p, _i64, _p, _p, _p, _i32, _p, _p, _p, _i64, _i32, _f, _f,
+                                     _p, _p]),
+    "ge_transx_adv_step": (C.c_int, [C.c_int, C.c_int, _p, _i64, _p, _i64, _p, _p, _p, _i32, _p, _p, _p, _i64, _i32, _f, _f,
+                                     _f, _p, _p, _sz, _p]),
+    "ge_transx_adv_adagrad_step": (C.c_int, [C.c_int, C.c_int, _p, _i64, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _p,
+                                             _p, _p, _i64, _i32, _f, _f, _f, _p, _p, _sz, _p]),
+    "ge_transx_adv_train_steps": (C.c_int, [C.c_int, C.c_int, _p, _i64, _p, _i64, _p, _p, _p, _i32, _p, _i64, _p, _p, _p, _p,
+                                            _i64, _p, _u64, _u64, _i64, _i64, _i32, _f, _f, _f, _p, _p, _sz, _p]),
+    "ge_transx_adv_train_steps_adagrad": (C.c_int, [C.c_int, C.c_int, _p, _i64, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _p,
+                                                    _i32, _p, _i64, _p, _p, _p, _p, _i64, _p, _u64, _u64, _i64, _i64, _i32,
+                                                    _f, _f, _f, _p, _p, _sz, _p]),
     "ge_transr_max_dim": (C.c_int, []),
     "ge_transr_score": (C.c_int, [C.c_int, _p, _i64, _p, _p, _i64, _i32, _i32, _p, _i64, _p, _p]),
     "ge_transr_step_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32, _i64]),

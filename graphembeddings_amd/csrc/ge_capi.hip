@@ -779,6 +779,97 @@ int ge_rotate_adv_train_steps_adagrad(int l1, float* ent, int64_t n_ent, float* 
                                     margin, alpha, lr, losses, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
+// ---------------------------------------------------------------- TransE / TransH / TransD, the self-adversarial loss
+// rotate_adv_args' checks and order between the model (and accumulators) and the batch; the draw is RotatE's.
+size_t ge_transx_adv_step_workspace_bytes(int model, int64_t n_ent, int64_t n_rel, int32_t d, int64_t B, int32_t K) {
+  if (model < GE_TRANSX_TRANSE || model > GE_TRANSX_TRANSD) return 0;
+  if (n_ent <= 0 || n_rel <= 0 || d <= 0 || d > transx_max_dim() || B <= 0) return 0;
+  if (K < 1 || K > transx_adv_max_negatives() || !adv_count_ok(B, K)) return 0;
+  return transx_adv_ws_bytes(model, n_ent, n_rel, d, B, K);
+}
+
+int ge_transx_adv_max_negatives(void) { return transx_adv_max_negatives(); }
+
+int ge_transx_adv_loss(int model, int l1, const float* ent, int64_t n_ent, const float* rel, int64_t n_rel,
+                       const float* normal, const float* ent_transfer, const float* rel_transfer, int32_t d,
+                       const int32_t* pos, const int32_t* side, const int32_t* neg_ent, int64_t B, int32_t K,
+                       float margin, float alpha, float* out, void* stream) {
+  TransModel m;
+  if (int rc = transx_model(m, model, l1, ent, n_ent, rel, n_rel, normal, ent_transfer, rel_transfer, d)) return rc;
+  if (int rc = rotate_adv_args(K, B, B > 0, side, neg_ent, margin, alpha)) return rc;
+  if (B < 0) return GE_EINVAL;
+  if (B > 0 && (!pos || !out || !aligned4(pos) || !aligned4(side) || !aligned4(neg_ent) || !aligned4(out))) return GE_EINVAL;
+  return transx_adv_loss_launch(m, pos, side, neg_ent, B, K, margin, alpha, out, (hipStream_t)stream);
+}
+
+int ge_transx_adv_step(int model, int l1, float* ent, int64_t n_ent, float* rel, int64_t n_rel, float* normal,
+                       float* ent_transfer, float* rel_transfer, int32_t d, const int32_t* pos, const int32_t* side,
+                       const int32_t* neg_ent, int64_t B, int32_t K, float margin, float alpha, float lr, float* loss,
+                       void* workspace, size_t workspace_bytes, void* stream) {
+  TransModel m;
+  if (int rc = transx_model(m, model, l1, ent, n_ent, rel, n_rel, normal, ent_transfer, rel_transfer, d)) return rc;
+  if (int rc = rotate_adv_args(K, B, true, side, neg_ent, margin, alpha)) return rc;
+  if (int rc = rotate_adv_step_args_ok(B, pos, side, neg_ent, loss, workspace)) return rc;
+  return transx_adv_step_run(model, l1, ent, n_ent, rel, n_rel, normal, ent_transfer, rel_transfer, nullptr, d, pos, side,
+                             neg_ent, B, K, margin, alpha, lr, loss, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int ge_transx_adv_adagrad_step(int model, int l1, float* ent, int64_t n_ent, float* rel, int64_t n_rel, float* normal,
+                               float* ent_transfer, float* rel_transfer, float* acc_ent, float* acc_rel,
+                               float* acc_normal, float* acc_ent_transfer, float* acc_rel_transfer, int32_t d,
+                               const int32_t* pos, const int32_t* side, const int32_t* neg_ent, int64_t B, int32_t K,
+                               float margin, float alpha, float lr, float* loss, void* workspace, size_t workspace_bytes,
+                               void* stream) {
+  TransModel m;
+  TransAccs c;
+  if (int rc = transx_model(m, model, l1, ent, n_ent, rel, n_rel, normal, ent_transfer, rel_transfer, d)) return rc;
+  if (int rc = transx_accs(c, m, acc_ent, acc_rel, acc_normal, acc_ent_transfer, acc_rel_transfer)) return rc;
+  if (int rc = rotate_adv_args(K, B, true, side, neg_ent, margin, alpha)) return rc;
+  if (int rc = rotate_adv_step_args_ok(B, pos, side, neg_ent, loss, workspace)) return rc;
+  return transx_adv_step_run(model, l1, ent, n_ent, rel, n_rel, normal, ent_transfer, rel_transfer, &c, d, pos, side,
+                             neg_ent, B, K, margin, alpha, lr, loss, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int ge_transx_adv_train_steps(int model, int l1, float* ent, int64_t n_ent, float* rel, int64_t n_rel, float* normal,
+                              float* ent_transfer, float* rel_transfer, int32_t d, const int32_t* triples, int64_t T,
+                              const int64_t* bh_key, const int32_t* bh_ent, const int64_t* bt_key, const int32_t* bt_ent,
+                              int64_t n_known, const uint32_t* tail_threshold, uint64_t seed, uint64_t first_step,
+                              int64_t n_steps, int64_t B, int32_t K, float margin, float alpha, float lr, float* losses,
+                              void* workspace, size_t workspace_bytes, void* stream) {
+  TransModel m;
+  SamplerArgs s;
+  if (int rc = transx_model(m, model, l1, ent, n_ent, rel, n_rel, normal, ent_transfer, rel_transfer, d)) return rc;
+  if (int rc = rotate_adv_args(K, B, false, nullptr, nullptr, margin, alpha)) return rc;
+  if (B <= 0 || n_steps < 0 || !losses || !workspace || ((uintptr_t)workspace & 255)) return GE_EINVAL;
+  if (!sampler_ok(s, triples, T, tail_threshold, n_known, bh_key, bh_ent, bt_key, bt_ent, (int32_t)n_rel, (int32_t)n_ent))
+    return GE_EINVAL;
+  return transx_adv_train_steps_run(model, l1, ent, n_ent, rel, n_rel, normal, ent_transfer, rel_transfer, nullptr, d, s,
+                                    seed, first_step, n_steps, B, K, margin, alpha, lr, losses, workspace,
+                                    workspace_bytes, (hipStream_t)stream);
+}
+
+int ge_transx_adv_train_steps_adagrad(int model, int l1, float* ent, int64_t n_ent, float* rel, int64_t n_rel,
+                                      float* normal, float* ent_transfer, float* rel_transfer, float* acc_ent,
+                                      float* acc_rel, float* acc_normal, float* acc_ent_transfer, float* acc_rel_transfer,
+                                      int32_t d, const int32_t* triples, int64_t T, const int64_t* bh_key,
+                                      const int32_t* bh_ent, const int64_t* bt_key, const int32_t* bt_ent,
+                                      int64_t n_known, const uint32_t* tail_threshold, uint64_t seed, uint64_t first_step,
+                                      int64_t n_steps, int64_t B, int32_t K, float margin, float alpha, float lr,
+                                      float* losses, void* workspace, size_t workspace_bytes, void* stream) {
+  TransModel m;
+  TransAccs c;
+  SamplerArgs s;
+  if (int rc = transx_model(m, model, l1, ent, n_ent, rel, n_rel, normal, ent_transfer, rel_transfer, d)) return rc;
+  if (int rc = transx_accs(c, m, acc_ent, acc_rel, acc_normal, acc_ent_transfer, acc_rel_transfer)) return rc;
+  if (int rc = rotate_adv_args(K, B, false, nullptr, nullptr, margin, alpha)) return rc;
+  if (B <= 0 || n_steps < 0 || !losses || !workspace || ((uintptr_t)workspace & 255)) return GE_EINVAL;
+  if (!sampler_ok(s, triples, T, tail_threshold, n_known, bh_key, bh_ent, bt_key, bt_ent, (int32_t)n_rel, (int32_t)n_ent))
+    return GE_EINVAL;
+  return transx_adv_train_steps_run(model, l1, ent, n_ent, rel, n_rel, normal, ent_transfer, rel_transfer, &c, d, s, seed,
+                                    first_step, n_steps, B, K, margin, alpha, lr, losses, workspace, workspace_bytes,
+                                    (hipStream_t)stream);
+}
+
 // ---------------------------------------------------------------- TransR
 // 4B entity slots and every sorted position fit an int32
 static inline bool transr_batch_ok(int64_t B) { return sweep_batch_ok(B); }

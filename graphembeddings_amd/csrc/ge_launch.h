@@ -398,11 +398,29 @@ int rotate_adv_step_run(int l1, float* ent, int64_t E, float* rel, int64_t R, fl
                         const int32_t* pos, const int32_t* side, const int32_t* neg_ent, int64_t B, int32_t K,
                         float margin, float alpha, float lr, float* loss, void* workspace, size_t workspace_bytes,
                         hipStream_t st);
+// (the draw reads no table: ge_transx_adv.hip's loops call it for TransE / TransH / TransD as well)
 int rotate_adv_draw_launch(const SamplerArgs& s, int64_t B, int32_t K, uint64_t seed, uint64_t step, int32_t* pos,
                            int32_t* side, int32_t* neg_ent, hipStream_t st);
 int rotate_adv_train_steps_run(int l1, float* ent, int64_t E, float* rel, int64_t R, float* acc_ent, float* acc_rel,
                                int32_t d, const SamplerArgs& sa, uint64_t seed, uint64_t first_step, int64_t n_steps,
                                int64_t B, int32_t K, float margin, float alpha, float lr, float* losses, void* workspace,
+                               size_t workspace_bytes, hipStream_t st);
+
+// ge_transx_adv.hip: the same loss for TransE / TransH / TransD on ge_transx.hip's tables and distance: per-row losses, the
+// step and the native loop (accs null: SGD; set: AdaGrad, the accumulators under their tables' names), with
+// ge_rotate_adv.hip's batch, slots and draw.  The workspace depends on the model: TransE has no second gradient plane.
+int transx_adv_max_negatives();
+size_t transx_adv_ws_bytes(int model, int64_t E, int64_t R, int32_t d, int64_t B, int32_t K);
+int transx_adv_loss_launch(const TransModel& m, const int32_t* pos, const int32_t* side, const int32_t* neg_ent, int64_t B,
+                           int32_t K, float margin, float alpha, float* out, hipStream_t st);
+int transx_adv_step_run(int model, int l1, float* ent, int64_t E, float* rel, int64_t R, float* normal, float* ent_transfer,
+                        float* rel_transfer, const TransAccs* accs, int32_t d, const int32_t* pos, const int32_t* side,
+                        const int32_t* neg_ent, int64_t B, int32_t K, float margin, float alpha, float lr, float* loss,
+                        void* workspace, size_t workspace_bytes, hipStream_t st);
+int transx_adv_train_steps_run(int model, int l1, float* ent, int64_t E, float* rel, int64_t R, float* normal,
+                               float* ent_transfer, float* rel_transfer, const TransAccs* accs, int32_t d,
+                               const SamplerArgs& sa, uint64_t seed, uint64_t first_step, int64_t n_steps, int64_t B,
+                               int32_t K, float margin, float alpha, float lr, float* losses, void* workspace,
                                size_t workspace_bytes, hipStream_t st);
 
 // ge_classify.hip: triple classification -- per-segment thresholds fitted from sorted labelled scores, the decision

@@ -29,6 +29,7 @@
 // ge_rotate.hip's hinge step.  No float atomics.
 #include <rocprim/device/device_radix_sort.hpp>
 
+#include "ge_adv_dev.h"      // softplus, sigmoid, the softmax's reductions: shared with ge_transx_adv.hip
 #include "ge_common.h"
 #include "ge_bernoulli_dev.h"
 #include "ge_launch.h"
@@ -38,39 +39,7 @@
 namespace ge {
 namespace {
 
-constexpr int kAdvMaxK = 1024;
-constexpr int kWaves = kBlock / kWave;
-
 __device__ __forceinline__ bool id_ok(int32_t x, int64_t n) { return x >= 0 && x < n; }
-
-// log(1 + e^x) = -log sigma(-x)
-__device__ __forceinline__ float softplus_dev(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }
-// sigma(x) in the form that never overflows
-__device__ __forceinline__ float sigmoid_stable(float x) {
-  const float e = expf(-fabsf(x));
-  return x >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
-}
-
-// -alpha D, and 0 at alpha == 0 whatever D is (a distance that overflowed to inf keeps its uniform weight)
-__device__ __forceinline__ float neg_scaled(float alpha, float D) { return alpha == 0.f ? 0.f : -alpha * D; }
-
-// Sum / maximum over the workgroup, to every thread: an xor tree in each wave, then the four waves in order.  The
-// leading barrier frees `red` of the previous reduction.
-__device__ __forceinline__ float block_sum(float v, float* red) {
-  v = group_sum<kWave>(v);
-  __syncthreads();
-  if ((threadIdx.x & (kWave - 1)) == 0) red[threadIdx.x / kWave] = v;
-  __syncthreads();
-  return ((red[0] + red[1]) + red[2]) + red[3];
-}
-__device__ __forceinline__ float block_max(float v, float* red) {
-#pragma unroll
-  for (int m = kWave / 2; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m, kWave));
-  __syncthreads();
-  if ((threadIdx.x & (kWave - 1)) == 0) red[threadIdx.x / kWave] = v;
-  __syncthreads();
-  return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-}
 
 // GRAD = false: the loss rows alone (NaN for an invalid row); keys, slots and g0 are not touched.
 template <bool L1, int VEC, int LPT, bool GRAD>
@@ -266,6 +235,7 @@ __global__ __launch_bounds__(kBlock) void rotate_adv_kernel(
 }
 
 // ------------------------------------------------------------------------------------------- draw (loop)
+// The draw reads no table: ge_transx_adv.hip's loops call rotate_adv_draw_launch for TransE / TransH / TransD as well.
 #define GE_TAG_ADVPICK 0x61647670u
 
 // One thread per (row i, negative j).  The positive and the side are ge_transx_draw_batch's of (seed, step, i): the same
@@ -304,8 +274,6 @@ __global__ __launch_bounds__(kBlock) void rotate_adv_draw_kernel(
 }
 
 // ------------------------------------------------------------------------------------------- host side
-inline int lpt_for(int nvec) { return nvec <= 8 ? 8 : nvec <= 16 ? 16 : nvec <= 32 ? 32 : 64; }
-
 // The step's workspace: sort keys and slots (in, out) [(K+3)B] each | loss rows [B] | gradient rows [(K+3)B, d] | the
 // apply's partials [windows][4][d] | the loop's pos [B,3], side [B], neg_ent [B,K] | rocPRIM's scratch; each padded to
 // 256 B.
@@ -357,7 +325,7 @@ void launch_adv_v(int lpt, int grid, hipStream_t st, const AdvArgs& a) {
 // v4: the float4 path (d % 8 == 0 and every buffer the kernels vector-load 16-byte aligned)
 template <bool GRAD>
 int launch_adv(int l1, bool v4, hipStream_t st, const AdvArgs& a) {
-  const int nvec = v4 ? a.d / 8 : a.d / 2, lpt = lpt_for(nvec);
+  const int nvec = v4 ? a.d / 8 : a.d / 2, lpt = adv_lpt_for(nvec);
   const int grid = grid_for(a.B, 1);
   if (v4) {
     if (l1) launch_adv_v<true, 4, GRAD>(lpt, grid, st, a);

@@ -22,78 +22,22 @@ from __future__ import annotations
 import math
 from typing import Dict, Optional
 
-import numpy as np
 import torch
 
 from . import _lib
-from .hole import _need_cuda, _stream
-from .transx import Trainer, TransX, _Model, read_kg, read_triples  # noqa: F401  (the same *2id.txt readers)
+from .hole import _stream
+# the same *2id.txt readers; the self-adversarial loss's shared host side (MAX_NEGATIVES = ge_rotate_adv_max_negatives())
+from .transx import (LOSSES, MAX_NEGATIVES, AdvTrainer, Trainer, TransX, _AdvLoss, _Model,  # noqa: F401
+                     check_adv_hyperparameters, read_kg, read_triples)
 
 MAX_DIM = 1024
-MAX_NEGATIVES = 1024            # ge_rotate_adv_max_negatives()
-LOSSES = ("hinge", "self_adversarial")
-
-
-def check_adv_hyperparameters(negatives, adversarial_temperature, margin) -> None:
-    """K in [1, MAX_NEGATIVES], alpha finite and >= 0, margin finite: ValueError otherwise (no device work)."""
-    if isinstance(negatives, bool) or not isinstance(negatives, (int, np.integer)) or not 1 <= negatives <= MAX_NEGATIVES:
-        raise ValueError(f"negatives must be an integer in [1, {MAX_NEGATIVES}], got {negatives!r}")
-    alpha = float(adversarial_temperature)
-    if not math.isfinite(alpha) or alpha < 0:
-        raise ValueError(f"adversarial_temperature must be finite and >= 0, got {adversarial_temperature!r}")
-    if not math.isfinite(float(margin)):
-        raise ValueError(f"margin must be finite, got {margin!r}")
-
-
-class AdvTrainer(Trainer):
-    """The native loop of the self-adversarial loss: the Trainer's positives and sides for the same seed, K filtered
-    negatives per positive (ge_rotate_adv_draw_batch), one ge_rotate_adv_train_steps[_adagrad] call per run().  Its
-    workspace depends on K as well as on B and is cached here, not in the model."""
-
-    def __init__(self, model, triples, batch_size: int, *, negatives: int, adversarial_temperature: float,
-                 margin: float = 1.0, learning_rate: float = 0.001, seed: int = 0):
-        check_adv_hyperparameters(negatives, adversarial_temperature, margin)
-        super().__init__(model, triples, batch_size, margin=margin, learning_rate=learning_rate, seed=seed)
-        self.K, self.alpha = int(negatives), float(adversarial_temperature)
-        self._ws = None
-
-    def workspace(self) -> torch.Tensor:
-        if self._ws is None:
-            self._ws = self.model._adv_workspace(self.B, self.K)
-        return self._ws
-
-    def draw(self, step: int):
-        """The (pos [B,3], side [B], neg_ent [B,K]) batch the loop uses at `step`."""
-        dev = self.triples.device
-        pos = torch.empty(self.B, 3, dtype=torch.int32, device=dev)
-        side = torch.empty(self.B, dtype=torch.int32, device=dev)
-        neg_ent = torch.empty(self.B, self.K, dtype=torch.int32, device=dev)
-        a = self._sampler_args()
-        _lib.call("ge_rotate_adv_draw_batch", *a[:2], self.B, *a[2:], self.sampler.n_rel, self.sampler.n_ent,
-                  self.seed & (2**64 - 1), int(step) & (2**64 - 1), self.K, pos.data_ptr(), side.data_ptr(),
-                  neg_ent.data_ptr(), _stream())
-        return pos, side, neg_ent
-
-    def run(self, n: int) -> torch.Tensor:
-        """n steps in one native call; returns the [n] per-step batch losses (device)."""
-        losses = torch.empty(max(int(n), 0), dtype=torch.float32, device=self.triples.device)
-        if n <= 0:
-            return losses
-        m, ws = self.model, self.workspace()
-        ada = self.optimizer == "adagrad"
-        _lib.call("ge_rotate_adv_train_steps_adagrad" if ada else "ge_rotate_adv_train_steps",
-                  *(m._adagrad_ptrs() if ada else m._ptrs()), *self._sampler_args(), self.seed & (2**64 - 1),
-                  self.step_count, int(n), self.B, self.K, self.margin, self.alpha, self.lr, losses.data_ptr(),
-                  ws.data_ptr(), ws.numel(), _stream())
-        self.step_count += int(n)
-        return losses
 
 
 def _out_of_scope(what: str):
     return NotImplementedError(f"RotatE has no {what}: the ge_rotate_* entry points score, train and rank over every entity")
 
 
-class RotatE(_Model):
+class RotatE(_AdvLoss, _Model):
     """The two tables of one RotatE model.  `l1` selects the sum of complex moduli (the paper's norm), else the sum of
     their squares."""
     PREFIX = "ge_rotate"
@@ -160,93 +104,9 @@ class RotatE(_Model):
                   *(self._adagrad_ptrs() if ada else self._ptrs()), *tr._sampler_args(), tr.seed & (2**64 - 1),
                   tr.step_count, n, tr.B, tr.margin, tr.lr, losses.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
 
-    # --- the self-adversarial negative-sampling loss (ge_rotate_adv_*)
-    _adv_ws = None                                       # ((B, K), workspace) of the last adv_step / adv_adagrad_step
-
-    def _adv_workspace(self, B: int, K: int) -> torch.Tensor:
-        nbytes = _lib.load().ge_rotate_adv_step_workspace_bytes(self.n_ent, self.n_rel, self.d, int(B), int(K))
-        if nbytes == 0:
-            raise RuntimeError("ge_rotate_adv_step_workspace_bytes failed")
-        return torch.empty(nbytes, dtype=torch.uint8, device=self.tables["ent"].device)
-
-    def _adv_step_workspace(self, B: int, K: int) -> torch.Tensor:
-        """The single steps' workspace, kept while (B, K) stays (as _Model.workspace keeps the hinge step's by B)."""
-        if self._adv_ws is None or self._adv_ws[0] != (B, K):
-            self._adv_ws = ((B, K), self._adv_workspace(B, K))
-        return self._adv_ws[1]
-
-    @staticmethod
-    def _adv_batch(pos, side, neg_ent, margin, alpha):
-        """(pos, side, neg_ent) as contiguous int32 device tensors; shapes, dtypes, K and the two hyperparameters are
-        checked first, on the host.  An int64 value that int32 does not hold is clamped to [-1, 2^31 - 1] before the
-        cast, so that it stays what it was: out of range (an empty slot, an invalid row), never wrapped into a valid id."""
-        for name, t in (("pos", pos), ("side", side), ("neg_ent", neg_ent)):
-            if not isinstance(t, torch.Tensor) or t.dtype not in (torch.int32, torch.int64):
-                raise ValueError(f"{name} must be an int32 or int64 tensor")
-        if pos.dim() != 2 or pos.shape[1] != 3 or pos.shape[0] == 0:
-            raise ValueError("pos must have shape [B, 3] (head, tail, relation) with B >= 1")
-        B = pos.shape[0]
-        if side.dim() != 1 or side.shape[0] != B:
-            raise ValueError("side must have shape [B]")
-        if neg_ent.dim() != 2 or neg_ent.shape[0] != B:
-            raise ValueError("neg_ent must have shape [B, K]")
-        check_adv_hyperparameters(int(neg_ent.shape[1]), alpha, margin)
-        out = []
-        for name, t in (("pos", pos), ("side", side), ("neg_ent", neg_ent)):
-            _need_cuda(t, name)
-            out.append((t.clamp(-1, 2**31 - 1) if t.dtype == torch.int64 else t).to(torch.int32).contiguous())
-        return out
-
-    def adv_loss(self, pos: torch.Tensor, side: torch.Tensor, neg_ent: torch.Tensor, margin: float,
-                 alpha: float) -> torch.Tensor:
-        """The [B] per-row self-adversarial losses (NaN for a row with a positive id out of range or a side outside
-        {0, 1}); a slot of neg_ent outside [0, n_ent) is empty."""
-        pb, sb, nb = self._adv_batch(pos, side, neg_ent, margin, alpha)
-        out = torch.empty(pb.shape[0], dtype=torch.float32, device=pb.device)
-        _lib.call("ge_rotate_adv_loss", *self._ptrs(), pb.data_ptr(), sb.data_ptr(), nb.data_ptr(), pb.shape[0],
-                  nb.shape[1], float(margin), float(alpha), out.data_ptr(), _stream())
-        return out
-
-    def _adv_step(self, entry, ptrs, pos, side, neg_ent, margin, alpha, lr):
-        pb, sb, nb = self._adv_batch(pos, side, neg_ent, margin, alpha)
-        ws = self._adv_step_workspace(pb.shape[0], nb.shape[1])
-        _lib.call(entry, *ptrs(), pb.data_ptr(), sb.data_ptr(), nb.data_ptr(), pb.shape[0], nb.shape[1], float(margin),
-                  float(alpha), float(lr), self._loss.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
-        return self._loss[0].clone()
-
-    def adv_step(self, pos, side, neg_ent, margin: float, alpha: float, lr: float) -> torch.Tensor:
-        """One SGD step on the summed self-adversarial loss; returns that batch loss (device scalar, before the step)."""
-        return self._adv_step("ge_rotate_adv_step", self._ptrs, pos, side, neg_ent, margin, alpha, lr)
-
-    def adv_adagrad_step(self, pos, side, neg_ent, margin: float, alpha: float, lr: float) -> torch.Tensor:
-        """The same step with AdaGrad's update (enable_adagrad() first)."""
-        self._adagrad_ptrs()
-        return self._adv_step("ge_rotate_adv_adagrad_step", self._adagrad_ptrs, pos, side, neg_ent, margin, alpha, lr)
-
-    def trainer(self, triples, batch_size: int, *, loss: str = "hinge", negatives: Optional[int] = None,
-                adversarial_temperature: Optional[float] = None, margin: float = 1.0, learning_rate: float = 0.001,
-                seed: int = 0, optimizer: str = "sgd", initial_accumulator_value: float = 0.1) -> Trainer:
-        """loss="hinge" (the default): _Model.trainer's loop, one negative per positive.  loss="self_adversarial": an
-        AdvTrainer with `negatives` = K per positive (default 64) and `adversarial_temperature` = alpha (default 1.0);
-        margin is gamma.  Either optimizer."""
-        if loss not in LOSSES:
-            raise ValueError(f"loss must be one of {LOSSES}, got {loss!r}")
-        if loss == "hinge":
-            if negatives is not None or adversarial_temperature is not None:
-                raise ValueError("negatives and adversarial_temperature need loss='self_adversarial'")
-            return super().trainer(triples, batch_size, margin=margin, learning_rate=learning_rate, seed=seed,
-                                   optimizer=optimizer, initial_accumulator_value=initial_accumulator_value)
-        K = 64 if negatives is None else negatives
-        alpha = 1.0 if adversarial_temperature is None else adversarial_temperature
-        check_adv_hyperparameters(K, alpha, margin)
-        if optimizer not in ("sgd", "adagrad"):
-            raise ValueError(f"optimizer must be 'sgd' or 'adagrad', got {optimizer!r}")
-        if optimizer == "adagrad":
-            self._trainer_adagrad(initial_accumulator_value)
-        tr = AdvTrainer(self, triples, batch_size, negatives=K, adversarial_temperature=alpha, margin=margin,
-                        learning_rate=learning_rate, seed=seed)
-        tr.optimizer = optimizer
-        return tr
+    # --- the self-adversarial negative-sampling loss (ge_rotate_adv_*): transx._AdvLoss's methods, _Model.trainer
+    def _adv_ws_bytes(self, B: int, K: int) -> int:
+        return _lib.load().ge_rotate_adv_step_workspace_bytes(self.n_ent, self.n_rel, self.d, B, K)
 
     # --- what this model does not have
     def rank_counts(self, triples: torch.Tensor, cand_is_head: bool = False, known_off: torch.Tensor = None,

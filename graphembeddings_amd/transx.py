@@ -6,9 +6,15 @@ Reference semantics: separate `ent [E,d]` / `rel [R,d]` tables (TransH adds `nor
 D = sum |h_p + r - t_p| (L1) or sum (h_p + r - t_p)^2, loss = sum_batch max(D+ - D- + margin, 0), plain SGD
 (tf.train.GradientDescentOptimizer) on every table, or TF1's AdagradOptimizer in its place (enable_adagrad,
 adagrad_step, trainer(optimizer="adagrad")).  There is no CPU path: every call runs a HIP kernel.
+
+The self-adversarial negative-sampling loss of Sun et al. 2019 (adv_loss / adv_step / adv_adagrad_step,
+trainer(loss="self_adversarial"); ge_transx_adv_*): K negatives per positive, all on one side of it, weighted by a
+softmax over their own scores that is not differentiated.  What it shares with RotatE (the batch checks, the
+hyperparameter checks, AdvTrainer) lives here, parametrised by the model's PREFIX; rotate.py re-exports it.
 """
 from __future__ import annotations
 
+import math
 import os
 from typing import Dict, Optional
 
@@ -21,6 +27,8 @@ from .hole import BernoulliSampler, _need_cuda, _stream, init_embeddings
 MODELS = {"transe": 0, "transh": 1, "transd": 2}
 # the extra tables of each model, in the order they are stored
 EXTRA_TABLES = {"transe": (), "transh": ("normal_vector",), "transd": ("ent_transfer", "rel_transfer")}
+MAX_NEGATIVES = 1024            # ge_rotate_adv_max_negatives() and ge_transx_adv_max_negatives()
+LOSSES = ("hinge", "self_adversarial")
 
 
 def _count(path: str) -> int:
@@ -141,6 +149,62 @@ class Trainer:
         if n <= 0:
             return losses
         self.model._train_steps(self, int(n), losses, self.model.workspace(self.B))
+        self.step_count += int(n)
+        return losses
+
+
+def check_adv_hyperparameters(negatives, adversarial_temperature, margin) -> None:
+    """K in [1, MAX_NEGATIVES], alpha finite and >= 0, margin finite: ValueError otherwise (no device work)."""
+    if isinstance(negatives, bool) or not isinstance(negatives, (int, np.integer)) or not 1 <= negatives <= MAX_NEGATIVES:
+        raise ValueError(f"negatives must be an integer in [1, {MAX_NEGATIVES}], got {negatives!r}")
+    alpha = float(adversarial_temperature)
+    if not math.isfinite(alpha) or alpha < 0:
+        raise ValueError(f"adversarial_temperature must be finite and >= 0, got {adversarial_temperature!r}")
+    if not math.isfinite(float(margin)):
+        raise ValueError(f"margin must be finite, got {margin!r}")
+
+
+class AdvTrainer(Trainer):
+    """The native loop of the self-adversarial loss: the Trainer's positives and sides for the same seed, K filtered
+    negatives per positive (ge_rotate_adv_draw_batch, which reads no table and serves every model), one
+    <PREFIX>_adv_train_steps[_adagrad] call per run().  Its workspace depends on K as well as on B and is cached here,
+    not in the model."""
+
+    def __init__(self, model, triples, batch_size: int, *, negatives: int, adversarial_temperature: float,
+                 margin: float = 1.0, learning_rate: float = 0.001, seed: int = 0):
+        check_adv_hyperparameters(negatives, adversarial_temperature, margin)
+        super().__init__(model, triples, batch_size, margin=margin, learning_rate=learning_rate, seed=seed)
+        self.K, self.alpha = int(negatives), float(adversarial_temperature)
+        self._ws = None
+
+    def workspace(self) -> torch.Tensor:
+        if self._ws is None:
+            self._ws = self.model._adv_workspace(self.B, self.K)
+        return self._ws
+
+    def draw(self, step: int):
+        """The (pos [B,3], side [B], neg_ent [B,K]) batch the loop uses at `step`."""
+        dev = self.triples.device
+        pos = torch.empty(self.B, 3, dtype=torch.int32, device=dev)
+        side = torch.empty(self.B, dtype=torch.int32, device=dev)
+        neg_ent = torch.empty(self.B, self.K, dtype=torch.int32, device=dev)
+        a = self._sampler_args()
+        _lib.call("ge_rotate_adv_draw_batch", *a[:2], self.B, *a[2:], self.sampler.n_rel, self.sampler.n_ent,
+                  self.seed & (2**64 - 1), int(step) & (2**64 - 1), self.K, pos.data_ptr(), side.data_ptr(),
+                  neg_ent.data_ptr(), _stream())
+        return pos, side, neg_ent
+
+    def run(self, n: int) -> torch.Tensor:
+        """n steps in one native call; returns the [n] per-step batch losses (device)."""
+        losses = torch.empty(max(int(n), 0), dtype=torch.float32, device=self.triples.device)
+        if n <= 0:
+            return losses
+        m, ws = self.model, self.workspace()
+        ada = self.optimizer == "adagrad"
+        _lib.call(m.PREFIX + ("_adv_train_steps_adagrad" if ada else "_adv_train_steps"),
+                  *(m._adagrad_ptrs() if ada else m._ptrs()), *self._sampler_args(), self.seed & (2**64 - 1),
+                  self.step_count, int(n), self.B, self.K, self.margin, self.alpha, self.lr, losses.data_ptr(),
+                  ws.data_ptr(), ws.numel(), _stream())
         self.step_count += int(n)
         return losses
 
@@ -329,16 +393,38 @@ class _Model:
         from .classify import triple_classification
         return triple_classification(self, valid_pos, test_pos, valid_neg, test_neg, known=known, seed=seed, mode=mode)
 
-    def trainer(self, triples, batch_size: int, *, margin: float = 1.0, learning_rate: float = 0.001,
+    def trainer(self, triples, batch_size: int, *, loss: str = "hinge", negatives: Optional[int] = None,
+                adversarial_temperature: Optional[float] = None, margin: float = 1.0, learning_rate: float = 0.001,
                 seed: int = 0, optimizer: str = "sgd", initial_accumulator_value: float = 0.1) -> Trainer:
-        """The model's native loop.  optimizer="sgd" (the default) is the model's own step: plain SGD for TransX, Adam
-        for TransR.  optimizer="adagrad" (TransX only) enables AdaGrad with initial_accumulator_value unless the model
-        already has accumulators, which are kept; its run(n) is one ge_transx_train_steps_adagrad call."""
+        """The model's native loop.  optimizer="sgd" (the default) is the model's own step: plain SGD for TransX and
+        RotatE, Adam for TransR.  optimizer="adagrad" (not TransR) enables AdaGrad with initial_accumulator_value unless
+        the model already has accumulators, which are kept; its run(n) is one <PREFIX>_train_steps_adagrad call.
+        loss="hinge" (the default): one negative per positive under the margin hinge.  loss="self_adversarial" (TransX
+        and RotatE): an AdvTrainer with `negatives` = K per positive (default 64) and `adversarial_temperature` = alpha
+        (default 1.0); margin is gamma.  Either optimizer."""
+        if loss not in LOSSES:
+            raise ValueError(f"loss must be one of {LOSSES}, got {loss!r}")
+        if loss == "hinge":
+            if negatives is not None or adversarial_temperature is not None:
+                raise ValueError("negatives and adversarial_temperature need loss='self_adversarial'")
+            if optimizer not in ("sgd", "adagrad"):
+                raise ValueError(f"optimizer must be 'sgd' or 'adagrad', got {optimizer!r}")
+            if optimizer == "adagrad":
+                self._trainer_adagrad(initial_accumulator_value)
+            tr = self._trainer(self, triples, batch_size, margin=margin, learning_rate=learning_rate, seed=seed)
+            tr.optimizer = optimizer
+            return tr
+        if not isinstance(self, _AdvLoss):
+            raise ValueError(f"{type(self).__name__} has no self-adversarial step: loss must be 'hinge'")
+        K = 64 if negatives is None else negatives
+        alpha = 1.0 if adversarial_temperature is None else adversarial_temperature
+        check_adv_hyperparameters(K, alpha, margin)
         if optimizer not in ("sgd", "adagrad"):
             raise ValueError(f"optimizer must be 'sgd' or 'adagrad', got {optimizer!r}")
         if optimizer == "adagrad":
             self._trainer_adagrad(initial_accumulator_value)
-        tr = self._trainer(self, triples, batch_size, margin=margin, learning_rate=learning_rate, seed=seed)
+        tr = AdvTrainer(self, triples, batch_size, negatives=K, adversarial_temperature=alpha, margin=margin,
+                        learning_rate=learning_rate, seed=seed)
         tr.optimizer = optimizer
         return tr
 
@@ -365,7 +451,74 @@ class _Model:
             t.copy_(state[name].to(device=t.device, dtype=torch.float32))
 
 
-class TransX(_Model):
+class _AdvLoss:
+    """The self-adversarial negative-sampling loss of a model whose PREFIX has <PREFIX>_adv_* entry points (TransX,
+    RotatE): per-row losses and the two single steps.  The model supplies _ptrs(), _adagrad_ptrs() and
+    _adv_ws_bytes(B, K); trainer(loss="self_adversarial") is _Model's."""
+    _adv_ws = None                                       # ((B, K), workspace) of the last adv_step / adv_adagrad_step
+
+    def _adv_workspace(self, B: int, K: int) -> torch.Tensor:
+        nbytes = self._adv_ws_bytes(int(B), int(K))
+        if nbytes == 0:
+            raise RuntimeError(f"{self.PREFIX}_adv_step_workspace_bytes failed")
+        return torch.empty(nbytes, dtype=torch.uint8, device=self.tables["ent"].device)
+
+    def _adv_step_workspace(self, B: int, K: int) -> torch.Tensor:
+        """The single steps' workspace, kept while (B, K) stays (as _Model.workspace keeps the hinge step's by B)."""
+        if self._adv_ws is None or self._adv_ws[0] != (B, K):
+            self._adv_ws = ((B, K), self._adv_workspace(B, K))
+        return self._adv_ws[1]
+
+    @staticmethod
+    def _adv_batch(pos, side, neg_ent, margin, alpha):
+        """(pos, side, neg_ent) as contiguous int32 device tensors; shapes, dtypes, K and the two hyperparameters are
+        checked first, on the host.  An int64 value that int32 does not hold is clamped to [-1, 2^31 - 1] before the
+        cast, so that it stays what it was: out of range (an empty slot, an invalid row), never wrapped into a valid id."""
+        for name, t in (("pos", pos), ("side", side), ("neg_ent", neg_ent)):
+            if not isinstance(t, torch.Tensor) or t.dtype not in (torch.int32, torch.int64):
+                raise ValueError(f"{name} must be an int32 or int64 tensor")
+        if pos.dim() != 2 or pos.shape[1] != 3 or pos.shape[0] == 0:
+            raise ValueError("pos must have shape [B, 3] (head, tail, relation) with B >= 1")
+        B = pos.shape[0]
+        if side.dim() != 1 or side.shape[0] != B:
+            raise ValueError("side must have shape [B]")
+        if neg_ent.dim() != 2 or neg_ent.shape[0] != B:
+            raise ValueError("neg_ent must have shape [B, K]")
+        check_adv_hyperparameters(int(neg_ent.shape[1]), alpha, margin)
+        out = []
+        for name, t in (("pos", pos), ("side", side), ("neg_ent", neg_ent)):
+            _need_cuda(t, name)
+            out.append((t.clamp(-1, 2**31 - 1) if t.dtype == torch.int64 else t).to(torch.int32).contiguous())
+        return out
+
+    def adv_loss(self, pos: torch.Tensor, side: torch.Tensor, neg_ent: torch.Tensor, margin: float,
+                 alpha: float) -> torch.Tensor:
+        """The [B] per-row self-adversarial losses (NaN for a row with a positive id out of range or a side outside
+        {0, 1}); a slot of neg_ent outside [0, n_ent) is empty."""
+        pb, sb, nb = self._adv_batch(pos, side, neg_ent, margin, alpha)
+        out = torch.empty(pb.shape[0], dtype=torch.float32, device=pb.device)
+        _lib.call(self.PREFIX + "_adv_loss", *self._ptrs(), pb.data_ptr(), sb.data_ptr(), nb.data_ptr(), pb.shape[0],
+                  nb.shape[1], float(margin), float(alpha), out.data_ptr(), _stream())
+        return out
+
+    def _adv_step(self, entry, ptrs, pos, side, neg_ent, margin, alpha, lr):
+        pb, sb, nb = self._adv_batch(pos, side, neg_ent, margin, alpha)
+        ws = self._adv_step_workspace(pb.shape[0], nb.shape[1])
+        _lib.call(entry, *ptrs(), pb.data_ptr(), sb.data_ptr(), nb.data_ptr(), pb.shape[0], nb.shape[1], float(margin),
+                  float(alpha), float(lr), self._loss.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+        return self._loss[0].clone()
+
+    def adv_step(self, pos, side, neg_ent, margin: float, alpha: float, lr: float) -> torch.Tensor:
+        """One SGD step on the summed self-adversarial loss; returns that batch loss (device scalar, before the step)."""
+        return self._adv_step(self.PREFIX + "_adv_step", self._ptrs, pos, side, neg_ent, margin, alpha, lr)
+
+    def adv_adagrad_step(self, pos, side, neg_ent, margin: float, alpha: float, lr: float) -> torch.Tensor:
+        """The same step with AdaGrad's update (enable_adagrad() first)."""
+        self._adagrad_ptrs()
+        return self._adv_step(self.PREFIX + "_adv_adagrad_step", self._adagrad_ptrs, pos, side, neg_ent, margin, alpha, lr)
+
+
+class TransX(_AdvLoss, _Model):
     """The tables of one translation model.  `model` in {"transe", "transh", "transd"}; `l1` selects the L1
     distance (the reference's L1_flag), else the squared L2 one."""
     PREFIX = "ge_transx"
@@ -393,6 +546,9 @@ class TransX(_Model):
     def _ws_bytes(self, kind: str, B: int, *extra) -> int:
         lead = (MODELS[self.model],) if kind in ("rank", "topk", "relation_rank") else ()
         return getattr(_lib.load(), f"ge_transx_{kind}_workspace_bytes")(*lead, self.n_ent, self.n_rel, self.d, B, *extra)
+
+    def _adv_ws_bytes(self, B: int, K: int) -> int:
+        return _lib.load().ge_transx_adv_step_workspace_bytes(MODELS[self.model], self.n_ent, self.n_rel, self.d, B, K)
 
     def step(self, pos: torch.Tensor, neg: torch.Tensor, lr: float, margin: float) -> torch.Tensor:
         """One SGD step on sum max(D(pos) - D(neg) + margin, 0); returns that batch loss (device scalar, before

@@ -3,14 +3,19 @@
 Reads relation2id.txt, entity2id.txt and triple2id.txt from --data_dir, trains for --train_times epochs of
 --nbatches batches of triples // nbatches pairs (Config, transE.py:12-21), prints each epoch's summed loss as the
 reference does, and saves the tables with torch.save (TF's model.vec checkpoint format is not reproduced).
+--loss self_adversarial trains on the self-adversarial negative-sampling loss of Sun et al. 2019 instead of the margin
+hinge: --negatives K filtered negatives per positive, weighted by a softmax at --adversarial_temperature, --margin = gamma.
 The flags, checks and run() both translation drivers share live here; transr_train adds TransR's own.
 """
 from __future__ import annotations
 
 import argparse
 import json
+import math
 import os
 import sys
+
+MAX_NEGATIVES = 1024    # graphembeddings_amd.transx.MAX_NEGATIVES, kept here so that checking flags imports no torch
 
 FILTER_HELP = ("filtered evaluation (Bordes et al.): the filter is triple2id.txt + the --test_file + every --filter_file; "
                "unlike the ComplEx evaluator, which filters train + valid as holE.py does")
@@ -122,7 +127,7 @@ def run(a, driver: str, make_model, name: str, trainer_kw=None) -> int:
     into <name>_test.json (with --relation_ranks, relations too; with --candidate_sets, the `constrained` block and
     line); with --predict_k, write <name>_predict.tsv (from the relation's set with --candidate_sets); with
     --predict_relations_k, <name>_predict_relations.tsv; with --classify, <name>_classify.json and
-    <name>_thresholds.tsv.  trainer_kw: further keywords of the model's trainer() (rotate_train's loss)."""
+    <name>_thresholds.tsv.  trainer_kw: further keywords of the model's trainer() (the loss of transx_train and rotate_train)."""
     import numpy as np
     from .transx import read_kg, read_triples
     E, R, tri = read_kg(a.data_dir)
@@ -208,7 +213,36 @@ def build_parser() -> argparse.ArgumentParser:
                         "restores them")
     p.add_argument("--adagrad_init", type=float, default=0.1,
                    help="AdagradOptimizer's initial_accumulator_value (with --optimizer adagrad)")
+    p.add_argument("--loss", choices=("hinge", "self_adversarial"), default="hinge",
+                   help="hinge (the default): the reference's loss, one negative per positive; self_adversarial: the "
+                        "negative-sampling loss of Sun et al. 2019 over --negatives negatives per positive (--margin is "
+                        "its gamma)")
+    p.add_argument("--negatives", type=int, default=None,
+                   help=f"negatives per positive, 1 to {MAX_NEGATIVES} (with --loss self_adversarial; default 64)")
+    p.add_argument("--adversarial_temperature", type=float, default=None,
+                   help="alpha >= 0 of the softmax over a positive's negatives, 0: uniform weights (with --loss "
+                        "self_adversarial; default 1.0)")
     return p
+
+
+def check_loss_args(a) -> None:
+    """--loss, --negatives and --adversarial_temperature, with rotate_train's rules and defaults (64 and 1.0)."""
+    loss = getattr(a, "loss", "hinge")                   # (a Namespace built without the flags: the hinge)
+    negatives, alpha = getattr(a, "negatives", None), getattr(a, "adversarial_temperature", None)
+    if loss not in ("hinge", "self_adversarial"):
+        raise ValueError(f"--loss must be 'hinge' or 'self_adversarial', got {loss!r}")
+    if loss != "self_adversarial":
+        if negatives is not None or alpha is not None:
+            raise ValueError("--negatives and --adversarial_temperature need --loss self_adversarial")
+        return
+    a.negatives = 64 if negatives is None else negatives
+    a.adversarial_temperature = 1.0 if alpha is None else alpha
+    if not 1 <= a.negatives <= MAX_NEGATIVES:
+        raise ValueError(f"--negatives must lie in [1, {MAX_NEGATIVES}], got {a.negatives}")
+    if not math.isfinite(a.adversarial_temperature) or a.adversarial_temperature < 0:
+        raise ValueError(f"--adversarial_temperature must be finite and >= 0, got {a.adversarial_temperature}")
+    if not math.isfinite(a.margin):
+        raise ValueError(f"--margin must be finite, got {a.margin}")
 
 
 def check_args(a) -> None:
@@ -220,6 +254,7 @@ def check_args(a) -> None:
         raise ValueError(f"--optimizer must be 'sgd' or 'adagrad', got {optimizer!r}")
     if not a0 > 0:
         raise ValueError(f"--adagrad_init must be positive, got {a0}")
+    check_loss_args(a)
     check_training_args(a)
     check_eval_args(a)
 
@@ -228,7 +263,10 @@ def main(argv=None) -> int:
     a = build_parser().parse_args(argv)
     check_args(a)
     from .transx import TransX
-    return run(a, "transx_train", lambda E, R: TransX(a.model, E, R, a.hidden_size, l1=a.l1, seed=a.seed), a.model)
+    kw = dict(loss=a.loss, negatives=a.negatives, adversarial_temperature=a.adversarial_temperature) \
+        if a.loss == "self_adversarial" else {}
+    return run(a, "transx_train", lambda E, R: TransX(a.model, E, R, a.hidden_size, l1=a.l1, seed=a.seed), a.model,
+               trainer_kw=kw)
 
 
 if __name__ == "__main__":

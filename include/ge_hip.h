@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define GE_VERSION 447 /* 0.4.4.7: + ge_rotate_adv_* (RotatE: the self-adversarial negative-sampling loss, its step with SGD / AdaGrad, draw and native loops) */
+#define GE_VERSION 448 /* 0.4.4.8: + ge_transx_adv_* (TransE / TransH / TransD: the self-adversarial negative-sampling loss, its step with SGD / AdaGrad and native loops) */
 
 /* argument errors (negative, -errno style) */
 #define GE_EINVAL (-22)  /* bad dimension / null pointer / misaligned buffer */
@@ -520,7 +520,7 @@ int ge_rotate_adv_adagrad_step(int l1, float* ent, int64_t n_ent, float* rel, in
  * Philox words -- and neg_ent[i,j] is the entity that the word at row index i K + j under the tag 'advp' draws among
  * those that are not known completions of (fixed entity, r): ge_bernoulli_corrupt_batch's pick with ent_lo = 0.  Picks
  * may repeat.  A key with no free entity gives -1 in all K slots.  Refused: what ge_transx_draw_batch refuses, then K as
- * above, then null outputs with B > 0. */
+ * above, then null outputs with B > 0.  The draw reads no table: it is also the draw of ge_transx_adv_train_steps*. */
 int ge_rotate_adv_draw_batch(const int32_t* triples, int64_t T, int64_t B, const int64_t* bh_key, const int32_t* bh_ent,
                              const int64_t* bt_key, const int32_t* bt_ent, int64_t n_known,
                              const uint32_t* tail_threshold, int32_t n_rel, int32_t n_ent, uint64_t seed, uint64_t step,
@@ -541,6 +541,66 @@ int ge_rotate_adv_train_steps_adagrad(int l1, float* ent, int64_t n_ent, float* 
                                       uint64_t seed, uint64_t first_step, int64_t n_steps, int64_t B, int32_t K,
                                       float margin, float alpha, float lr, float* losses, void* workspace,
                                       size_t workspace_bytes, void* stream);
+
+/* --- TransE / TransH / TransD, the self-adversarial negative-sampling loss: ge_rotate_adv_*'s loss on ge_transx_*'s
+ * tables.  The tables, the distance D, the projections and TransH's clamp are ge_transx_score's (model, l1, the five
+ * tables, d); the batch (pos [B,3], side [B], neg_ent [B,K]), gamma = margin, alpha, p_ij, loss_i, the two coefficients,
+ * live slots, invalid rows, the fp32 forms of softplus / sigma / the softmax, the (K+3) B gradient slots and the draw are
+ * ge_rotate_adv_*'s above, word for word.
+ * Gradients: a triple with coefficient a (sigma(D+ - gamma), or -p_ij sigma(gamma - D-_ij)) contributes a times the
+ * hinge step's gradient of D: sign(0) = 0 for L1, TransH's l2_normalize differentiated on the branch max takes (ties to
+ * n.n).  Plane 0 of a slot carries the ent / rel gradient, plane 1 ent_transfer on entity slots (TransD) and
+ * normal_vector / rel_transfer on the relation slot.  The fixed entity and the relation of row i are the same table rows
+ * in the positive and all K negatives: their K + 1 contributions are summed into the positive's slot for that entity and
+ * into the relation slot, in both planes, in a fixed order (a team's negatives j = q, q + NT, ... ascending, a fixed tree
+ * over the teams, the positive's term last); through TransH's normalisation that sum goes once.  The update is
+ * ge_transx_hinge_step's / ge_transx_adagrad_step's sort-and-apply stage.  No float atomics: two calls from one state
+ * give the same bits in every table, accumulator and loss.
+ * Refused before any launch, in this order: what ge_transx_hinge_step (ge_transx_adagrad_step) refuses about the model,
+ * its tables and accumulators; GE_EINVAL for K < 1; GE_ENOTSUP for K > ge_transx_adv_max_negatives() (1024); GE_EINVAL for
+ * (K + 3) B >= 2^31; GE_EINVAL for a null side or neg_ent (steps and ge_transx_adv_loss with B > 0); GE_EINVAL for a
+ * margin or alpha that is not finite, then for alpha < 0; then GE_EINVAL for B < 1 (ge_transx_adv_loss: B < 0; its B = 0
+ * returns 0), a null or misaligned pos / side / neg_ent / loss(es) / workspace, n_steps < 0 and a bad sampler, as the
+ * hinge counterpart; GE_ENOMEM below the size function. */
+int ge_transx_adv_max_negatives(void);
+/* Workspace of one step (either optimizer) / of either native loop of `model`: TransE has one gradient plane, TransH and
+ * TransD two.  Monotone in B, K and d, a multiple of 256; 0 for a refused shape (the model code, the tables' sizes, d,
+ * B < 1, K outside [1, max], (K + 3) B >= 2^31). */
+size_t ge_transx_adv_step_workspace_bytes(int model, int64_t n_ent, int64_t n_rel, int32_t d, int64_t B, int32_t K);
+/* out[i] = loss_i ([B] fp32); NaN for an invalid row. */
+int ge_transx_adv_loss(int model, int l1, const float* ent, int64_t n_ent, const float* rel, int64_t n_rel,
+                       const float* normal, const float* ent_transfer, const float* rel_transfer, int32_t d,
+                       const int32_t* pos, const int32_t* side, const int32_t* neg_ent, int64_t B, int32_t K,
+                       float margin, float alpha, float* out, void* stream);
+/* One SGD step (row -= lr * sum) / one AdaGrad step (acc += s * s, row -= lr * s / sqrtf(acc)) on the loss above; *loss
+ * (device, one float) = the batch loss before the step. */
+int ge_transx_adv_step(int model, int l1, float* ent, int64_t n_ent, float* rel, int64_t n_rel, float* normal,
+                       float* ent_transfer, float* rel_transfer, int32_t d, const int32_t* pos, const int32_t* side,
+                       const int32_t* neg_ent, int64_t B, int32_t K, float margin, float alpha, float lr, float* loss,
+                       void* workspace, size_t workspace_bytes, void* stream);
+int ge_transx_adv_adagrad_step(int model, int l1, float* ent, int64_t n_ent, float* rel, int64_t n_rel, float* normal,
+                               float* ent_transfer, float* rel_transfer, float* acc_ent, float* acc_rel,
+                               float* acc_normal, float* acc_ent_transfer, float* acc_rel_transfer, int32_t d,
+                               const int32_t* pos, const int32_t* side, const int32_t* neg_ent, int64_t B, int32_t K,
+                               float margin, float alpha, float lr, float* loss, void* workspace, size_t workspace_bytes,
+                               void* stream);
+/* n_steps steps in one call: step s draws ge_rotate_adv_draw_batch(.., seed, first_step + s, K, ..) -- the draw reads no
+ * table, so both families share it -- into the workspace and runs ge_transx_adv_step (ge_transx_adv_adagrad_step) on it;
+ * losses[s] (device) = its batch loss.  n_steps = 0 returns 0 after the checks.  No host synchronisation, no allocation. */
+int ge_transx_adv_train_steps(int model, int l1, float* ent, int64_t n_ent, float* rel, int64_t n_rel, float* normal,
+                              float* ent_transfer, float* rel_transfer, int32_t d, const int32_t* triples, int64_t T,
+                              const int64_t* bh_key, const int32_t* bh_ent, const int64_t* bt_key, const int32_t* bt_ent,
+                              int64_t n_known, const uint32_t* tail_threshold, uint64_t seed, uint64_t first_step,
+                              int64_t n_steps, int64_t B, int32_t K, float margin, float alpha, float lr, float* losses,
+                              void* workspace, size_t workspace_bytes, void* stream);
+int ge_transx_adv_train_steps_adagrad(int model, int l1, float* ent, int64_t n_ent, float* rel, int64_t n_rel,
+                                      float* normal, float* ent_transfer, float* rel_transfer, float* acc_ent,
+                                      float* acc_rel, float* acc_normal, float* acc_ent_transfer, float* acc_rel_transfer,
+                                      int32_t d, const int32_t* triples, int64_t T, const int64_t* bh_key,
+                                      const int32_t* bh_ent, const int64_t* bt_key, const int32_t* bt_ent,
+                                      int64_t n_known, const uint32_t* tail_threshold, uint64_t seed, uint64_t first_step,
+                                      int64_t n_steps, int64_t B, int32_t K, float margin, float alpha, float lr,
+                                      float* losses, void* workspace, size_t workspace_bytes, void* stream);
 
 /* --- TransR (transR.py).  Row-major fp32 tables: ent [n_ent,dim_e], rel [n_rel,dim_r] and rel_matrix
  * [n_rel, dim_r*dim_e], whose row r read as [dim_r][dim_e] is M_r.  Triples are int32 [B,3] (h, t, r).
