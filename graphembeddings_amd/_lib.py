@@ -84,6 +84,8 @@ SYMBOLS = {
     "ge_topk_1vK_masked": (C.c_int, [_p, _i64, _i32, _p, _i64, _p, _i64, _f, C.c_int, C.c_int, _p, _p, _i32, _p, _p, _p,
                                      _p, _sz, _p, _p, _i32, _p]),
     "ge_rank_metrics": (C.c_int, [_p, _p, _p, _i64, _p, _p, _p, _p]),
+    "ge_copy_if_chunk": (C.c_int, []),
+    "ge_copy_if": (C.c_int, [_p, _i32, _p, _p, _p, _p]),      # src, dst, count: HOST arrays of n_seg entries
     "ge_rank_tick_workspace_bytes": (_sz, [_i64]),
     "ge_rank_validation_tick": (C.c_int, [_p, _i64, _i32, _p, _p, _i64, _p, _i64, _f, C.c_int, _p, _p, _p, _p, _p, _p, _p, _p,
                                           _i32, _p, _p, _p, _p, _p, _p, _sz, _p]),
@@ -251,7 +253,7 @@ def load():
             fn = getattr(lib, name)  # AttributeError if the ABI and the header diverge
             fn.restype = res
             fn.argtypes = args
-        if lib.ge_version() < 447:
+        if lib.ge_version() < 449:
             raise RuntimeError("libge_hip.so is older than the Python host expects")
         _lib = lib
     return _lib
@@ -261,3 +263,9 @@ def call(name: str, *args):
     rc = getattr(load(), name)(*args)
     if rc != 0:
         raise GeError(name, rc)
+
+
+def copy_if_args(src_ptrs, dst_ptrs, counts):
+    """(n_seg, src, dst, count) of a ge_copy_if call: the host arrays it reads, from device addresses and word counts."""
+    n = len(counts)
+    return n, (C.c_void_p * n)(*src_ptrs), (C.c_void_p * n)(*dst_ptrs), (C.c_int64 * n)(*counts)

@@ -1413,6 +1413,38 @@ int ge_rank_metrics(const int32_t* n_before, const int32_t* n_known_before, cons
   return rank_metrics_launch(n_before, n_known_before, true_loss, M, metrics_out, best, improved, (hipStream_t)stream);
 }
 
+// ---------------------------------------------------------------- the gated copy of several buffers
+constexpr int64_t kCopyIfMaxCount = (int64_t)1 << 44;       // words of one segment: byte ranges stay far from wrapping
+
+int ge_copy_if_chunk(void) { return kCopyIfChunk; }
+
+int ge_copy_if(const int32_t* flag, int32_t n_seg, const float* const* src, float* const* dst, const int64_t* count,
+               void* stream) {
+  if (!flag || !src || !dst || !count || n_seg < 1 || n_seg > GE_COPY_IF_MAX_SEGMENTS) return GE_EINVAL;
+  uintptr_t s0[GE_COPY_IF_MAX_SEGMENTS], d0[GE_COPY_IF_MAX_SEGMENTS], bytes[GE_COPY_IF_MAX_SEGMENTS];
+  bool too_long = false;
+  for (int32_t s = 0; s < n_seg; ++s) {
+    if (count[s] < 0) return GE_EINVAL;
+    s0[s] = reinterpret_cast<uintptr_t>(src[s]);
+    d0[s] = reinterpret_cast<uintptr_t>(dst[s]);
+    if (count[s] > 0 && (!s0[s] || !d0[s] || s0[s] % 4 != 0 || d0[s] % 4 != 0)) return GE_EINVAL;
+    too_long = too_long || count[s] > kCopyIfMaxCount;
+    bytes[s] = 4 * (uintptr_t)std::min(count[s], kCopyIfMaxCount);
+  }
+  // a dst range against every other dst range and every src range: any order of the segments gives the same result
+  auto overlap = [](uintptr_t a, uintptr_t na, uintptr_t b, uintptr_t nb) { return a < b + nb && b < a + na; };
+  for (int32_t s = 0; s < n_seg; ++s) {
+    if (count[s] == 0) continue;
+    for (int32_t u = 0; u < n_seg; ++u) {
+      if (count[u] == 0) continue;
+      if (u != s && overlap(d0[s], bytes[s], d0[u], bytes[u])) return GE_EINVAL;
+      if (overlap(d0[s], bytes[s], s0[u], bytes[u])) return GE_EINVAL;
+    }
+  }
+  if (too_long) return GE_ENOTSUP;
+  return copy_if_segments_launch(flag, n_seg, src, dst, count, (hipStream_t)stream);
+}
+
 // the tick's workspace: n_before [2V] | n_known_before [2V] | true_loss [2V] | flag -- the tail side's V rows first, so
 // that the three vectors are what ge_rank_metrics takes for M = 2V
 struct RankTickWs { int32_t* raw; int32_t* skip; float* true_loss; int32_t* flag; size_t bytes; };

@@ -77,6 +77,15 @@ int select_rows_launch(const int32_t* valid, int64_t V, int64_t B, uint64_t seed
 int mean_pocket_launch(const float* loss, int64_t B, float* mean_out, float* best, int32_t* flag, hipStream_t st);
 int copy_if_launch(const float* src, float* dst, int64_t n, const int32_t* flag, hipStream_t st);
 bool copy_if_ok(const float* src, const float* dst, int64_t n);   // false: copy_if_launch would refuse these buffers
+// ge_copy_if: the segments as the kernel takes them, by value.  Non-empty segments only, chunk_start ascending from 0.
+constexpr int kCopyIfChunk = 8192;   // 32-bit words one workgroup moves: 8 x 16 bytes a lane (ge_copy_if_chunk())
+struct CopyIfSegments {
+  const uint32_t* src[GE_COPY_IF_MAX_SEGMENTS]; uint32_t* dst[GE_COPY_IF_MAX_SEGMENTS];
+  int64_t count[GE_COPY_IF_MAX_SEGMENTS], chunk_start[GE_COPY_IF_MAX_SEGMENTS]; int32_t n_seg;
+};
+// the host arrays as ge_copy_if checked them (n_seg in [1, 16], counts >= 0); one launch, none when every count is 0
+int copy_if_segments_launch(const int32_t* flag, int32_t n_seg, const float* const* src, float* const* dst,
+                            const int64_t* count, hipStream_t st);
 // the summary of a rank sweep's counts (metrics_out [8]) and the pocket decision on its filtered MRR: one workgroup
 int rank_metrics_launch(const int32_t* n_before, const int32_t* n_known_before, const float* true_loss, int64_t M,
                         float* metrics_out, float* best, int32_t* improved, hipStream_t st);

@@ -255,6 +255,59 @@ __global__ __launch_bounds__(kBlock) void copy_if_kernel(const float4* __restric
   if (blockIdx.x == 0 && (int)threadIdx.x < n_tail) dst_tail[threadIdx.x] = src_tail[threadIdx.x];
 }
 
+// ge_copy_if: every segment's dst <- src iff *flag, all segments in one launch.  Workgroup b moves chunk b of
+// kCopyIfChunk words; chunk_start[s] is the first chunk of segment s (ascending: the launcher drops empty segments), so
+// the segment of b is the number of starts at or below it.  b, the starts and the table entries are wave-uniform: the
+// lookup reads the by-value table with scalar loads.  A chunk begins a multiple of 32 KiB into its segment, so it is
+// 16-byte aligned iff the segment is.
+__global__ __launch_bounds__(kBlock) void copy_if_segments_kernel(const int32_t* __restrict__ flag, CopyIfSegments t) {
+  if (*flag == 0) return;
+  const int64_t b = blockIdx.x;
+  int s = 0;
+#pragma unroll
+  for (int k = 1; k < GE_COPY_IF_MAX_SEGMENTS; ++k) s += (k < t.n_seg && b >= t.chunk_start[k]) ? 1 : 0;
+  const int64_t off = (b - t.chunk_start[s]) * kCopyIfChunk;
+  const uint32_t* src = t.src[s] + off;
+  uint32_t* dst = t.dst[s] + off;
+  const int n = (int)std::min<int64_t>(t.count[s] - off, kCopyIfChunk);
+  if ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) % 16 == 0) {
+    const int n4 = n / 4;
+    const uint4* src4 = reinterpret_cast<const uint4*>(src);
+    uint4* dst4 = reinterpret_cast<uint4*>(dst);
+    if (n == kCopyIfChunk) {                            // a whole chunk: its 8 loads a lane in flight together
+      uint4 v[kCopyIfChunk / 4 / kBlock];
+#pragma unroll
+      for (int j = 0; j < kCopyIfChunk / 4 / kBlock; ++j) v[j] = src4[j * kBlock + threadIdx.x];
+#pragma unroll
+      for (int j = 0; j < kCopyIfChunk / 4 / kBlock; ++j) dst4[j * kBlock + threadIdx.x] = v[j];
+      return;
+    }
+    for (int i = threadIdx.x; i < n4; i += kBlock) dst4[i] = src4[i];
+    const int i = 4 * n4 + (int)threadIdx.x;            // the count % 4 words after the last whole 16 bytes
+    if (i < n) dst[i] = src[i];
+  } else {
+    for (int i = threadIdx.x; i < n; i += kBlock) dst[i] = src[i];
+  }
+}
+
+int copy_if_segments_launch(const int32_t* flag, int32_t n_seg, const float* const* src, float* const* dst,
+                            const int64_t* count, hipStream_t st) {
+  CopyIfSegments t{};
+  int64_t chunks = 0;
+  for (int32_t s = 0; s < n_seg; ++s) {
+    if (count[s] == 0) continue;
+    t.src[t.n_seg] = reinterpret_cast<const uint32_t*>(src[s]);
+    t.dst[t.n_seg] = reinterpret_cast<uint32_t*>(dst[s]);
+    t.count[t.n_seg] = count[s];
+    t.chunk_start[t.n_seg++] = chunks;
+    chunks += (count[s] + kCopyIfChunk - 1) / kCopyIfChunk;
+  }
+  if (chunks == 0) return 0;
+  if (chunks > INT32_MAX) return GE_ENOTSUP;
+  hipLaunchKernelGGL(copy_if_segments_kernel, dim3((unsigned)chunks), dim3(kBlock), 0, st, flag, t);
+  return launch_status();
+}
+
 int select_rows_launch(const int32_t* valid, int64_t V, int64_t B, uint64_t seed, uint64_t counter, int32_t* out,
                        hipStream_t st) {
   if (B == 0) return 0;

@@ -992,6 +992,139 @@ def constrained_line(m: dict) -> str:
             f"entity admissible {100.0 * m['admissible_true']:.2f} %; mean set size {m['mean_set_size']:.1f}")
 
 
+class TranslationPocket:
+    """RankPocket for a TransX, TransR or RotatE model: validation ticks on the filtered MRR of translation_ranks over
+    both sides, without a host decision per tick.  tick() enqueues the model's rank sweeps of the validation rows' tails
+    and heads into fixed buffers, ge_rank_metrics over the 2V rows into `hist`, `best` (a device scalar that starts at
+    0; a tie keeps the first best, a NaN never improves) and `improved`, and one ge_copy_if on that flag: `pocket`
+    {name: tensor} <- the model's _pocket_tensors() (the tables, adagrad_<table> per accumulator, TransR's m and v).
+    The model's host scalars of that state (TransR.t) are recorded per tick; restore() puts the best tick's tensors and
+    scalars back.  The constructor does all that does not depend on the tables; tick() neither synchronises nor
+    allocates; read() synchronises once for all pending ticks.
+    known: the triples to filter ([n,3], None: filtered == raw) or {"tail": KnownIndex, "head": KnownIndex} built with
+    n_rows = max(n_ent, n_rel).  rows=n: only the first n rows of np.random.default_rng(seed).permutation(len(valid))
+    are ranked (`row_index`, in the order they are swept).  candidate_sets = {"tail": CandidateSets, "head":
+    CandidateSets} for arange(n_ent): every row against its relation's set, the `constrained` ranks of
+    evaluate_translation (not RotatE).  keep_state=False: no pocket and no copy.  batch: rows per native call.
+    ValueError on the host: an empty validation set, ids outside the tables, rows < 1, a KnownIndex of the wrong n_rows."""
+
+    KEYS = RankPocket.KEYS
+
+    def __init__(self, model, validation_triples, known=None, *, rows: int = None, seed: int = 0, candidate_sets=None,
+                 keep_state: bool = True, capacity: int = 4096, batch: int = None):
+        valid = _translation_test(model, validation_triples)
+        if len(valid) == 0:
+            raise ValueError("TranslationPocket: the validation set is empty")
+        index = np.arange(len(valid))
+        if rows is not None:
+            if rows < 1:
+                raise ValueError(f"TranslationPocket: rows must be >= 1, got {rows}")
+            index = np.random.default_rng(seed).permutation(len(valid))[:rows]
+        if batch is None:
+            batch = 1 << 17
+        if batch <= 0 or capacity < 1:
+            raise ValueError("TranslationPocket: batch and capacity must be positive")
+        if 2 * len(index) > 1 << 24:
+            raise ValueError("TranslationPocket: more than 2^23 validation rows (ge_rank_metrics counts 2^24); use rows=")
+        self.sets = None
+        if candidate_sets is not None:
+            model._check_candidate_sets()
+            if not isinstance(candidate_sets, dict) or any(s not in candidate_sets for s in ("tail", "head")):
+                raise ValueError("candidate_sets must be a dict with a CandidateSets per side ('tail', 'head')")
+            for side in ("tail", "head"):
+                _translation_sets(model, candidate_sets[side], None, len(index), "TranslationPocket")
+            self.sets = candidate_sets
+        self.model, dev, E = model, model.tables["ent"].device, model.n_ent
+        self.row_index = index[np.argsort(valid[index, 2], kind="stable")]      # grouped by relation, as translation_ranks
+        valid = valid[self.row_index]
+        self.V = V = len(valid)
+        self.triples = torch.as_tensor(valid).to(dev).to(torch.int32).contiguous()
+        self.row_set = self.triples[:, 2].contiguous() if self.sets else None
+        if self.sets:
+            for side in ("tail", "head"):
+                self.sets[side]._check(torch.arange(E, dtype=torch.int32, device=dev), "TranslationPocket")
+        self._chunks = [(s, min(s + int(batch), V)) for s in range(0, V, int(batch))]
+        q = self.triples.to(torch.int64)
+        self._cells = {}
+        for side, col in (("tail", 0), ("head", 1)):
+            _, ki, pos_of = _translation_sweep_setup(model, valid[:, 2], known[side] if isinstance(known, dict) else known, side)
+            self._cells[side] = [ki.cells(q[a:b, col], q[a:b, 2], pos_of, E) for a, b in self._chunks]
+        self.n_before = torch.empty(2 * V, dtype=torch.int32, device=dev)
+        self.n_known_before = torch.empty(2 * V, dtype=torch.int32, device=dev)
+        self.true_dist = torch.empty(2 * V, dtype=torch.float32, device=dev)
+        nbytes = model._ws_bytes("rank", min(int(batch), V))
+        if nbytes == 0:
+            raise RuntimeError(f"{model.PREFIX}_rank_workspace_bytes failed")
+        self._ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        self.hist = torch.zeros(int(capacity), 8, dtype=torch.float32, device=dev)
+        self.improved = torch.zeros(int(capacity), dtype=torch.int32, device=dev)
+        self.best = torch.zeros((), dtype=torch.float32, device=dev)
+        self._shapes = {k: tuple(t.shape) for k, t in model._pocket_tensors().items()}
+        self.pocket = {k: torch.empty_like(t) for k, t in model._pocket_tensors().items()} if keep_state else None
+        self._pending = []      # (global step, host scalars) of each tick since the last read()
+        self._best = None       # ... of the best tick read so far
+
+    def tick(self, global_step: int) -> None:
+        i = len(self._pending)
+        if i >= self.hist.shape[0]:
+            raise RuntimeError("TranslationPocket: read() the pending ticks first (capacity %d)" % self.hist.shape[0])
+        m, V = self.model, self.V
+        state = m._pocket_tensors()
+        if {k: tuple(t.shape) for k, t in state.items()} != self._shapes:
+            raise RuntimeError("TranslationPocket: the model's state tensors are no longer the constructor's (%s, now %s): "
+                               "build the pocket after enable_adagrad() / trainer()" % (sorted(self._shapes), sorted(state)))
+        for k, side in enumerate(("tail", "head")):
+            for (a, b), (off, rc) in zip(self._chunks, self._cells[side]):
+                sets = {"row_set": self.row_set[a:b], "mask": self.sets[side].mask} if self.sets else {}
+                lo, hi = k * V + a, k * V + b
+                m.rank_counts(self.triples[a:b], cand_is_head=(side == "head"), known_off=off, known_rc=rc, **sets,
+                              out=(self.n_before[lo:hi], self.n_known_before[lo:hi], self.true_dist[lo:hi]), workspace=self._ws)
+        flag = self.improved.data_ptr() + 4 * i
+        H._lib.call("ge_rank_metrics", self.n_before.data_ptr(), self.n_known_before.data_ptr(), self.true_dist.data_ptr(),
+                    2 * V, self.hist.data_ptr() + 32 * i, self.best.data_ptr(), flag, H._stream())
+        if self.pocket is not None:
+            names = list(state)
+            H._lib.call("ge_copy_if", flag, *H._lib.copy_if_args([state[n].data_ptr() for n in names],
+                                                                 [self.pocket[n].data_ptr() for n in names],
+                                                                 [state[n].numel() for n in names]), H._stream())
+        self._pending.append((int(global_step), m._pocket_scalars()))
+
+    def read(self):
+        """[(global_step, metrics)] of the ticks since the last read, in order (synchronises): RankPocket.KEYS plus
+        `improved`, whether the tick's filtered MRR became `best` (and its state the pocket)."""
+        n = len(self._pending)
+        if n == 0:
+            return []
+        rows, flags = self.hist[:n].cpu().tolist(), self.improved[:n].cpu().tolist()
+        out = []
+        for (step, scalars), row, flag in zip(self._pending, rows, flags):
+            mt = dict(zip(self.KEYS, row))
+            mt["counted"] = int(mt["counted"])
+            mt["improved"] = bool(flag)
+            if flag:
+                self._best = (step, scalars)
+            out.append((step, mt))
+        self._pending = []
+        return out
+
+    @torch.no_grad()
+    def restore(self):
+        """pocket -> model: the best tick's tensors and host scalars (reads the pending ticks first).  Returns that
+        tick's global_step; None, and nothing is written, if no tick improved on 0 or keep_state is False."""
+        self.read()
+        if self._best is None or self.pocket is None:
+            return None
+        step, scalars = self._best
+        state = self.model._pocket_tensors()
+        if {k: tuple(t.shape) for k, t in state.items()} != self._shapes:
+            raise RuntimeError("TranslationPocket: the model's state tensors are no longer the constructor's")
+        for name, t in state.items():
+            t.copy_(self.pocket[name])
+        for name, value in scalars.items():
+            setattr(self.model, name, value)
+        return step
+
+
 def _translation_queries(model, queries) -> np.ndarray:
     """The query rows as int64 [n,2] (fixed entity, relation), ids checked against the model's tables on the host."""
     q = np.asarray(queries.cpu().numpy() if isinstance(queries, torch.Tensor) else queries)

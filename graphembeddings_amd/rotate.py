@@ -111,11 +111,14 @@ class RotatE(_AdvLoss, _Model):
     # --- what this model does not have
     def rank_counts(self, triples: torch.Tensor, cand_is_head: bool = False, known_off: torch.Tensor = None,
                     known_rc: torch.Tensor = None, return_scores: bool = False, row_set: torch.Tensor = None,
-                    mask: torch.Tensor = None):
+                    mask: torch.Tensor = None, out=None, workspace: torch.Tensor = None):
         """ge_rotate_rank on the [B,3] rows as given: _Model.rank_counts without candidate sets."""
         if row_set is not None or mask is not None:
             raise _out_of_scope("candidate sets")
-        return super().rank_counts(triples, cand_is_head, known_off, known_rc, return_scores)
+        return super().rank_counts(triples, cand_is_head, known_off, known_rc, return_scores, out=out, workspace=workspace)
+
+    def _check_candidate_sets(self) -> None:
+        raise _out_of_scope("candidate sets")
 
     def ranks(self, test, known=None, side: str = "tail", batch: int = None, candidate_sets=None, row_sets=None,
               return_admissible: bool = False):

@@ -4,7 +4,8 @@ Reads relation2id.txt, entity2id.txt and triple2id.txt from --data_dir, trains f
 --nbatches batches of triples // nbatches pairs with SGD or AdaGrad on the margin hinge (--loss hinge, the default) or on
 the paper's self-adversarial negative-sampling loss (--loss self_adversarial: --negatives K filtered negatives per
 positive, weighted by a softmax at --adversarial_temperature, --margin = gamma), prints each epoch's summed loss, and saves the tables (and the AdaGrad accumulators) with torch.save as rotate.pt; with --test_file the filtered
-ranks over all entities, heads and tails, go to rotate_test.json.
+ranks over all entities, heads and tails, go to rotate_test.json.  --validation_file adds filtered-MRR validation ticks
+during training, as in transx_train: rotate.pt is then the best tick's state.
 The flags of operations RotatE does not have (top-k prediction, candidate sets, relation prediction, triple
 classification files, nearest neighbours) are not defined.
 """
@@ -14,7 +15,7 @@ import argparse
 import math
 import sys
 
-from .transx_train import FILTER_HELP, check_eval_args, check_training_args, run
+from .transx_train import FILTER_HELP, add_validation_flags, check_eval_args, check_training_args, run
 
 MAX_DIM = 1024          # graphembeddings_amd.rotate.MAX_DIM, kept here so that checking flags imports no torch
 MAX_NEGATIVES = 1024    # graphembeddings_amd.rotate.MAX_NEGATIVES, likewise
@@ -53,7 +54,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--filter_file", action="append", default=[],
                    help="a further *2id.txt file of known triples for the filter (repeatable; e.g. valid2id.txt)")
     p.add_argument("--load", default=None, help="a saved state_dict to start from (with --train_times 0: evaluate only)")
-    p.set_defaults(predict_k=None)                      # what run() and check_eval_args read of the undefined flags
+    add_validation_flags(p, "rotate")
+    p.set_defaults(predict_k=None)                    # what run() and check_eval_args read of the undefined flags
     return p
 
 

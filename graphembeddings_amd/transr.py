@@ -108,6 +108,12 @@ class TransR(_Model):
     def _state_tensors(self) -> Dict[str, torch.Tensor]:
         return {**self.tables, "m": self.m, "v": self.v}
 
+    def _pocket_tensors(self) -> Dict[str, torch.Tensor]:
+        return self._state_tensors()                     # the tables and Adam's flat m and v
+
+    def _pocket_scalars(self) -> Dict[str, object]:
+        return {"t": self.t}                             # Adam's step count goes with m and v
+
     def state_dict(self) -> Dict[str, object]:
         return {"model": "transr", "l1": self.l1, "n_ent": self.n_ent, "n_rel": self.n_rel, "dim_e": self.dim_e,
                 "dim_r": self.dim_r, "t": self.t, "m": self.m.detach().cpu().clone(), "v": self.v.detach().cpu().clone(),

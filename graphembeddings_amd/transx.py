@@ -268,13 +268,17 @@ class _Model:
 
     def rank_counts(self, triples: torch.Tensor, cand_is_head: bool = False, known_off: torch.Tensor = None,
                     known_rc: torch.Tensor = None, return_scores: bool = False, row_set: torch.Tensor = None,
-                    mask: torch.Tensor = None):
+                    mask: torch.Tensor = None, out=None, workspace: torch.Tensor = None):
         """ge_transx_rank / ge_transr_rank on the [B,3] rows as given: (n_before, n_known_before, true_dist) device
         tensors, plus the [B, n_ent] distances with return_scores (tests).  known_off / known_rc: ge_known_cells'
         lists for these rows with pos_of = the identity (None: unfiltered).  Rows with an id out of range get -1
         counts.  row_set / mask (int32 [B]; int32 [n_sets, words], CandidateSets.mask for arange(n_ent)): only the
         entities admissible in the row's set are counted (ge_transx_rank_masked / ge_transr_rank_masked, which store no
-        distances: not with return_scores); a set index outside [-1, n_sets) gives the row -1 counts."""
+        distances: not with return_scores); a set index outside [-1, n_sets) gives the row -1 counts.
+        out = (n_before, n_known_before, true_dist): contiguous int32 / int32 / float32 [B] device tensors (views of a
+        caller's buffers) to write and return instead of new ones; workspace: a uint8 device tensor of at least the
+        rank workspace's size for B rows, used instead of a new one.  With both (int32 contiguous rows, no
+        return_scores) the call allocates nothing."""
         tb = _pairs(triples, "triples")
         B, dev = tb.shape[0], tb.device
         sets = self._sets_args(B, row_set, mask)
@@ -285,11 +289,24 @@ class _Model:
             raise ValueError("known_off and known_rc come together")
         if ws_bytes == 0:
             raise RuntimeError(f"{self.PREFIX}_rank_workspace_bytes failed")
-        nb = torch.empty(B, dtype=torch.int32, device=dev)
-        nk = torch.empty(B, dtype=torch.int32, device=dev)
-        td = torch.empty(B, dtype=torch.float32, device=dev)
-        sc = torch.empty((B, self.n_ent) if return_scores else (0,), dtype=torch.float32, device=dev)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        if out is None:
+            nb = torch.empty(B, dtype=torch.int32, device=dev)
+            nk = torch.empty(B, dtype=torch.int32, device=dev)
+            td = torch.empty(B, dtype=torch.float32, device=dev)
+        else:
+            nb, nk, td = out
+            for t, dt, name in ((nb, torch.int32, "n_before"), (nk, torch.int32, "n_known_before"), (td, torch.float32, "true_dist")):
+                _need_cuda(t, "out " + name)
+                if t.dtype != dt or t.dim() != 1 or t.numel() != B or not t.is_contiguous():
+                    raise ValueError(f"out {name} must be a contiguous {dt} [{B}] tensor")
+        sc = torch.empty(B, self.n_ent, dtype=torch.float32, device=dev) if return_scores else None
+        if workspace is None:
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        else:
+            ws = workspace
+            _need_cuda(ws, "workspace")
+            if ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < ws_bytes:
+                raise ValueError(f"workspace must be a contiguous uint8 tensor of at least {ws_bytes} bytes")
         p = lambda t: None if t is None else t.data_ptr()
         if sets:
             _lib.call(self.PREFIX + "_rank_masked", *self._ptrs(), tb.data_ptr(), B, int(bool(cand_is_head)),
@@ -297,8 +314,7 @@ class _Model:
                       ws.numel(), _stream())
             return nb, nk, td
         _lib.call(self.PREFIX + "_rank", *self._ptrs(), tb.data_ptr(), B, int(bool(cand_is_head)), p(known_off),
-                  p(known_rc), nb.data_ptr(), nk.data_ptr(), td.data_ptr(), sc.data_ptr() if return_scores else None,
-                  ws.data_ptr(), ws.numel(), _stream())
+                  p(known_rc), nb.data_ptr(), nk.data_ptr(), td.data_ptr(), p(sc), ws.data_ptr(), ws.numel(), _stream())
         return (nb, nk, td, sc) if return_scores else (nb, nk, td)
 
     def topk_candidates(self, queries: torch.Tensor, k: int, cand_is_head: bool = False, known_off: torch.Tensor = None,
@@ -434,6 +450,19 @@ class _Model:
 
     def _state_tensors(self) -> Dict[str, torch.Tensor]:
         return self.tables
+
+    def _pocket_tensors(self) -> Dict[str, torch.Tensor]:
+        """Every device tensor of the training state, under its state_dict name: what a validation pocket
+        (evaluate.TranslationPocket) copies on an improving tick -- the tables, and adagrad_<table> per accumulator."""
+        acc = getattr(self, "accumulators", None) or {}
+        return {**self.tables, **{"adagrad_" + k: v for k, v in acc.items()}}
+
+    def _pocket_scalars(self) -> Dict[str, object]:
+        """The host attributes that belong to that state (recorded per tick, set again by the pocket's restore())."""
+        return {}
+
+    def _check_candidate_sets(self) -> None:
+        """Raises where the model's sweeps take no candidate sets."""
 
     def _check_state(self, state: Dict[str, object], keys, what: str) -> None:
         """The sizes in `keys` and the shape of every tensor, checked before anything is copied."""

@@ -5,6 +5,8 @@ Reads relation2id.txt, entity2id.txt and triple2id.txt from --data_dir, trains f
 reference does, and saves the tables with torch.save (TF's model.vec checkpoint format is not reproduced).
 --loss self_adversarial trains on the self-adversarial negative-sampling loss of Sun et al. 2019 instead of the margin
 hinge: --negatives K filtered negatives per positive, weighted by a softmax at --adversarial_temperature, --margin = gamma.
+--validation_file adds filtered-MRR validation ticks during training (evaluate.TranslationPocket): the saved state is the
+best tick's, --patience stops early, <model>_validation.json records the ticks.
 The flags, checks and run() both translation drivers share live here; transr_train adds TransR's own.
 """
 from __future__ import annotations
@@ -74,6 +76,40 @@ def add_common_flags(p: argparse.ArgumentParser, dims, out: str) -> None:
                         "table (lines: query, position, neighbor, distance)")
     p.add_argument("--neighbors_metric", choices=("cosine", "euclidean"), default="cosine",
                    help="the distance of --neighbors_k")
+    add_validation_flags(p, out)
+
+
+def add_validation_flags(p: argparse.ArgumentParser, out: str = "<name>") -> None:
+    """--validation_file and the flags that need it (transx_train, transr_train, rotate_train)."""
+    p.add_argument("--validation_file", default=None,
+                   help="a *2id.txt file of validation triples: every --validation_every epochs (and after the last one) "
+                        "they are ranked over all entities, heads and tails, filtered by triple2id.txt + this file + the "
+                        f"--test_file + every --filter_file; {out}.pt and everything after training then hold the state "
+                        f"of the tick with the best filtered MRR, and {out}_validation.json the ticks")
+    p.add_argument("--validation_every", type=int, default=None, help="epochs between validation ticks (default 10)")
+    p.add_argument("--validation_rows", type=int, default=None,
+                   help="rank only this many validation triples, drawn once with --seed (default: all)")
+    p.add_argument("--patience", type=int, default=None,
+                   help="stop after this many validation ticks in a row without a better filtered MRR")
+
+
+def check_validation_args(a) -> None:
+    """The four validation flags, read with getattr (a Namespace built without them: no validation); sets the default
+    --validation_every."""
+    path = getattr(a, "validation_file", None)
+    rest = {k: getattr(a, k, None) for k in ("validation_every", "validation_rows", "patience")}
+    if path is None:
+        given = [k for k, v in rest.items() if v is not None]
+        if given:
+            raise ValueError("--%s needs --validation_file" % given[0])
+        return
+    for k, v in rest.items():
+        if v is not None and v < 1:
+            raise ValueError(f"--{k} must be >= 1, got {v}")
+    if not os.path.isfile(path):
+        raise ValueError(f"no such file: {path}")
+    if rest["validation_every"] is None:
+        a.validation_every = 10
 
 
 def check_training_args(a) -> None:
@@ -119,11 +155,18 @@ def check_eval_args(a) -> None:
             + [f for f in classify_files if f]:
         if not os.path.isfile(path):
             raise ValueError(f"no such file: {path}")
+    check_validation_args(a)
+
+
+def validation_line(epoch: int, step: int, m: dict) -> str:
+    return (f"Epoch {epoch} Step {step} Validation MRR: {m['filtered_mrr']:.6f} (hits@10 {m['hits10']:.2f} %)"
+            + (" *" if m["improved"] else ""))
 
 
 def run(a, driver: str, make_model, name: str, trainer_kw=None) -> int:
-    """Everything after the flags are checked: read --data_dir, build make_model(E, R), --load, train, save
-    <name>.pt (with --neighbors_k, <name>_neighbors.tsv) and, with --test_file, rank it (heads and tails, printed)
+    """Everything after the flags are checked: read --data_dir, build make_model(E, R), --load, train (with
+    --validation_file: a validation tick every --validation_every epochs, the best tick's state restored after the last,
+    <name>_validation.json), save <name>.pt (with --neighbors_k, <name>_neighbors.tsv) and, with --test_file, rank it (heads and tails, printed)
     into <name>_test.json (with --relation_ranks, relations too; with --candidate_sets, the `constrained` block and
     line); with --predict_k, write <name>_predict.tsv (from the relation's set with --candidate_sets); with
     --predict_relations_k, <name>_predict_relations.tsv; with --classify, <name>_classify.json and
@@ -146,12 +189,40 @@ def run(a, driver: str, make_model, name: str, trainer_kw=None) -> int:
             print(f"{a.load} holds no AdaGrad accumulators: they start at --adagrad_init {a.adagrad_init}")
     kw = dict(optimizer="adagrad", initial_accumulator_value=getattr(a, "adagrad_init", 0.1)) if adagrad else {}
     tr = m.trainer(tri, B, margin=a.margin, learning_rate=a.learning_rate, seed=a.seed, **kw, **(trainer_kw or {}))
+    vp, history, stopped_early, since = None, [], False, 0    # since: ticks in a row without a better MRR
+    if getattr(a, "validation_file", None):   # filter: triple2id.txt + validation + test + --filter_file
+        from .evaluate import TranslationPocket
+        valid = read_triples(a.validation_file, E, R)
+        more = [read_triples(f, E, R) for f in ([a.test_file] if a.test_file else []) + list(a.filter_file)]
+        vp = TranslationPocket(m, valid, np.concatenate([tri, valid] + more, 0), rows=getattr(a, "validation_rows", None), seed=a.seed)
     for epoch in range(a.train_times):
         res = float(tr.run(a.nbatches).double().sum())
         print(epoch)
         print(res)
+        if vp is not None and ((epoch + 1) % a.validation_every == 0 or epoch + 1 == a.train_times):
+            vp.tick(tr.step_count)
+            (step, mt), = vp.read()           # (the loss above has synchronised this epoch already)
+            history.append({"epoch": epoch, "step": step, **mt})
+            print(validation_line(epoch, step, mt))
+            since = 0 if mt["improved"] else since + 1
+            if getattr(a, "patience", None) is not None and since >= a.patience:
+                stopped_early = True
+                print(f"no better validation MRR in {since} ticks: stopping after epoch {epoch}")
+                sys.stdout.flush()
+                break
         sys.stdout.flush()
     os.makedirs(a.output_dir, exist_ok=True)
+    if vp is not None:                        # the best tick's state: what is saved, evaluated and written from here on
+        best_step = vp.restore()
+        best = next((h for h in history if h["step"] == best_step and h["improved"]), None)
+        json_path = os.path.join(a.output_dir, f"{name}_validation.json")
+        with open(json_path, "w") as f:
+            json.dump({"history": history, "pocket_mrr": best["filtered_mrr"] if best else None,
+                       "pocket_epoch": best["epoch"] if best else None, "pocket_step": best_step,
+                       "stopped_early": stopped_early, "rows": vp.V}, f, indent=1, sort_keys=True)
+        if best:
+            print(f"restored the state of epoch {best['epoch']} (step {best_step}): validation MRR {best['filtered_mrr']:.6f}")
+        print(f"wrote {json_path}")
     out = os.path.join(a.output_dir, f"{name}.pt")
     torch.save(m.state_dict(), out)
     print(f"saved {out}")

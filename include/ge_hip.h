@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define GE_VERSION 448 /* 0.4.4.8: + ge_transx_adv_* (TransE / TransH / TransD: the self-adversarial negative-sampling loss, its step with SGD / AdaGrad and native loops) */
+#define GE_VERSION 449 /* 0.4.4.9: + ge_copy_if (a copy of up to 16 buffers gated by a device flag: the pocket of the translation models' validation ticks) */
 
 /* argument errors (negative, -errno style) */
 #define GE_EINVAL (-22)  /* bad dimension / null pointer / misaligned buffer */
@@ -938,6 +938,26 @@ int ge_topk_1vK_masked(const float* table, int64_t N, int32_t d, const int32_t* 
  * GE_EINVAL: n_before, n_known_before or metrics_out NULL, M < 1.  GE_ENOTSUP: M > 2^24 (n stays exact in entry 7). */
 int ge_rank_metrics(const int32_t* n_before, const int32_t* n_known_before, const float* true_loss, int64_t M,
                     float* metrics_out, float* best, int32_t* improved, void* stream);
+
+/* --- a copy gated by a device flag, for a pocket of several buffers (the tables and optimiser state of a translation
+ * model): iff *flag != 0 when the kernel runs, dst[s][0 .. count[s]) <- src[s] for every segment s, as 32-bit words
+ * (NaN payloads survive); iff *flag == 0, no byte of any dst is written.  flag: a device int32, e.g. ge_rank_metrics'
+ * `improved`.  src, dst and count are HOST arrays of n_seg entries, read during the call and handed to the kernel by
+ * value: the caller may free them on return.  One launch for all segments, enqueued on `stream`; no synchronisation, no
+ * allocation.  count[s] == 0 is allowed and skipped (its pointers are not looked at); every count 0: nothing is
+ * launched, 0 is returned.
+ * Any 4-byte alignment is served: a segment whose src and dst are both 16-byte aligned moves 16 bytes a lane, any
+ * other moves dwords; the count % 4 tail is covered by both.  Each workgroup moves ge_copy_if_chunk() = 8192 words of
+ * one segment (the last chunk of a segment is shorter) and reads *flag first.
+ * Refusals, all before the launch.  GE_EINVAL: flag, src, dst or count NULL; n_seg outside [1,
+ * GE_COPY_IF_MAX_SEGMENTS]; a negative count; with count[s] > 0, src[s] or dst[s] NULL or not 4-byte aligned, or
+ * dst[s]'s range overlapping another segment's dst range or any segment's src range (its own included; checked on the
+ * host, so the result never depends on the order of the segments).  GE_ENOTSUP: a count above 2^44, or more than
+ * 2^31 - 1 chunks in all. */
+#define GE_COPY_IF_MAX_SEGMENTS 16
+int ge_copy_if_chunk(void);
+int ge_copy_if(const int32_t* flag, int32_t n_seg, const float* const* src, float* const* dst, const int64_t* count,
+               void* stream);
 
 /* --- one validation tick on the evaluation's own metric, enqueued on `stream` without a host decision, a
  * synchronisation or an allocation: `planes` rebuilt from the table as it is now (ge_rank_planes), the V tail-side rows
