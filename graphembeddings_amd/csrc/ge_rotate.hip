@@ -19,9 +19,11 @@
 //
 // Ranks: a row kernel stores q once per row -- q = h o e^{i theta} on the tail side, q = t o e^{-i theta} on the head
 // side (|c e^{i theta} - t| = |c - t e^{-i theta}|) -- and the sweep, the true distance and the filter pass all evaluate
-//   a = q_re,j - c_re,j;  b = q_im,j - c_im,j;  m2 = fmaf(b, b, a * a);  acc += l1 ? sqrtf(m2) : m2     for j in order
-// on that stored q (rot_term: every operation explicit, so contraction cannot differ between them).  The target never
-// ranks before itself and the filter counts exactly the cells the sweep counted.
+//   a = q_re,j - c_re,j;  b = q_im,j - c_im,j;  m2 = fmaf(b, b, a * a);  part += l1 ? sqrtf(m2) : m2     for j in order
+// on that stored q (rot_term: every operation explicit, so contraction cannot differ between them), a partial sum per
+// block of kRotSumBlock coordinates, the partial sums added in block order: at k = 512 one serial fp32 sum lies ten
+// times further from the exact one than a pairwise sum does.  The target never ranks before itself and the filter
+// counts exactly the cells the sweep counted.
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "ge_common.h"
@@ -34,6 +36,7 @@ namespace {
 
 constexpr int kRows = 16;                 // rows per sweep workgroup
 constexpr int kKnownTile = 128;           // ge_known_cells' tile edge
+constexpr int kRotSumBlock = 32;          // coordinates per partial sum of a rank distance (a multiple of 4)
 
 __device__ __forceinline__ bool id_ok(int32_t x, int64_t n) { return x >= 0 && x < n; }
 
@@ -185,11 +188,17 @@ __device__ __forceinline__ float rot_term(bool l1, float acc, float qre, float q
   return __fadd_rn(acc, l1 ? sqrtf(m2) : m2);
 }
 
-// D of candidate row c (entity row [Re | Im]) for the stored query q: the sweep's sequence, one lane.
+// D of candidate row c (entity row [Re | Im]) for the stored query q: the sweep's sequence, one lane.  (At
+// k <= kRotSumBlock the one partial sum is added to 0: the distance is the serial sum.)
 template <bool L1>
 __device__ __forceinline__ float rot_dist(const float* __restrict__ q, const float* __restrict__ c, int k) {
   float acc = 0.f;
-  for (int j = 0; j < k; ++j) acc = rot_term(L1, acc, q[j], q[k + j], c[j], c[k + j]);
+  for (int j0 = 0; j0 < k; j0 += kRotSumBlock) {
+    const int j1 = j0 + kRotSumBlock < k ? j0 + kRotSumBlock : k;
+    float part = 0.f;
+    for (int j = j0; j < j1; ++j) part = rot_term(L1, part, q[j], q[k + j], c[j], c[k + j]);
+    acc = __fadd_rn(acc, part);
+  }
   return acc;
 }
 
@@ -258,17 +267,25 @@ __global__ __launch_bounds__(kBlock) void rotate_rank_sweep_kernel(const float* 
     float acc[kRows];
 #pragma unroll
     for (int j = 0; j < kRows; ++j) acc[j] = 0.f;
-    for (int x = 0; x < k; x += VEC) {
-      float cre[VEC], cim[VEC];
-      load_vec<VEC>(e + x, cre); load_vec<VEC>(e + k + x, cim);
+    for (int x0 = 0; x0 < k; x0 += kRotSumBlock) {      // rot_dist's sequence: a partial sum per block of coordinates
+      const int x1 = x0 + kRotSumBlock < k ? x0 + kRotSumBlock : k;
+      float part[kRows];
 #pragma unroll
-      for (int j = 0; j < kRows; ++j) {
-        if (j < nrows) {
-          const float* qj = q + (row0 + j) * d + x;
+      for (int j = 0; j < kRows; ++j) part[j] = 0.f;
+      for (int x = x0; x < x1; x += VEC) {
+        float cre[VEC], cim[VEC];
+        load_vec<VEC>(e + x, cre); load_vec<VEC>(e + k + x, cim);
 #pragma unroll
-          for (int v = 0; v < VEC; ++v) acc[j] = rot_term(L1, acc[j], qj[v], qj[k + v], cre[v], cim[v]);
+        for (int j = 0; j < kRows; ++j) {
+          if (j < nrows) {
+            const float* qj = q + (row0 + j) * d + x;
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) part[j] = rot_term(L1, part[j], qj[v], qj[k + v], cre[v], cim[v]);
+          }
         }
       }
+#pragma unroll
+      for (int j = 0; j < kRows; ++j) acc[j] = __fadd_rn(acc[j], part[j]);
     }
 #pragma unroll
     for (int j = 0; j < kRows; ++j) {

@@ -239,3 +239,84 @@ def collinear_tables(E, R, d, seed=0, amp=3):
     rng = np.random.default_rng(seed)
     n = rng.integers(-amp, amp + 1, size=(E, d // 2)).astype(np.float64)
     return {"ent": np.concatenate([3 * n, 4 * n], 1), "rel": np.zeros((R, d // 2))}
+
+
+FP32_EXACT = 2.0 ** 24
+
+
+def valid_mask(pos, neg, E, R):
+    """The gradient kernel's `ok`: every id in range and the negative on the positive's relation."""
+    pos, neg = np.asarray(pos, dtype=np.int64), np.asarray(neg, dtype=np.int64)
+    ok = (pos[:, 2] >= 0) & (pos[:, 2] < R) & (neg[:, 2] == pos[:, 2])
+    for a in (pos[:, 0], pos[:, 1], neg[:, 0], neg[:, 1]):
+        ok &= (a >= 0) & (a < E)
+    return ok
+
+
+def exact_step_bound(tabs, pos, neg, lr, margin):
+    """For exact_tables_l2's form (integer entities, theta = 0), the squared norm, an integer margin and lr = 2^-n: the
+    largest sum of |terms| any sum of one SGD step can reach in any order, counted on the value's own grid (1 for the
+    distances, the loss and the summed gradient rows; lr for row - lr * sum).  Below 2^24 fp32 computes every one of them
+    exactly, so the step's loss and tables must equal sgd_step's bitwise.  Pairs the kernel drops (valid_mask) write
+    nothing and are left out.  Raises ValueError for a fixture not of this form."""
+    tabs = _cast(tabs, np.float64)
+    if not np.array_equal(tabs["ent"], np.round(tabs["ent"])) or np.any(tabs["rel"] != 0) or margin != round(margin):
+        raise ValueError("integer entities, zero phases and an integer margin are needed")
+    if not lr > 0 or np.frexp(lr)[0] != 0.5:
+        raise ValueError(f"lr={lr} is not a power of two")
+    pos, neg = np.asarray(pos, dtype=np.int64), np.asarray(neg, dtype=np.int64)
+    ok = valid_mask(pos, neg, len(tabs["ent"]), len(tabs["rel"]))
+    pos, neg = pos[ok], neg[ok]
+    parts = [_parts(tabs, tri[:, 0], tri[:, 1], tri[:, 2]) for tri in (pos, neg)]
+    dp, dn = _norm(parts[0][2], parts[0][3], False), _norm(parts[1][2], parts[1][3], False)
+    z = dp - dn + margin
+    active = z >= 0
+    worst = max(float((dp + dn + abs(margin)).max()), float(np.abs(z[active]).sum()))
+    mag = {k: np.zeros_like(v) for k, v in tabs.items()}
+    for tri, (wre, wim, ure, uim, _, _) in ((pos, parts[0]), (neg, parts[1])):
+        g = np.abs(np.concatenate([2 * ure, 2 * uim], 1))[active]          # |dD/dh| = |dD/dt| at theta = 0
+        np.add.at(mag["ent"], tri[active, 0], g)
+        np.add.at(mag["ent"], tri[active, 1], g)
+        np.add.at(mag["rel"], tri[active, 2], (np.abs(2 * uim * wre) + np.abs(2 * ure * wim))[active])
+    for k, v in tabs.items():
+        worst = max(worst, float((np.abs(v) / lr + mag[k]).max()))
+    return worst
+
+
+def is_exact_step(tabs, pos, neg, lr, margin):
+    """True iff every sum of |terms| of the squared-norm step stays below 2^24: fp32 gives the fp64 result bitwise in any
+    order (the distances, the loss, every summed gradient row and lr * sum against the row)."""
+    try:
+        return exact_step_bound(tabs, pos, neg, lr, margin) < FP32_EXACT
+    except ValueError:
+        return False
+
+
+def known_mask(test, known, E, side="tail"):
+    """[n, E] bool: cell (i, c) is known iff the test row with c in the candidate's place is a known triple.  Every
+    triple is encoded as one integer (fixed entity, relation, candidate) and the cells are looked up with np.isin, a block
+    of rows at a time."""
+    test, known = np.asarray(test, dtype=np.int64), np.asarray(known, dtype=np.int64).reshape(-1, 3)
+    fix, cand = (0, 1) if side == "tail" else (1, 0)
+    R = int(max(test[:, 2].max(initial=0), known[:, 2].max(initial=0))) + 1
+    inside = (known[:, cand] >= 0) & (known[:, cand] < E)
+    keys = np.unique((known[inside, fix] * R + known[inside, 2]) * E + known[inside, cand])
+    out = np.empty((len(test), E), dtype=bool)
+    ids = np.arange(E, dtype=np.int64)[None, :]
+    for s in range(0, len(test), 4096):
+        rows = test[s:s + 4096]
+        out[s:s + 4096] = np.isin(((rows[:, fix] * R + rows[:, 2]) * E)[:, None] + ids, keys)
+    return out
+
+
+def all_dists_blocked(tabs, tri, side="tail", l1=True, dtype=np.float64, block=2048):
+    """all_dists for many rows: the same statements, a block of rows at a time instead of one."""
+    qre, qim = rank_query(tabs, tri, side, dtype)
+    ent = np.asarray(tabs["ent"], dtype=dtype)
+    k = ent.shape[1] // 2
+    out = np.empty((len(qre), len(ent)), dtype=dtype)
+    for s in range(0, len(qre), block):
+        a, b = qre[s:s + block, None, :] - ent[None, :, :k], qim[s:s + block, None, :] - ent[None, :, k:]
+        m2 = a * a + b * b
+        out[s:s + block] = (np.sqrt(m2) if l1 else m2).sum(2)
+    return out
