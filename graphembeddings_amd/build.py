@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libge_hip.so")
 SOURCES = ["ge_capi.hip", "ge_complex.hip", "ge_rows.hip", "ge_hole.hip", "ge_1vk.hip", "ge_train.hip", "ge_prep_big.hip", "ge_shard.hip", "ge_spectral.hip", "ge_rank.hip", "ge_rank_pipe.hip", "ge_rank_f16.hip", "ge_rank_f16_masked.hip", "ge_known.hip", "ge_transx.hip", "ge_rotate.hip", "ge_rotate_adv.hip", "ge_transx_adv.hip", "ge_transr.hip", "ge_transx_rank.hip", "ge_transx_rank_masked.hip", "ge_neighbors.hip", "ge_transx_relrank.hip", "ge_classify.hip", "ge_adagrad.hip", "ge_softmax.hip", "ge_softmax_sampled.hip", "ge_softmax_masked.hip", "ge_softmax_labels.hip"]
-HEADERS = ["ge_common.h", "ge_launch.h", "ge_step_id.h", "ge_prep.h", "ge_complex_dev.h", "ge_rank_dev.h", "ge_sweep_route.h", "ge_trans.h", "ge_trans_dev.h", "ge_f16_dev.h", "ge_rank_f16_kern.h", "ge_transx_rank_kern.h", "ge_transx_apply.h", "ge_softmax_kern.h", "ge_topk_dev.h", "ge_bernoulli_dev.h", "ge_rotate_dev.h", "ge_adv_dev.h", os.path.join("..", "..", "include", "ge_hip.h")]
+HEADERS = ["ge_common.h", "ge_launch.h", "ge_step_id.h", "ge_prep.h", "ge_complex_dev.h", "ge_rank_dev.h", "ge_sweep_route.h", "ge_trans.h", "ge_trans_dev.h", "ge_f16_dev.h", "ge_rank_f16_kern.h", "ge_transx_rank_kern.h", "ge_transx_apply.h", "ge_softmax_kern.h", "ge_softmax_route.h", "ge_topk_dev.h", "ge_bernoulli_dev.h", "ge_rotate_dev.h", "ge_adv_dev.h", os.path.join("..", "..", "include", "ge_hip.h")]
 ARCH = "gfx950"
 
 

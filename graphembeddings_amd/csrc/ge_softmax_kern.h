@@ -6,39 +6,18 @@
 #pragma once
 #include "ge_common.h"
 #include "ge_launch.h"
+#include "ge_softmax_route.h"   // kSm*, sm_tiles, sm_split, sm_maxcb, sm_plan: the launch arithmetic, host only
 
 namespace ge {
 
 using sm_f32x16 = __attribute__((ext_vector_type(16))) float;
-
-constexpr int kSmTile = 64;          // X and Y rows of a tile
-constexpr int kSmChunk = 32;         // X columns staged at a time
-constexpr int kSmLdx = kSmChunk + 1; // LDS row strides are odd: the 32 rows a half-wave reads fall in 32 banks
-constexpr int kSmLdw = kSmTile + 1;
-constexpr int kSmMaxSplit = 8;       // Y ranges of a split sweep
-constexpr int kSmXresMaxDim = 256;   // up to here X and Y tiles fit whole in LDS together (149 KB with the W tile)
-
-static inline int sm_col_blocks(int d) { return (d + 31) / 32; }
-static inline int sm_ldy(int d) { return 32 * sm_col_blocks(d) + 1; }
-static inline int64_t sm_tiles(int64_t n) { return (n + kSmTile - 1) / kSmTile; }
-// Y ranges of a sweep of NX fixed rows against NY: enough workgroups for the device at a small NX, never more than
-// kSmMaxSplit or than Y tiles
-static inline int sm_split(int64_t NX, int64_t NY) {
-  const int64_t tx = sm_tiles(NX), ty = sm_tiles(NY);
-  int64_t s = 512 / tx;
-  if (s < 1) s = 1;
-  if (s > kSmMaxSplit) s = kSmMaxSplit;
-  if (s > ty) s = ty;
-  return (int)s;
-}
 
 // What a MASKED sweep takes beside the operands (all null / zero otherwise): set [queries] the rows' set ids, mask
 // [n_sets][W] in the format of ge_candidate_mask_words (W a multiple of 4: both words of a 64-candidate tile are in
 // bounds), live [query tiles][live_words] one bit per (query tile, candidate tile), bit ct & 31 of word ct >> 5: a pair
 // whose bit is clear is skipped.
 struct SmMaskArgs { const int32_t* set; const uint32_t* mask; const uint32_t* live; int64_t W; int32_t n_sets; int32_t live_words; };
-// words per query tile of the live bitmap: even, so that a wave's 64-bit ballot is two whole words
-static inline int64_t sm_live_words(int64_t K) { return 2 * ((sm_tiles(K) + 63) / 64); }
+// (sm_live_words(K), the words per query tile of the live bitmap: ge_softmax_route.h)
 
 __device__ __forceinline__ float sm_wave_sum(float v) { return group_sum<kWave>(v); }
 
@@ -328,11 +307,9 @@ __global__ __launch_bounds__(kBlock) void softmax_sweep_kernel(
 template <int MODE, bool XQ, bool SAMPLED, bool MASKED = false>
 static int sm_sweep(const float* xp, const int32_t* xkey, int64_t NX, const float* yp, const int32_t* ykey, int64_t NY, int d,
                     float scale, const float* lse, int n_ranges, float* out, hipStream_t st, const SmMaskArgs& mk = SmMaskArgs{}) {
-  const int64_t ty = sm_tiles(NY);
-  const int tpr = (int)((ty + n_ranges - 1) / n_ranges);
-  const int xres = d <= kSmXresMaxDim;
-  const size_t lds = sizeof(float) * ((size_t)kSmTile * sm_ldy(d) + kSmTile * (xres ? sm_ldy(d) : kSmLdx) + kSmTile * kSmLdw +
-                                      4 * kSmTile + (MASKED ? 3 * kSmTile : 0));
+  const SmPlan pl = sm_plan(NY, n_ranges, d, MASKED);
+  const int tpr = pl.tiles_per_range, xres = pl.xres;
+  const size_t lds = pl.lds_bytes;
   const dim3 grid((unsigned)sm_tiles(NX), (unsigned)n_ranges);
   auto go = [&](auto kern) -> int {
     if (int rc = lds_opt_in(kern)) return rc;
@@ -340,7 +317,7 @@ static int sm_sweep(const float* xp, const int32_t* xkey, int64_t NX, const floa
     return launch_status();
   };
   if constexpr (MODE == 0) return go(softmax_sweep_kernel<MODE, XQ, 1, SAMPLED, MASKED>);
-  else switch ((sm_col_blocks(d) + 1) / 2) {
+  else switch (sm_maxcb(d)) {
     case 1: return go(softmax_sweep_kernel<MODE, XQ, 1, SAMPLED, MASKED>);
     case 2: return go(softmax_sweep_kernel<MODE, XQ, 2, SAMPLED, MASKED>);
     case 3: return go(softmax_sweep_kernel<MODE, XQ, 3, SAMPLED, MASKED>);

@@ -22,15 +22,7 @@
 
 namespace ge {
 
-// rows of dL/dC' partials: split * K for every split softmax_sampled_launch can choose (sm_split(K, B) is at most
-// min(8, tiles(B)) and at most max(1, 512 / tiles(K))), in a form that never shrinks as B or K grow
-static inline size_t sm_gc_rows(int64_t B, int64_t K) {
-  const int64_t tb = sm_tiles(B), tk = sm_tiles(K);
-  const int64_t by_b = (tb < kSmMaxSplit ? tb : kSmMaxSplit) * K;
-  const int64_t by_k = (int64_t)kSmTile * (tk > 512 ? tk : 512);
-  return (size_t)(by_b < by_k ? by_b : by_k);
-}
-
+// (sm_gc_rows(B, K), the rows of dL/dC' partials for every split softmax_sampled_launch can choose: ge_softmax_route.h)
 SoftmaxSampledWs softmax_sampled_ws(void* base, int64_t B, int64_t K, int32_t d) {
   SoftmaxSampledWs w;
   size_t off = 0;

@@ -19,7 +19,9 @@ from tests import softmax_sampled_ref as SS
 pytestmark = pytest.mark.gpu
 
 I32, F32 = np.int32, np.float32
-SHAPES = [(1, 1, 8), (65, 129, 64), (130, 300, 200)]
+# (512, 4095, 8): with the appended row and candidate B1 = 513, K1 = 4096 -- sm_split(K1, B1) * K1 = sm_gc_rows(B1, K1) =
+# 32,768 (csrc/ge_softmax_route.h): the candidate-side partials, the workspace's last part, end on its last row
+SHAPES = [(1, 1, 8), (65, 129, 64), (130, 300, 200), (512, 4095, 8)]
 
 
 @pytest.fixture(autouse=True)

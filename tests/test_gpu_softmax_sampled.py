@@ -33,6 +33,7 @@ pytestmark = pytest.mark.gpu
 I32, F32 = np.int32, np.float32
 N_REL, EXTRA = 4, 120
 X_TRUE, X_ABSENT, X_FIXED = slice(0, 34), slice(34, 50), slice(50, 120)    # what the 120 non-candidate entities are for
+N_OWN_TRUE, N_OWN_FIXED = 34, 70                         # rows of kind 0, of kinds 0 and 2, that X_TRUE and X_FIXED serve
 A0 = TS.A0
 dev, bits = TS.dev, TS.bits
 
@@ -57,7 +58,8 @@ def build(B, K, d, max_norm, head, seed=0):
     the largest logit the row can have (p_true near 1); 1 -- the true id is no candidate; 2 -- the true id is no candidate
     and one candidate's row is set to -1.5 max_norm Q'_i / |Q'_i| (exp overflows without the running maximum; p_true near
     0); 3 -- the true id sits in a random column.  The rows of kinds 0 and 2 have a fixed entity of their own that is
-    nothing else.  Rows 0..2 share their fixed entity, which is candidate 0; rows with B in (63, 130) all share relation 1.
+    nothing else; once 34 rows of kind 0, or 70 of kinds 0 and 2, have taken theirs (no shape of this file: B = 512 and more
+    of tests/test_gpu_softmax_sweep_edges.py), further rows of those kinds are of kind 1.  Rows 0..2 share their fixed entity, which is candidate 0; rows with B in (63, 130) all share relation 1.
     B = 1: the one row is of kind (K + head) mod 4, with 3 meaning column 0."""
     rng = np.random.default_rng(1000 * B + 7 * K + d + seed)
     n_ent = K + EXTRA
@@ -94,6 +96,8 @@ def build(B, K, d, max_norm, head, seed=0):
     for i, kind in zip(range(n_hit, B), kinds):
         if kind == 2 and n_cand >= len(free):
             kind = 1
+        if (kind == 0 and n_true >= N_OWN_TRUE) or (kind in (0, 2) and n_fix >= N_OWN_FIXED):
+            kind = 1                                    # (B > 300 or so: the entities set aside for these kinds are used up)
         if kind == 3:
             true[i] = cand[free[rng.integers(len(free))] if free else 0]
             continue
@@ -115,7 +119,7 @@ def build(B, K, d, max_norm, head, seed=0):
         assert (~hit).any() and all((true == cand[c]).any() for c in cols[:B])
         v = cand[cand >= 0]
         assert (cand < 0).any() and len(np.unique(v)) <= len(v) - 2 and (cand == true[0]).sum() == 2
-        assert n_true >= (B - n_hit) // 4 and n_cand >= min((B - n_hit) // 4, 1)
+        assert n_true >= min((B - n_hit) // 4, N_OWN_TRUE) and n_cand >= min((B - n_hit) // 4, 1)
     return t, hr, true, cand
 
 
